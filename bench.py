@@ -25,7 +25,7 @@ host launches step i + 1's build before it waits for step i's words.  `value` = 
 max-over-ranks time ("strong" scaling: the query is fixed, ranks split it).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload sf100|sf10|sf1] [--no-cpu] [--no-extras]
-                    [--mat-steps M] [--mat-budget-gb G] [--no-pmc]
+                    [--mat-steps M] [--mat-budget-gb G] [--no-pmc] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task statement):
@@ -387,25 +387,87 @@ def extra_materialised(pkg, orc, device):
 MAT_KERNELS = ["mat_mid2", "mat_mid2_prepare", "mat_tile_entries"]
 
 
-def match_step(gg, build, budget_bytes, verify=False):
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all arrays together, as float64
+DUMP_SEED = 0x5EED0D0
+MAT_SAMPLE_BLOCK = 1024  # rows per sampled block of region B (one gg_result_fetch: GG_CHUNK_ROWS)
+
+
+def _dump_positions(n, k, seed):
+    """k sorted distinct positions in [0, n), a function of (n, k, seed) alone: the same sample from every run and build."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng([DUMP_SEED, seed, n])
+    return np.unique(rng.integers(0, n, size=k, dtype=np.int64))
+
+
+def _mat_sample_blocks(total_rows, n_blocks=64):
+    """Start rows of the --dump-outputs sample of region B: n_blocks seeded blocks of up to MAT_SAMPLE_BLOCK rows each."""
+    return _dump_positions(total_rows, n_blocks, 2)
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes what the timed path returned, one float64 .npy per array (every value here is an integer below 2^53,
+    so the cast is exact), at most DUMP_LIMIT_BYTES in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(np.asarray(a).size * 8 for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        if a.size and np.abs(a.astype(np.float64)).max() >= 2.0**53:
+            raise SystemExit(f"--dump-outputs: {name} holds values float64 cannot represent exactly")
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    log(f"dumped {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {out_dir}")
+
+
+def csr_sample(csr, max_values=2 << 20):
+    """The CSR a step built, as its caller receives it (gg_csr_export): offsets, neighbour indices and vertex ids in
+    full where they fit the budget, else at seeded positions (the positions are dumped beside them)."""
+    off, nbr, _, vid = csr.export()  # (edge rowids are not carried on the benchmarked path: set_edge_rowid(False))
+    out = {}
+    for name, a, seed in (("csr_offsets", off, 3), ("csr_neighbours", nbr, 4), ("csr_vertex_ids", vid, 5)):
+        pos = _dump_positions(a.size, max_values, seed)
+        out[name] = a[pos]
+        if pos.size < a.size:
+            out[name + "_positions"] = pos
+    return out
+
+
+def match_step(gg, build, budget_bytes, verify=False, sample=None):
     """One step of region B on this rank: build, then every 2-hop row whose middle vertex this rank owns (all of them
     at N = 1) written to HBM as three int64 id columns, part by part under the device-memory budget.  The number of
     rows comes from degrees (gg_khop_count) and sizes the parts; parts are middle-vertex ranges of near-equal work
     (gg_khop_partition_mid), each produced by gg_expand_khop_mid_result, handed over and freed.  verify: every part's
     rows are digested on the device (gg_result_digest maps every id of every row back to its dense index and sums the
-    row hashes) — the untimed parity pass."""
+    row hashes) — the untimed parity pass.  sample (a dict): seeded blocks of the rows are fetched into it
+    (--dump-outputs).  A part's kernels are still queued when it is handed over, so the device is synchronised first
+    (that wait is the step's own work and stays in the caller's timing); only the seconds of the host copies after it
+    go to sample["seconds"], for the caller to leave out of its timing."""
     c = build()
     total = gg.khop_count(c, 2, 2)[2]
     n_parts = max(1, int(-(-total * 24 // budget_bytes)))
     bounds = gg.khop_partition_mid(c, n_parts) if n_parts > 1 else [0, c.V]
     rows = dig = 0
+    starts = _mat_sample_blocks(total) if sample is not None else None
     for lo, hi in zip(bounds[:-1], bounds[1:]):
         res = gg.expand_khop_mid_result(c, lo, hi, k_min=2, with_stats=False)  # (rows only: the count came from degrees)
         if verify:
             n, d = res.digest(c, 2)
             assert n == res.rows(2)
             dig = (dig + d) & 0xFFFFFFFF
-        rows += res.rows(2)
+        n_part = res.rows(2)
+        picked = starts[(starts >= rows) & (starts < rows + n_part)] if sample is not None else ()
+        if len(picked):
+            import torch
+
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for s0 in picked:
+                got = res.fetch(2, int(s0 - rows), int(min(MAT_SAMPLE_BLOCK, rows + n_part - s0)))
+                sample.setdefault("rows", []).append(got)
+                sample.setdefault("positions", []).append(np.arange(s0, s0 + got.shape[0], dtype=np.int64))
+            sample["seconds"] = sample.get("seconds", 0.0) + time.perf_counter() - t0
+        rows += n_part
         res.close()
     c.close()
     return rows, dig, n_parts
@@ -622,7 +684,15 @@ def main():
                     help="device-memory budget of one materialised part (GiB; the operators' GG_RESULT_BUDGET_MB default)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 counter passes (traffic from profiles/)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of each region returned as DIR/<name>.npy "
+                         "(float64; seeded samples of the CSR and of the materialised rows; <= 64 MiB in all).  Written "
+                         "by rank 0: the counts are the whole query's, the CSR and row samples rank 0's own shard")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0 or args.mat_steps < 0:
+        ap.error("--warmup and --mat-steps must not be negative")
     if args.pmc_child:
         return _pmc_child(args)
 
@@ -694,28 +764,34 @@ def main():
             return gg.build_csr_shard(0, args.shard_of)
         return gg.build_csr_shard(rank, world) if world > 1 else gg.build_csr()
 
-    def run_steps(n):
+    def run_steps(n, keep_last=False):
         """n complete steps of region A — build, counting expansion, combine of the ranks' results.  With a process
         group the expansion leaves its six result words on the device (gg_expand_khop_dev: no host synchronisation),
         the NEXT step's build is launched (gg_csr_build returns once its status is known, two thirds of its kernels
         still queued), and only then are the words all-reduced in place and copied to the host once
         (sharding.combine_dev) — the collective and its one round trip run beside the build's queued kernels.  Every
         step's build, expansion and combine lie inside the caller's timed region; no CSR is built that is not
-        expanded."""
-        vec = st = None
+        expanded.  keep_last: the last step's CSR is returned open instead of closed (--dump-outputs)."""
+        vec = st = last = None
         c = build()
         for i in range(n):
             if dist is None:
                 st = gg.expand_khop(c, 1, 2)
-                c.close()
+                if keep_last and i + 1 == n:
+                    last = c
+                else:
+                    c.close()
                 c = build() if i + 1 < n else None
                 vec = sharding.stats_to_vec(st)
             else:
                 words = gg.expand_khop_dev(c, 1)
-                c.close()  # (blocks go back to the pool in stream order; the queued expansion still reads them first)
+                if keep_last and i + 1 == n:
+                    last = c
+                else:
+                    c.close()  # (blocks go back to the pool in stream order; the queued expansion still reads them first)
                 c = build() if i + 1 < n else None
                 vec = sharding.combine_dev(gg, words, dist)
-        return vec, st
+        return (vec, st, last) if keep_last else (vec, st)
 
     def step():
         return run_steps(1)
@@ -734,11 +810,21 @@ def main():
     torch.cuda.synchronize()
     barrier()
     t0 = time.perf_counter()
-    tot, st_local = run_steps(args.steps)
+    tot, st_local, last_csr = run_steps(args.steps, keep_last=True) if args.dump_outputs else (*run_steps(args.steps), None)
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
     gg.profile(False)
+    dump = {}
+    if last_csr is not None:
+        # region A's last timed step as its caller receives it: the 1..2-hop row counts, digests and edge counts
+        # (combined over the ranks), and the CSR that step built (this rank's shard)
+        r1, r2, d1, d2, te, fr = (int(x) for x in tot)
+        dump.update({"count_rows": np.array([r1, r2]), "count_digest": np.array([d1, d2]),
+                     "count_traversed_edges": np.array([te]), "count_frontier_entries": np.array([fr])})
+        if rank == 0:
+            dump.update(csr_sample(last_csr))
+        last_csr.close()
     prof = gg.profile_get()
     # untimed: every kernel, for the breakdown (kernels[...]["timed_region"] tells the two apart)
     TABLE_STEPS = 3
@@ -767,8 +853,12 @@ def main():
         torch.cuda.synchronize()
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.mat_steps):
-            rows_l, _, n_parts_l = match_step(gg, build, budget)
+        mat_sample = None
+        for i in range(args.mat_steps):
+            if args.dump_outputs and i + 1 == args.mat_steps:
+                # (rank 0's shard: fetched inside the last step; only the host copies are taken out of mat_elapsed below)
+                mat_sample = {} if rank == 0 else None
+            rows_l, _, n_parts_l = match_step(gg, build, budget, sample=mat_sample)
             rt = torch.tensor([rows_l], dtype=torch.int64, device="cuda")
             if dist is not None:
                 dist.all_reduce(rt)  # the query's row count, once per step (the rows themselves stay sharded in HBM)
@@ -776,6 +866,14 @@ def main():
         torch.cuda.synchronize()
         barrier()
         mat_elapsed = time.perf_counter() - t0
+        if mat_sample is not None:
+            mat_elapsed -= mat_sample.get("seconds", 0.0)
+            if rank == 0:
+                rows_s = mat_sample.get("rows", [])
+                dump["match_rows_total"] = np.array([int(step_rows[-1].item())])  # (combined over the ranks)
+                dump["match_rows_sample"] = np.concatenate(rows_s) if rows_s else np.zeros((0, 3), np.int64)
+                dump["match_rows_sample_positions"] = (np.concatenate(mat_sample["positions"]) if rows_s
+                                                       else np.zeros(0, np.int64))
         gg.profile(False)
         mat_prof = gg.profile_get()
         if dist is not None:
@@ -790,6 +888,9 @@ def main():
         v_rows, v_dig = int(vt[0].item()), int(vt[1].item()) & 0xFFFFFFFF
         mat = {"elapsed": mat_elapsed, "prof": mat_prof, "rows_local": rows_l, "parts_local": n_parts_l,
                "rows_steps": [int(t.item()) for t in step_rows], "verify_rows": v_rows, "verify_digest": v_dig}
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dump)
 
     if st_local is None:  # (device-side combine: the rank's own counts never came to the host inside the timed region)
         c = build()

@@ -1,6 +1,6 @@
 // gg_duckdb_extension.cpp — zero-patch SQL surface for the GPU graph operators.
 //
-// Loaded with   LOAD '<repo>/duckdb_pgq_amd/gg_duckdb.duckdb_extension';
+// Loaded with   LOAD '<repo>/oracle/_ref/ext/gg_duckdb.duckdb_extension';
 // (PhysicalLoad: dlopen + <basename>_init / <basename>_version,
 //  src/execution/operator/helper/physical_load.cpp:29-70 of the reference).  It registers table
 // functions that the planner wraps in an ordinary PhysicalTableScan, so no reference

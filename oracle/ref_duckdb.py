@@ -21,15 +21,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 # product's operators need, as the maintainers would add them): the extension registers its rules there, the
 # interposition shim is NOT loaded, and the extension is the build without access to private members.
 VARIANT = os.environ.get("GG_REF_VARIANT", "")
-_DIR = {"hoisted": "_ref_hoisted", "patched": "_ref_patched"}.get(VARIANT, "_ref")
+_DIR = os.path.join("_ref", {"hoisted": "hoisted", "patched": "patched"}.get(VARIANT, ""))
 LIBDUCKDB = os.path.join(HERE, _DIR, "libduckdb.so")
 LIBGGREF = os.path.join(HERE, _DIR, "libggref.so")
-_PKG = os.path.join(os.path.dirname(HERE), "duckdb_pgq_amd")
+# the host-side objects (duckdb_pgq_amd/host/Makefile) are compiled against the reference's headers: they sit beside it
+_EXT = os.path.join(HERE, "_ref", "ext")
 # interposition shim of the product's planner rules (duckdb_pgq_amd/host/gg_plan_hook.c): a pass-through
 # until the extension registers its rules, but it has to be in the global scope BEFORE libduckdb
-PLAN_HOOK = os.path.join(_PKG, "libgg_plan_hook.so")
+PLAN_HOOK = os.path.join(_EXT, "libgg_plan_hook.so")
 # the loadable extension that goes with this variant of the reference
-EXTENSION = os.path.join(_PKG, "callouts" if VARIANT == "patched" else "", "gg_duckdb.duckdb_extension")
+EXTENSION = os.path.join(_EXT, "callouts" if VARIANT == "patched" else "", "gg_duckdb.duckdb_extension")
 
 
 def rules_route() -> str:

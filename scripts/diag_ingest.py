@@ -16,7 +16,7 @@ from duckdb_pgq_amd import datagen  # noqa: E402
 
 scale = sys.argv[1] if len(sys.argv) > 1 else "sf100"
 threads = [int(x) for x in sys.argv[2].split(",")] if len(sys.argv) > 2 else [8, 16, 32, 64, 128, 256]
-EXT = os.path.join(ROOT, "duckdb_pgq_amd", "gg_duckdb.duckdb_extension")
+EXT = os.path.join(ROOT, "oracle", "_ref", "ext", "gg_duckdb.duckdb_extension")
 vid, src, dst = datagen.ldbc(scale)
 d = R.RefDuckDB(threads=threads[0])
 d.load_ldbc(vid, src, dst)

@@ -4,7 +4,7 @@ UNIONs the friends of one person with the friends of those friends, joined with 
 forum / organisation / tag columns, aggregated, ordered, limited).
 
 The statements are generated here (table and column names are the schema's, benchmark/ldbc/schema.sql); the shipped
-texts themselves are read from the reference tree where it exists (tests/test_plan_rule.py) and never stored.
+texts themselves are stored as shipped in tests/golden/ldbc_queries.json (tests/test_plan_rule.py).
 """
 import numpy as np
 

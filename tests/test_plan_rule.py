@@ -3,6 +3,7 @@ reference are taken over and which are left alone.  Only EXPLAIN is used here â€
 (the scans open at execution time); result parity of the substituted plans is in
 tests/test_duckdb_extension.py (-m gpu).  Needs oracle/_ref (the compiled reference), the extension and
 the interposition shim, all built by __graft_entry__.build() where /root/reference exists."""
+import json
 import os
 
 import pytest
@@ -251,8 +252,13 @@ def test_payload_column_keeps_its_join_on_the_cpu(traindb):
     assert "HASH_JOIN" in plan
 
 
-# ---- the reference's own LDBC query texts ----------------------------------------------------------------
-LDBC_DIR = "/root/reference/benchmark/ldbc"
+# ---- the reference's own LDBC query texts (benchmark/ldbc/, stored as shipped: tests/golden/make_ldbc_queries.py) ----
+LDBC_TEXTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ldbc_queries.json")
+
+
+def _ldbc_texts():
+    with open(LDBC_TEXTS) as f:
+        return json.load(f)
 
 
 def _ldbc_database(populated=False):
@@ -260,7 +266,7 @@ def _ldbc_database(populated=False):
     to EMPTY_RESULT before any planner rule sees them) and a few knows rows; `populated` adds the few thousand
     rows of tests/ldbc_shapes.py on top."""
     d = R.RefDuckDB(threads=2)
-    ddl = open(os.path.join(LDBC_DIR, "schema.sql")).read()
+    ddl = _ldbc_texts()["schema.sql"]
     for stmt in ddl.split(";"):
         lines = [ln for ln in stmt.splitlines() if not ln.strip().startswith("--")]
         if "".join(lines).strip():
@@ -381,7 +387,6 @@ def test_unions_that_are_not_friends_and_friends_of_friends_keep_their_dedupe():
     d.close()
 
 
-@pytest.mark.skipif(not os.path.isdir(LDBC_DIR), reason="reference tree not present")
 @pytest.mark.parametrize("populated", [False, True])
 def test_the_references_ldbc_queries_get_gpu_operators(populated):
     """The LDBC interactive queries of the reference that walk KNOWS twice (friends of friends:
@@ -397,8 +402,8 @@ def test_the_references_ldbc_queries_get_gpu_operators(populated):
               "interactive-complex-6.sql": "GG_WALK_ENDPOINTS", "interactive-complex-9.sql": "GG_WALK_ENDPOINTS",
               "interactive-complex-11.sql": "GG_WALK_ENDPOINTS"}
     seen = {}
-    for name in sorted(os.listdir(os.path.join(LDBC_DIR, "queries"))):
-        sql = open(os.path.join(LDBC_DIR, "queries", name)).read().strip().rstrip(";")
+    for name, text in sorted(_ldbc_texts()["queries"].items()):
+        sql = text.strip().rstrip(";")
         try:
             plan = d.explain(sql)
         except RuntimeError:

@@ -11,11 +11,11 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PATCHED = os.path.join(ROOT, "oracle", "_ref_patched", "libduckdb.so")
-EXT = os.path.join(ROOT, "duckdb_pgq_amd", "callouts", "gg_duckdb.duckdb_extension")
+PATCHED = os.path.join(ROOT, "oracle", "_ref", "patched", "libduckdb.so")
+EXT = os.path.join(ROOT, "oracle", "_ref", "ext", "callouts", "gg_duckdb.duckdb_extension")
 
 pytestmark = pytest.mark.skipif(not (os.path.exists(PATCHED) and os.path.exists(EXT)),
-                                reason="oracle/_ref_patched / callouts extension not built (needs /root/reference)")
+                                reason="oracle/_ref/patched / callouts extension not built (needs /root/reference)")
 
 
 def _run(args, timeout):
@@ -33,7 +33,7 @@ def test_the_rules_register_through_the_call_outs_without_the_shim():
             "assert R.rules_route() == 'callouts'; d = R.RefDuckDB(threads=2); assert d.hook is None; "
             "d.execute(\"LOAD '\" + R.EXTENSION + \"'\"); ext = ctypes.CDLL(R.EXTENSION); "
             "assert ext.gg_plan_rules_available() == 1 and ext.gg_plan_rules_by_callout() == 1; "
-            "maps = open('/proc/self/maps').read(); assert 'libgg_plan_hook' not in maps and '_ref_patched' in maps; "
+            "maps = open('/proc/self/maps').read(); assert 'libgg_plan_hook' not in maps and '_ref/patched/' in maps; "
             "d.close(); print('callouts ok')" % ROOT)
     r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, GG_REF_VARIANT="patched"),
                        capture_output=True, text=True, timeout=300)
@@ -45,7 +45,7 @@ def test_no_private_access_in_the_call_out_build_of_the_extension():
     on the preprocessed text of ALL FIVE host sources where the reference's headers are present.  (The planner rules
     get the connection they plan for from the call-out's first argument, oracle/callout.patch: PlanCallouts::plan_fn.)"""
     ref = "/root/reference/src/include"
-    patched = os.path.join(ROOT, "oracle", "_ref_patched", "src", "include")
+    patched = os.path.join(ROOT, "oracle", "_ref", "patched", "src", "include")
     if not os.path.isdir(ref):
         pytest.skip("reference headers not present")
     host = os.path.join(ROOT, "duckdb_pgq_amd", "host")

@@ -56,9 +56,8 @@ def test_connectedsegments_sql_on_reference():
     db.load_table("Segment", {"id": t["Segment"][:, 0], "length": t["Segment"][:, 1]})
     db.load_table("connectsTo", {"TrackElement1_id": t["connectsTo"][:, 0], "TrackElement2_id": t["connectsTo"][:, 1]})
     db.load_table("monitoredBy", {"TrackElement_id": t["monitoredBy"][:, 0], "Sensor_id": t["monitoredBy"][:, 1]})
-    # the statement is generated (tests/trainbenchmark.py), or read where the reference's own file is present
-    path = "/root/reference/benchmark/trainbenchmark/queries/connectedsegments.sql"
-    sql = open(path).read() if os.path.exists(path) else tb.connectedsegments_sql()
+    # the reference's own statement (benchmark/trainbenchmark/queries/connectedsegments.sql, stored as shipped)
+    sql = open(os.path.join(tb.DIR, "connectedsegments.sql")).read()
     assert np.array_equal(sort_rows(db.execute(sql)), sort_rows(tb.CONNECTEDSEGMENTS_GOLDEN))
     db.close()
 
@@ -72,8 +71,8 @@ def test_hoisted_build_variant_of_the_reference_returns_the_same_relation():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.exists(os.path.join(root, "oracle", "_ref_hoisted", "libduckdb.so")):
-        pytest.skip("oracle/_ref_hoisted not built (make -C oracle ref_hoisted)")
+    if not os.path.exists(os.path.join(root, "oracle", "_ref", "hoisted", "libduckdb.so")):
+        pytest.skip("oracle/_ref/hoisted not built (make -C oracle ref_hoisted)")
     out = {}
     for variant in ("", "hoisted"):
         env = dict(os.environ, GG_REF_VARIANT=variant)

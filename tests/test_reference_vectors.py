@@ -167,10 +167,10 @@ def test_vectors_hold_with_the_planner_rules_on():
 
 @pytest.mark.gpu
 def test_vectors_hold_on_the_call_out_route():
-    patched = os.path.join(ROOT, "oracle", "_ref_patched", "libduckdb.so")
-    ext = os.path.join(ROOT, "duckdb_pgq_amd", "callouts", "gg_duckdb.duckdb_extension")
+    patched = os.path.join(ROOT, "oracle", "_ref", "patched", "libduckdb.so")
+    ext = os.path.join(ROOT, "oracle", "_ref", "ext", "callouts", "gg_duckdb.duckdb_extension")
     if not (os.path.exists(patched) and os.path.exists(ext)):
-        pytest.skip("oracle/_ref_patched / callouts extension not built")
+        pytest.skip("oracle/_ref/patched / callouts extension not built")
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", "-m", "gpu",
                         "tests/test_reference_vectors.py::test_vectors_hold_with_the_planner_rules_on"], cwd=ROOT,
                        env=dict(os.environ, GG_REF_VARIANT="patched"), capture_output=True, text=True, timeout=1500)

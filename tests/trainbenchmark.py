@@ -1,5 +1,5 @@
-"""Train Benchmark SF1 fixture (data files the reference ships under benchmark/trainbenchmark/sf1/,
-copied to tests/golden/trainbenchmark_sf1/) and the ConnectedSegments golden rows
+"""Train Benchmark SF1 fixture (data files the reference ships under benchmark/trainbenchmark/sf1/, and its
+queries/connectedsegments.sql, copied to tests/golden/trainbenchmark_sf1/) and the ConnectedSegments golden rows
 (benchmark/trainbenchmark/connectedsegments.benchmark:34-38)."""
 import os
 
