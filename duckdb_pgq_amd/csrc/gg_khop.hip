@@ -2711,20 +2711,21 @@ extern "C" int gg_result_fetch(const gg_result *res, int hops, uint64_t offset, 
 // Reads the id columns a materialising expansion left in HBM, maps every id back to its dense index through the
 // CSR's id table and sums the low halves of the row hashes (DESIGN.md "Row digest"): the checksum a count-mode
 // expansion of the same walks reports, taken from what was actually WRITTEN.
-__global__ __launch_bounds__(256) void k_result_digest(const int64_t *__restrict__ c0, const int64_t *__restrict__ c1,
-                                                       const int64_t *__restrict__ c2, const int64_t *__restrict__ c3,
-                                                       const int64_t *__restrict__ c4, int hops, uint64_t n,
+struct IdColsIn {
+  const int64_t *c[GG_MAX_HOPS + 1];
+};
+
+__global__ __launch_bounds__(256) void k_result_digest(IdColsIn cols, int hops, uint64_t n,
                                                        const HtSlot *__restrict__ ht, uint64_t cap, int64_t min_idx,
                                                        unsigned long long *__restrict__ out /* [2]: digest, bad ids */) {
-  const int64_t *cols[5] = {c0, c1, c2, c3, c4};
   uint32_t sum = 0, bad = 0;
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t P = 0;
     bool ok = true;
 #pragma unroll
-    for (int j = 0; j < 5; j++) {
+    for (int j = 0; j <= GG_MAX_HOPS; j++) {
       if (j <= hops) {
-        const uint32_t d = ht_lookup(ht, cap, min_idx, cols[j][r]);
+        const uint32_t d = ht_lookup(ht, cap, min_idx, cols.c[j][r]);
         ok = ok && d != INVALID_U32;
         P = j == 0 ? (uint64_t)d : dig_leaf(dig_q(P, j - 1), d);
       }
@@ -2745,8 +2746,8 @@ __global__ __launch_bounds__(256) void k_result_digest(const int64_t *__restrict
 extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result *res, int hops, uint64_t *n_rows,
                                 uint64_t *digest) {
   if (!ctx || !csr || !res || !digest || res->ctx != ctx || csr->ctx != ctx) return GG_ERR_INVALID_ARG;
-  if (hops < res->k_min || hops > res->k_max || hops < 1 || hops > 4) {
-    set_error("gg_result_digest: hops %d outside the result's range or above 4", hops);
+  if (hops < res->k_min || hops > res->k_max || hops < 1 || hops > GG_MAX_HOPS) {
+    set_error("gg_result_digest: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
     return GG_ERR_INVALID_ARG;
   }
   ApiScope scope(ctx);
@@ -2758,10 +2759,10 @@ extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result 
   GG_HIP(hipMemsetAsync(out, 0, 2 * sizeof(unsigned long long), ctx->stream));
   if (n) {
     const uint64_t want = (n + 255) / 256, cap = (uint64_t)ctx->num_cus * 32;
-    GG_LAUNCH(ctx, "result_digest", k_result_digest, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0,
-              (const int64_t *)res->cols[hops][0], (const int64_t *)res->cols[hops][1],
-              (const int64_t *)res->cols[hops][2], (const int64_t *)res->cols[hops][3],
-              (const int64_t *)res->cols[hops][4], hops, n, (const HtSlot *)csr->ht, csr->ht_cap, csr->ht_min_idx, out);
+    IdColsIn cols{};
+    for (int c = 0; c <= hops; c++) cols.c[c] = (const int64_t *)res->cols[hops][c];
+    GG_LAUNCH(ctx, "result_digest", k_result_digest, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, cols,
+              hops, n, (const HtSlot *)csr->ht, csr->ht_cap, csr->ht_min_idx, out);
   }
   GG_HIP(hipMemcpyAsync(ctx->pin_scratch, out, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   GG_HIP(hipStreamSynchronize(ctx->stream));

@@ -434,8 +434,9 @@ class GG:
             self._chk(self.lib.gg_khop_count(self.ctx, csr.handle, p, a.size, k_min, k_max, rows))
         return list(rows)
 
-    def expand_khop_result(self, csr: Csr, k: int, sources=None) -> KhopResult:
-        """k-hop walks from `sources` (None: all vertices) materialised in HBM; nothing crosses PCIe."""
+    def expand_khop_result(self, csr: Csr, k: int, sources=None, k_min: int | None = None) -> KhopResult:
+        """k-hop walks from `sources` (None: all vertices) materialised in HBM; nothing crosses PCIe.  k_min: also the
+        tables of k_min..k - 1 hops."""
         st = KhopStats()
         res = C.c_void_p()
         if sources is None:
@@ -443,7 +444,8 @@ class GG:
         else:
             a, sp = _i64(sources)
             ns = a.size
-        self._chk(self.lib.gg_expand_khop_result(self.ctx, csr.handle, sp, ns, k, k, C.byref(st), C.byref(res)))
+        self._chk(self.lib.gg_expand_khop_result(self.ctx, csr.handle, sp, ns, k if k_min is None else k_min, k,
+                                                 C.byref(st), C.byref(res)))
         return KhopResult(self, res, self._stats_dict(st))
 
     def expand_khop_edges(self, csr: Csr, k: int, sources=None) -> "KhopResult":

@@ -226,10 +226,11 @@ int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids,
 /* Copy rows [offset, offset+max_rows) of the edge columns e1..e_hops into ecols[0..hops-1]. */
 int gg_result_fetch_edges(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *const *ecols,
                           uint32_t *n_out);
-/* Checksum of the `hops`-hop rows (1 <= hops <= 4) as they stand in HBM: every id of every row is mapped back to its
- * dense index and the rows' hashes are summed exactly as gg_khop_stats.digest[hops] sums them, so a materialising
- * expansion can be compared with the count-only expansion (and with the oracle) over ALL its rows without fetching
- * them.  Fails with GG_ERR_STATE if a row holds an id that is not a vertex of `csr`. */
+/* Checksum of the `hops`-hop rows (k_min <= hops <= k_max of the result, so up to GG_MAX_HOPS) as they stand in HBM:
+ * every id of every row is mapped back to its dense index and the rows' hashes are summed exactly as
+ * gg_khop_stats.digest[hops] sums them, so a materialising expansion can be compared with the count-only expansion (and
+ * with the oracle) over ALL its rows without fetching them.  Fails with GG_ERR_STATE if a row holds an id that is not a
+ * vertex of `csr`. */
 int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result *res, int hops, uint64_t *n_rows,
                      uint64_t *digest);
 void gg_result_destroy(gg_result *res);

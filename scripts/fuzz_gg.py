@@ -58,9 +58,12 @@ def draw_graph(rng, max_rows, max_vertices=300_000, min_frac=0.0):
     kind, vid = draw_ids(rng, V)
     V = vid.size
     E = 0 if rng.random() < 0.03 else min(log_uniform(rng, max(1, max_rows * min_frac), max_rows), max(1, V) * 4000)
-    model = rng.choice(["uniform", "powerlaw", "hubs", "sorted_src", "chain"])
+    model = rng.choice(["uniform", "powerlaw", "hubs", "sorted_src", "chain", "sparse"])
     if E == 0:
         s = d = np.zeros(0, np.int64)
+    elif model == "sparse":  # mean out-degree 1 to 2.5: walks of 5 to 8 hops stay within the walk cap
+        E = max(1, min(max_rows, int(round(V * rng.uniform(1.0, 2.5)))))
+        s, d = rng.integers(0, V, E), rng.integers(0, V, E)
     elif model == "uniform":
         s, d = rng.integers(0, V, E), rng.integers(0, V, E)
     elif model == "powerlaw":
@@ -178,7 +181,7 @@ def one_iteration(gg, orc, rng, a, note):
                         sources = np.concatenate([sources, np.array([12345678901, -77], np.int64), sources[:3]])
                     dense = dense_of(o_vid, sources)
                     w0 = np.bincount(dense, minlength=V).astype(np.float64) if V else np.zeros(0)
-                k_max = int(rng.integers(1, 5))
+                k_max = int(rng.integers(1, 9))  # (up to GG_MAX_HOPS; the cap below shortens deep draws on dense graphs)
                 est = walks(k_max, w0) if V else [0.0] * k_max
                 while k_max > 1 and sum(est[:k_max]) > 4e7:
                     k_max -= 1
@@ -280,7 +283,7 @@ def one_iteration(gg, orc, rng, a, note):
             elif op == "endpoints" and V:
                 n_src = log_uniform(rng, 1, max(1, min(V, 2000)))
                 sources = vtab[rng.integers(0, V, n_src)]
-                k = int(rng.integers(1, 4))
+                k = int(rng.integers(1, 9))
                 dense = dense_of(o_vid, sources)
                 w0 = np.bincount(dense, minlength=V).astype(np.float64)
                 if sum(walks(k, w0)) <= 2e7:

@@ -1,7 +1,8 @@
 """Generate golden vectors by running the COMPILED REFERENCE (oracle/_ref/libduckdb.so, built from
 /root/reference by oracle/Makefile `ref`) on seeded synthetic LDBC-shaped tables.
 
-    python tests/golden/make_golden.py          # rewrites tests/golden/ldbc_*.npz
+    python tests/golden/make_golden.py            # rewrites every tests/golden/ldbc_*.npz (ldbc_deep included)
+    python tests/golden/make_golden.py ldbc_deep  # rewrites only the named files
 
 The reference cannot travel to the GPU box, so the vectors are committed: each .npz holds the INPUT
 tables (person ids, knows src/dst) and the EXPECTED OUTPUT relations of the reference's SQL
@@ -48,13 +49,33 @@ def make(name, vid, src, dst, hops_rows, hops_count, bfs):
     print(name, {k: v.shape for k, v in out.items()}, os.path.getsize(path), "bytes")
 
 
-if __name__ == "__main__":
+def ldbc_tiny():
     # tiny multigraph with self-loops, duplicate edge rows and dangling endpoints
     vid, src, dst = datagen.small_graph(40, 160, 1234, dangling=6, dup_edges=12)
     make("ldbc_tiny", vid, src, dst, hops_rows=[1, 2, 3], hops_count=[1, 2, 3, 4], bfs=[(9, 1, 3), (9, 2, 6)])
+
+
+def ldbc_small():
     # LDBC-shaped (power-law, mirrored) small graph
     vid, src, dst = datagen.ldbc_knows(400, 4000, 0x5EED)
     make("ldbc_small", vid, src, dst, hops_rows=[1, 2], hops_count=[1, 2, 3], bfs=[(64, 3, 2), (64, 4, 5)])
+
+
+def ldbc_sf0_1():
     # SF0.1-sized: counts and BFS relation only
     vid, src, dst = datagen.ldbc("sf0.1")
     make("ldbc_sf0_1", vid, src, dst, hops_rows=[], hops_count=[1, 2], bfs=[(64, 5, 3)])
+
+
+def ldbc_deep():
+    # walks of up to 8 hops: a sparse multigraph (mean out-degree ~1.4, self-loops, duplicate rows, dangling ids), so
+    # that the 8-join statements stay small (a few thousand rows per hop)
+    vid, src, dst = datagen.small_graph(120, 170, 0xDEE9, dangling=5, dup_edges=12)
+    make("ldbc_deep", vid, src, dst, hops_rows=[1, 2, 3, 4, 5, 6], hops_count=[1, 2, 3, 4, 5, 6, 7, 8], bfs=[(9, 6, 8)])
+
+
+MAKERS = {f.__name__: f for f in (ldbc_tiny, ldbc_small, ldbc_sf0_1, ldbc_deep)}
+
+if __name__ == "__main__":
+    for name in sys.argv[1:] or list(MAKERS):
+        MAKERS[name]()

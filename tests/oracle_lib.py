@@ -237,3 +237,67 @@ def sort_rows(a: np.ndarray) -> np.ndarray:
     if a.shape[0] == 0:
         return a
     return a[np.lexsort(a.T[::-1])]
+
+
+def exact_walk_counts(vid, src, dst, k_max, sources=None, with_max=False):
+    """Exact number of h-hop walks (h = 0..k_max) over the edge rows whose endpoints are both vertices, in Python
+    integers: w_0 is the source multiplicity (sources None: every vertex once; otherwise how often each vertex id
+    appears in `sources`, ids that are no vertex ignored), w_h(v) = sum of w_{h-1}(u) over the rows u -> v, and
+    rows_h = sum over v of w_{h-1}(v) * outdeg(v).  No floating point anywhere (bincount weights are inexact past
+    2^53).  Returns (exact, exact mod 2^64), each a list of MAX_HOPS + 1 ints (0 beyond k_max); with_max: also the
+    largest single w_h(v) of every level h, a third such list."""
+    vid = np.asarray(vid, np.int64)
+    V = vid.size
+    order = np.argsort(vid, kind="stable")
+    keys = vid[order]
+
+    def dense(ids):
+        ids = np.asarray(ids, np.int64)
+        if V == 0:
+            return np.zeros(ids.size, np.int64), np.zeros(ids.size, bool)
+        at = np.minimum(np.searchsorted(keys, ids), V - 1)
+        return order[at], keys[at] == ids
+
+    s, ks = dense(src)
+    d, kd = dense(dst)
+    keep = ks & kd
+    s, d = s[keep], d[keep]
+    if sources is None:
+        w = np.array([1] * V, dtype=object)
+    else:
+        i, ok = dense(sources)
+        w = np.array([0] * V, dtype=object)
+        for v, c in zip(*np.unique(i[ok], return_counts=True)):
+            w[v] = int(c)
+    by_dst = np.argsort(d, kind="stable")
+    s_by, d_by = s[by_dst], d[by_dst]
+    starts = np.flatnonzero(np.r_[True, d_by[1:] != d_by[:-1]]) if d_by.size else np.zeros(0, np.int64)
+    exact = [0] * (MAX_HOPS + 1)
+    exact[0] = int(sum(w))
+    w_max = [0] * (MAX_HOPS + 1)
+    w_max[0] = int(max(w, default=0))
+    for h in range(1, k_max + 1):
+        nxt = np.array([0] * V, dtype=object)
+        if d_by.size:
+            nxt[d_by[starts]] = np.add.reduceat(w[s_by], starts)  # (object arrays: Python-int sums)
+        w = nxt
+        exact[h] = int(sum(w))
+        w_max[h] = int(max(w, default=0))
+    mod = [x % (1 << 64) for x in exact]
+    return (exact, mod, w_max) if with_max else (exact, mod)
+
+
+def endpoint_sets(off, nbr, sources_dense, k_max):
+    """CPU restatement of gg_walk_endpoints: level h = set image of level h - 1 under the oracle's CSR (walk endpoints,
+    no seen mask); bit h of masks[v] is set iff a walk of exactly h edges ends at v."""
+    V = off.size - 1
+    level = np.zeros(V, bool)
+    level[sources_dense] = True
+    masks = np.zeros(V, np.int64)
+    for h in range(1, k_max + 1):
+        nxt = np.zeros(V, bool)
+        for v in np.flatnonzero(level):
+            nxt[nbr[off[v]:off[v + 1]]] = True
+        masks |= nxt.astype(np.int64) << h
+        level = nxt
+    return masks

@@ -1023,3 +1023,91 @@ def test_randomised_statements_with_the_rules_off_and_on():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "fuzz_sql.py"), "--seed", "11", "--iterations", "300"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0 and "fuzz_sql ok: 300 statements" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+
+
+@pytest.mark.skipif(not bool(R.rules_route()), reason="plan hook shim not built")
+def test_join_chains_of_five_to_eight_edges_give_the_reference_result(monkeypatch):
+    """The planner rules take join chains of up to GG_MAX_HOPS = 8 edges.  On a sparse edge table of its own (3 420 rows,
+    mean out-degree 1.7, self-loops, parallel rows, dangling ids; ~10^5 walks of 8 edges) and a keyed vertex table:
+    count(*) and every walk position of 5- to 8-edge chains, the vertex-validated chains, a source pinned by a constant,
+    a 6-edge chain under a 1 MiB result budget (expanded part by part over source ranges) and gg_khop(..., 1, 8) all
+    give the reference's rows.  A 9-edge chain and a 5-edge chain that projects an edge payload column are longer than
+    one device operator takes (8 edges; 4 with payload columns): a hash join of the reference stays in the plan, and the
+    result is still the reference's."""
+    vid, src, dst = datagen.small_graph(2000, 3300, 0x5A1, dangling=20, dup_edges=120)
+    d = R.RefDuckDB(threads=4)
+    d.load_table("dv_in", {"id": vid})
+    d.load_table("de_in", {"a": src, "b": dst})
+    d.execute("CREATE TABLE dv (id BIGINT PRIMARY KEY)")
+    d.execute("INSERT INTO dv SELECT id FROM dv_in")
+    d.execute("CREATE TABLE de (a BIGINT NOT NULL, b BIGINT NOT NULL, w INTEGER)")
+    d.execute("INSERT INTO de SELECT a, b, CAST(a % 97 AS INTEGER) FROM de_in")
+    d.execute(f"LOAD '{EXT}'")
+
+    def chain(h, select, extra=""):  # edge-only: every id that occurs is a vertex
+        frm = ", ".join(f"de k{i}" for i in range(1, h + 1))
+        cond = " AND ".join(f"k{i}.b = k{i + 1}.a" for i in range(1, h))
+        return f"SELECT {select} FROM {frm} WHERE {cond}{extra}"
+
+    def vchain(h, select):  # every position joined with the vertex table: dangling rows drop out
+        frm = ["dv p0"] + [f"de k{i}, dv p{i}" for i in range(1, h + 1)]
+        cond = [c for i in range(1, h + 1) for c in (f"p{i - 1}.id = k{i}.a", f"k{i}.b = p{i}.id")]
+        return f"SELECT {select} FROM {', '.join(frm)} WHERE {' AND '.join(cond)}"
+
+    def positions(h):
+        return ", ".join(["k1.a"] + [f"k{i}.b" for i in range(1, h + 1)])
+
+    ids, n_out = np.unique(src, return_counts=True)
+    s = int(ids[np.argmax(n_out)])
+    try:
+        for h in (5, 6, 7, 8):
+            cpu, gpu = _both_plans(d, chain(h, "count(*)"))
+            assert cpu[0, 0] > 1000 and np.array_equal(cpu, gpu), h
+            cpu, gpu = _both_plans(d, chain(h, positions(h)))
+            assert cpu.shape[1] == h + 1 and cpu.shape[0] > 1000 and np.array_equal(sort_rows(cpu), sort_rows(gpu)), h
+            cpu, gpu = _both_plans(d, vchain(h, "count(*)"))
+            assert cpu[0, 0] > 1000 and np.array_equal(cpu, gpu), h
+            cpu, gpu = _both_plans(d, vchain(h, ", ".join(f"p{i}.id" for i in range(h + 1))))
+            assert np.array_equal(sort_rows(cpu), sort_rows(gpu)), h
+            cpu, gpu = _both_plans(d, chain(h, positions(h), f" AND k1.a = {s}"))
+            assert cpu.shape[0] > 0 and (cpu[:, 0] == s).all() and np.array_equal(sort_rows(cpu), sort_rows(gpu)), h
+            cpu, gpu = _both_plans(d, chain(h, "count(*)", f" AND k1.a = {s}"))
+            assert np.array_equal(cpu, gpu), h
+
+        # 6 edges, 1 MiB of device memory for a materialised part: the walks (7 id columns) need several parts
+        sql = chain(6, positions(6))
+        d.execute("PRAGMA disable_gpu_graph")
+        cpu = d.execute(sql)
+        assert cpu.shape[0] * 7 * 8 > 2 * (1 << 20)
+        ref6 = d.execute(vchain(6, ", ".join(f"p{i}.id" for i in range(7))))
+        d.execute("PRAGMA enable_gpu_graph")
+        monkeypatch.setenv("GG_RESULT_BUDGET_MB", "1")
+        try:
+            assert "GG_PATH" in d.explain(sql)
+            gpu = d.execute(sql)
+            parts = d.execute("SELECT v0, v1, v2, v3, v4, v5, v6 FROM gg_khop('dv', 'id', 'de', 'a', 'b', 6, 6)")
+        finally:
+            monkeypatch.delenv("GG_RESULT_BUDGET_MB")
+            d.execute("PRAGMA disable_gpu_graph")
+        assert np.array_equal(sort_rows(cpu), sort_rows(gpu))
+        assert np.array_equal(sort_rows(parts), sort_rows(ref6))
+
+        # the table function: every length from 1 to 8 in one call, against the reference's joins
+        got = d.execute("SELECT hops, v0, v1, v2, v3, v4, v5, v6, v7, v8 FROM gg_khop('dv', 'id', 'de', 'a', 'b', 1, 8)")
+        for h in range(1, 9):
+            ref = d.execute(vchain(h, ", ".join(f"p{i}.id" for i in range(h + 1))))
+            assert ref.shape[0] > 0 and np.array_equal(sort_rows(got[got[:, 0] == h][:, 1:h + 2]), sort_rows(ref)), h
+
+        # longer than one device operator takes: a hash join of the reference stays in the plan
+        for sql in (chain(9, "count(*)"), chain(9, positions(9)), chain(5, "k1.a, k3.b, k5.w"),
+                    chain(5, "count(*), sum(k5.w)")):
+            d.execute("PRAGMA enable_gpu_graph")
+            try:
+                plan = d.explain(sql)
+            finally:
+                d.execute("PRAGMA disable_gpu_graph")
+            assert "HASH_JOIN" in plan and "GG_PATH_COUNT" not in plan, plan
+            cpu, gpu = _both_plans(d, sql)
+            assert cpu.shape[0] > 0 and np.array_equal(sort_rows(cpu), sort_rows(gpu)), sql
+    finally:
+        d.close()

@@ -4,8 +4,9 @@ import numpy as np
 import pytest
 
 from duckdb_pgq_amd import datagen
+from tests import deep_graphs
 from tests import trainbenchmark as tb
-from tests.oracle_lib import sort_rows
+from tests.oracle_lib import exact_walk_counts, sort_rows
 
 
 def test_jht_chain_prepend_order(orc):
@@ -65,6 +66,57 @@ def test_khop_sources_subset_and_missing(orc):
         assert st["rows"][h] == j[h].shape[0]
         assert st["digest"][h] == orc.digest_rows(j[h])
     g.close()
+
+
+@pytest.mark.parametrize("name", deep_graphs.SMALL)
+@pytest.mark.parametrize("k_max", [5, 6, 7, 8])
+def test_khop_join_equals_csr_at_depth(orc, name, k_max):
+    """5 to 8 hops, where the GPU's deep paths run: the hash-join chain and the CSR formulation give the same rows, the
+    walk counter gives the same counts and digests on one thread and on several, and the counts are the exact walk
+    counts — every vertex as source, a source list with repeats and strangers, and a range of sources."""
+    vid, src, dst = deep_graphs.shape(name)
+    rc, g = orc.csr_build(vid, src, dst)
+    assert rc == 0
+    sources = deep_graphs.sources_of(name, vid)
+    dense = g.lookup(sources)
+    dense = dense[dense >= 0].astype(np.uint32)
+    lo, hi = vid.size // 4, vid.size - vid.size // 5
+    cases = [("all", None, {}, None), ("list", sources, {"sources_dense": dense}, sources),
+             ("range", vid[lo:hi], {"lo": lo, "hi": hi}, vid[lo:hi])]
+    for what, join_sources, sel, exact_sources in cases:
+        j = orc.khop_join(vid, src, dst, 1, k_max, sources=join_sources)
+        c = g.khop_rows(1, k_max, **sel)
+        one = g.khop(1, k_max, threads=1, **sel)
+        many = g.khop(1, k_max, threads=max(2, orc.num_threads()), **sel)
+        assert one == many, what
+        exact, _ = exact_walk_counts(vid, src, dst, k_max, sources=exact_sources)
+        for h in range(1, k_max + 1):
+            jr = vid[j[h]] if j[h].size else j[h].reshape(0, h + 1)
+            assert sort_rows(jr).tolist() == sort_rows(c[h]).tolist(), (what, h)
+            assert one["rows"][h] == j[h].shape[0] == exact[h], (what, h)
+            assert one["digest"][h] == orc.digest_rows(j[h]), (what, h)
+    g.close()
+
+
+def test_exact_walk_counts_by_hand():
+    """The exact reference on graphs whose counts are known in closed form: a 2-cycle with one row doubled (h-hop walks:
+    2^floor(h/2) from one end, 2^ceil(h/2) from the other), dangling rows, a source list with repeats and a stranger, and
+    a vertex with 300 self-loops (300^h walks, past 2^64 at 8 hops)."""
+    vid = np.array([10, 20, 30], np.int64)
+    src = np.array([10, 20, 20, 30, 99, 10], np.int64)
+    dst = np.array([20, 10, 10, 99, 30, 77], np.int64)  # 30 -> 99, 99 -> 30 and 10 -> 77 are dangling
+    exact, mod = exact_walk_counts(vid, src, dst, 8)
+    # from 10: 1, 2, 2, 4, 4, ...; from 20: 2, 2, 4, 4, ...; from 30: nothing
+    want = [3] + [2 ** (h // 2) + 2 ** ((h + 1) // 2) for h in range(1, 9)]
+    assert exact == want and mod == want
+    exact, _ = exact_walk_counts(vid, src, dst, 3, sources=np.array([10, 10, 30, 5], np.int64))
+    assert exact == [3, 2, 4, 4] + [0] * 5
+    loops = np.full(300, 7, np.int64)
+    exact, mod = exact_walk_counts(np.array([7], np.int64), loops, loops, 8)
+    assert exact == [300 ** h for h in range(9)] and mod == [300 ** h % (1 << 64) for h in range(9)]
+    assert exact[8] > 1 << 64
+    _, _, w_max = exact_walk_counts(vid, src, dst, 4, with_max=True)
+    assert w_max == [1, 2, 2, 4, 4] + [0] * 4  # (the largest w_h(v): at vertex 10 on even levels, 20 on odd ones)
 
 
 def test_duplicate_vertex_rejected(orc):
