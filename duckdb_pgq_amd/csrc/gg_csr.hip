@@ -1165,6 +1165,7 @@ struct SetStatus2 {
   unsigned long long n;            // ids compacted (from whichever table holds them)
   unsigned long long id_min_u, id_max_u;  // over the compacted ids, sign bit flipped (unsigned order = signed order)
   unsigned long long max_bucket;   // largest bucket of the bucket sort
+  uint32_t mirror[2];              // rows sampled / mirrored by the stage-0 warm-up (mirror_sample)
 };
 
 // The table is probed two slots at a time: a PAIR of adjacent 8-byte slots is one aligned 16-byte load (what a probe
@@ -1225,17 +1226,26 @@ __device__ __forceinline__ void set_insert_chain(int64_t key, uint64_t pair, set
 // contention (a vertex of degree d is in the first s of E rows with probability 1 - (1 - s/E)^2d), and the full grid
 // then probes a table whose lines are what it reads.
 constexpr int SET_ROWS = 4;
-template <int ROWS>
+// h = E / 2 > 0 (mirrored halves, gg_internal.h mirror_sample): the stage-0 warm-up samples the table, and each full-grid
+// pass is launched in both forms, of which the sample picks one (the other returns at once).  PAIRED takes row i < h
+// together with row i + h, which then usually holds the same two ids swapped: once row i's ids are in, the partner's ids
+// are looked at, and only those row i did not have go in, in a second round that a wave skips when it has none.  The
+// walk covers h pairs, then the rows from 2h on (an odd E's last row, the extra ids).
+template <int ROWS, bool PAIRED = false>
 __global__ __launch_bounds__(256) void k_set_insert2(const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
                                                      uint64_t E, const int64_t *__restrict__ extra, uint64_t n_extra,
                                                      uint64_t rows_limit, int64_t *__restrict__ set, uint64_t pairs,
                                                      uint64_t limit, uint32_t max_probes, int stage,
-                                                     SetStatus2 *__restrict__ st) {
+                                                     SetStatus2 *__restrict__ st, uint64_t h) {
   __shared__ uint32_t s_new;
   if (stage == 1 && st->overflow[0] == 0ULL) return;  // (set, if at all, by an earlier kernel: uniform over the grid)
   if (threadIdx.x == 0) s_new = 0;
   __syncthreads();
-  const uint64_t rows = E + n_extra < rows_limit ? E + n_extra : rows_limit, tile_rows = (uint64_t)ROWS * 256;
+  if (ROWS == 1 && stage == 0 && h) mirror_sample(src, dst, h, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                                                  (uint64_t)gridDim.x * blockDim.x, st->mirror);
+  if (ROWS > 1 && h && mirror_pays(st->mirror) != PAIRED) return;  // (uniform over the grid) the other form's work
+  if (!PAIRED) h = 0;  // (the warm-ups walk the first rows as they come)
+  const uint64_t rows = (E + n_extra < rows_limit ? E + n_extra : rows_limit) - h, tile_rows = (uint64_t)ROWS * 256;
   uint32_t inserted = 0, trip = 0;
   bool saw_min = false;
   for (uint64_t t0 = (uint64_t)blockIdx.x * tile_rows; t0 < rows; t0 += (uint64_t)gridDim.x * tile_rows, trip++) {
@@ -1245,11 +1255,22 @@ __global__ __launch_bounds__(256) void k_set_insert2(const int64_t *__restrict__
     int64_t key[2 * ROWS];
     set_ll2 got[2 * ROWS];
     uint64_t pair[2 * ROWS];
+    auto insert_keys = [&]() {
+#pragma unroll
+      for (int q = 0; q < 2 * ROWS; q++) {
+        pair[q] = set_home_pair(key[q], pairs);
+        if (key[q] != HT_EMPTY) got[q] = *reinterpret_cast<const set_ll2 *>(set + 2 * pair[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < 2 * ROWS; q++)
+        if (key[q] != HT_EMPTY && got[q].x != key[q] && got[q].y != key[q])
+          set_insert_chain(key[q], pair[q], got[q], set, pairs, max_probes, &st->overflow[stage], &inserted);
+    };
 #pragma unroll
     for (int j = 0; j < ROWS; j++) {
-      const uint64_t i = t0 + (uint64_t)j * 256 + threadIdx.x;
+      const uint64_t r = t0 + (uint64_t)j * 256 + threadIdx.x, i = r < h ? r : r + h;
       int64_t ka = HT_EMPTY, kb = HT_EMPTY;  // (HT_EMPTY: nothing to insert)
-      if (i >= rows) {
+      if (r >= rows) {
       } else if (i < E) {
         ka = src[i];
         kb = dst[i];
@@ -1262,15 +1283,26 @@ __global__ __launch_bounds__(256) void k_set_insert2(const int64_t *__restrict__
       key[2 * j] = ka;
       key[2 * j + 1] = kb;
     }
+    insert_keys();
+    if (h) {  // (uniform) the partners (+h) of the rows just inserted
+      bool more = false;
 #pragma unroll
-    for (int q = 0; q < 2 * ROWS; q++) {
-      pair[q] = set_home_pair(key[q], pairs);
-      if (key[q] != HT_EMPTY) got[q] = *reinterpret_cast<const set_ll2 *>(set + 2 * pair[q]);
+      for (int j = 0; j < ROWS; j++) {
+        const uint64_t r = t0 + (uint64_t)j * 256 + threadIdx.x;
+        int64_t ka = HT_EMPTY, kb = HT_EMPTY;
+        if (r < h) {
+          ka = src[r + h];
+          kb = dst[r + h];
+          saw_min = saw_min || ka == HT_EMPTY || kb == HT_EMPTY;
+          if (kb == ka || kb == key[2 * j] || kb == key[2 * j + 1]) kb = HT_EMPTY;  // (a mirror image: both in already)
+          if (ka == key[2 * j] || ka == key[2 * j + 1]) ka = HT_EMPTY;
+        }
+        key[2 * j] = ka;
+        key[2 * j + 1] = kb;
+        more = more || ka != HT_EMPTY || kb != HT_EMPTY;
+      }
+      if (__ballot(more) != 0) insert_keys();  // (uniform) a wave whose partners were all mirror images skips it
     }
-#pragma unroll
-    for (int q = 0; q < 2 * ROWS; q++)
-      if (key[q] != HT_EMPTY && got[q].x != key[q] && got[q].y != key[q])
-        set_insert_chain(key[q], pair[q], got[q], set, pairs, max_probes, &st->overflow[stage], &inserted);
     if (ROWS > 1) {
       // the full grid: new ids are counted per wavefront and tile (behind the warm-up hardly any wavefront has one), so
       // that a table about to pass its limit is noticed while it still has room
@@ -1307,6 +1339,7 @@ __global__ __launch_bounds__(256) void k_set_init2(int64_t *__restrict__ set0, u
   if (i == 0) {
     st->count[0] = st->count[1] = st->has_min = st->overflow[0] = st->overflow[1] = st->n = st->max_bucket = 0ULL;
     st->id_min_u = ~0ull;
+    st->mirror[0] = st->mirror[1] = 0u;
     st->id_max_u = 0ull;
   }
 }
@@ -1543,20 +1576,33 @@ extern "C" int gg_vertices_from_edges(gg_ctx *ctx, int keep_staged_vertices, uin
   GG_TRY(ctx->dev_alloc((void **)&start, ((size_t)B + 1) * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&base, (size_t)SET_WG * B * sizeof(uint32_t)));
   GG_HIP(hipMemsetAsync(hist, 0, (size_t)B * sizeof(uint32_t), s));
+  // the full-grid passes may take row i < h = E/2 together with its mirror candidate i + h (k_set_insert2)
+  const uint64_t h = ctx->mirror_pairs && E >= 2 ? E / 2 : 0;
   const unsigned rows_grid = (unsigned)std::min<uint64_t>((E + n_old + SET_ROWS * 256 - 1) / (SET_ROWS * 256), 256 * 16);
+  const unsigned rows_grid_h = (unsigned)std::min<uint64_t>((E - h + n_old + SET_ROWS * 256 - 1) / (SET_ROWS * 256), 256 * 16);
   // (probe runs are bounded at 64: at load <= 0.625 a longer one means the hash clusters these ids — the next stage,
   //  or the general path with its unbounded probes, takes over)
   GG_LAUNCH(ctx, "set_init", k_set_init2, dim3((unsigned)((cap0 + 255) / 256)), dim3(256), 0, set0, cap0, st);
   const uint64_t warm_rows = std::min<uint64_t>(E, cap0 + cap0 / 2);
   GG_LAUNCH(ctx, "set_warm", k_set_insert2<1>, dim3(1024), dim3(256), 0, (const int64_t *)ctx->c_src.dev,
-            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, warm_rows, set0, cap0 / 2, lim0, 64u, 0, st);
-  GG_LAUNCH(ctx, "set_insert", k_set_insert2<SET_ROWS>, dim3(rows_grid), dim3(256), 0, (const int64_t *)ctx->c_src.dev,
-            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, ~0ull, set0, cap0 / 2, lim0, 64u, 0, st);
+            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, warm_rows, set0, cap0 / 2, lim0, 64u, 0, st, h);
+  if (h)
+    GG_LAUNCH(ctx, "set_insert", (k_set_insert2<SET_ROWS, true>), dim3(rows_grid_h), dim3(256), 0,
+              (const int64_t *)ctx->c_src.dev, (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old,
+              ~0ull, set0, cap0 / 2, lim0, 64u, 0, st, h);
+  GG_LAUNCH(ctx, h ? "set_insert_unpaired" : "set_insert", k_set_insert2<SET_ROWS>, dim3(rows_grid), dim3(256), 0,
+            (const int64_t *)ctx->c_src.dev, (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old,
+            ~0ull, set0, cap0 / 2, lim0, 64u, 0, st, h);
   GG_LAUNCH(ctx, "set_init", k_set_init_stage1, dim3(2048), dim3(256), 0, set1, cap1, (const SetStatus2 *)st);
   GG_LAUNCH(ctx, "set_warm", k_set_insert2<1>, dim3(1024), dim3(256), 0, (const int64_t *)ctx->c_src.dev,
-            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, cap1 + cap1 / 2, set1, cap1 / 2, lim1, 64u, 1, st);
-  GG_LAUNCH(ctx, "set_insert", k_set_insert2<SET_ROWS>, dim3(rows_grid), dim3(256), 0, (const int64_t *)ctx->c_src.dev,
-            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, ~0ull, set1, cap1 / 2, lim1, 64u, 1, st);
+            (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, cap1 + cap1 / 2, set1, cap1 / 2, lim1, 64u, 1, st, h);
+  if (h)
+    GG_LAUNCH(ctx, "set_insert", (k_set_insert2<SET_ROWS, true>), dim3(rows_grid_h), dim3(256), 0,
+              (const int64_t *)ctx->c_src.dev, (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old,
+              ~0ull, set1, cap1 / 2, lim1, 64u, 1, st, h);
+  GG_LAUNCH(ctx, h ? "set_insert_unpaired" : "set_insert", k_set_insert2<SET_ROWS>, dim3(rows_grid), dim3(256), 0,
+            (const int64_t *)ctx->c_src.dev, (const int64_t *)ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old,
+            ~0ull, set1, cap1 / 2, lim1, 64u, 1, st, h);
   GG_LAUNCH(ctx, "set_compact", k_set_compact2, dim3((unsigned)std::min<uint64_t>((cap0 + 255) / 256, 1024)), dim3(256), 0,
             (const int64_t *)set0, cap0, 0, st, keys, keys_cap);
   GG_LAUNCH(ctx, "set_compact", k_set_compact2, dim3((unsigned)std::min<uint64_t>((cap1 + 255) / 256, 1024)), dim3(256), 0,

@@ -6,7 +6,8 @@
 // passes, six scans, two row-offset passes at SF100).  Here the dense source index u is split into a HIGH
 // part (<= 10 bits: the bucket) and a LOW part (<= 12 bits: the vertex inside the bucket):
 //
-//   D  k_densify_pairs    one read of the (src, dst) id columns; two dictionary probes per edge row
+//   D  k_densify_pairs    one read of the (src, dst) id columns; two dictionary probes per edge row, or per PAIR of
+//                         rows where row i + E/2 mirrors row i (an undirected table loaded twice: "mirrored halves")
 //                         (gg_dict.h: direct array / packed 8-byte slots / 16-byte slots); writes the dense
 //                         pair (u, v) in rowid order; counts, per tile, the bucket of u (forward) and the
 //                         bucket of v (reverse) in LDS
@@ -28,6 +29,8 @@
 #include "gg_dict.h"
 #include "gg_internal.h"
 #include "gg_runs.h"
+
+#include <type_traits>
 
 using namespace gg;
 
@@ -86,7 +89,19 @@ struct FastGeom {
   uint32_t part;      // shard builds (gg_csr_build_shard): forward rows of owned sources, reverse rows of owned
   uint32_t n_parts;   // destinations only; 1: whole graph
   uint32_t rank_atomic;  // 1: stable ranks straight from ds_add_rtn (lds_order_ok), 0: from match masks
+  uint32_t h;         // mirrored halves (whole builds): floor(E / 2), row i + h is expected to be row i reversed;
+  uint32_t nt1;       // tiles of the first half [0, h).  0 and 0: one run of tiles from row 0
 };
+
+// Rows [*r0, *r1) of a tile of D and A.  Tiles stay in rowid order; with h > 0 the first nt1 tiles cover [0, h) (the
+// last of them may be partial) and the rest start at h, so no tile straddles h and second-half tile nt1 + t holds,
+// row for row, the partners (+h) of first-half tile t.
+__device__ __forceinline__ void tile_rows(const FastGeom &g, uint64_t E, uint64_t tile, uint64_t *r0, uint64_t *r1) {
+  const bool first = tile < g.nt1;
+  const uint64_t b = first ? tile * FB_TILE : g.h + (tile - g.nt1) * FB_TILE, end = first ? g.h : E;
+  *r0 = b;
+  *r1 = b + FB_TILE < end ? b + FB_TILE : end;
+}
 // Shard builds mark, in the dense pair, the direction a row does not take part in: bit 31 of u = "source not
 // owned: no forward entry", bit 31 of v = "destination not owned: no reverse entry" (dense indices stay below 2^22).
 constexpr uint32_t FB_SKIP = 0x80000000u;
@@ -147,79 +162,121 @@ static int lds_order_ok(gg_ctx *ctx, uint32_t *ok) {
 
 // ---- D: densify + per-tile bucket histograms of both directions ---------------------------------------------
 // counts[tile * 2 nb + dir * nb + bucket]: tile-major, one contiguous 2 nb row per tile
+#ifndef GG_FB_DB
+#define GG_FB_DB 2  // (4 rows per batch need 102 VGPRs = 16 waves per CU: 731 us at SF100 against 695 with 2 and 32 waves)
+#endif
+
+// A value the compiler cannot see through: what is derived from it again is computed again, not kept in registers.
+__device__ __forceinline__ int64_t opaque(int64_t x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+
+// Dense indices of a batch of B rows: keys ks / kd -> us / vs (INVALID_U32: not a vertex).  The first probes of the
+// whole batch issue back to back, then each lookup is finished; row j of a lane whose on[j] is false issues nothing
+// (its indices are INVALID_U32).  MODE 99: the timing probe, a hash of the key instead of a lookup.  LEAN: the home
+// slot and tag of a key are computed again after its first probe returns instead of held across its latency (16
+// fewer VGPRs for a few VALU instructions).
+template <int MODE, int B, bool LEAN = false>
+__device__ __forceinline__ void probe_batch(const int64_t (&ks)[B], const int64_t (&kd)[B], const bool (&on)[B],
+                                            const HtSlot *__restrict__ ht, uint64_t cap, int64_t min_idx,
+                                            const uint32_t *__restrict__ dir, const unsigned long long *__restrict__ tab,
+                                            int64_t min_id, int64_t max_id, const PkGeom &pk, uint32_t (&us)[B],
+                                            uint32_t (&vs)[B]) {
+  if (MODE == 99) {
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      us[j] = on[j] ? (uint32_t)((uint64_t)ks[j] * DIG_GOLD >> 45) : INVALID_U32;
+      vs[j] = on[j] ? (uint32_t)((uint64_t)kd[j] * DIG_GOLD >> 45) : INVALID_U32;
+    }
+  } else if (MODE == DICT_DIRECT) {
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      us[j] = on[j] ? direct_lookup(dir, (uint64_t)min_id, ks[j]) : INVALID_U32;
+      vs[j] = on[j] ? direct_lookup(dir, (uint64_t)min_id, kd[j]) : INVALID_U32;
+    }
+  } else if (MODE == DICT_PACKED8) {
+    uint64_t hs[B], hd[B], ts[B], td[B];
+    uint4 rs[B], rd[B];
+#pragma unroll
+    for (int j = 0; j < B; j++) {  // first probes of the whole batch issue back to back
+      pk.locate(ks[j], &hs[j], &ts[j]);
+      pk.locate(kd[j], &hd[j], &td[j]);
+      rs[j] = rd[j] = make_uint4(0u, 0u, 0u, 0u);
+      if (on[j]) {
+        rs[j] = *reinterpret_cast<const uint4 *>(&tab[2 * hs[j]]);
+        rd[j] = *reinterpret_cast<const uint4 *>(&tab[2 * hd[j]]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      if (LEAN) {
+        pk.locate(opaque(ks[j]), &hs[j], &ts[j]);
+        pk.locate(opaque(kd[j]), &hd[j], &td[j]);
+      }
+      us[j] = packed_resolve(tab, pk, on[j] && ks[j] >= min_id && ks[j] <= max_id, hs[j], ts[j], rs[j]);
+      vs[j] = packed_resolve(tab, pk, on[j] && kd[j] >= min_id && kd[j] <= max_id, hd[j], td[j], rd[j]);
+    }
+  } else {
+    uint64_t ss[B], sd[B];
+    uint4 rs[B], rd[B];
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      ss[j] = ht_slot(ks[j], cap);
+      sd[j] = ht_slot(kd[j], cap);
+      rs[j] = rd[j] = make_uint4(0u, 0u, 0u, 0u);
+      if (on[j]) {
+        rs[j] = *reinterpret_cast<const uint4 *>(&ht[ss[j]]);
+        rd[j] = *reinterpret_cast<const uint4 *>(&ht[sd[j]]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      if (LEAN) {
+        ss[j] = ht_slot(opaque(ks[j]), cap);
+        sd[j] = ht_slot(opaque(kd[j]), cap);
+      }
+      us[j] = on[j] ? ht_resolve(ht, cap, min_idx, ks[j], ss[j], rs[j]) : INVALID_U32;
+      vs[j] = on[j] ? ht_resolve(ht, cap, min_idx, kd[j], sd[j], rd[j]) : INVALID_U32;
+    }
+  }
+}
+
+// rows [r0, r1): one tile
 template <int MODE>
 __device__ __forceinline__ void densify_tile(const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
-                                             uint64_t E, uint64_t base, const HtSlot *__restrict__ ht, uint64_t cap,
+                                             uint64_t r0, uint64_t r1, const HtSlot *__restrict__ ht, uint64_t cap,
                                              int64_t min_idx, const uint32_t *__restrict__ dir,
                                              const unsigned long long *__restrict__ tab,
                                              const DirectMap *__restrict__ dm, u32x2 *__restrict__ pairs,
                                              uint32_t low, uint32_t part, uint32_t n_parts, uint32_t *hist_f,
                                              uint32_t *hist_r) {
-#ifndef GG_FB_DB
-#define GG_FB_DB 2  // (4 rows per batch need 102 VGPRs = 16 waves per CU: 731 us at SF100 against 695 with 2 and 32 waves)
-#endif
   constexpr int B = GG_FB_DB;  // edge rows per batch: 2*B independent first probes in flight per lane
   static_assert(FB_ITEMS % B == 0, "a tile is a whole number of batches");
   const int64_t min_id = dm->min_id, max_id = dm->max_id;
   PkGeom pk;
   pk.load(dm);
+  // A tile that starts inside a group of 64 rows (the second half's tiles when h is not a multiple of 64) is walked from
+  // the group's start: each wave's 64 rows then are whole 128-byte lines of the id columns and of the pairs (SF100 rows
+  // shuffled, h odd: 707 us with every second-half wave straddling lines, 672 without).
+  const uint64_t al = r0 & ~(uint64_t)63;
 #pragma unroll 1
-  for (int it0 = 0; it0 < FB_ITEMS; it0 += B) {
+  for (int it0 = 0; al + (uint64_t)it0 * FB_THREADS < r1; it0 += B) {
     int64_t ks[B], kd[B];
     uint32_t us[B], vs[B];
+    bool on[B];
 #pragma unroll
     for (int j = 0; j < B; j++) {
-      const uint64_t e = base + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
-      ks[j] = e < E ? ld_stream(src + e) : HT_EMPTY;
-      kd[j] = e < E ? ld_stream(dst + e) : HT_EMPTY;
+      const uint64_t e = al + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
+      ks[j] = e >= r0 && e < r1 ? ld_stream(src + e) : HT_EMPTY;
+      kd[j] = e >= r0 && e < r1 ? ld_stream(dst + e) : HT_EMPTY;
+      on[j] = true;
     }
-    if (MODE == 99) {  // timing probe: the streams without the dictionary probes
-#pragma unroll
-      for (int j = 0; j < B; j++) {
-        us[j] = (uint32_t)((uint64_t)ks[j] * DIG_GOLD >> 45);
-        vs[j] = (uint32_t)((uint64_t)kd[j] * DIG_GOLD >> 45);
-      }
-    } else if (MODE == DICT_DIRECT) {
-#pragma unroll
-      for (int j = 0; j < B; j++) {
-        us[j] = direct_lookup(dir, (uint64_t)min_id, ks[j]);
-        vs[j] = direct_lookup(dir, (uint64_t)min_id, kd[j]);
-      }
-    } else if (MODE == DICT_PACKED8) {
-      uint64_t hs[B], hd[B], ts[B], td[B];
-      uint4 rs[B], rd[B];
-#pragma unroll
-      for (int j = 0; j < B; j++) {  // first probes of the whole batch issue back to back
-        pk.locate(ks[j], &hs[j], &ts[j]);
-        pk.locate(kd[j], &hd[j], &td[j]);
-        rs[j] = *reinterpret_cast<const uint4 *>(&tab[2 * hs[j]]);
-        rd[j] = *reinterpret_cast<const uint4 *>(&tab[2 * hd[j]]);
-      }
-#pragma unroll
-      for (int j = 0; j < B; j++) {
-        us[j] = packed_resolve(tab, pk, ks[j] >= min_id && ks[j] <= max_id, hs[j], ts[j], rs[j]);
-        vs[j] = packed_resolve(tab, pk, kd[j] >= min_id && kd[j] <= max_id, hd[j], td[j], rd[j]);
-      }
-    } else {
-      uint64_t ss[B], sd[B];
-      uint4 rs[B], rd[B];
-#pragma unroll
-      for (int j = 0; j < B; j++) {
-        ss[j] = ht_slot(ks[j], cap);
-        sd[j] = ht_slot(kd[j], cap);
-        rs[j] = *reinterpret_cast<const uint4 *>(&ht[ss[j]]);
-        rd[j] = *reinterpret_cast<const uint4 *>(&ht[sd[j]]);
-      }
-#pragma unroll
-      for (int j = 0; j < B; j++) {
-        us[j] = ht_resolve(ht, cap, min_idx, ks[j], ss[j], rs[j]);
-        vs[j] = ht_resolve(ht, cap, min_idx, kd[j], sd[j], rd[j]);
-      }
-    }
+    probe_batch<MODE, B>(ks, kd, on, ht, cap, min_idx, dir, tab, min_id, max_id, pk, us, vs);
 #pragma unroll
     for (int j = 0; j < B; j++) {
-      const uint64_t e = base + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
-      if (e >= E) continue;
+      const uint64_t e = al + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
+      if (e < r0 || e >= r1) continue;
       uint32_t u = us[j], v = vs[j];
       if (u == INVALID_U32 || v == INVALID_U32) {
         u = INVALID_U32;  // dropped: an endpoint is not a vertex (inner-join semantics)
@@ -244,34 +301,147 @@ __device__ __forceinline__ void densify_tile(const int64_t *__restrict__ src, co
   }
 }
 
+// Mirrored halves (whole builds): rows [a0, a1) of a first-half tile and their partners [b0, b1) = [a0 + h, ...)
+// of the second half, where row i + h usually is row i with source and destination swapped (an undirected edge table
+// loaded twice, the second time with the id columns exchanged).  A lane loads both rows of a pair and looks up only
+// the first one's ids; where the partner is (dst, src) of it, the partner's dense pair is (v, u) without a probe.
+// Partners that differ are looked up in a second round, which a wave skips when every one of its pairs matched.
+// Row b0 + k past a1 - a0 (row 2h of an odd E) has no partner and takes the first round itself.
+// hist: [4][nb], forward and reverse counts of the first tile, then of the second.  (Whole builds own everything.)
+template <int MODE>
+__device__ __forceinline__ void densify_tile_pairs(const int64_t *__restrict__ src, const int64_t *__restrict__ dst,
+                                                   uint64_t a0, uint64_t a1, uint64_t b0, uint64_t b1,
+                                                   const HtSlot *__restrict__ ht, uint64_t cap, int64_t min_idx,
+                                                   const uint32_t *__restrict__ dir,
+                                                   const unsigned long long *__restrict__ tab,
+                                                   const DirectMap *__restrict__ dm, u32x2 *__restrict__ pairs,
+                                                   uint32_t low, uint32_t nb, uint32_t *hist) {
+  constexpr int B = GG_FB_DB;  // row pairs per batch: the first probes of 2*B lookups in flight per lane
+  const int64_t min_id = dm->min_id, max_id = dm->max_id;
+  PkGeom pk;
+  pk.load(dm);
+#pragma unroll 1
+  for (int it0 = 0; it0 < FB_ITEMS; it0 += B) {
+    int64_t ks[B], kd[B], ps[B], pd[B];
+    uint32_t us[B], vs[B];
+    bool on[B], two[B];
+    bool any2 = false;
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      const uint64_t o = (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
+      const uint64_t a = a0 + o, b = b0 + o;
+      const bool pa = a < a1, pb = b < b1;  // (pa implies pb)
+      const uint64_t r = pa ? a : b;
+      ks[j] = pa || pb ? ld_stream(src + r) : HT_EMPTY;
+      kd[j] = pa || pb ? ld_stream(dst + r) : HT_EMPTY;
+      ps[j] = pa ? ld_stream(src + b) : HT_EMPTY;
+      pd[j] = pa ? ld_stream(dst + b) : HT_EMPTY;
+      on[j] = true;
+    }
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      two[j] = a0 + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x < a1 && (ps[j] != kd[j] || pd[j] != ks[j]);
+      any2 = any2 || two[j];
+    }
+    probe_batch<MODE, B, true>(ks, kd, on, ht, cap, min_idx, dir, tab, min_id, max_id, pk, us, vs);
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      const uint64_t o = (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
+      const uint64_t a = a0 + o, b = b0 + o;
+      const bool pa = a < a1;
+      if (!pa && b >= b1) continue;
+      uint32_t u = us[j], v = vs[j];
+      const bool keep = u != INVALID_U32 && v != INVALID_U32;
+      if (!keep) {
+        u = INVALID_U32;  // dropped: an endpoint is not a vertex (inner-join semantics)
+        v = INVALID_U32;
+      }
+      uint32_t *hf = pa ? hist : hist + 2 * nb;
+      if (keep) {
+        atomicAdd(&hf[u >> low], 1u);
+        atomicAdd(&hf[nb + (v >> low)], 1u);
+      }
+      u32x2 pr;
+      pr.x = u;
+      pr.y = v;
+      st_stream(pairs + (pa ? a : b), pr);
+      if (pa && !two[j]) {  // the mirrored partner: (v, u), forward bucket of v, reverse bucket of u
+        if (keep) {
+          atomicAdd(&hist[2 * nb + (v >> low)], 1u);
+          atomicAdd(&hist[3 * nb + (u >> low)], 1u);
+        }
+        pr.x = v;
+        pr.y = u;
+        st_stream(pairs + b, pr);
+      }
+    }
+    if (__ballot(any2) == 0) continue;  // (uniform) every pair of the wave mirrored
+    probe_batch<MODE, B, true>(ps, pd, two, ht, cap, min_idx, dir, tab, min_id, max_id, pk, us, vs);
+#pragma unroll
+    for (int j = 0; j < B; j++) {
+      if (!two[j]) continue;
+      const uint64_t b = b0 + (uint64_t)(it0 + j) * FB_THREADS + threadIdx.x;
+      uint32_t u = us[j], v = vs[j];
+      if (u == INVALID_U32 || v == INVALID_U32) {
+        u = INVALID_U32;
+        v = INVALID_U32;
+      } else {
+        atomicAdd(&hist[2 * nb + (u >> low)], 1u);
+        atomicAdd(&hist[3 * nb + (v >> low)], 1u);
+      }
+      u32x2 pr;
+      pr.x = u;
+      pr.y = v;
+      st_stream(pairs + b, pr);
+    }
+  }
+}
+
 #define GG_FB_DATTR
-template <bool PROBE = false>  // PROBE: timing probe without dictionary lookups (its output is overwritten)
+// PROBE: timing probe without dictionary lookups (its output is overwritten).  With g.h > 0 the build launches both
+// forms and the sampled rows (mirror_tally, k_dict_insert) pick the one that works, the other returns at once:
+//   PAIRED   workgroup t densifies first-half tile t (if t < g.nt1) together with its partner, second-half tile g.nt1 + t
+//   !PAIRED  workgroup t densifies tile t alone (always where g.h == 0)
+// (One kernel with both forms ran the unpaired one 9 % slower than this kernel does at SF100.)
+template <bool PROBE = false, bool PAIRED = false>
 __global__ __launch_bounds__(FB_THREADS) GG_FB_DATTR void k_densify_pairs(
     const int64_t *__restrict__ src, const int64_t *__restrict__ dst, uint64_t E, const HtSlot *__restrict__ ht,
     uint64_t cap, const BuildStatus *__restrict__ st, const uint32_t *__restrict__ dir,
     const unsigned long long *__restrict__ tab, const DirectMap *__restrict__ dm, u32x2 *__restrict__ pairs,
-    FastGeom g, uint64_t nblocks, uint32_t *__restrict__ counts) {
-  __shared__ uint32_t hist[2 << FB_MAX_HB];
+    FastGeom g, uint64_t nblocks, uint32_t *__restrict__ counts, const uint32_t *__restrict__ mirror_tally) {
+  constexpr uint32_t NH = PAIRED ? 4 : 2;  // LDS histograms: forward and reverse of each tile
+  __shared__ uint32_t hist[NH << FB_MAX_HB];
+  if (g.h && mirror_pays(mirror_tally) != PAIRED) return;  // (uniform over the grid) the other form's work
   const uint32_t nb = 1u << g.hb;
-  for (uint32_t i = threadIdx.x; i < 2 * nb; i += FB_THREADS) hist[i] = 0;
+  for (uint32_t i = threadIdx.x; i < NH * nb; i += FB_THREADS) hist[i] = 0;
   __syncthreads();
-  const uint64_t base = (uint64_t)blockIdx.x * FB_TILE;
+  const uint64_t ta = blockIdx.x, tb = PAIRED ? g.nt1 + ta : ta;
+  const bool has_a = PAIRED && ta < g.nt1;
+  uint64_t a0 = 0, a1 = 0, b0, b1;
+  if (has_a) tile_rows(g, E, ta, &a0, &a1);
+  tile_rows(g, E, tb, &b0, &b1);
+  auto run = [&](auto mode_tag) {
+    constexpr int M = decltype(mode_tag)::value;
+    if (PAIRED)
+      densify_tile_pairs<M>(src, dst, a0, a1, b0, b1, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, nb, hist);
+    else
+      densify_tile<M>(src, dst, b0, b1, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
+                      hist + nb);
+  };
   const unsigned long long mode = PROBE ? 99ULL : dm->mode;  // uniform over the grid
   if (PROBE)
-    densify_tile<99>(src, dst, E, base, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
-                          hist + nb);
+    run(std::integral_constant<int, 99>());
   else if (mode == DICT_DIRECT)
-    densify_tile<DICT_DIRECT>(src, dst, E, base, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
-                          hist + nb);
+    run(std::integral_constant<int, DICT_DIRECT>());
   else if (mode == DICT_PACKED8)
-    densify_tile<DICT_PACKED8>(src, dst, E, base, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
-                          hist + nb);
+    run(std::integral_constant<int, DICT_PACKED8>());
   else
-    densify_tile<DICT_WIDE16>(src, dst, E, base, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
-                          hist + nb);
+    run(std::integral_constant<int, DICT_WIDE16>());
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < 2 * nb; i += FB_THREADS)
-    counts[(uint64_t)blockIdx.x * 2 * nb + i] = hist[i];  // i = dir * nb + bucket
+  for (uint32_t i = threadIdx.x; i < 2 * nb; i += FB_THREADS) {  // i = dir * nb + bucket
+    if (has_a) counts[ta * 2 * nb + i] = hist[i];
+    counts[tb * 2 * nb + i] = hist[(NH - 2) * nb + i];
+  }
 }
 
 // ---- A: two stable bucket partitions from one read of the pairs ---------------------------------------------
@@ -298,7 +468,8 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
   const uint64_t chunk = (nblocks + 7) / 8;
   const uint64_t tile = (uint64_t)(blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
   if (tile >= nblocks) return;
-  const uint64_t tile_base = tile * FB_TILE;
+  uint64_t tile_base, tile_end;
+  tile_rows(g, E, tile, &tile_base, &tile_end);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t low_mask = (1u << g.low) - 1u;
 
@@ -310,7 +481,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
     u32x2 p;
     p.x = INVALID_U32;
     p.y = INVALID_U32;
-    if (idx < E) p = ld_stream(pairs + idx);
+    if (idx < tile_end) p = ld_stream(pairs + idx);
     u[it] = p.x;
     v[it] = p.y;
   }
@@ -1521,10 +1692,14 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   g.ss = vsort ? (1u << low) + 1u : sub > 6 ? 129u : 65u;
   g.part = (uint32_t)csr->part;
   g.n_parts = (uint32_t)csr->n_parts;
+  // mirrored halves: whole builds pair row i with row i + h in D (a shard's rows are filtered, the pairing would not hold)
+  const uint64_t h = ctx->mirror_pairs && csr->n_parts <= 1 && E >= 2 ? E / 2 : 0;
+  g.h = (uint32_t)h;
+  g.nt1 = (uint32_t)((h + FB_TILE - 1) / FB_TILE);
   *taken = 1;
   const uint32_t nb = 1u << hb;
   const bool rowid = ctx->keep_edge_rowid && csr->n_parts <= 1;  // a shard only serves 2-hop counting and BFS: no rowids
-  const uint64_t nblocks64 = (E + FB_TILE - 1) / FB_TILE;
+  const uint64_t nblocks64 = g.nt1 + (E - h + FB_TILE - 1) / FB_TILE;  // tiles of D and A
   const unsigned nblocks = (unsigned)nblocks64;
 
   // ---- dictionary (device-side choice) ---------------------------------------------------------------------
@@ -1553,8 +1728,9 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   while ((nblocks64 + gsz - 1) / gsz > 512) gsz *= 2;
   const uint32_t ngroups = (uint32_t)((nblocks64 + gsz - 1) / gsz);
   uint32_t *partial = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&partial, ((uint64_t)ngroups + 1) * ncol * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&partial, (((uint64_t)ngroups + 1) * ncol + 2) * sizeof(uint32_t)));
   uint32_t *coltot = partial + (uint64_t)ngroups * ncol;  // column totals, then column (= bucket) starts
+  uint32_t *mirror_tally = coltot + ncol;                   // [2] rows sampled / mirrored (h > 0), zeroed with coltot
   {
     uint64_t span = csr->ht_cap > 2 * npairs ? csr->ht_cap : 2 * npairs;
     if (span < DIRECT_MAX_RANGE) span = DIRECT_MAX_RANGE;
@@ -1562,9 +1738,10 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "dict_init", k_dict_init, dim3((unsigned)((span + 255) / 256)), dim3(256), 0,
               (const int64_t *)ctx->c_vid.dev, V, csr->ht,
               csr->ht_cap, tab, 2 * npairs, dir, dm, st, (uint32_t)csr->part, (uint32_t)csr->n_parts, csr->vid, coltot,
-              ncol);
+              ncol + 2);
     GG_LAUNCH(ctx, "dict_insert", k_dict_insert, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, csr->vid, V, csr->ht,
-              csr->ht_cap, tab, dir, dm, idx_bits, (uint32_t)npairs, st);
+              csr->ht_cap, tab, dir, dm, idx_bits, (uint32_t)npairs, st, (const int64_t *)ctx->c_src.dev,
+              (const int64_t *)ctx->c_dst.dev, h, mirror_tally);
     GG_LAUNCH(ctx, "dict_wide", k_dict_wide, dim3((unsigned)((V + 255) / 256 < 512 ? (V + 255) / 256 : 512)), dim3(256), 0,
               csr->vid, V, csr->ht,
               csr->ht_cap, (const DirectMap *)dm, st);
@@ -1579,9 +1756,17 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&counts, ncount * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&bstart, 2 * (nb + 1) * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
-  GG_LAUNCH(ctx, "densify_pairs", k_densify_pairs<false>, dim3(nblocks), dim3(FB_THREADS), 0, ctx->c_src.dev, ctx->c_dst.dev, E,
-            csr->ht, csr->ht_cap, st, (const uint32_t *)dir, (const unsigned long long *)tab, (const DirectMap *)dm,
-            pairs, g, nblocks64, counts);
+  // h > 0: the paired form (its grid: the second-half tiles) and the unpaired one; one of them returns at once.  The
+  // unpaired launch is timed as "densify_unpaired" then, so that each name's time per launch is one form's
+  if (h)
+    GG_LAUNCH(ctx, "densify_pairs", (k_densify_pairs<false, true>), dim3((unsigned)(nblocks64 - g.nt1)), dim3(FB_THREADS),
+              0, ctx->c_src.dev, ctx->c_dst.dev, E, csr->ht, csr->ht_cap, st, (const uint32_t *)dir,
+              (const unsigned long long *)tab, (const DirectMap *)dm, pairs, g, nblocks64, counts,
+              (const uint32_t *)mirror_tally);
+  GG_LAUNCH(ctx, h ? "densify_unpaired" : "densify_pairs", (k_densify_pairs<false, false>), dim3(nblocks),
+            dim3(FB_THREADS), 0, ctx->c_src.dev, ctx->c_dst.dev, E, csr->ht, csr->ht_cap, st, (const uint32_t *)dir,
+            (const unsigned long long *)tab, (const DirectMap *)dm, pairs, g, nblocks64, counts,
+            (const uint32_t *)mirror_tally);
   const uint64_t pmax = 2 * (nblocks64 + nb);  // chunks: every bucket may end in a partial one
   uint4 *part_of = nullptr;
   uint32_t *cstart = nullptr, *offs = nullptr, *substart = nullptr;

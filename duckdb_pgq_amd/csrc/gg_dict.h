@@ -288,8 +288,12 @@ static __global__ __launch_bounds__(256) void k_dict_insert(const int64_t *__res
                                                             unsigned long long *__restrict__ tab,
                                                             uint32_t *__restrict__ dir, DirectMap *__restrict__ dm,
                                                             uint32_t idx_bits, uint32_t pairs,
-                                                            BuildStatus *__restrict__ st) {
+                                                            BuildStatus *__restrict__ st, const int64_t *__restrict__ src,
+                                                            const int64_t *__restrict__ dst, uint64_t h,
+                                                            uint32_t *__restrict__ mirror_tally) {
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // (h > 0: the rows the densification would pair are sampled on the way, into a tally k_dict_init zeroed)
+  if (h) mirror_sample(src, dst, h, i, (uint64_t)gridDim.x * blockDim.x, mirror_tally);
   const long long min_id = dm->min_id, max_id = dm->max_id;  // complete: k_dict_init has finished
   uint32_t span_bits;
   const unsigned long long mode = dict_mode_of(min_id, max_id, V, idx_bits, pairs, &span_bits);

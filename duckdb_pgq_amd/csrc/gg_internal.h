@@ -178,6 +178,8 @@ struct gg_ctx {
   int rank_mode = 0;            // gg_debug_rank_mode: 0 probe the LDS atomic order once, 1 ds_add_rtn ranks, 2 match masks
   bool legacy_build = false;    // gg_debug_force_legacy_build: the multi-pass LSD build (also taken for > 2^22 vertices)
   bool keep_edge_rowid = true;  // gg_ctx_set_edge_rowid
+  bool mirror_pairs = true;     // GG_MIRROR_PAIRS=0 at context creation: whole builds and the endpoint set never pair row i
+                                // with row i + E/2 (gg_csr_fast.hip, k_set_insert2); results are the same either way
   uint64_t max_grid_tiles = 0;  // gg_debug_max_grid_tiles: workgroups per expansion launch (0: the hardware bound)
   bool profiling = false;
   std::vector<std::string> prof_names;
@@ -386,6 +388,30 @@ __device__ __forceinline__ uint32_t ht_resolve(const HtSlot *__restrict__ ht, ui
     slot = ht_next(slot, cap);
     raw = *reinterpret_cast<const uint4 *>(&ht[slot]);
   }
+}
+
+// Mirrored halves: an undirected edge table loaded twice, the second time with the id columns swapped, has row i + h =
+// (dst[i], src[i]) for h = E / 2.  Whole builds look at up to MIRROR_SAMPLES rows spread over [0, h) first (threads
+// i < n of some grid, whole waves calling): tally[0] += rows looked at, tally[1] += rows mirrored; they pair rows only if
+// mirror_pays(tally) — on a table without such pairs the paired walk costs a few percent.
+constexpr uint64_t MIRROR_SAMPLES = 4096;
+__device__ __forceinline__ void mirror_sample(const int64_t *__restrict__ src, const int64_t *__restrict__ dst, uint64_t h,
+                                              uint64_t i, uint64_t nthreads, uint32_t *__restrict__ tally) {
+  uint64_t n = h < MIRROR_SAMPLES ? h : MIRROR_SAMPLES;
+  n = n < nthreads ? n : nthreads;
+  bool m = false;
+  if (i < n) {
+    const uint64_t r = i * h / n;
+    m = src[r + h] == dst[r] && dst[r + h] == src[r];
+  }
+  const uint64_t in = __ballot(i < n), mm = __ballot(m);
+  if ((threadIdx.x & 63) == 0 && in) {
+    atomicAdd(&tally[0], (uint32_t)__popcll(in));
+    if (mm) atomicAdd(&tally[1], (uint32_t)__popcll(mm));
+  }
+}
+__device__ __forceinline__ bool mirror_pays(const uint32_t *__restrict__ tally) {  // a quarter of the rows or more
+  return tally[1] > 0 && 4ull * tally[1] >= tally[0];
 }
 
 // shard ownership of a vertex id: independent of table order, so every rank decides it alone

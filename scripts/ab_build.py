@@ -29,6 +29,10 @@ if os.environ.get("AB_SORT", "0") == "1":  # an edge table sorted by source id (
     import numpy as np
     order = np.argsort(src, kind="stable")
     src, dst = src[order], dst[order]
+if os.environ.get("AB_SHUFFLE", "0") == "1":  # rows in random order: no row i + E/2 mirrors row i
+    import numpy as np
+    order = np.random.default_rng(2).permutation(src.size)
+    src, dst = src[order], dst[order]
 out = {}
 ref = None
 for rep in range(2):

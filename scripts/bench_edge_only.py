@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: the build the reference's own 2-hop SQL takes (k1.k_person2id = k2.k_person1id: no vertex table in the
 pattern) — gg_vertices_from_edges + gg_csr_build over the staged edge table, per-kernel times from the library's events.
-    python3 scripts/bench_edge_only.py [scale] [steps]"""
+    python3 scripts/bench_edge_only.py [scale] [steps]      (AB_SHUFFLE=1: the rows in random order)"""
 import json
 import os
 import sys
@@ -17,6 +17,9 @@ import duckdb_pgq_amd as pkg  # noqa: E402
 scale = sys.argv[1] if len(sys.argv) > 1 else "sf100"
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
 vid, src, dst = pkg.datagen.ldbc(scale)
+if os.environ.get("AB_SHUFFLE", "0") == "1":  # rows in random order: no row i + E/2 mirrors row i
+    order = np.random.default_rng(2).permutation(src.size)
+    src, dst = src[order], dst[order]
 g = pkg.GG(0)
 g.set_edge_rowid(False)
 g.append_edges(src, dst)
