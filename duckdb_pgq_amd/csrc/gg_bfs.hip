@@ -497,6 +497,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
                    uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats, bool *overflow,
                    gg_result *pairs = nullptr /* filled with (source, vertex, distance) rows if non-null */) {
   constexpr int MAX_LEVEL = sizeof(DistT) == 1 ? 254 : 65534;
+  ApiScope scope(ctx);  // (per run: an 8-bit run's blocks are back in the pool before the 16-bit rerun)
   *overflow = false;
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -519,18 +520,13 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
   uint64_t *fa = nullptr, *fb = nullptr, *fnext = nullptr, *seen = nullptr, *dist8 = nullptr;
   BfsStep *steps = nullptr;            // steps[L]: the frontier level L produced (L = 0: the seed)
   constexpr size_t STEP_SLOTS = (size_t)MAX_LEVEL + 2;
-  GG_TRY(ctx->dev_alloc((void **)&ids_dev, GG_BFS_LANES * sizeof(int64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&src_dense, GG_BFS_LANES * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&fa, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&fb, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&fnext, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&seen, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&dist8, V * 64 * sizeof(DistT)));
   GG_TRY(ctx->dev_alloc((void **)&steps, STEP_SLOTS * sizeof(BfsStep)));
-
-  // (pageable source: the runtime stages it before the call returns; no synchronisation needed here)
-  GG_HIP(hipMemcpyAsync(ids_dev, src_ids, (size_t)n_src * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  GG_TRY(lookup_ids(ctx, csr, ids_dev, (uint64_t)n_src, src_dense));
+  GG_TRY(upload_ids(ctx, csr, src_ids, (uint64_t)n_src, &src_dense, &ids_dev));  // (the level loop synchronises)
   {
     const uint64_t dist_words = V * 64 * sizeof(DistT) / sizeof(uint64_t);
     const uint64_t steps_words = STEP_SLOTS * sizeof(BfsStep) / sizeof(uint64_t);
@@ -599,81 +595,44 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
   }
   st.reached_pairs = reached;
 
-  int rc = GG_OK;
   if (pairs && !*overflow && reached) {
     if (reached >= (uint64_t)INVALID_U32) {
       set_error("gg_bfs64_pairs: more than 2^32-2 reached pairs in one batch");
-      rc = GG_ERR_TOO_LARGE;
+      return GG_ERR_TOO_LARGE;
     }
     const bool packed = pairs->k_max == 0;  // one packed word per row (table 0) instead of three ids (table 2)
     const int table = packed ? 0 : 2, ncols = packed ? 1 : 3;
     uint32_t *counts = nullptr;
-    if (rc == GG_OK) rc = ctx->dev_alloc((void **)&counts, V * sizeof(uint32_t));
-    for (int c = 0; c < ncols && rc == GG_OK; c++)
-      rc = ctx->dev_alloc((void **)&pairs->cols[table][c], reached * sizeof(int64_t));
-    if (rc == GG_OK) {
-      hipLaunchKernelGGL((k_bfs_pairs_count<DistT>), dim3(vgrid), dim3(256), 0, s, (const DistT *)dist8, V, n_src, counts);
-      rc = scan_exclusive_u32(ctx, counts, counts, V, nullptr);
-    }
-    if (rc == GG_OK) {
-      if (packed)
-        hipLaunchKernelGGL((k_bfs_pairs_fill_packed<DistT>), dim3(vgrid), dim3(256), 0, s, (const DistT *)dist8, V, n_src,
-                           (const uint32_t *)counts, pairs->cols[0][0]);
-      else
-        hipLaunchKernelGGL((k_bfs_pairs_fill<DistT>), dim3(vgrid), dim3(256), 0, s, (const DistT *)dist8, V, n_src,
-                           (const uint32_t *)counts, (const int64_t *)ids_dev, (const int64_t *)csr->vid,
-                           pairs->cols[2][0], pairs->cols[2][1], pairs->cols[2][2]);
-      if (hipGetLastError() != hipSuccess) rc = GG_ERR_HIP;
-    }
-    if (rc == GG_OK) rc = scan_error_fetch(ctx);
-    if (rc == GG_OK && hipStreamSynchronize(s) != hipSuccess) rc = GG_ERR_HIP;
-    if (rc == GG_OK) rc = scan_error_test(ctx);
-    if (rc == GG_OK) {
-      for (int c = 0; c < ncols; c++) ctx->keep(pairs->cols[table][c]);
-      pairs->rows[table] = reached;
-    }
-    ctx->dev_free(counts);
+    GG_TRY(ctx->dev_alloc((void **)&counts, V * sizeof(uint32_t)));
+    for (int c = 0; c < ncols; c++) GG_TRY(ctx->dev_alloc((void **)&pairs->cols[table][c], reached * sizeof(int64_t)));
+    GG_LAUNCH(ctx, "bfs_pairs_count", (k_bfs_pairs_count<DistT>), dim3(vgrid), dim3(256), 0, (const DistT *)dist8, V, n_src,
+              counts);
+    GG_TRY(scan_exclusive_u32(ctx, counts, counts, V, nullptr));
+    if (packed)
+      GG_LAUNCH(ctx, "bfs_pairs_fill_packed", (k_bfs_pairs_fill_packed<DistT>), dim3(vgrid), dim3(256), 0,
+                (const DistT *)dist8, V, n_src, (const uint32_t *)counts, pairs->cols[0][0]);
+    else
+      GG_LAUNCH(ctx, "bfs_pairs_fill", (k_bfs_pairs_fill<DistT>), dim3(vgrid), dim3(256), 0, (const DistT *)dist8, V, n_src,
+                (const uint32_t *)counts, (const int64_t *)ids_dev, (const int64_t *)csr->vid, pairs->cols[2][0],
+                pairs->cols[2][1], pairs->cols[2][2]);
+    GG_TRY(scan_error_fetch(ctx));
+    GG_HIP(hipStreamSynchronize(s));
+    GG_TRY(scan_error_test(ctx));
+    for (int c = 0; c < ncols; c++) ctx->keep(pairs->cols[table][c]);
+    pairs->rows[table] = reached;
   }
   if (out_dist && !*overflow) {
-    int64_t *dst_dev = nullptr;
     uint32_t *dst_dense = nullptr;
     int32_t *out_dev = nullptr;
-    rc = ctx->dev_alloc((void **)&out_dev, (uint64_t)n_src * n_out * sizeof(int32_t));
-    if (rc == GG_OK && dst_ids) {
-      rc = ctx->dev_alloc((void **)&dst_dev, n_dst * sizeof(int64_t));
-      if (rc == GG_OK) rc = ctx->dev_alloc((void **)&dst_dense, n_dst * sizeof(uint32_t));
-      if (rc == GG_OK) {
-        hipError_t e = hipMemcpyAsync(dst_dev, dst_ids, n_dst * sizeof(int64_t), hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) rc = GG_ERR_HIP;
-      }
-      if (rc == GG_OK) rc = lookup_ids(ctx, csr, dst_dev, n_dst, dst_dense);
-    }
-    if (rc == GG_OK) {
-      hipLaunchKernelGGL((k_bfs_widen<DistT>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, (const DistT *)dist8, V,
-                         n_src, (const uint32_t *)dst_dense, n_out, out_dev);
-      hipError_t e =
-          hipMemcpyAsync(out_dist, out_dev, (uint64_t)n_src * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);
-      if (e != hipSuccess) {
-        set_error("gg_bfs64: result copy failed: %s", hipGetErrorString(e));
-        rc = GG_ERR_HIP;
-      }
-    }
-    ctx->dev_free(dst_dev);
-    ctx->dev_free(dst_dense);
-    ctx->dev_free(out_dev);
+    GG_TRY(ctx->dev_alloc((void **)&out_dev, (uint64_t)n_src * n_out * sizeof(int32_t)));
+    if (dst_ids) GG_TRY(upload_ids(ctx, csr, dst_ids, n_dst, &dst_dense));
+    GG_LAUNCH(ctx, "bfs_widen", (k_bfs_widen<DistT>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0,
+              (const DistT *)dist8, V, n_src, (const uint32_t *)dst_dense, n_out, out_dev);
+    GG_HIP(hipMemcpyAsync(out_dist, out_dev, (uint64_t)n_src * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    GG_HIP(hipStreamSynchronize(s));
   }
-  ctx->dev_free(ids_dev);
-  ctx->dev_free(src_dense);
-  ctx->dev_free(fnext);
-  ctx->dev_free(fa);
-  ctx->dev_free(fb);
-  ctx->dev_free(seen);
-  ctx->dev_free(dist8);
-  ctx->dev_free(steps);
   if (stats) *stats = st;
-  return rc;
+  return GG_OK;
 }
 
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
@@ -703,15 +662,9 @@ static int bfs_pairs(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int
   if (!out_result) return GG_ERR_INVALID_ARG;
   *out_result = nullptr;
   if (!ctx) return GG_ERR_INVALID_ARG;
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = res->k_max = table;  // table 2: three id columns; table 0: one packed column
-  int rc = bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, res);
-  if (rc != GG_OK) {
-    gg_result_destroy(res);
-    return rc;
-  }
-  *out_result = res;
+  ResultOwner res = make_result(ctx, table, table);  // table 2: three id columns; table 0: one packed column
+  GG_TRY(bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, res.get()));
+  *out_result = res.release();
   return GG_OK;
 }
 
@@ -719,7 +672,6 @@ static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
                         gg_result *pairs) {
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
-  ApiScope scope(ctx);
   if (!ctx || !csr || csr->ctx != ctx || n_src < 0 || n_src > GG_BFS_LANES || (n_src && !src_ids) ||
       (n_dst && !dst_ids)) {
     set_error("gg_bfs64: bad argument (n_src must be 0..%d)", GG_BFS_LANES);
@@ -729,19 +681,16 @@ static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids
     set_error("gg_bfs64 needs a whole CSR, not a shard");
     return GG_ERR_STATE;
   }
-  // one byte per (vertex, lane) covers 254 levels; deeper searches rerun with two-byte cells
+  // one byte per (vertex, lane) covers 254 levels; deeper searches (max_hops < 0 or > 254 only) rerun with two-byte cells
   bool overflow = false;
-  if (max_hops < 0 || max_hops > 254) {
-    int rc = bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs);
-    if (rc != GG_OK || !overflow) return rc;
-    rc = bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs);
-    if (rc == GG_OK && overflow) {
-      set_error("gg_bfs64: search deeper than 65534 levels is not supported");
-      return GG_ERR_TOO_LARGE;
-    }
-    return rc;
+  GG_TRY(bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs));
+  if (!overflow) return GG_OK;
+  GG_TRY(bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs));
+  if (overflow) {
+    set_error("gg_bfs64: search deeper than 65534 levels is not supported");
+    return GG_ERR_TOO_LARGE;
   }
-  return bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs);
+  return GG_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -907,29 +856,16 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const uint64_t V = csr->V ? csr->V : 1;
-  gg_bfs_run *run = new gg_bfs_run();
+  Owner<gg_bfs_run, gg_bfs_sharded_end> run(new gg_bfs_run());
   run->ctx = ctx;
   run->csr = csr;
   run->n_src = n_src;
-  struct Guard {
-    gg_bfs_run *r;
-    bool armed = true;
-    ~Guard() {
-      if (armed) gg_bfs_sharded_end(r);
-    }
-  } guard{run};
-  uint32_t *src_dense = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&run->ids_dev, GG_BFS_LANES * sizeof(int64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&src_dense, GG_BFS_LANES * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->front, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->next, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->seen, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->dist8, V * 64 * sizeof(uint8_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->acc, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->lv, 2 * sizeof(BfsLevel)));
-  for (void *p : {(void *)run->ids_dev, (void *)run->front, (void *)run->next, (void *)run->seen, (void *)run->dist8,
-                  (void *)run->acc, (void *)run->lv})
-    ctx->keep(p);
   if (csr->V && csr->n_parts > 1) {  // (a whole CSR pushes along its forward rows)
     if (!csr->rrow) {
       set_error("gg_bfs_sharded: the shard has no reverse COO column");
@@ -937,9 +873,11 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
     }
     GG_TRY(ensure_push_in(ctx, csr));
   }
-  if (n_src) GG_HIP(hipMemcpyAsync(run->ids_dev, src_ids, (size_t)n_src * sizeof(int64_t), hipMemcpyHostToDevice, s));
-  GG_HIP(hipStreamSynchronize(s));
-  GG_TRY(lookup_ids(ctx, csr, run->ids_dev, (uint64_t)n_src, src_dense));
+  uint32_t *src_dense = nullptr;
+  GG_TRY(upload_ids(ctx, csr, src_ids, (uint64_t)n_src, &src_dense, &run->ids_dev));
+  for (void *p : {(void *)run->ids_dev, (void *)run->front, (void *)run->next, (void *)run->seen, (void *)run->dist8,
+                  (void *)run->acc, (void *)run->lv})
+    ctx->keep(p);
   GG_HIP(hipMemsetAsync(run->front, 0, V * sizeof(uint64_t), s));
   GG_HIP(hipMemsetAsync(run->next, 0, V * sizeof(uint64_t), s));
   GG_HIP(hipMemsetAsync(run->seen, 0, V * sizeof(uint64_t), s));
@@ -950,8 +888,7 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
     GG_LAUNCH(ctx, "bfs_seed", (k_bfs_seed<uint8_t>), dim3(1), dim3(64), 0, src_dense, n_src, csr->off, run->front,
               run->seen, run->dist8, run->lv, (const int64_t *)csr->vid, (uint32_t)csr->part, (uint32_t)csr->n_parts);
   GG_HIP(hipStreamSynchronize(s));
-  guard.armed = false;
-  *out = run;
+  *out = run.release();
   return GG_OK;
 }
 
@@ -1038,16 +975,7 @@ extern "C" int gg_bfs_sharded_pairs(gg_bfs_run *run, gg_result **out_result) {
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const uint64_t V = csr->V;
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = res->k_max = 2;
-  struct Guard {
-    gg_result *r;
-    bool armed = true;
-    ~Guard() {
-      if (armed) gg_result_destroy(r);
-    }
-  } guard{res};
+  ResultOwner res = make_result(ctx, 2, 2);
   if (V) {
     uint32_t *counts = nullptr;
     uint64_t *total = nullptr;
@@ -1072,8 +1000,7 @@ extern "C" int gg_bfs_sharded_pairs(gg_bfs_run *run, gg_result **out_result) {
     }
   }
   GG_HIP(hipStreamSynchronize(s));
-  guard.armed = false;
-  *out_result = res;
+  *out_result = res.release();
   return GG_OK;
 }
 
@@ -1094,29 +1021,16 @@ extern "C" int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const uint64_t V = csr->V;
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = res->k_max = 1;  // table 1: (vertex id, mask of walk lengths)
-  struct Guard {  // hand the result out only on success
-    gg_result *r;
-    ~Guard() {
-      if (r) gg_result_destroy(r);
-    }
-  } guard{res};
+  ResultOwner res = make_result(ctx, 1, 1);  // table 1: (vertex id, mask of walk lengths)
   if (V && n_src) {
     const uint64_t words = (V + 31) / 32;
-    int64_t *ids_dev = nullptr;
     uint32_t *dense = nullptr, *bits = nullptr, *counts = nullptr;
     uint64_t *total = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&ids_dev, n_src * sizeof(int64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&dense, n_src * sizeof(uint32_t)));
     GG_TRY(ctx->dev_alloc((void **)&bits, (uint64_t)(k_max + 1) * words * sizeof(uint32_t)));
     GG_TRY(ctx->dev_alloc((void **)&counts, V * sizeof(uint32_t)));
     GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
-    GG_HIP(hipMemcpyAsync(ids_dev, src_ids, n_src * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    GG_HIP(hipStreamSynchronize(s));  // src_ids is caller memory: consumed before return
     GG_HIP(hipMemsetAsync(bits, 0, (uint64_t)(k_max + 1) * words * sizeof(uint32_t), s));
-    GG_TRY(lookup_ids(ctx, csr, ids_dev, n_src, dense));
+    GG_TRY(upload_ids(ctx, csr, src_ids, n_src, &dense));
     GG_LAUNCH(ctx, "set_seed", k_set_seed, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, (const uint32_t *)dense, n_src,
               bits);
     const unsigned vgrid = (unsigned)((V + 255) / 256), xgrid = (unsigned)((V * 16 + 255) / 256);
@@ -1140,7 +1054,6 @@ extern "C" int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
       res->rows[1] = rows;
     }
   }
-  guard.r = nullptr;
-  *out_result = res;
+  *out_result = res.release();
   return GG_OK;
 }

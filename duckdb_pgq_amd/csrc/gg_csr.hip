@@ -538,8 +538,9 @@ namespace {
 
 // Stable sort of (key, a[, b]) by key < 2^key_bits.  Pass 0 input is (key0, a0, b generated from the
 // position when gen_b); counts of pass 0 may already be available (fused producer) in counts0.
-// Outputs land in (key_out, a_out, b_out).  n: host bound (grid sizing); n_dev: actual count for
-// passes >= 1 (null: n is exact everywhere).  *total_dev receives the number of valid elements.
+// Outputs land in (key_out, a_out, b_out).  n: host bound (grid sizing); *total_dev: the element count on the device,
+// read by pass 0's histogram and overwritten with the number of valid elements (null: n is exact, a slot of the sort's
+// own holds it).
 struct RadixIO {
   const uint32_t *key0, *a0, *b0;
   uint32_t *key_out, *a_out, *b_out;
@@ -548,7 +549,7 @@ struct RadixIO {
 int radix_sort_stable(gg_ctx *ctx, const RadixIO &io, uint64_t n, bool has_b, bool gen_b, int key_bits,
                       uint32_t *counts0 /* nullable: pass-0 histogram already computed */, int bits0,
                       unsigned long long *total_dev /* nullable: where pass 0's valid count goes / comes from */,
-                      bool n_exact, const uint32_t *tile_valid0 = nullptr /* pass-0 input is tile-compacted */) {
+                      const uint32_t *tile_valid0 = nullptr /* pass-0 input is tile-compacted */) {
   if (n == 0) return GG_OK;
   int passes = (key_bits + RB_MAX_BITS - 1) / RB_MAX_BITS;
   if (passes < 1) passes = 1;
@@ -562,8 +563,10 @@ int radix_sort_stable(gg_ctx *ctx, const RadixIO &io, uint64_t n, bool has_b, bo
     if (has_b) GG_TRY(ctx->dev_alloc((void **)&bbuf[i], n * sizeof(uint32_t)));
   }
   unsigned long long *own_total = nullptr;
-  if (!total_dev) {
+  if (!total_dev) {  // pass 0's histogram reads n from the device: a slot of our own, seeded without host memory
     GG_TRY(ctx->dev_alloc((void **)&own_total, sizeof(unsigned long long)));
+    GG_HIP(hipMemsetD32Async((hipDeviceptr_t)own_total, (int)(uint32_t)n, 1, ctx->stream));
+    GG_HIP(hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)own_total + 1), (int)(uint32_t)(n >> 32), 1, ctx->stream));
     total_dev = own_total;
   }
   const uint32_t *kin = io.key0, *ain = io.a0, *bin = io.b0;
@@ -609,7 +612,6 @@ int radix_sort_stable(gg_ctx *ctx, const RadixIO &io, uint64_t n, bool has_b, bo
     ain = aout;
     bin = bout;
   }
-  (void)n_exact;
   for (int i = 0; i < 2; i++) {
     ctx->dev_free(kbuf[i]);
     ctx->dev_free(abuf[i]);
@@ -625,27 +627,13 @@ namespace gg {
 // (key, value) pairs sorted by key < 2^key_bits, stable (gg_internal.h): the LSD passes of the multi-pass build
 int sort_pairs_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *val, uint64_t n, int key_bits, uint32_t *key_out,
                       uint32_t *val_out) {
-  if (n == 0) return GG_OK;
-  unsigned long long *tot = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&tot, sizeof(unsigned long long)));
-  const unsigned long long n_host = n;  // (pageable source: staged by the runtime before the call returns)
-  GG_HIP(hipMemcpyAsync(tot, &n_host, sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   RadixIO io{key, val, nullptr, key_out, val_out, nullptr};
-  GG_TRY(radix_sort_stable(ctx, io, n, false, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, tot, true));
-  ctx->dev_free(tot);
-  return GG_OK;
+  return radix_sort_stable(ctx, io, n, false, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, nullptr);
 }
 int sort_triples_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, const uint32_t *b, uint64_t n, int key_bits,
                         uint32_t *key_out, uint32_t *a_out, uint32_t *b_out) {
-  if (n == 0) return GG_OK;
-  unsigned long long *tot = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&tot, sizeof(unsigned long long)));
-  const unsigned long long n_host = n;
-  GG_HIP(hipMemcpyAsync(tot, &n_host, sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
   RadixIO io{key, a, b, key_out, a_out, b_out};
-  GG_TRY(radix_sort_stable(ctx, io, n, true, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, tot, true));
-  ctx->dev_free(tot);
-  return GG_OK;
+  return radix_sort_stable(ctx, io, n, true, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, nullptr);
 }
 }  // namespace gg
 
@@ -682,19 +670,13 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   const uint64_t V = ctx->n_vertices, E = ctx->n_edges;
   hipStream_t s = ctx->stream;
 
-  gg_csr *csr = new gg_csr();
+  Owner<gg_csr, gg_csr_destroy> owner(new gg_csr());  // (frees the half-built CSR on any early return)
+  gg_csr *csr = owner.get();
   csr->ctx = ctx;
   csr->V = V;
   csr->E_cap = E;
   csr->part = part;
   csr->n_parts = n_parts;
-  struct Guard {  // frees the half-built CSR on any early return
-    gg_csr *c;
-    bool armed = true;
-    ~Guard() {
-      if (armed) gg_csr_destroy(c);
-    }
-  } guard{csr};
 
   // ---- id hash table --------------------------------------------------------------------
   // load factor ~0.7: a smaller table keeps more of it in the 4 MiB per-XCD L2 (probes are random)
@@ -769,10 +751,10 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
                 (uint32_t)bits0, nblocks64, counts0, counts0r, tvf, tvr);
       // a shard only serves all-source 2-hop counting: no edge-rowid payload (csr->epos stays unset)
       RadixIO io{su, dv, nullptr, csr->row, csr->nbr, nullptr};
-      GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, counts0, bits0, kept_dev, false, tvf));
+      GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, counts0, bits0, kept_dev, tvf));
       // reverse CSR of the edges whose DESTINATION this shard owns (rowid order inside a row)
       RadixIO ior{rk, rv, nullptr, rkey_sorted, csr->rnbr, nullptr};
-      GG_TRY(radix_sort_stable(ctx, ior, E, false, false, key_bits, counts0r, bits0, kept_rev_dev, false, tvr));
+      GG_TRY(radix_sort_stable(ctx, ior, E, false, false, key_bits, counts0r, bits0, kept_rev_dev, tvr));
     } else {
       // direct-address dictionary for dense ids (decided on the device; see DirectMap)
       DirectMap *dm = nullptr;
@@ -797,7 +779,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
       // ---- stable radix scatter by source: (u, v, position) -> (row, nbr, epos) ------------------------
       const bool rowid = ctx->keep_edge_rowid;
       RadixIO io{su, dv, nullptr, csr->row, csr->nbr, rowid ? csr->epos : nullptr};
-      GG_TRY(radix_sort_stable(ctx, io, E, rowid, rowid, key_bits, counts0, bits0, kept_dev, false));
+      GG_TRY(radix_sort_stable(ctx, io, E, rowid, rowid, key_bits, counts0, bits0, kept_dev));
     }
     ctx->dev_free(tvf);
     ctx->dev_free(tvr);
@@ -869,8 +851,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   for (void *p : {(void *)csr->off, (void *)csr->nbr, (void *)csr->row, (void *)csr->epos, (void *)csr->eid,
                   (void *)csr->vid, (void *)csr->ht, (void *)csr->roff, (void *)csr->rnbr, (void *)csr->rrow})
     ctx->keep(p);
-  guard.armed = false;
-  *out = csr;
+  *out = owner.release();
   return GG_OK;
 }
 
@@ -929,13 +910,7 @@ int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
   if (E) {
     const int key_bits = ceil_log2_u64(V < 2 ? 2 : V);
     RadixIO io{csr->nbr, csr->row, nullptr, rkey, csr->rnbr, nullptr};
-    // pass 0 needs a device-side n for its histogram: reuse total slot seeded with E
-    unsigned long long *tot = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&tot, sizeof(unsigned long long)));
-    const unsigned long long e_host = E;  // pageable source: staged by the runtime before the call returns
-    GG_HIP(hipMemcpyAsync(tot, &e_host, sizeof(unsigned long long), hipMemcpyHostToDevice, ctx->stream));
-    GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, nullptr, 0, tot, true));
-    ctx->dev_free(tot);
+    GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, nullptr, 0, nullptr));
   }
   GG_LAUNCH(ctx, "row_offsets", k_row_offsets, dim3((unsigned)(((E ? E : 1) + 1023) / 1024)), dim3(256), 0, rkey, E,
             (const unsigned long long *)nullptr, V, csr->roff, (const unsigned long long *)ctx->dev_err);
@@ -1129,7 +1104,7 @@ static int vertices_from_edges_general(gg_ctx *ctx, int keep_staged_vertices, ui
       // pass 0 of a sort reads its element count from the device: `cursor` holds exactly n
       GG_HIP(hipMemcpyAsync(tot, cursor, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
       RadixIO io{key, lo[cur], hi[cur], key_sorted, lo[cur ^ 1], hi[cur ^ 1]};
-      GG_TRY(radix_sort_stable(ctx, io, n, true, false, round == 2 ? 20 : 22, nullptr, 0, tot, true));
+      GG_TRY(radix_sort_stable(ctx, io, n, true, false, round == 2 ? 20 : 22, nullptr, 0, tot));
       cur ^= 1;
     }
     GG_LAUNCH(ctx, "set_emit", k_set_emit, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lo[cur], hi[cur], n,

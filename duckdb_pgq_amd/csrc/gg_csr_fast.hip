@@ -148,6 +148,7 @@ static int lds_order_ok(gg_ctx *ctx, uint32_t *ok) {
     uint32_t *bad = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&bad, sizeof(uint32_t)));
     GG_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), ctx->stream));
+    // (bare launch, not GG_LAUNCH: a launch that fails is an answer here, not an error)
     hipLaunchKernelGGL(k_lds_order_probe, dim3(256), dim3(512), 0, ctx->stream, 256u, bad);
     const bool launched = hipGetLastError() == hipSuccess;  // a probe that did not run proves nothing: match masks
     uint32_t h = 1;

@@ -77,16 +77,7 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t n_rows = res->rows[hops];
   const int ncols = hops + 1;
-  gg_result *o = new gg_result();
-  o->ctx = ctx;
-  o->k_min = o->k_max = hops + 1;  // the table with hops+2 columns: (w, v0..vh)
-  struct Guard {
-    gg_result *r;
-    bool armed = true;
-    ~Guard() {
-      if (armed) gg_result_destroy(r);
-    }
-  } guard{o};
+  ResultOwner o = make_result(ctx, hops + 1, hops + 1);  // the table with hops+2 columns: (w, v0..vh)
   RowCols in;
   for (int c = 0; c < ncols; c++) in.c[c] = res->cols[hops][c];
   OutCols oc;
@@ -117,8 +108,6 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
                 filter->ht_cap, filter->ht_min_idx, filter->off, filter->nbr, filter->vid,
                 (uint64_t *)nullptr, (const uint64_t *)counts, oc);
     GG_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->dev_free(counts);
-    ctx->dev_free(tot);
   } else {
     for (int c = 0; c <= ncols; c++) {
       GG_TRY(ctx->dev_alloc((void **)&o->cols[hops + 1][c], sizeof(int64_t)));
@@ -126,7 +115,6 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
     }
   }
   o->rows[hops + 1] = total;
-  guard.armed = false;
-  *out = o;
+  *out = o.release();
   return GG_OK;
 }

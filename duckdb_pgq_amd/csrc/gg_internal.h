@@ -8,6 +8,7 @@
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -280,6 +281,11 @@ namespace gg {
 // Put one at the top of every C-ABI entry point that allocates: whatever the call allocated from the pool
 // and neither freed nor handed to a long-lived object (gg_ctx::keep) goes back to the pool when the call
 // returns — including every early error return.
+//
+// The rules of an entry point: every launch goes through GG_LAUNCH; caller ids reach the device through upload_ids;
+// a result (or any other C-ABI object) under construction is held by an Owner and release()d only on success;
+// failures return at once through GG_TRY / GG_HIP, and the ApiScope frees the pool blocks.  An explicit dev_free is
+// only worth writing where it lowers the pool's peak, i.e. before a later allocation in the same call.
 struct ApiScope {
   gg_ctx *ctx;
   uint64_t mark;
@@ -291,6 +297,23 @@ struct ApiScope {
       if (b.in_use && !b.keep && b.serial >= mark) b.in_use = false;
   }
 };
+
+// Owns a C-ABI object under construction: Destroy runs on every early return unless the object was release()d.
+template <typename T, void (*Destroy)(T *)>
+struct DestroyWith {
+  void operator()(T *p) const { Destroy(p); }
+};
+template <typename T, void (*Destroy)(T *)>
+using Owner = std::unique_ptr<T, DestroyWith<T, Destroy>>;
+using ResultOwner = Owner<gg_result, gg_result_destroy>;
+
+inline ResultOwner make_result(gg_ctx *ctx, int k_min, int k_max) {
+  ResultOwner res(new gg_result());
+  res->ctx = ctx;
+  res->k_min = k_min;
+  res->k_max = k_max;
+  return res;
+}
 
 // RAII-free helper: launch wrapper that records events when profiling is on.
 // (A launch of 2^32 threads or more is not refused by the runtime: the global size WRAPS and the kernel silently covers
@@ -321,8 +344,14 @@ int scan_error_test(gg_ctx *ctx);
 // exclusive scan of n uint64 values
 int scan_exclusive_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_dev);
 
-// id -> dense lookup of n host ids; writes dense (uint32, INVALID_U32 if absent) to out_dev
+// id -> dense lookup of n device ids; writes dense (uint32, INVALID_U32 if absent) to out_dev
 int lookup_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids_dev, uint64_t n, uint32_t *out_dev);
+// Caller ids -> dense indices: allocates *dense (and the device copy of the ids, handed back in *ids_dev if that is
+// non-null) from the pool, n entries but at least one, and enqueues the copy of `ids` and lookup_ids.  It does NOT
+// synchronise: `ids` is caller memory, and every entry point that calls this reaches a stream synchronisation before
+// it returns, so the copy has read it by then.
+int upload_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64_t n, uint32_t **dense,
+               int64_t **ids_dev = nullptr);
 // n (key, value) pairs of u32 sorted by key < 2^key_bits, stably, into (key_out, val_out) — device arrays (gg_csr.hip)
 int sort_pairs_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *val, uint64_t n, int key_bits, uint32_t *key_out,
                       uint32_t *val_out);

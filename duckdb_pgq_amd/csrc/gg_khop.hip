@@ -1173,20 +1173,20 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     const uint32_t *keys = cur.fv;
     if (cur_ident) {
       GG_TRY(ctx->dev_alloc((void **)&fv, nf * sizeof(uint32_t)));
-      hipLaunchKernelGGL(k_front_ident, dim3(fgrid), dim3(256), 0, ctx->stream, lo, nf, fv, qlo, qhi);
+      GG_LAUNCH(ctx, "front_ident", k_front_ident, dim3(fgrid), dim3(256), 0, lo, nf, fv, qlo, qhi);
       keys = fv;
     } else {
-      hipLaunchKernelGGL(k_front_split, dim3(fgrid), dim3(256), 0, ctx->stream, (const uint64_t *)cur.fq, nf, qlo, qhi);
+      GG_LAUNCH(ctx, "front_split", k_front_split, dim3(fgrid), dim3(256), 0, (const uint64_t *)cur.fq, nf, qlo, qhi);
     }
     int key_bits = 1;
     while ((1ull << key_bits) < V) key_bits++;
     GG_TRY(sort_triples_by_key(ctx, keys, qlo, qhi, nf, key_bits, sv, slo, shi));
-    hipLaunchKernelGGL(k_front_offsets, dim3((unsigned)((nf + 256) / 256)), dim3(256), 0, ctx->stream, (const uint32_t *)sv,
-                       (const uint32_t *)slo, (const uint32_t *)shi, nf, V, froff, fqs);
+    GG_LAUNCH(ctx, "front_offsets", k_front_offsets, dim3((unsigned)((nf + 256) / 256)), dim3(256), 0, (const uint32_t *)sv,
+              (const uint32_t *)slo, (const uint32_t *)shi, nf, V, froff, fqs);
     GG_TRY(ctx->dev_alloc((void **)&foff2, (E + 1) * sizeof(uint64_t)));
     if (E)
-      hipLaunchKernelGGL(k_front3_prepare, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const uint32_t *)froff, (const uint32_t *)csr->rnbr, E, foff2);
+      GG_LAUNCH(ctx, "front3_prepare", k_front3_prepare, dim3((unsigned)((E + 255) / 256)), dim3(256), 0,
+                (const uint32_t *)froff, (const uint32_t *)csr->rnbr, E, foff2);
     uint64_t M2 = 0;
     GG_TRY(offsets_from_deg(ctx, foff2, E, &M2));
     if (M2 != M) {
@@ -1392,8 +1392,8 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
                 csr->rnbr, fbase, M, (int)(k_min <= 1), partial, tmp);
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
     }
-    hipLaunchKernelGGL(k_pack_stats, dim3(1), dim3(64), 0, ctx->stream, (const unsigned long long *)tmp,
-                       (unsigned long long)M, (unsigned long long)frontier_entries, (int)(k_min <= 1), dev_out6);
+    GG_LAUNCH(ctx, "pack_stats", k_pack_stats, dim3(1), dim3(64), 0, (const unsigned long long *)tmp, (unsigned long long)M,
+              (unsigned long long)frontier_entries, (int)(k_min <= 1), dev_out6);
     ctx->dev_free(tmp);
     ctx->dev_free(partial);
     return GG_OK;
@@ -1826,12 +1826,12 @@ int khop_materialise_front(gg_ctx *ctx, const gg_csr *csr, const std::vector<uin
   GG_TRY(ctx->dev_alloc((void **)&perm, n_prev * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&foff, (n_prev + 1) * sizeof(uint64_t)));
   const unsigned grid = (unsigned)((n_prev + 255) / 256);
-  hipLaunchKernelGGL(k_iota_u32, dim3(grid), dim3(256), 0, ctx->stream, n_prev, iota);
+  GG_LAUNCH(ctx, "iota_u32", k_iota_u32, dim3(grid), dim3(256), 0, n_prev, iota);
   int key_bits = 1;
   while ((1ull << key_bits) < csr->V) key_bits++;
   GG_TRY(sort_pairs_by_key(ctx, prev_cols[P], iota, n_prev, key_bits, skey, perm));
-  hipLaunchKernelGGL(k_mat_front_prepare, dim3(grid), dim3(256), 0, ctx->stream, (const uint32_t *)csr->off,
-                     (const uint32_t *)skey, n_prev, foff);
+  GG_LAUNCH(ctx, "mat_front_prepare", k_mat_front_prepare, dim3(grid), dim3(256), 0, (const uint32_t *)csr->off,
+            (const uint32_t *)skey, n_prev, foff);
   uint64_t M2 = 0;
   GG_TRY(offsets_from_deg(ctx, foff, n_prev, &M2));
   if (M2 != M) {
@@ -2213,12 +2213,14 @@ int khop_count_rows(gg_ctx *ctx, gg_csr *csr, const uint32_t *dense_src, uint64_
   return GG_OK;
 }
 
-int check_args(gg_ctx *ctx, const gg_csr *csr, int k_min, int k_max, gg_khop_stats *stats) {
+// whole: the call needs a whole CSR (a source list, a part of the vertices, rows); a shard only counts 2-hop walks from
+// every vertex
+int check_args(gg_ctx *ctx, const gg_csr *csr, int k_min, int k_max, gg_khop_stats *stats, bool whole = false) {
   if (!ctx || !csr || !stats || csr->ctx != ctx) {
     set_error("gg_expand_khop: bad context/csr/stats argument");
     return GG_ERR_INVALID_ARG;
   }
-  if (csr->n_parts > 1 && k_max != 2) {
+  if (csr->n_parts > 1 && (k_max != 2 || whole)) {
     set_error("a CSR shard (gg_csr_build_shard) only supports all-source 2-hop count expansion");
     return GG_ERR_STATE;
   }
@@ -2229,20 +2231,53 @@ int check_args(gg_ctx *ctx, const gg_csr *csr, int k_min, int k_max, gg_khop_sta
   return GG_OK;
 }
 
+// Level 0 from caller ids: the vertices among them, compacted (k_compact_sources; f->foff holds their degrees, for
+// offsets_from_deg).  Synchronises the stream when n > 0.
+int frontier_from_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64_t n, DevFrontier *f) {
+  unsigned long long *cursor = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&f->fv, (n ? n : 1) * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&f->fq, (n ? n : 1) * sizeof(uint64_t)));
+  GG_TRY(ctx->dev_alloc((void **)&f->foff, (n + 1) * sizeof(uint64_t)));
+  GG_TRY(ctx->dev_alloc((void **)&cursor, sizeof(unsigned long long)));
+  GG_HIP(hipMemsetAsync(cursor, 0, sizeof(unsigned long long), ctx->stream));
+  uint32_t *dense = nullptr;
+  GG_TRY(upload_ids(ctx, csr, ids, n, &dense));
+  f->n = 0;
+  if (n) {
+    GG_LAUNCH(ctx, "compact_sources", k_compact_sources, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, dense, n,
+              f->fv, f->fq, f->foff, csr->off, cursor);
+    GG_TRY(read_u64(ctx, (const uint64_t *)cursor, &f->n));
+  }
+  return GG_OK;
+}
+
+// Level 0 = the vertices [lo, lo + n) as a list (k_iota_deg writes their degrees too; nothing reads them)
+int frontier_from_range(gg_ctx *ctx, const gg_csr *csr, uint32_t lo, uint64_t n, uint32_t **fv) {
+  uint64_t *fdeg = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)fv, (n ? n : 1) * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&fdeg, (n ? n : 1) * sizeof(uint64_t)));
+  if (n)
+    GG_LAUNCH(ctx, "iota_deg", k_iota_deg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lo, n, csr->off, *fv, fdeg);
+  ctx->dev_free(fdeg);
+  return GG_OK;
+}
+
 }  // namespace
 
 extern "C" int gg_expand_khop_range(gg_ctx *ctx, const gg_csr *csr, uint64_t src_lo, uint64_t src_hi, int k_min,
                                     int k_max, int materialise, gg_khop_stats *stats, gg_result **out_result) {
   ApiScope scope(ctx);
-  GG_TRY(check_args(ctx, csr, k_min, k_max, stats));
   if (out_result) *out_result = nullptr;
   if (materialise && !out_result) return GG_ERR_INVALID_ARG;
-  if (src_hi > csr->V) src_hi = csr->V;
+  const uint64_t V = csr ? csr->V : 0;
+  if (src_hi > V) src_hi = V;
   if (src_lo > src_hi) src_lo = src_hi;
+  const bool all = src_lo == 0 && src_hi == V;
+  GG_TRY(check_args(ctx, csr, k_min, k_max, stats, materialise || !all));
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t n0 = src_hi - src_lo;
   uint64_t M1 = csr->E;
-  if (!(src_lo == 0 && src_hi == csr->V)) {
+  if (!all) {
     uint32_t ends[2] = {0, 0};
     GG_HIP(hipMemcpyAsync(ctx->pin_scratch, csr->off + src_lo, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 1, csr->off + src_hi, sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -2252,46 +2287,26 @@ extern "C" int gg_expand_khop_range(gg_ctx *ctx, const gg_csr *csr, uint64_t src
     memcpy(&ends[1], ctx->pin_scratch + 1, sizeof(uint32_t));
     M1 = (uint64_t)ends[1] - ends[0];
   }
-  if (csr->n_parts > 1 && (materialise || !(src_lo == 0 && src_hi == csr->V))) {
-    set_error("a CSR shard (gg_csr_build_shard) only supports all-source 2-hop count expansion");
-    return GG_ERR_STATE;
-  }
-  if (k_max == 2 && src_lo == 0 && src_hi == csr->V && (ctx->force_frontier == 0 || csr->n_parts > 1)) {
+  if (k_max == 2 && all && (ctx->force_frontier == 0 || csr->n_parts > 1)) {
     // every vertex is a source: the 2-hop walks are the per-vertex products in(x) x out(x)
     GG_TRY(khop_count_mid(ctx, const_cast<gg_csr *>(csr), 0, csr->V, k_min, stats));
-  } else if (k_max == 3 && src_lo == 0 && src_hi == csr->V && ctx->force_frontier == 0 && csr->n_parts <= 1) {
+  } else if (k_max == 3 && all && ctx->force_frontier == 0 && csr->n_parts <= 1) {
     // ... and the 3-hop walks the products {2-hop rows ending in b} x out(b)
     GG_TRY(khop_count_mid3(ctx, const_cast<gg_csr *>(csr), k_min, stats));
   } else {
     GG_TRY(khop_count(ctx, csr, true, (uint32_t)src_lo, n0, M1, DevFrontier(), k_min, k_max, stats));
   }
   if (materialise) {
-    gg_result *res = new gg_result();
-    res->ctx = ctx;
-    res->k_min = k_min;
-    res->k_max = k_max;
-    uint32_t *fv = nullptr;
-    uint64_t *fdeg = nullptr;
-    int rc = GG_OK;
-    if (k_max == 2 && src_lo == 0 && src_hi == csr->V && ctx->force_frontier == 0) {
+    ResultOwner res = make_result(ctx, k_min, k_max);
+    if (k_max == 2 && all && ctx->force_frontier == 0) {
       // every vertex is a source: the rows are the per-vertex products in(x) x out(x), grouped by x (k_mat_mid2)
-      rc = khop_materialise_mid2(ctx, const_cast<gg_csr *>(csr), 0, csr->V, k_min, res);
+      GG_TRY(khop_materialise_mid2(ctx, const_cast<gg_csr *>(csr), 0, csr->V, k_min, res.get()));
     } else {
-      rc = ctx->dev_alloc((void **)&fv, (n0 ? n0 : 1) * sizeof(uint32_t));
-      if (rc == GG_OK) rc = ctx->dev_alloc((void **)&fdeg, (n0 ? n0 : 1) * sizeof(uint64_t));
-      if (rc == GG_OK && n0) {
-        hipLaunchKernelGGL(k_iota_deg, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, ctx->stream, (uint32_t)src_lo,
-                           n0, csr->off, fv, fdeg);
-      }
-      if (rc == GG_OK) rc = khop_materialise(ctx, csr, fv, n0, k_min, k_max, res);
+      uint32_t *fv = nullptr;
+      GG_TRY(frontier_from_range(ctx, csr, (uint32_t)src_lo, n0, &fv));
+      GG_TRY(khop_materialise(ctx, csr, fv, n0, k_min, k_max, res.get()));
     }
-    ctx->dev_free(fv);
-    ctx->dev_free(fdeg);
-    if (rc != GG_OK) {
-      gg_result_destroy(res);
-      return rc;
-    }
-    *out_result = res;
+    *out_result = res.release();
   }
   return GG_OK;
 }
@@ -2301,59 +2316,23 @@ extern "C" int gg_expand_khop(gg_ctx *ctx, const gg_csr *csr, const int64_t *src
   ApiScope scope(ctx);
   if (!src_ids)
     return gg_expand_khop_range(ctx, csr, 0, csr ? csr->V : 0, k_min, k_max, materialise, stats, out_result);
-  GG_TRY(check_args(ctx, csr, k_min, k_max, stats));
-  if (csr->n_parts > 1) {
-    set_error("a CSR shard (gg_csr_build_shard) only supports all-source 2-hop count expansion");
-    return GG_ERR_STATE;
-  }
+  GG_TRY(check_args(ctx, csr, k_min, k_max, stats, true));
   if (out_result) *out_result = nullptr;
   if (materialise && !out_result) return GG_ERR_INVALID_ARG;
   GG_HIP(hipSetDevice(ctx->device));
-
-  // ids -> dense -> compacted frontier 0
-  int64_t *ids_dev = nullptr;
-  uint32_t *dense = nullptr;
   DevFrontier f0;
-  unsigned long long *cursor = nullptr;
-  const uint64_t n = n_src;
-  GG_TRY(ctx->dev_alloc((void **)&ids_dev, (n ? n : 1) * sizeof(int64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&dense, (n ? n : 1) * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&f0.fv, (n ? n : 1) * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&f0.fq, (n ? n : 1) * sizeof(uint64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&f0.foff, (n + 1) * sizeof(uint64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&cursor, sizeof(unsigned long long)));
-  GG_HIP(hipMemsetAsync(cursor, 0, sizeof(unsigned long long), ctx->stream));
-  uint64_t n_valid = 0, M1 = 0;
-  if (n) {
-    GG_HIP(hipMemcpyAsync(ids_dev, src_ids, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));  // src_ids is caller memory: consumed before return
-    GG_TRY(lookup_ids(ctx, csr, ids_dev, n, dense));
-    GG_LAUNCH(ctx, "compact_sources", k_compact_sources, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, dense, n,
-              f0.fv, f0.fq, f0.foff, csr->off, cursor);
-    GG_TRY(read_u64(ctx, (const uint64_t *)cursor, &n_valid));
-    GG_TRY(offsets_from_deg(ctx, f0.foff, n_valid, &M1));
-  } else {
+  GG_TRY(frontier_from_ids(ctx, csr, src_ids, n_src, &f0));
+  if (n_src)
+    GG_TRY(offsets_from_deg(ctx, f0.foff, f0.n, &f0.M));
+  else
     GG_HIP(hipMemsetAsync(f0.foff, 0, sizeof(uint64_t), ctx->stream));
+  GG_TRY(khop_count(ctx, csr, false, 0, f0.n, f0.M, f0, k_min, k_max, stats));
+  if (materialise) {
+    ResultOwner res = make_result(ctx, k_min, k_max);
+    GG_TRY(khop_materialise(ctx, csr, f0.fv, f0.n, k_min, k_max, res.get()));
+    *out_result = res.release();
   }
-  f0.n = n_valid;
-  f0.M = M1;
-  int rc = khop_count(ctx, csr, false, 0, n_valid, M1, f0, k_min, k_max, stats);
-  if (rc == GG_OK && materialise) {
-    gg_result *res = new gg_result();
-    res->ctx = ctx;
-    res->k_min = k_min;
-    res->k_max = k_max;
-    rc = khop_materialise(ctx, csr, f0.fv, n_valid, k_min, k_max, res);
-    if (rc != GG_OK)
-      gg_result_destroy(res);
-    else
-      *out_result = res;
-  }
-  ctx->dev_free(ids_dev);
-  ctx->dev_free(dense);
-  ctx->dev_free(cursor);
-  free_frontier(ctx, f0);
-  return rc;
+  return GG_OK;
 }
 
 extern "C" int gg_join_probe(gg_ctx *ctx, const gg_csr *csr, const int64_t *keys, uint64_t n, uint64_t *n_matches,
@@ -2367,48 +2346,28 @@ extern "C" int gg_join_probe(gg_ctx *ctx, const gg_csr *csr, const int64_t *keys
     return GG_ERR_STATE;
   }
   GG_HIP(hipSetDevice(ctx->device));
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = res->k_max = 1;
+  ResultOwner res = make_result(ctx, 1, 1);
   uint64_t M = 0;
-  int64_t *ids_dev = nullptr;
   uint32_t *dense = nullptr;
   uint64_t *poff = nullptr;
-  int rc = GG_OK;
   if (n && csr->V) {
-    rc = ctx->dev_alloc((void **)&ids_dev, n * sizeof(int64_t));
-    if (rc == GG_OK) rc = ctx->dev_alloc((void **)&dense, n * sizeof(uint32_t));
-    if (rc == GG_OK) rc = ctx->dev_alloc((void **)&poff, (n + 1) * sizeof(uint64_t));
-    if (rc == GG_OK) {
-      hipError_t e = hipMemcpyAsync(ids_dev, keys, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // keys is caller memory: consumed before return
-      if (e != hipSuccess) {
-        set_error("gg_join_probe: %s", hipGetErrorString(e));
-        rc = GG_ERR_HIP;
-      }
-    }
-    if (rc == GG_OK) rc = lookup_ids(ctx, csr, ids_dev, n, dense);
-    if (rc == GG_OK) {
-      hipLaunchKernelGGL(k_join_deg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t *)dense, n,
-                         (const uint32_t *)csr->off, poff);
-      rc = offsets_from_deg(ctx, poff, n, &M);
-    }
+    GG_TRY(ctx->dev_alloc((void **)&poff, (n + 1) * sizeof(uint64_t)));
+    GG_TRY(upload_ids(ctx, csr, keys, n, &dense));
+    GG_LAUNCH(ctx, "join_deg", k_join_deg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const uint32_t *)dense, n,
+              (const uint32_t *)csr->off, poff);
+    GG_TRY(offsets_from_deg(ctx, poff, n, &M));
   }
-  for (int c = 0; c < 2 && rc == GG_OK; c++) {
-    rc = ctx->dev_alloc((void **)&res->cols[1][c], (M ? M : 1) * sizeof(int64_t));
-    if (rc == GG_OK) ctx->keep(res->cols[1][c]);
+  for (int c = 0; c < 2; c++) {
+    GG_TRY(ctx->dev_alloc((void **)&res->cols[1][c], (M ? M : 1) * sizeof(int64_t)));
+    ctx->keep(res->cols[1][c]);
   }
-  if (rc == GG_OK && M)
-    hipLaunchKernelGGL(k_join_emit, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t *)poff, n, M,
-                       (const uint32_t *)dense, (const uint32_t *)csr->off, (const int64_t *)csr->eid,
-                       (const uint32_t *)csr->epos, res->cols[1][0], res->cols[1][1]);
-  if (rc != GG_OK) {
-    gg_result_destroy(res);
-    return rc;
-  }
+  if (M)
+    GG_LAUNCH(ctx, "join_emit", k_join_emit, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, (const uint64_t *)poff, n,
+              M, (const uint32_t *)dense, (const uint32_t *)csr->off, (const int64_t *)csr->eid,
+              (const uint32_t *)csr->epos, res->cols[1][0], res->cols[1][1]);
   res->rows[1] = M;
   *n_matches = M;
-  *out_result = res;
+  *out_result = res.release();
   return GG_OK;
 }
 
@@ -2416,28 +2375,14 @@ extern "C" int gg_khop_count(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_
                             uint64_t *rows) {
   ApiScope scope(ctx);
   gg_khop_stats unused;
-  GG_TRY(check_args(ctx, csr, k_min, k_max, &unused));
+  GG_TRY(check_args(ctx, csr, k_min, k_max, &unused, src_ids != nullptr));
   if (!rows) return GG_ERR_INVALID_ARG;
-  if (csr->n_parts > 1 && src_ids) {
-    set_error("a CSR shard (gg_csr_build_shard) only supports all-source 2-hop count expansion");
-    return GG_ERR_STATE;
-  }
   GG_HIP(hipSetDevice(ctx->device));
-  if (!src_ids) return khop_count_rows(ctx, const_cast<gg_csr *>(csr), nullptr, 0, k_min, k_max, rows);
-  int64_t *ids_dev = nullptr;
+  // (no vertices: every count is 0, and khop_count_rows returns before it synchronises)
+  if (!src_ids || csr->V == 0) return khop_count_rows(ctx, const_cast<gg_csr *>(csr), nullptr, 0, k_min, k_max, rows);
   uint32_t *dense = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&ids_dev, (n_src ? n_src : 1) * sizeof(int64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&dense, (n_src ? n_src : 1) * sizeof(uint32_t)));
-  int rc = GG_OK;
-  if (n_src) {
-    GG_HIP(hipMemcpyAsync(ids_dev, src_ids, n_src * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));  // src_ids is caller memory: consumed before return
-    rc = lookup_ids(ctx, csr, ids_dev, n_src, dense);
-  }
-  if (rc == GG_OK) rc = khop_count_rows(ctx, const_cast<gg_csr *>(csr), dense, n_src, k_min, k_max, rows);
-  ctx->dev_free(ids_dev);
-  ctx->dev_free(dense);
-  return rc;
+  GG_TRY(upload_ids(ctx, csr, src_ids, n_src, &dense));
+  return khop_count_rows(ctx, const_cast<gg_csr *>(csr), dense, n_src, k_min, k_max, rows);
 }
 
 extern "C" int gg_expand_khop_result(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int k_min,
@@ -2457,58 +2402,21 @@ extern "C" int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_
   }
   GG_HIP(hipSetDevice(ctx->device));
   // level 0: the given sources (dense, compacted) or every vertex
-  int64_t *ids_dev = nullptr;
-  uint32_t *dense = nullptr, *fv = nullptr;
-  uint64_t n0 = 0;
-  DevFrontier f0;
-  unsigned long long *cursor = nullptr;
-  int rc = GG_OK;
+  uint32_t *fv = nullptr;
+  uint64_t n0 = csr->V;
   if (src_ids) {
-    const uint64_t n = n_src;
-    GG_TRY(ctx->dev_alloc((void **)&ids_dev, (n ? n : 1) * sizeof(int64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&dense, (n ? n : 1) * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&f0.fv, (n ? n : 1) * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&f0.fq, (n ? n : 1) * sizeof(uint64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&f0.foff, (n + 1) * sizeof(uint64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&cursor, sizeof(unsigned long long)));
-    GG_HIP(hipMemsetAsync(cursor, 0, sizeof(unsigned long long), ctx->stream));
-    if (n) {
-      GG_HIP(hipMemcpyAsync(ids_dev, src_ids, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-      GG_HIP(hipStreamSynchronize(ctx->stream));  // src_ids is caller memory: consumed before return
-      GG_TRY(lookup_ids(ctx, csr, ids_dev, n, dense));
-      GG_LAUNCH(ctx, "compact_sources", k_compact_sources, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, dense, n,
-                f0.fv, f0.fq, f0.foff, csr->off, cursor);
-      GG_TRY(read_u64(ctx, (const uint64_t *)cursor, &n0));
-    }
+    DevFrontier f0;
+    GG_TRY(frontier_from_ids(ctx, csr, src_ids, n_src, &f0));
     fv = f0.fv;
+    n0 = f0.n;
   } else {
-    n0 = csr->V;
-    uint64_t *fdeg = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&fv, (n0 ? n0 : 1) * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&fdeg, (n0 ? n0 : 1) * sizeof(uint64_t)));
-    if (n0)
-      hipLaunchKernelGGL(k_iota_deg, dim3((unsigned)((n0 + 255) / 256)), dim3(256), 0, ctx->stream, 0u, n0, csr->off, fv,
-                         fdeg);
-    ctx->dev_free(fdeg);
+    GG_TRY(frontier_from_range(ctx, csr, 0, n0, &fv));
   }
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = res->k_max = k;
-  rc = khop_materialise(ctx, csr, fv, n0, k, k, res, true);
-  if (rc == GG_OK) {
-    memset(stats, 0, sizeof(*stats));
-    stats->rows[k] = res->rows[k];
-  }
-  if (!src_ids) ctx->dev_free(fv);
-  ctx->dev_free(ids_dev);
-  ctx->dev_free(dense);
-  ctx->dev_free(cursor);
-  if (src_ids) free_frontier(ctx, f0);
-  if (rc != GG_OK) {
-    gg_result_destroy(res);
-    return rc;
-  }
-  *out_result = res;
+  ResultOwner res = make_result(ctx, k, k);
+  GG_TRY(khop_materialise(ctx, csr, fv, n0, k, k, res.get(), true));
+  memset(stats, 0, sizeof(*stats));
+  stats->rows[k] = res->rows[k];
+  *out_result = res.release();
   return GG_OK;
 }
 
@@ -2558,7 +2466,6 @@ extern "C" int gg_khop_partition(gg_ctx *ctx, const gg_csr *csr, int n_parts, ui
   GG_TRY(offsets_from_deg(ctx, work, V, &total));
   std::vector<uint64_t> h(V + 1);
   GG_HIP(hipMemcpy(h.data(), work, (V + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  ctx->dev_free(work);
   for (int i = 1; i < n_parts; i++) {
     uint64_t target = (uint64_t)((__uint128_t)total * (unsigned)i / (unsigned)n_parts);
     uint64_t lo = 0, hi = V;  // first vertex whose exclusive prefix >= target
@@ -2601,16 +2508,9 @@ extern "C" int gg_expand_khop_mid_result(gg_ctx *ctx, gg_csr *csr, uint64_t mid_
   GG_HIP(hipSetDevice(ctx->device));
   // (stats == NULL: the rows only — no counting expansion in front of the materialisation; gg_result_rows has the counts)
   if (stats) GG_TRY(khop_count_mid(ctx, csr, mid_lo, mid_hi, k_min, stats));
-  gg_result *res = new gg_result();
-  res->ctx = ctx;
-  res->k_min = k_min;
-  res->k_max = 2;
-  const int rc = khop_materialise_mid2(ctx, csr, mid_lo, mid_hi, k_min, res);
-  if (rc != GG_OK) {
-    gg_result_destroy(res);
-    return rc;
-  }
-  *out_result = res;
+  ResultOwner res = make_result(ctx, k_min, 2);
+  GG_TRY(khop_materialise_mid2(ctx, csr, mid_lo, mid_hi, k_min, res.get()));
+  *out_result = res.release();
   return GG_OK;
 }
 
@@ -2661,7 +2561,6 @@ extern "C" int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint
   GG_TRY(offsets_from_deg(ctx, work, V, &total));
   std::vector<uint64_t> h(V + 1);
   GG_HIP(hipMemcpy(h.data(), work, (V + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  ctx->dev_free(work);
   for (int i = 1; i < n_parts; i++) {
     uint64_t target = (uint64_t)((__uint128_t)total * (unsigned)i / (unsigned)n_parts);
     uint64_t lo = 0, hi = V;
@@ -2766,7 +2665,6 @@ extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result 
   }
   GG_HIP(hipMemcpyAsync(ctx->pin_scratch, out, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   GG_HIP(hipStreamSynchronize(ctx->stream));
-  ctx->dev_free(out);
   if (ctx->pin_scratch[1]) {
     set_error("gg_result_digest: %llu rows hold an id that is not a vertex", (unsigned long long)ctx->pin_scratch[1]);
     return GG_ERR_STATE;

@@ -195,6 +195,7 @@ int gg_ctx::dev_alloc_columns(void **cols, size_t col_bytes) {
     for (int rep = 0; rep < 2; rep++) {  // (the first launch after an allocation pays for its page tables)
       float ms = 0.f;
       (void)hipEventRecord(e0, stream);
+      // (bare launch, not GG_LAUNCH: timed alone between e0 and e1; a failure shows in the events and stops the probing)
       hipLaunchKernelGGL(k_place_probe, dim3(grid), dim3(256), 0, stream, (place_ll2 *)x, (place_ll2 *)y, pairs, sample);
       (void)hipEventRecord(e1, stream);
       if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess || ms <= 0.f) {
@@ -1066,6 +1067,17 @@ int lookup_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids_dev, uint64_t 
   return GG_OK;
 }
 
+int upload_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64_t n, uint32_t **dense, int64_t **ids_dev) {
+  int64_t *dev = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&dev, (n ? n : 1) * sizeof(int64_t)));
+  GG_TRY(ctx->dev_alloc((void **)dense, (n ? n : 1) * sizeof(uint32_t)));
+  if (ids_dev) *ids_dev = dev;
+  if (n == 0) return GG_OK;
+  GG_TRY(ensure_ht(ctx, const_cast<gg_csr *>(csr)));  // (first: once the copy is queued only the launch can fail)
+  GG_HIP(hipMemcpyAsync(dev, ids, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  return lookup_ids(ctx, csr, dev, n, *dense);
+}
+
 }  // namespace gg
 
 extern "C" int gg_csr_lookup(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64_t n, uint32_t *dense_out) {
@@ -1073,13 +1085,8 @@ extern "C" int gg_csr_lookup(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids,
   if (n == 0) return GG_OK;
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
-  int64_t *ids_dev = nullptr;
   uint32_t *out_dev = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&ids_dev, n * sizeof(int64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&out_dev, n * sizeof(uint32_t)));
-  GG_HIP(hipMemcpyAsync(ids_dev, ids, n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));  // `ids` may be pageable: do not return before it was read
-  GG_TRY(gg::lookup_ids(ctx, csr, ids_dev, n, out_dev));
+  GG_TRY(gg::upload_ids(ctx, csr, ids, n, &out_dev));
   GG_HIP(hipMemcpyAsync(dense_out, out_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   GG_HIP(hipStreamSynchronize(ctx->stream));
   return GG_OK;

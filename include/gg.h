@@ -141,7 +141,8 @@ int gg_csr_info(const gg_csr *csr, uint64_t *n_vertices, uint64_t *n_edges_kept,
  * with gg_result_rows(res, 1, &m) / gg_result_fetch(res, 1, offset, max, cols[2], &got).  This is the device side of a
  * generic single-key inner hash join: JoinHashTable::Probe + ScanStructure::NextInnerJoin for one probe chunk
  * (src/execution/join_hashtable.cpp:304-476); the host operator (PhysicalGGKeyJoin) slices the probe chunk by i and
- * fetches the build side's columns by rowid.  The CSR must have been built with edge rowids kept. */
+ * fetches the build side's columns by rowid.  The CSR must have been built with edge rowids kept.  A batch of 2^32
+ * matches or more returns GG_ERR_TOO_LARGE: probe it in smaller batches. */
 int gg_join_probe(gg_ctx *ctx, const gg_csr *csr, const int64_t *keys, uint64_t n, uint64_t *n_matches,
                   gg_result **out_result);
 /* Parity export.  off: V+1 entries; nbr: E_kept dense neighbour indices; eid: E_kept edge rowids

@@ -373,6 +373,38 @@ def test_join_probe_returns_every_matching_build_row_per_probe_key(gg, orc):
     csr.close()
 
 
+def test_join_frontier_and_bfs_pair_launches_are_profiled(gg, orc):
+    """Every launch goes through GG_LAUNCH (bounds check, error check, profiling): the join probe's kernels, the
+    sorted-frontier form of the last two hops (knob 3) and the BFS pair table appear in the profile by name."""
+    vid, src, dst = datagen.small_graph(3000, 40000, 4)
+    csr, g = build_both(gg, orc, vid, src, dst)
+
+    def launched(fn):
+        gg.profile_reset()
+        gg.profile_select(None)
+        gg.profile(True)
+        try:
+            fn()
+        finally:
+            gg.profile(False)
+        names = set(gg.profile_get())
+        gg.profile_reset()
+        return names
+
+    try:
+        assert {"lookup_ids", "join_deg", "join_emit"} <= launched(lambda: gg.join_probe(csr, vid[:100]))
+        gg.force_frontier(3)
+        assert {"front_split", "front_offsets", "front3_prepare", "expand_front3"} <= launched(
+            lambda: gg.expand_khop(csr, 1, 3, sources=vid[:300]))
+        assert {"front_ident", "front3_prepare", "expand_front3"} <= launched(lambda: gg.expand_khop(csr, 1, 2))
+        gg.force_frontier(0)
+        assert {"bfs_pairs_count", "bfs_pairs_fill"} <= launched(lambda: gg.bfs64_pairs(csr, vid[:64], 3))
+    finally:
+        gg.force_frontier(0)
+    csr.close()
+    g.close()
+
+
 def test_khop_ranges_partition_the_result(gg, orc):
     """Sharding entry point: per-range counts/digests add up to the whole (what the multi-GPU path sums)."""
     vid, src, dst = datagen.ldbc_knows(5000, 200_000, 17)
