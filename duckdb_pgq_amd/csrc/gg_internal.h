@@ -274,6 +274,10 @@ struct gg_result {
   uint64_t rows[GG_MAX_HOPS + 1] = {0};
   int64_t *cols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};  // cols[h][c], device
   int64_t *ecols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};  // ecols[h][j]: rowid of the walk's (j + 1)-th edge (gg_expand_khop_edges)
+  // gg_walk_closure (k_min > k_max: no fixed-length table): one row per walk of >= 1 edges, level by level
+  std::vector<uint64_t> level_rows;  // level_rows[L - 1]: walks of L edges
+  int64_t *walk_seed = nullptr;      // device: index into the seed list of the walk's seed
+  int64_t *walk_rowid = nullptr;     // device: rowid of the walk's last edge (as staged)
 };
 
 namespace gg {
@@ -333,6 +337,16 @@ inline ResultOwner make_result(gg_ctx *ctx, int k_min, int k_max) {
     if (prof_rec_ >= 0) (ctx)->prof_end(prof_rec_);                                   \
     GG_HIP(hipGetLastError());                                                        \
   } while (0)
+
+// Load-balanced expansion over a flattened frontier (gg_khop.hip, gg_closure.hip): entry i of a frontier owns the child
+// positions [foff[i], foff[i+1]); a workgroup of XT threads takes XT consecutive positions, tile_entry[t] being the
+// entry that tile t starts in (make_tiles_u64: one binary search per tile).
+constexpr int XT = 256;  // child positions per tile == threads per workgroup
+int make_tiles_u64(gg_ctx *ctx, const uint64_t *foff, uint64_t n_entries, uint64_t M, uint32_t **tile_entry,
+                   uint64_t *n_tiles);
+// GG_ERR_INVALID_ARG for a bad context / CSR pair, GG_ERR_STATE for a shard (gg_csr_build_shard): calls that need a
+// whole CSR
+int check_whole_csr(gg_ctx *ctx, const gg_csr *csr);
 
 // exclusive scan of n uint32 values (in place allowed: out may equal in); writes the grand
 // total (as uint64) to *total_dev if non-null.  One hand-written kernel, tiles chained by decoupled
@@ -494,6 +508,46 @@ __device__ __forceinline__ uint64_t wave_reduce_add_u64(uint64_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// Locate the frontier entry that owns flattened child position p.  s_foff holds foff[i0..i0+XT]
+// (UINT64_MAX past the end).  Returns entry index and writes the position inside the entry.
+template <typename OffT>
+__device__ __forceinline__ uint64_t locate_entry(const uint64_t *s_foff, const OffT *__restrict__ foff,
+                                                 uint64_t n_entries, uint64_t i0, uint64_t p, uint64_t *k) {
+  uint32_t lo = 0, hi = XT + 1;  // first idx in [0, XT+1) with s_foff[idx] > p
+  while (lo < hi) {
+    uint32_t mid = (lo + hi) >> 1;
+    if (s_foff[mid] <= p)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  uint64_t idx = i0 + lo - 1;
+  uint64_t start = s_foff[lo - 1];
+  if (lo == XT + 1) {  // window exhausted by zero-degree entries: finish the search in global memory
+    uint64_t glo = i0 + XT, ghi = n_entries;
+    while (glo < ghi) {
+      uint64_t mid = (glo + ghi) >> 1;
+      if ((uint64_t)foff[mid] <= p)
+        glo = mid + 1;
+      else
+        ghi = mid;
+    }
+    idx = glo - 1;
+    start = (uint64_t)foff[idx];
+  }
+  *k = p - start;
+  return idx;
+}
+
+template <typename OffT>
+__device__ __forceinline__ void load_window(uint64_t *s_foff, const OffT *__restrict__ foff, uint64_t n_entries,
+                                            uint64_t i0) {
+  for (uint32_t t = threadIdx.x; t <= XT; t += XT) {
+    uint64_t gi = i0 + t;
+    s_foff[t] = gi <= n_entries ? (uint64_t)foff[gi] : UINT64_MAX;
+  }
 }
 
 }  // namespace gg

@@ -25,7 +25,6 @@ using namespace gg;
 
 namespace gg {
 
-constexpr int XT = 256;  // child positions per tile == threads per workgroup
 // The runtime takes a grid as gridDim.x * blockDim.x threads in 32 bits: at most this many XT-thread workgroups per
 // launch (about 1.3e10 3-hop tile rows; SF100's 12.8 G 2-hop rows are 16.6 M tiles of 768, just below it).
 constexpr uint64_t MAX_GRID_TILES = 0xFFFFFFFFull / XT;
@@ -51,46 +50,6 @@ __global__ __launch_bounds__(256) void k_tile_partition(const OffT *__restrict__
       hi = mid;
   }
   tile_entry[t] = (uint32_t)(lo - 1);
-}
-
-// Locate the frontier entry that owns flattened child position p.  s_foff holds foff[i0..i0+XT]
-// (UINT64_MAX past the end).  Returns entry index and writes the position inside the entry.
-template <typename OffT>
-__device__ __forceinline__ uint64_t locate_entry(const uint64_t *s_foff, const OffT *__restrict__ foff,
-                                                 uint64_t n_entries, uint64_t i0, uint64_t p, uint64_t *k) {
-  uint32_t lo = 0, hi = XT + 1;  // first idx in [0, XT+1) with s_foff[idx] > p
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (s_foff[mid] <= p)
-      lo = mid + 1;
-    else
-      hi = mid;
-  }
-  uint64_t idx = i0 + lo - 1;
-  uint64_t start = s_foff[lo - 1];
-  if (lo == XT + 1) {  // window exhausted by zero-degree entries: finish the search in global memory
-    uint64_t glo = i0 + XT, ghi = n_entries;
-    while (glo < ghi) {
-      uint64_t mid = (glo + ghi) >> 1;
-      if ((uint64_t)foff[mid] <= p)
-        glo = mid + 1;
-      else
-        ghi = mid;
-    }
-    idx = glo - 1;
-    start = (uint64_t)foff[idx];
-  }
-  *k = p - start;
-  return idx;
-}
-
-template <typename OffT>
-__device__ __forceinline__ void load_window(uint64_t *s_foff, const OffT *__restrict__ foff, uint64_t n_entries,
-                                            uint64_t i0) {
-  for (uint32_t t = threadIdx.x; t <= XT; t += XT) {
-    uint64_t gi = i0 + t;
-    s_foff[t] = gi <= n_entries ? (uint64_t)foff[gi] : UINT64_MAX;
-  }
 }
 
 struct Frontier {
@@ -2264,6 +2223,17 @@ int frontier_from_range(gg_ctx *ctx, const gg_csr *csr, uint32_t lo, uint64_t n,
 
 }  // namespace
 
+namespace gg {
+int make_tiles_u64(gg_ctx *ctx, const uint64_t *foff, uint64_t n_entries, uint64_t M, uint32_t **tile_entry,
+                   uint64_t *n_tiles) {
+  return make_tiles<uint64_t>(ctx, foff, n_entries, M, tile_entry, n_tiles);
+}
+int check_whole_csr(gg_ctx *ctx, const gg_csr *csr) {
+  gg_khop_stats unused;
+  return check_args(ctx, csr, 1, 1, &unused, true);
+}
+}  // namespace gg
+
 extern "C" int gg_expand_khop_range(gg_ctx *ctx, const gg_csr *csr, uint64_t src_lo, uint64_t src_hi, int k_min,
                                     int k_max, int materialise, gg_khop_stats *stats, gg_result **out_result) {
   ApiScope scope(ctx);
@@ -2686,6 +2656,8 @@ extern "C" void gg_result_destroy(gg_result *res) {
         ctx->dev_free(res->cols[h][c]);
         ctx->dev_free(res->ecols[h][c]);
       }
+    ctx->dev_free(res->walk_seed);
+    ctx->dev_free(res->walk_rowid);
   }
   delete res;
 }

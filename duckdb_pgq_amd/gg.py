@@ -23,7 +23,8 @@ SYMBOLS = [
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
     "gg_result_filter_common_neighbour", "gg_staging_clear_edges", "gg_vertices_from_edges",
-    "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_walk_endpoints", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
+    "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
+    "gg_walk_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
@@ -124,6 +125,9 @@ def load_library(path: str | None = None):
     lib.gg_bfs64_pairs.argtypes = [P, P, i64p, C.c_int, C.c_int, C.POINTER(BfsStats), C.POINTER(P)]
     lib.gg_bfs64_pairs_packed.argtypes = [P, P, i64p, C.c_int, C.c_int, C.POINTER(BfsStats), C.POINTER(P)]
     lib.gg_walk_endpoints.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
+    lib.gg_walk_closure.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
+    lib.gg_walk_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
+    lib.gg_walk_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.gg_bfs_sharded_begin.argtypes = [P, P, i64p, C.c_int, C.POINTER(P)]
     lib.gg_bfs_sharded_expand.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(u64), C.POINTER(u64)]
     lib.gg_bfs_sharded_words.argtypes = [P, C.POINTER(C.c_uint64), C.c_int]
@@ -251,6 +255,52 @@ class KhopResult:
         got = C.c_uint32()
         self.gg._chk(self.gg.lib.gg_result_fetch(self.handle, h, offset, min(max_rows, GG_CHUNK_ROWS), ptrs, C.byref(got)))
         return np.stack([b[: got.value] for b in bufs], axis=1)
+
+    def close(self):
+        if self.handle:
+            self.gg.lib.gg_result_destroy(self.handle)
+            self.handle = None
+
+
+class WalkClosure:
+    """Every walk from a seed list (gg_walk_closure), left in HBM: level counts and row slices on demand."""
+
+    def __init__(self, gg: "GG", handle):
+        self.gg, self.handle = gg, handle
+
+    def levels(self) -> int:
+        """the deepest level with walks (0: none)"""
+        n = C.c_int()
+        self.gg._chk(self.gg.lib.gg_walk_closure_levels(self.handle, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def rows(self, level: int | None = None):
+        """walks of `level` edges (level >= 1); without a level, every level's count as a list"""
+        n = self.levels()
+        counts = (C.c_uint64 * max(n, 1))()
+        got = C.c_int()
+        self.gg._chk(self.gg.lib.gg_walk_closure_levels(self.handle, counts, n, C.byref(got)))
+        if level is None:
+            return [int(counts[i]) for i in range(n)]
+        return int(counts[level - 1]) if 1 <= level <= n else 0
+
+    def fetch(self, offset: int = 0, max_rows: int | None = None):
+        """(seed_index int64, edge_rowid int64, level int32) of rows [offset, offset + max_rows), in row order"""
+        total = sum(self.rows())
+        want = max(0, total - offset) if max_rows is None else max(0, min(max_rows, total - offset))
+        seed, rowid, level = np.empty(want, np.int64), np.empty(want, np.int64), np.empty(want, np.int32)
+        i64p = C.POINTER(C.c_int64)
+        done = 0
+        while done < want:
+            got = C.c_uint32()
+            take = min(want - done, 1 << 30)
+            self.gg._chk(self.gg.lib.gg_walk_closure_fetch(
+                self.handle, offset + done, take, seed[done:].ctypes.data_as(i64p), rowid[done:].ctypes.data_as(i64p),
+                level[done:].ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got)))
+            if got.value == 0:
+                break
+            done += got.value
+        return seed[:done], rowid[:done], level[:done]
 
     def close(self):
         if self.handle:
@@ -636,6 +686,15 @@ class GG:
         finally:
             self.lib.gg_result_destroy(res)
         return out[0].copy(), out[1].copy()
+
+    def walk_closure(self, csr: Csr, seeds, max_levels: int | None = None) -> WalkClosure:
+        """gg_walk_closure: every walk of >= 1 edges from the seeds (max_levels None: until a level is empty).  The CSR
+        must keep edge rowids (the default)."""
+        s, ps = _i64(seeds)
+        res = C.c_void_p()
+        self._chk(self.lib.gg_walk_closure(self.ctx, csr.handle, ps, s.size, -1 if max_levels is None else max_levels,
+                                           C.byref(res)))
+        return WalkClosure(self, res)
 
     # ---- graph-sharded BFS (one shard per GPU; see include/gg.h)
     def bfs_sharded_begin(self, shard: Csr, sources) -> "ShardedBfs":

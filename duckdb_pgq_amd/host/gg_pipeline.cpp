@@ -443,7 +443,8 @@ static int GGBuildPipelinesRule(void *executor_p, void *op_p, void *current_p) {
 			for (auto reader : readers) {
 				reader->AddDependency(pipeline);
 			}
-			// (a sink's child is a table scan: its own traversal never meets the recursive CTE)
+			// (a sink's child is a table scan, or — under GG_RECURSIVE_WALKS — a plan made with every gg rule suspended:
+			// the reference's own traversal builds it, and it never holds a graph scan or meets this recursive CTE)
 			build(executor_p, child->children[0].get(), pipeline.get());
 			added.push_back(pipeline);
 			previous = pipeline;

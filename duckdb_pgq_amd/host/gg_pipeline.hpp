@@ -3,6 +3,8 @@
 
 #include <functional>
 
+#include "duckdb/common/types/chunk_collection.hpp"
+
 #include "gg_extension.hpp"
 #include "gg_operators.hpp"
 
@@ -84,6 +86,77 @@ public:
 		return parallel_result;
 	}
 	string GetName() const override;
+	string ParamsToString() const override;
+};
+
+//===--------------------------------------------------------------------===//
+// UNION ALL recursion over one keyed table (gg_recursive_walks.cpp, rule: PlanRecursiveWalks in gg_plan_rule.cpp)
+//===--------------------------------------------------------------------===//
+//! What one output column of the recursive arm is
+struct GGWalkColumn {
+	enum Kind { CARRIED, TABLE, CONSTANT, COUNTER } kind = CARRIED;
+	idx_t index = 0;     // TABLE: column of the arm table's rows
+	Value constant;      // CONSTANT
+	int64_t step = 0;    // COUNTER: anchor value + step x level
+};
+
+//! The rows both sinks collect and the source reads
+struct GGWalkInput {
+	mutex lock;
+	ChunkCollection anchor; // the anchor's rows, in the CTE's column layout
+	ChunkCollection table;  // the arm table's rows (row number = edge rowid)
+	idx_t link_column = 0;  // of the anchor (and of the CTE)
+	idx_t key_column = 0;   // of the table: joined with the link
+	idx_t next_column = 0;  // of the table: the next level's link
+	int max_levels = -1;    // from `counter < K` on the CTE side; -1: until a level is empty
+	vector<GGWalkColumn> columns;
+	string description;
+};
+
+//! Keeps the rows of the anchor (table_side false) or of the arm table on the host; the table side's Finalize stages
+//! its rows as edges key -> next and builds the CSR into the slot
+class PhysicalGGWalkRowSink : public PhysicalOperator {
+public:
+	PhysicalGGWalkRowSink(shared_ptr<GGWalkInput> input, shared_ptr<GGGraphSlot> slot, bool table_side,
+	                      vector<LogicalType> types, idx_t estimated_cardinality);
+	shared_ptr<GGWalkInput> input;
+	shared_ptr<GGGraphSlot> slot;
+	bool table_side;
+
+public:
+	unique_ptr<GlobalSinkState> GetGlobalSinkState(ClientContext &context) const override;
+	SinkResultType Sink(ExecutionContext &context, GlobalSinkState &gstate, LocalSinkState &lstate,
+	                    DataChunk &input) const override;
+	SinkFinalizeType Finalize(Pipeline &pipeline, Event &event, ClientContext &context,
+	                          GlobalSinkState &gstate) const override;
+	bool IsSink() const override {
+		return true;
+	}
+	bool ParallelSink() const override {
+		return true;
+	}
+	string GetName() const override;
+};
+
+//! Source: the anchor's rows, then every walk of the closure (gg_walk_closure) level by level, its columns gathered
+//! from its seed's anchor row and its last edge's table row
+class PhysicalGGRecursiveWalks : public PhysicalOperator {
+public:
+	PhysicalGGRecursiveWalks(vector<LogicalType> types, shared_ptr<GGGraph> graph, shared_ptr<GGWalkInput> input,
+	                         idx_t estimated_cardinality);
+	shared_ptr<GGGraph> graph;
+	shared_ptr<GGWalkInput> input;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_RECURSIVE_WALKS";
+	}
 	string ParamsToString() const override;
 };
 

@@ -4,7 +4,8 @@
  * PhysicalPlanGenerator::CreatePlan(LogicalComparisonJoin &) / (LogicalAggregate &)
  * (src/execution/physical_plan/plan_comparison_join.cpp:146, plan_aggregate.cpp:20 of the reference;
  * INTEGRATION.md §3).  The reference tree is read-only here, so this shim supplies the same call-out from
- * the outside: it DEFINES those two member functions under their Itanium-mangled names.  Loaded before
+ * the outside: it DEFINES those member functions (and CreatePlan(LogicalRecursiveCTE &), the walk closure's rule)
+ * under their Itanium-mangled names.  Loaded before
  * libduckdb (LD_PRELOAD, or dlopen(RTLD_GLOBAL) from the host process), the dynamic linker binds
  * libduckdb's own PLT calls to the definitions below; each one offers the logical operator to the rule
  * the extension registered (gg_plan_rule.cpp) and otherwise forwards to libduckdb's original.
@@ -30,13 +31,14 @@
 #define SYM_UPDATE "_ZN6duckdb21PhysicalPlanGenerator10CreatePlanERNS_13LogicalUpdateE"
 #define SYM_DISTINCT "_ZN6duckdb21PhysicalPlanGenerator10CreatePlanERNS_15LogicalDistinctE"
 #define SYM_PIPELINES "_ZN6duckdb8Executor14BuildPipelinesEPNS_16PhysicalOperatorEPNS_8PipelineE"
+#define SYM_RECURSIVE_CTE "_ZN6duckdb21PhysicalPlanGenerator10CreatePlanERNS_19LogicalRecursiveCTEE"
 
 typedef void *(*create_plan_fn)(void *ret_slot, void *generator, void *logical_op);
 
 static gg_plan_rule_fn g_rule[GG_PLAN_HOOK_KINDS];
 static create_plan_fn g_orig[GG_PLAN_HOOK_KINDS];
 static const char *const g_sym[GG_PLAN_HOOK_KINDS] = {SYM_JOIN, SYM_AGGR, SYM_INSERT, SYM_DELETE, SYM_UPDATE,
-                                                          SYM_DISTINCT, SYM_PIPELINES};
+                                                          SYM_DISTINCT, SYM_PIPELINES, SYM_RECURSIVE_CTE};
 
 void *gg_hook_create_plan_join(void *ret_slot, void *generator, void *op) __asm__(SYM_JOIN);
 void *gg_hook_create_plan_aggregate(void *ret_slot, void *generator, void *op) __asm__(SYM_AGGR);
@@ -44,6 +46,7 @@ void *gg_hook_create_plan_insert(void *ret_slot, void *generator, void *op) __as
 void *gg_hook_create_plan_delete(void *ret_slot, void *generator, void *op) __asm__(SYM_DELETE);
 void *gg_hook_create_plan_update(void *ret_slot, void *generator, void *op) __asm__(SYM_UPDATE);
 void *gg_hook_create_plan_distinct(void *ret_slot, void *generator, void *op) __asm__(SYM_DISTINCT);
+void *gg_hook_create_plan_recursive_cte(void *ret_slot, void *generator, void *op) __asm__(SYM_RECURSIVE_CTE);
 /* void Executor::BuildPipelines(PhysicalOperator *op, Pipeline *current): `this`, then the two pointers; no return slot */
 void gg_hook_build_pipelines(void *executor, void *op, void *current) __asm__(SYM_PIPELINES);
 
@@ -121,6 +124,10 @@ void *gg_hook_create_plan_distinct(void *ret_slot, void *generator, void *op) {
   return dispatch(GG_PLAN_HOOK_DISTINCT, (void *)gg_hook_create_plan_distinct, ret_slot, generator, op);
 }
 
+void *gg_hook_create_plan_recursive_cte(void *ret_slot, void *generator, void *op) {
+  return dispatch(GG_PLAN_HOOK_RECURSIVE_CTE, (void *)gg_hook_create_plan_recursive_cte, ret_slot, generator, op);
+}
+
 void gg_hook_build_pipelines(void *executor, void *op, void *current) {
   /* Only the call from Executor::Initialize arrives here: libduckdb's recursive calls of BuildPipelines are direct.
    * The rule therefore wraps the whole traversal: it calls the original itself (gg_plan_hook_original). */
@@ -134,7 +141,7 @@ void *gg_plan_hook_original(int kind) {
   static void *const self[GG_PLAN_HOOK_KINDS] = {
       (void *)gg_hook_create_plan_join,   (void *)gg_hook_create_plan_aggregate, (void *)gg_hook_create_plan_insert,
       (void *)gg_hook_create_plan_delete, (void *)gg_hook_create_plan_update,    (void *)gg_hook_create_plan_distinct,
-      (void *)gg_hook_build_pipelines};
+      (void *)gg_hook_build_pipelines,    (void *)gg_hook_create_plan_recursive_cte};
   if (kind < 0 || kind >= GG_PLAN_HOOK_KINDS) return NULL;
   return (void *)original(kind, self[kind]);
 }

@@ -19,7 +19,9 @@ enum {
   /* not a CreatePlan: Executor::BuildPipelines(PhysicalOperator *, Pipeline *) — the rule gets (executor, operator,
    * current pipeline) and returns non-zero if it built the operator's pipelines itself (gg_pipeline.cpp) */
   GG_PLAN_HOOK_PIPELINES = 6,
-  GG_PLAN_HOOK_KINDS = 7
+  /* CreatePlan(LogicalRecursiveCTE &): UNION ALL recursion over one keyed table (gg_plan_rule.cpp, PlanRecursiveWalks) */
+  GG_PLAN_HOOK_RECURSIVE_CTE = 7,
+  GG_PLAN_HOOK_KINDS = 8
 };
 
 /* A rule looks at the logical operator about to be planned.  To take it over it constructs a

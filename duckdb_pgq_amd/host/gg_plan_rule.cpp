@@ -2336,6 +2336,275 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 }
 
 //===--------------------------------------------------------------------===//
+// Recursive-CTE rule: UNION ALL recursion over one keyed table -> the walk closure
+//===--------------------------------------------------------------------===//
+// benchmark/ldbc/queries/bi-9.sql (post_all) and interactive-short-6.sql (chain):
+//
+//   WITH RECURSIVE cte(...) AS (<anchor>  UNION ALL  SELECT <arm columns> FROM T, cte WHERE T.key = cte.link [AND ...])
+//
+// The reference runs PhysicalRecursiveCTE, its arm's hash join rebuilt per level
+// (src/execution/operator/set/physical_recursive_cte.cpp:60-139).  Taken over when the arm is
+// PROJECTION <- [FILTER] <- COMPARISON_JOIN(INNER, one equality) of the CTE scan (optionally under a filter) with a
+// subplan T that does not read the CTE, and every arm column is the CTE column at its own position (carried from the
+// anchor), a column of T, a constant, or the CTE column at its own position plus an integer constant (a depth
+// counter).  The arm's column at the link's position must be a column of T (the next link).  A CTE-side predicate
+// `counter < K` (or <=) on a counter whose anchor value is a constant bounds the levels; any other CTE-side predicate
+// declines.  T and the anchor are planned by the reference's own planner and feed PhysicalGGWalkRowSinks.
+namespace {
+
+//! does the subtree read the CTE `index`?
+bool ReadsCte(LogicalOperator &op, idx_t index) {
+	if (op.type == LogicalOperatorType::LOGICAL_CTE_REF && ((LogicalCTERef &)op).cte_index == index) {
+		return true;
+	}
+	for (auto &child : op.children) {
+		if (ReadsCte(*child, index)) {
+			return true;
+		}
+	}
+	return false;
+}
+
+//! the CTE scan under a side of the arm's join (and the filters over it)
+bool CteSide(LogicalOperator &op, idx_t index, vector<Expression *> &filters) {
+	if (op.type == LogicalOperatorType::LOGICAL_CTE_REF) {
+		return ((LogicalCTERef &)op).cte_index == index;
+	}
+	if (op.type == LogicalOperatorType::LOGICAL_FILTER && op.children.size() == 1 &&
+	    ((LogicalFilter &)op).projection_map.empty() && CteSide(*op.children[0], index, filters)) {
+		for (auto &expr : op.expressions) {
+			filters.push_back(expr.get());
+		}
+		return true;
+	}
+	return false;
+}
+
+bool IsIntegral(const LogicalType &type) {
+	return type.IsIntegral() && type.id() != LogicalTypeId::HUGEINT;
+}
+
+} // namespace
+
+// recursive CTEs under a `min(...) GROUP BY` the shortest-path rule declined (PlanAggregate, below), of the plan that
+// g_left_alone_generator makes (RuleEntryFor clears the set when another generator — another statement — comes)
+static thread_local std::unordered_set<const LogicalOperator *> g_ctes_left_alone;
+static thread_local const void *g_left_alone_generator = nullptr;
+// > 0 while PlanRecursiveWalks plans the subplans under its sinks: every rule declines (RuleEntryFor)
+static thread_local int g_rules_suspended = 0;
+struct RulesSuspended {
+	RulesSuspended() {
+		g_rules_suspended++;
+	}
+	~RulesSuspended() {
+		g_rules_suspended--;
+	}
+};
+
+unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
+	auto trace = [](const char *why) {
+		if (std::getenv("GG_RULE_TRACE")) {
+			fprintf(stderr, "[gg] recursive walks declined: %s\n", why);
+		}
+		return nullptr;
+	};
+	if (g_ctes_left_alone.erase(&op)) {
+		return trace("min(...) GROUP BY over it: the shortest-path rule's shape");
+	}
+	if (!op.union_all || op.children.size() != 2 || !g_plan_context || !g_plan_generator) {
+		return trace("not UNION ALL");
+	}
+	if (std::getenv("GG_NO_PIPELINE_SINKS") || !gg_pipeline_rule_registered() || !g_plan_generator->rec_ctes.empty()) {
+		return trace("no pipeline sinks, or inside another recursive CTE");
+	}
+	const idx_t n_cols = op.column_count;
+	auto &arm = *op.children[1];
+	if (arm.type != LogicalOperatorType::LOGICAL_PROJECTION || arm.children.size() != 1 ||
+	    arm.expressions.size() != n_cols || op.types.size() != n_cols) {
+		return trace("arm is not a projection");
+	}
+	auto node = arm.children[0].get();
+	vector<Expression *> join_filters; // over the join's output
+	if (node->type == LogicalOperatorType::LOGICAL_FILTER) {
+		if (!((LogicalFilter &)*node).projection_map.empty() || node->children.size() != 1) {
+			return trace("filter with a projection map");
+		}
+		for (auto &expr : node->expressions) {
+			join_filters.push_back(expr.get());
+		}
+		node = node->children[0].get();
+	}
+	if (node->type != LogicalOperatorType::LOGICAL_COMPARISON_JOIN) {
+		return trace("no join in the arm");
+	}
+	auto &join = (LogicalComparisonJoin &)*node;
+	if (join.join_type != JoinType::INNER || join.children.size() != 2 || join.conditions.size() != 1 ||
+	    join.conditions[0].comparison != ExpressionType::COMPARE_EQUAL || join.conditions[0].null_values_are_equal ||
+	    join.conditions[0].left->type != ExpressionType::BOUND_REF ||
+	    join.conditions[0].right->type != ExpressionType::BOUND_REF) {
+		return trace("not an inner join on one equality");
+	}
+	vector<Expression *> cte_filters; // over the CTE's columns
+	idx_t cte_child;
+	if (CteSide(*join.children[0], op.table_index, cte_filters)) {
+		cte_child = 0;
+	} else if (CteSide(*join.children[1], op.table_index, cte_filters)) {
+		cte_child = 1;
+	} else {
+		return trace("the join does not scan the CTE directly");
+	}
+	const idx_t t_child = 1 - cte_child;
+	auto &table = *join.children[t_child];
+	if (ReadsCte(table, op.table_index)) {
+		return trace("the joined table reads the CTE");
+	}
+	// the join's output column j -> (child, column of that child)
+	const idx_t left_width = join.left_projection_map.empty() ? join.children[0]->types.size() : join.left_projection_map.size();
+	auto join_column = [&](idx_t j, idx_t &child, idx_t &column) {
+		child = j < left_width ? 0 : 1;
+		const idx_t k = j < left_width ? j : j - left_width;
+		auto &map = child == 0 ? join.left_projection_map : join.right_projection_map;
+		column = map.empty() ? k : (k < map.size() ? map[k] : INVALID_INDEX);
+		return column < join.children[child]->types.size();
+	};
+	const idx_t link = ((BoundReferenceExpression &)*(cte_child == 0 ? join.conditions[0].left : join.conditions[0].right)).index;
+	const idx_t key = ((BoundReferenceExpression &)*(cte_child == 0 ? join.conditions[0].right : join.conditions[0].left)).index;
+	if (link >= n_cols || key >= table.types.size() || !IsIntegral(op.types[link]) || !IsIntegral(table.types[key])) {
+		return trace("link or key is not an integer column");
+	}
+	// ---- the arm's columns
+	auto input = make_shared<GGWalkInput>();
+	input->link_column = link;
+	input->key_column = key;
+	input->columns.resize(n_cols);
+	for (idx_t c = 0; c < n_cols; c++) {
+		auto &expr = *arm.expressions[c];
+		auto &spec = input->columns[c];
+		if (expr.return_type != op.types[c]) {
+			return trace("an arm column changes type");
+		}
+		idx_t ref, child, column;
+		int64_t step;
+		if (ReferenceIndex(expr, ref)) {
+			if (!join_column(ref, child, column)) {
+				return trace("unresolved arm column");
+			}
+			if (child == cte_child) {
+				if (column != c) {
+					return trace("a CTE column moves to another position");
+				}
+				spec.kind = GGWalkColumn::CARRIED;
+			} else {
+				spec.kind = GGWalkColumn::TABLE;
+				spec.index = column;
+			}
+		} else if (expr.type == ExpressionType::VALUE_CONSTANT) {
+			spec.kind = GGWalkColumn::CONSTANT;
+			spec.constant = ((BoundConstantExpression &)expr).value;
+		} else if (expr.GetExpressionClass() == ExpressionClass::BOUND_FUNCTION && IsIntegral(expr.return_type) &&
+		           ((BoundFunctionExpression &)expr).function.name == "+" &&
+		           ((BoundFunctionExpression &)expr).children.size() == 2) {
+			auto &add = (BoundFunctionExpression &)expr;
+			idx_t side = ReferenceIndex(*add.children[0], ref) ? 0 : 1;
+			if (!ReferenceIndex(*add.children[side], ref) || !IntegerConstant(*add.children[1 - side], step) ||
+			    !join_column(ref, child, column) || child != cte_child || column != c) {
+				return trace("an arm expression other than counter + constant");
+			}
+			spec.kind = GGWalkColumn::COUNTER;
+			spec.step = step;
+		} else {
+			return trace("an arm expression of another kind");
+		}
+	}
+	if (input->columns[link].kind != GGWalkColumn::TABLE || !IsIntegral(table.types[input->columns[link].index])) {
+		return trace("the next link is not an integer column of the table");
+	}
+	input->next_column = input->columns[link].index;
+	// ---- CTE-side predicates: `counter < K` only
+	// (CTE column, predicate) pairs; the logical plan is only read here — the rule may still decline
+	vector<std::pair<idx_t, Expression *>> bounds;
+	for (auto filter : cte_filters) {
+		idx_t column;
+		if (filter->GetExpressionClass() != ExpressionClass::BOUND_COMPARISON ||
+		    !ReferenceIndex(*((BoundComparisonExpression &)*filter).left, column)) {
+			return trace("a CTE-side predicate other than counter < K");
+		}
+		bounds.emplace_back(column, filter);
+	}
+	for (auto filter : join_filters) { // a predicate above the join that reads the CTE side only
+		idx_t ref, child, column;
+		if (filter->GetExpressionClass() != ExpressionClass::BOUND_COMPARISON ||
+		    !ReferenceIndex(*((BoundComparisonExpression &)*filter).left, ref) || !join_column(ref, child, column) ||
+		    child != cte_child) {
+			return trace("a predicate above the join on the table's columns");
+		}
+		bounds.emplace_back(column, filter);
+	}
+	for (auto &entry : bounds) {
+		const idx_t column = entry.first;
+		auto filter = entry.second;
+		int64_t bound, start;
+		if (filter->type != ExpressionType::COMPARE_LESSTHAN && filter->type != ExpressionType::COMPARE_LESSTHANOREQUALTO) {
+			return trace("a CTE-side predicate other than counter < K");
+		}
+		auto &cmp = (BoundComparisonExpression &)*filter;
+		if (column >= n_cols || !IntegerConstant(*cmp.right, bound) ||
+		    input->columns[column].kind != GGWalkColumn::COUNTER || input->columns[column].step <= 0) {
+			return trace("a CTE-side predicate other than counter < K");
+		}
+		// the counter of a level-L row is start + step * L: it is expanded iff that is < K, so the deepest level is the
+		// first L where it is not
+		auto &anchor = *op.children[0];
+		if (anchor.type != LogicalOperatorType::LOGICAL_PROJECTION || column >= anchor.expressions.size() ||
+		    !IntegerConstant(*anchor.expressions[column], start)) {
+			return trace("a counter whose anchor value is not a constant");
+		}
+		const int64_t limit = filter->type == ExpressionType::COMPARE_LESSTHAN ? bound : bound + 1;
+		const int64_t step = input->columns[column].step;
+		const int64_t levels = limit <= start ? 0 : (limit - start + step - 1) / step;
+		if (levels >= (1 << 30)) {
+			return trace("a level bound too large");
+		}
+		input->max_levels = input->max_levels < 0 ? (int)levels : std::min(input->max_levels, (int)levels);
+	}
+	// ---- plan: the anchor and the table by the reference's planner, under the sinks
+	string description = "link=#" + std::to_string(link) + " key=#" + std::to_string(key) + " next=#" +
+	                     std::to_string(input->next_column) +
+	                     (input->max_levels >= 0 ? " max_levels=" + std::to_string(input->max_levels) : string());
+	input->description = description;
+	const auto types = op.types;
+	const auto cardinality = op.estimated_cardinality;
+	// Both are planned with every gg rule suspended: their plans run under the walk sinks, whose pipelines are built by
+	// the reference's own traversal (gg_pipeline.cpp), which does not know a graph scan with sinks of its own — another
+	// recursive CTE, a join chain or a count inside them stays with the reference's operators.
+	auto generator = g_plan_generator;
+	unique_ptr<PhysicalOperator> anchor_plan, table_plan;
+	{
+		RulesSuspended suspended;
+		anchor_plan = generator->CreatePlan(move(op.children[0]));
+		table_plan = generator->CreatePlan(move(join.children[t_child]));
+	}
+	g_plan_generator = generator;
+	auto slot = make_shared<GGGraphSlot>();
+	auto scan = make_unique<PhysicalGGGraphScan>(
+	    types, "GG_RECURSIVE_WALKS", description, slot,
+	    [types, input, cardinality](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    return make_unique<PhysicalGGRecursiveWalks>(types, move(graph), input, cardinality);
+	    },
+	    false, cardinality);
+	auto anchor_sink = make_unique<PhysicalGGWalkRowSink>(input, slot, false, anchor_plan->types,
+	                                                      anchor_plan->estimated_cardinality);
+	anchor_sink->children.push_back(move(anchor_plan));
+	auto table_sink = make_unique<PhysicalGGWalkRowSink>(input, slot, true, table_plan->types,
+	                                                     table_plan->estimated_cardinality);
+	table_sink->children.push_back(move(table_plan));
+	scan->children.push_back(move(anchor_sink)); // (built in this order: the table's sink finds the anchor sunk)
+	scan->children.push_back(move(table_sink));
+	g_rules_fired++;
+	return move(scan);
+}
+
+//===--------------------------------------------------------------------===//
 // Distinct rule: the dedupe above a UNION of 1-hop and 2-hop endpoints of one source
 //===--------------------------------------------------------------------===//
 // benchmark/ldbc/queries/interactive-complex-3.sql:3-12 (and -5, -6, -9, -11): the friends of a person UNION the
@@ -2586,19 +2855,46 @@ unique_ptr<PhysicalOperator> PlanDistinctUnion(LogicalDistinct &op) {
 	return move(projection);
 }
 
+//! `min(x) GROUP BY a, b` directly over a recursive CTE that the shortest-path rule declined (bi-10's shape with UNION
+//! ALL, another bound, ...): the recursive-CTE rule leaves that CTE to the reference, so the statement keeps the plan it
+//! had before that rule existed (the shortest-path family is the BFS rule's to take or not)
+
+void LeaveShortestPathCteAlone(LogicalAggregate &op) {
+	if (op.groups.size() != 2 || op.expressions.size() != 1 || op.children.size() != 1 ||
+	    op.expressions[0]->GetExpressionClass() != ExpressionClass::BOUND_AGGREGATE ||
+	    ((BoundAggregateExpression &)*op.expressions[0]).function.name != "min") {
+		return;
+	}
+	auto node = op.children[0].get();
+	while (node->type == LogicalOperatorType::LOGICAL_PROJECTION && node->children.size() == 1) {
+		node = node->children[0].get();
+	}
+	if (node->type == LogicalOperatorType::LOGICAL_RECURSIVE_CTE) {
+		g_ctes_left_alone.insert(node);
+	}
+}
+
 unique_ptr<PhysicalOperator> PlanAggregate(LogicalAggregate &op) {
 	if (auto plan = PlanCountOverJoinChain(op)) {
 		return plan;
 	}
-	return PlanShortestPath(op);
+	auto plan = PlanShortestPath(op);
+	if (!plan) {
+		LeaveShortestPathCteAlone(op);
+	}
+	return plan;
 }
 
 //! The rule RULE offered the logical operator, for the connection `context` (dependencies and rec_ctes are public
 //! members of the generator).
 template <class OP, unique_ptr<PhysicalOperator> (*RULE)(OP &)>
 int RuleEntryFor(ClientContext &context, void *ret_slot, void *generator, void *logical_operator) {
-	if (!GGGetConnectionFlags(context).rules) {
-		return 0; // PRAGMA enable_gpu_graph was not issued on THIS connection
+	if (!GGGetConnectionFlags(context).rules || g_rules_suspended) {
+		return 0; // PRAGMA enable_gpu_graph was not issued on THIS connection, or a subplan under walk sinks is planned
+	}
+	if (generator != g_left_alone_generator) {
+		g_ctes_left_alone.clear();
+		g_left_alone_generator = generator;
 	}
 	unique_ptr<PhysicalOperator> plan;
 	g_plan_tables.clear();
@@ -2735,6 +3031,10 @@ void GGRegisterPlanRules(ClientContext &context) {
 	reg(GG_PLAN_HOOK_JOIN, RuleEntry<LogicalComparisonJoin, PlanJoin>);
 	reg(GG_PLAN_HOOK_AGGREGATE, RuleEntry<LogicalAggregate, PlanAggregate>);
 	reg(GG_PLAN_HOOK_DISTINCT, RuleEntry<LogicalDistinct, PlanDistinctUnion>);
+	auto kinds = (int (*)())dlsym(RTLD_DEFAULT, "gg_plan_hook_kinds");
+	if (kinds && kinds() > GG_PLAN_HOOK_RECURSIVE_CTE) { // (a shim built before it knew this hook: not offered)
+		reg(GG_PLAN_HOOK_RECURSIVE_CTE, RuleEntry<LogicalRecursiveCTE, PlanRecursiveWalks>);
+	}
 	GGRegisterPipelineRule();
 	reg(GG_PLAN_HOOK_INSERT, WriteObserver<LogicalInsert>);
 	reg(GG_PLAN_HOOK_DELETE, WriteObserver<LogicalDelete>);

@@ -38,6 +38,10 @@
  *        <- the six monitoredBy hash joins of benchmark/trainbenchmark/queries/connectedsegments.sql:1-25
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
+ *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
+ *        <- PhysicalRecursiveCTE over a UNION ALL arm that joins the CTE with one table (the join rebuilt per level)
+ *                                                               src/execution/operator/set/physical_recursive_cte.cpp:60-139
+ *           (the post_all / chain reply trees of benchmark/ldbc/queries/bi-9.sql, interactive-short-6.sql)
  *
  * Conventions
  *   - every int-returning function returns GG_OK (0) or a negative GG_ERR_*; the message is
@@ -300,6 +304,31 @@ int gg_bfs64_pairs_packed(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids
  * contribute nothing.  Fetch with gg_result_rows(res, 1, &n) / gg_result_fetch(res, 1, offset, n, cols[2], &got). */
 int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int k_max,
                       gg_result **out_result);
+
+/* Every walk from the seeds, to no fixed depth — the rows a UNION ALL recursive CTE adds to its anchor when its arm joins
+ * the CTE's link column with a table's key column and carries a column of the table forward as the next link
+ * (benchmark/ldbc/queries/bi-9.sql post_all, interactive-short-6.sql chain), which the reference computes by re-running
+ * the arm's pipeline, hash-join build included, once per level (src/execution/operator/set/physical_recursive_cte.cpp:60-139).
+ * The table's rows are the CSR's edges key -> next, built with edge rowids kept (gg_ctx_set_edge_rowid(ctx, 1)); seeds
+ * are looked up as gg_csr_lookup does, and a seed that is not a vertex has no walks.  One row per walk of L >= 1 edges:
+ * (index into seed_ids of its seed, rowid of its last edge as staged, L).  Rows come by level; inside a level in the
+ * order of their parent rows (level 1: of the seeds), then in CSR order (the append order of the edge rows) inside the
+ * parent's vertex row.
+ * max_levels >= 0: walks of at most that many edges; < 0: until a level is empty.  An unbounded run in which a level
+ * deeper than the vertex count is not empty has met a cycle — the reference would recurse until memory runs out — and
+ * fails with GG_ERR_STATE.  That test costs V + 1 levels, each a few launches and one host round trip: on a graph of many
+ * vertices a reachable cycle is a long run before the error (or a level of 2^32 walks, or the pool running out, comes
+ * first) — a caller that may meet cycles bounds max_levels.  A level of 2^32 walks or more fails with GG_ERR_TOO_LARGE;
+ * a shard CSR with GG_ERR_STATE.
+ * The result answers gg_walk_closure_levels / gg_walk_closure_fetch (not gg_result_rows / gg_result_fetch). */
+int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, uint64_t n_seeds, int max_levels,
+                    gg_result **out_result);
+/* *n_levels = the deepest level L with walks; rows_per_level[L - 1] = walks of L edges, for the first `capacity`. */
+int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
+/* Copy rows [offset, offset+max_rows) of the closure, in row order, into host arrays of >= max_rows entries (level may
+ * be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
+int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_index,
+                          int64_t *edge_rowid, int32_t *level, uint32_t *n_out);
 
 /* ---- graph-sharded 64-lane BFS (one shard of the graph per GPU) ------------------------------- */
 /* The layout north_star names for graphs that do not fit one GPU: `shard` comes from
