@@ -182,6 +182,8 @@ struct gg_ctx {
   bool mirror_pairs = true;     // GG_MIRROR_PAIRS=0 at context creation: whole builds and the endpoint set never pair row i
                                 // with row i + E/2 (gg_csr_fast.hip, k_set_insert2); results are the same either way
   uint64_t max_grid_tiles = 0;  // gg_debug_max_grid_tiles: workgroups per expansion launch (0: the hardware bound)
+  int reach_visited_mode = 0;   // gg_debug_reach_visited: 0 the budget decides, 1 bitmap, 2 hash set (gg_reach.hip)
+  uint64_t reach_hash_slots = 0;  // gg_debug_reach_visited: the hash set's first capacity (0: from the seed count)
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;
@@ -278,6 +280,9 @@ struct gg_result {
   std::vector<uint64_t> level_rows;  // level_rows[L - 1]: walks of L edges
   int64_t *walk_seed = nullptr;      // device: index into the seed list of the walk's seed
   int64_t *walk_rowid = nullptr;     // device: rowid of the walk's last edge (as staged)
+  // gg_reach_closure (reach: the same fields): level_rows[L - 1] new (class, vertex) rows of level L, walk_seed their
+  // classes, walk_rowid their vertex ids
+  bool reach = false;
 };
 
 namespace gg {

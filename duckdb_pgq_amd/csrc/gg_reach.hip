@@ -1,0 +1,344 @@
+// gg_reach.hip — reachability closure: every (class, vertex) reachable from a list of seeds, each pair once.
+//
+// Replaces the reference's PhysicalRecursiveCTE over a UNION (not UNION ALL) arm that joins the CTE with one table on
+// one column (src/execution/operator/set/physical_recursive_cte.cpp:47-70 ProbeHT / Sink: every produced row is probed
+// against a GroupedAggregateHashTable of every row emitted so far and only new groups are kept; :75-139 the loop, the
+// arm's hash join rebuilt per level).  The table's rows are the CSR's edges key -> next; a CTE row is (class, vertex):
+// the class stands for the columns the arm carries unchanged, the vertex for the link.  A multi-source BFS whose
+// visited set is keyed by (class, vertex):
+//   level 0   the frontier is every seed (class, dense id); the visited set holds the seeds marked seen (their anchor
+//             row equals an arm row: gg_reach_closure's seed_seen)
+//   level L   k_reach_deg       degree of every frontier entry's vertex (a gather of off[v], off[v+1])
+//             scan              exclusive prefix of the degrees (scan_exclusive_u64; one 8-byte read of the total)
+//             tile_partition    the entry each tile of XT children starts in (make_tiles_u64)
+//             k_reach_expand    one thread per child: test-and-set (class, nbr) in the visited set; the winners of a
+//                               wave append with ONE returning atomic add (ballot + popcount), not one per lane
+//             (one 4-byte read of the number of new rows)
+//             sort              the new rows by (class, vertex index): a stable radix sort by vertex, then by class
+//                               (sort_pairs_by_key; the second pass is skipped for one class) — so a level's rows do
+//                               not depend on the order the atomics arrived in
+//   The sorted new rows are level L's rows and level L + 1's frontier; the first empty level ends the recursion (each
+//   (class, vertex) enters the visited set once, so it always ends, cycles included).
+// Visited set, two forms (same rows, same order):
+//   bitmap    n_classes x V bits, claimed with a returning atomicOr; taken while that is at most REACH_BITMAP_MAX_BITS
+//             bits and a quarter of the device's free memory (single-source reachability, a tag-class hierarchy)
+//   hash set  open addressing over 64-bit keys class << 32 | vertex, claimed with a 64-bit atomicCAS.  Before a level
+//             expands M children the table holds at least 2 x (visited + M) slots, so an insert always finds an empty
+//             slot; it grows by a rebuild from the seen seeds plus every level's rows, which are exactly the visited set.
+// k_reach_emit finally writes the int64 (class, vertex id) columns a fetch reads.
+#include <algorithm>
+
+#include "gg_internal.h"
+
+using namespace gg;
+
+namespace {
+
+// the bitmap form's budget: 2^33 bits = 1 GiB (and never more than a quarter of the free device memory); above it —
+// e.g. 10 M classes over 100 M vertices — the hash set, whose size follows the rows actually reached
+constexpr uint64_t REACH_BITMAP_MAX_BITS = 1ull << 33;
+constexpr unsigned long long REACH_EMPTY = ~0ull;  // no key: a vertex index is never INVALID_U32
+constexpr uint64_t REACH_MIN_SLOTS = 1024;
+
+struct Visited {
+  uint32_t *bits = nullptr;           // bitmap form: bit class * V + vertex
+  uint64_t V = 0;
+  unsigned long long *slots = nullptr;  // hash form: cap slots of class << 32 | vertex
+  uint64_t cap = 0;
+};
+
+// true for the one caller that put (c, v) into the set.  Each form reads first and only does the atomic if the entry
+// may still be absent: on a mirrored graph most children are visited already.
+__device__ __forceinline__ bool claim(const Visited &vs, uint32_t c, uint32_t v) {
+  if (vs.bits) {
+    const uint64_t b = (uint64_t)c * vs.V + v;
+    const uint32_t mask = 1u << (b & 31);
+    if (__atomic_load_n(&vs.bits[b >> 5], __ATOMIC_RELAXED) & mask) return false;
+    return !(atomicOr(&vs.bits[b >> 5], mask) & mask);
+  }
+  const unsigned long long key = ((unsigned long long)c << 32) | v;
+  uint64_t s = __umul64hi(fmix64(key), vs.cap);
+  while (true) {
+    unsigned long long old = __atomic_load_n(&vs.slots[s], __ATOMIC_RELAXED);
+    if (old == REACH_EMPTY) old = atomicCAS(&vs.slots[s], REACH_EMPTY, key);
+    if (old == REACH_EMPTY) return true;
+    if (old == key) return false;
+    s = s + 1 == vs.cap ? 0 : s + 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reach_deg(const uint32_t *__restrict__ off, const uint32_t *__restrict__ vtx,
+                                                   uint64_t n, uint64_t *__restrict__ deg) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t v = vtx[i];
+    deg[i] = v == INVALID_U32 ? 0 : (uint64_t)(off[v + 1] - off[v]);
+  }
+}
+
+// (cls[i], vtx[i]) into the set, i < n (seen: only where seen[i] != 0; vertex INVALID_U32: skipped) — the seen seeds at
+// the start, and every visited entry again when the hash set is rebuilt larger
+__global__ __launch_bounds__(256) void k_reach_insert(const uint32_t *__restrict__ cls, const uint32_t *__restrict__ vtx,
+                                                      const uint8_t *__restrict__ seen, uint64_t n, Visited vs) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+    if ((!seen || seen[i]) && vtx[i] != INVALID_U32) claim(vs, cls[i], vtx[i]);
+  }
+}
+
+__global__ __launch_bounds__(XT) void k_reach_expand(const uint32_t *__restrict__ off, const uint32_t *__restrict__ nbr,
+                                                     const uint32_t *__restrict__ fcls, const uint32_t *__restrict__ fvtx,
+                                                     const uint64_t *__restrict__ foff, uint64_t n_entries, uint64_t M,
+                                                     const uint32_t *__restrict__ tile_entry, Visited vs,
+                                                     uint32_t *__restrict__ count, uint32_t *__restrict__ out_cls,
+                                                     uint32_t *__restrict__ out_vtx) {
+  __shared__ uint64_t s_foff[XT + 1];
+  const uint64_t p = (uint64_t)blockIdx.x * XT + threadIdx.x;  // foff[0] == 0: an exclusive scan
+  const uint64_t i0 = tile_entry[blockIdx.x];
+  load_window(s_foff, foff, n_entries, i0);
+  __syncthreads();
+  bool won = false;
+  uint32_t c = 0, w = 0;
+  if (p < M) {  // (no early return: the whole wave takes part in the ballot below)
+    uint64_t k;
+    const uint64_t i = locate_entry(s_foff, foff, n_entries, i0, p, &k);
+    c = fcls[i];
+    w = nbr[off[fvtx[i]] + (uint32_t)k];
+    won = claim(vs, c, w);
+  }
+  const uint64_t winners = __ballot(won);
+  if (!winners) return;
+  const int lane = threadIdx.x & 63, leader = __ffsll((unsigned long long)winners) - 1;
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(winners));
+  base = __shfl(base, leader, 64);
+  if (won) {
+    const uint32_t at = base + (uint32_t)__popcll(winners & ((1ull << lane) - 1));
+    out_cls[at] = c;
+    out_vtx[at] = w;
+  }
+}
+
+// rows of one level -> the result's int64 columns at their offset
+__global__ __launch_bounds__(256) void k_reach_emit(const uint32_t *__restrict__ cls, const uint32_t *__restrict__ vtx,
+                                                    uint64_t n, const int64_t *__restrict__ vid,
+                                                    int64_t *__restrict__ cls_out, int64_t *__restrict__ vid_out) {
+  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+    cls_out[r] = (int64_t)cls[r];
+    vid_out[r] = vid[vtx[r]];
+  }
+}
+
+dim3 stride_grid(gg_ctx *ctx, uint64_t n) {
+  const uint64_t want = (n + 255) / 256, cap = (uint64_t)ctx->num_cus * 32;
+  return dim3((unsigned)(want < cap ? (want ? want : 1) : cap));
+}
+
+int bits_for(uint64_t n) {  // bits of the largest value below n
+  int b = 1;
+  while (b < 64 && (1ull << b) < n) b++;
+  return b;
+}
+
+struct Level {
+  uint32_t *cls, *vtx;
+  uint64_t n;
+};
+
+// a hash set of `cap` slots holding the seen seeds and every level's rows so far
+int hash_build(gg_ctx *ctx, uint64_t cap, const uint32_t *seed_cls, const uint32_t *seed_dense, const uint8_t *seen,
+               uint64_t n_seeds, const std::vector<Level> &levels, Visited *vs) {
+  if (vs->slots) ctx->dev_free(vs->slots);
+  vs->slots = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&vs->slots, cap * sizeof(unsigned long long)));
+  vs->cap = cap;
+  GG_HIP(hipMemsetAsync(vs->slots, 0xFF, cap * sizeof(unsigned long long), ctx->stream));
+  if (seen && n_seeds)
+    GG_LAUNCH(ctx, "reach_insert", k_reach_insert, stride_grid(ctx, n_seeds), dim3(256), 0, seed_cls, seed_dense, seen,
+              n_seeds, *vs);
+  for (const Level &l : levels)
+    GG_LAUNCH(ctx, "reach_insert", k_reach_insert, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx,
+              (const uint8_t *)nullptr, l.n, *vs);
+  return GG_OK;
+}
+
+}  // namespace
+
+extern "C" int gg_debug_reach_visited(gg_ctx *ctx, int mode, uint64_t hash_initial_slots) {
+  if (!ctx || mode < 0 || mode > 2) return GG_ERR_INVALID_ARG;
+  ctx->reach_visited_mode = mode;
+  ctx->reach_hash_slots = hash_initial_slots;
+  return GG_OK;
+}
+
+extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, const uint32_t *seed_class,
+                                const uint8_t *seed_seen, uint64_t n_seeds, uint32_t n_classes, gg_result **out) {
+  ApiScope scope(ctx);
+  if (!out || (n_seeds && (!seed_ids || !seed_class))) return GG_ERR_INVALID_ARG;
+  *out = nullptr;
+  GG_TRY(check_whole_csr(ctx, csr));
+  if (n_seeds >= (1ull << 32)) {  // (classes: n_classes is a uint32_t, so every class index fits a key's high half)
+    set_error("gg_reach_closure: %llu seeds do not fit a 32-bit seed index", (unsigned long long)n_seeds);
+    return GG_ERR_TOO_LARGE;
+  }
+  uint64_t n_seen = 0;
+  for (uint64_t i = 0; i < n_seeds; i++) {
+    if (seed_class[i] >= n_classes) {
+      set_error("gg_reach_closure: seed %llu has class %u of %u", (unsigned long long)i, seed_class[i], n_classes);
+      return GG_ERR_INVALID_ARG;
+    }
+    n_seen += seed_seen && seed_seen[i];
+  }
+  GG_HIP(hipSetDevice(ctx->device));
+  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
+  res->reach = true;
+  uint32_t *seed_dense = nullptr, *seed_cls = nullptr;
+  uint8_t *seen = nullptr;
+  GG_TRY(upload_ids(ctx, csr, seed_ids, n_seeds, &seed_dense));
+  GG_TRY(ctx->dev_alloc((void **)&seed_cls, (n_seeds ? n_seeds : 1) * sizeof(uint32_t)));
+  if (n_seeds) GG_HIP(hipMemcpyAsync(seed_cls, seed_class, n_seeds * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+  if (n_seen) {
+    GG_TRY(ctx->dev_alloc((void **)&seen, n_seeds));
+    GG_HIP(hipMemcpyAsync(seen, seed_seen, n_seeds, hipMemcpyHostToDevice, ctx->stream));
+  }
+
+  // ---- the visited set's form
+  Visited vs;
+  vs.V = csr->V;
+  const uint64_t bits = (uint64_t)n_classes * csr->V;
+  bool bitmap = ctx->reach_visited_mode == 1;
+  if (ctx->reach_visited_mode == 0) {
+    size_t free_bytes = 0, total_bytes = 0;
+    GG_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+    bitmap = bits <= REACH_BITMAP_MAX_BITS && bits / 8 <= free_bytes / 4;
+  }
+  std::vector<Level> levels;
+  if (bitmap) {
+    const uint64_t words = (bits + 31) / 32;
+    GG_TRY(ctx->dev_alloc((void **)&vs.bits, (words ? words : 1) * sizeof(uint32_t)));
+    GG_HIP(hipMemsetAsync(vs.bits, 0, (words ? words : 1) * sizeof(uint32_t), ctx->stream));
+    if (n_seen)
+      GG_LAUNCH(ctx, "reach_insert", k_reach_insert, stride_grid(ctx, n_seeds), dim3(256), 0, seed_cls, seed_dense,
+                (const uint8_t *)seen, n_seeds, vs);
+  } else {
+    uint64_t cap = ctx->reach_hash_slots ? ctx->reach_hash_slots : std::max<uint64_t>(2 * n_seeds, REACH_MIN_SLOTS);
+    cap = std::max<uint64_t>(cap, 2 * n_seen + 1);
+    GG_TRY(hash_build(ctx, cap, seed_cls, seed_dense, seen, n_seeds, levels, &vs));
+  }
+  uint64_t visited = n_seen;  // an upper bound of the set's entries (a seen seed may repeat or be no vertex)
+
+  uint32_t *count = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&count, sizeof(uint32_t)));
+  const uint32_t *fcls = seed_cls, *fvtx = seed_dense;
+  uint64_t n_parent = n_seeds;
+  for (int level = 1; n_parent > 0; level++) {
+    uint64_t *foff = nullptr, *total = nullptr;
+    GG_TRY(ctx->dev_alloc((void **)&foff, (n_parent + 1) * sizeof(uint64_t)));
+    GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
+    GG_LAUNCH(ctx, "reach_deg", k_reach_deg, stride_grid(ctx, n_parent), dim3(256), 0, csr->off, fvtx, n_parent, foff);
+    GG_TRY(scan_exclusive_u64(ctx, foff, foff, n_parent, total));
+    GG_HIP(hipMemcpyAsync(foff + n_parent, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+    GG_TRY(scan_error_fetch(ctx));
+    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t M = ctx->pin_scratch[0];
+    GG_TRY(scan_error_test(ctx));
+    if (M == 0) break;
+    if (M >= (1ull << 32)) {
+      set_error("gg_reach_closure: level %d has %llu children (2^32 or more)", level, (unsigned long long)M);
+      return GG_ERR_TOO_LARGE;
+    }
+    // an insert must always find an empty slot; a rebuild sizes the table at twice the bound, so a closure that keeps
+    // growing rebuilds every other level at most (each rebuild re-inserts every visited entry — on the 10^8-message
+    // forest the rebuilds took 6.0 ms of 48 when the table grew only to the bound, 3.4 of 41 at twice it)
+    if (!bitmap && vs.cap < 2 * (visited + M))
+      GG_TRY(hash_build(ctx, std::max(4 * (visited + M), 2 * vs.cap), seed_cls, seed_dense, seen, n_seeds, levels, &vs));
+    uint32_t *tile_entry = nullptr;
+    uint64_t n_tiles = 0;
+    GG_TRY(make_tiles_u64(ctx, foff, n_parent, M, &tile_entry, &n_tiles));
+    uint32_t *new_cls = nullptr, *new_vtx = nullptr;
+    GG_TRY(ctx->dev_alloc((void **)&new_cls, M * sizeof(uint32_t)));
+    GG_TRY(ctx->dev_alloc((void **)&new_vtx, M * sizeof(uint32_t)));
+    GG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+    GG_LAUNCH(ctx, "reach_expand", k_reach_expand, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, fcls, fvtx,
+              foff, n_parent, M, tile_entry, vs, count, new_cls, new_vtx);
+    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP(hipStreamSynchronize(ctx->stream));
+    const uint64_t n_new = *(const uint32_t *)ctx->pin_scratch;
+    ctx->dev_free(tile_entry);
+    ctx->dev_free(total);
+    ctx->dev_free(foff);
+    if (n_new == 0) {
+      ctx->dev_free(new_vtx);
+      ctx->dev_free(new_cls);
+      break;
+    }
+    // (class, vertex index) ascending: by vertex, then stably by class
+    Level l{nullptr, nullptr, n_new};
+    GG_TRY(ctx->dev_alloc((void **)&l.cls, n_new * sizeof(uint32_t)));
+    GG_TRY(ctx->dev_alloc((void **)&l.vtx, n_new * sizeof(uint32_t)));
+    GG_TRY(sort_pairs_by_key(ctx, new_vtx, new_cls, n_new, bits_for(csr->V), l.vtx, l.cls));
+    if (n_classes > 1) {
+      GG_TRY(sort_pairs_by_key(ctx, l.cls, l.vtx, n_new, bits_for(n_classes), new_cls, new_vtx));
+      std::swap(l.cls, new_cls);
+      std::swap(l.vtx, new_vtx);
+    }
+    ctx->dev_free(new_vtx);
+    ctx->dev_free(new_cls);
+    levels.push_back(l);
+    res->level_rows.push_back(n_new);
+    visited += n_new;
+    fcls = l.cls;
+    fvtx = l.vtx;
+    n_parent = n_new;
+  }
+
+  uint64_t n_rows = 0;
+  for (uint64_t m : res->level_rows) n_rows += m;
+  GG_TRY(ctx->dev_alloc((void **)&res->walk_seed, (n_rows ? n_rows : 1) * sizeof(int64_t)));
+  ctx->keep(res->walk_seed);
+  GG_TRY(ctx->dev_alloc((void **)&res->walk_rowid, (n_rows ? n_rows : 1) * sizeof(int64_t)));
+  ctx->keep(res->walk_rowid);
+  uint64_t at = 0;
+  for (const Level &l : levels) {
+    GG_LAUNCH(ctx, "reach_emit", k_reach_emit, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx, l.n, csr->vid,
+              res->walk_seed + at, res->walk_rowid + at);
+    at += l.n;
+  }
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  *out = res.release();
+  return GG_OK;
+}
+
+extern "C" int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
+  if (!res || !res->reach || !n_levels || (capacity > 0 && !rows_per_level)) return GG_ERR_INVALID_ARG;
+  *n_levels = (int)res->level_rows.size();
+  for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
+  return GG_OK;
+}
+
+extern "C" int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
+                                      int64_t *vertex_id, int32_t *level, uint32_t *n_out) {
+  if (!res || !res->reach || !n_out || !seed_class || !vertex_id) return GG_ERR_INVALID_ARG;
+  gg_ctx *ctx = res->ctx;
+  uint64_t total = 0;
+  for (uint64_t m : res->level_rows) total += m;
+  if (offset >= total) {
+    *n_out = 0;
+    return GG_OK;
+  }
+  uint64_t take = total - offset;
+  if (take > max_rows) take = max_rows;
+  GG_HIP(hipSetDevice(ctx->device));
+  void *dst[2] = {seed_class, vertex_id};
+  const void *src[2] = {res->walk_seed + offset, res->walk_rowid + offset};
+  GG_TRY(ctx->fetch_columns(dst, src, 2, take * sizeof(int64_t)));
+  if (level) {  // the level of a row follows from the per-level row counts
+    uint64_t start = 0;
+    for (size_t l = 0; l < res->level_rows.size(); l++) {
+      const uint64_t end = start + res->level_rows[l];
+      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + take; r++) level[r - offset] = (int32_t)(l + 1);
+      start = end;
+    }
+  }
+  *n_out = (uint32_t)take;
+  return GG_OK;
+}

@@ -19,12 +19,12 @@ SYMBOLS = [
     "gg_ctx_set_edge_rowid", "gg_csr_build", "gg_csr_build_shard", "gg_csr_destroy", "gg_csr_info", "gg_csr_export",
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
-    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement",
+    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_reach_visited",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
     "gg_result_filter_common_neighbour", "gg_staging_clear_edges", "gg_vertices_from_edges",
     "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
-    "gg_walk_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
+    "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
@@ -106,6 +106,7 @@ def load_library(path: str | None = None):
     lib.gg_debug_max_grid_tiles.argtypes = [P, u64]
     lib.gg_debug_reset.argtypes = [P]
     lib.gg_debug_placement.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
+    lib.gg_debug_reach_visited.argtypes = [P, C.c_int, u64]
     lib.gg_result_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_result_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
     lib.gg_expand_khop_result.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.POINTER(KhopStats), C.POINTER(P)]
@@ -128,6 +129,10 @@ def load_library(path: str | None = None):
     lib.gg_walk_closure.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
     lib.gg_walk_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_walk_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    lib.gg_reach_closure.argtypes = [P, P, i64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), u64, C.c_uint32,
+                                     C.POINTER(P)]
+    lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
+    lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.gg_bfs_sharded_begin.argtypes = [P, P, i64p, C.c_int, C.POINTER(P)]
     lib.gg_bfs_sharded_expand.argtypes = [P, C.POINTER(C.c_void_p), C.POINTER(u64), C.POINTER(u64)]
     lib.gg_bfs_sharded_words.argtypes = [P, C.POINTER(C.c_uint64), C.c_int]
@@ -264,6 +269,7 @@ class KhopResult:
 
 class WalkClosure:
     """Every walk from a seed list (gg_walk_closure), left in HBM: level counts and row slices on demand."""
+    _levels_fn, _fetch_fn = "gg_walk_closure_levels", "gg_walk_closure_fetch"
 
     def __init__(self, gg: "GG", handle):
         self.gg, self.handle = gg, handle
@@ -271,7 +277,7 @@ class WalkClosure:
     def levels(self) -> int:
         """the deepest level with walks (0: none)"""
         n = C.c_int()
-        self.gg._chk(self.gg.lib.gg_walk_closure_levels(self.handle, None, 0, C.byref(n)))
+        self.gg._chk(getattr(self.gg.lib, self._levels_fn)(self.handle, None, 0, C.byref(n)))
         return int(n.value)
 
     def rows(self, level: int | None = None):
@@ -279,7 +285,7 @@ class WalkClosure:
         n = self.levels()
         counts = (C.c_uint64 * max(n, 1))()
         got = C.c_int()
-        self.gg._chk(self.gg.lib.gg_walk_closure_levels(self.handle, counts, n, C.byref(got)))
+        self.gg._chk(getattr(self.gg.lib, self._levels_fn)(self.handle, counts, n, C.byref(got)))
         if level is None:
             return [int(counts[i]) for i in range(n)]
         return int(counts[level - 1]) if 1 <= level <= n else 0
@@ -294,7 +300,7 @@ class WalkClosure:
         while done < want:
             got = C.c_uint32()
             take = min(want - done, 1 << 30)
-            self.gg._chk(self.gg.lib.gg_walk_closure_fetch(
+            self.gg._chk(getattr(self.gg.lib, self._fetch_fn)(
                 self.handle, offset + done, take, seed[done:].ctypes.data_as(i64p), rowid[done:].ctypes.data_as(i64p),
                 level[done:].ctypes.data_as(C.POINTER(C.c_int32)), C.byref(got)))
             if got.value == 0:
@@ -306,6 +312,12 @@ class WalkClosure:
         if self.handle:
             self.gg.lib.gg_result_destroy(self.handle)
             self.handle = None
+
+
+class ReachClosure(WalkClosure):
+    """Every (class, vertex) reachable from a seed list (gg_reach_closure), left in HBM.  fetch() gives (class int64,
+    vertex id int64, level int32) by level, inside a level ascending by (class, dense vertex index)."""
+    _levels_fn, _fetch_fn = "gg_reach_closure_levels", "gg_reach_closure_fetch"
 
 
 class Csr:
@@ -695,6 +707,29 @@ class GG:
         self._chk(self.lib.gg_walk_closure(self.ctx, csr.handle, ps, s.size, -1 if max_levels is None else max_levels,
                                            C.byref(res)))
         return WalkClosure(self, res)
+
+    def reach_closure(self, csr: Csr, seeds, classes, seen=None, n_classes: int | None = None) -> ReachClosure:
+        """gg_reach_closure: every (class, vertex) reachable from the seeds (seed i in class classes[i]; seen[i] true:
+        its (class, vertex) is visited from the start).  n_classes defaults to max(classes) + 1."""
+        s, ps = _i64(seeds)
+        c = np.ascontiguousarray(classes, dtype=np.uint32)
+        if c.size != s.size:
+            raise ValueError("one class per seed")
+        m = None
+        if seen is not None:
+            m = np.ascontiguousarray(seen, dtype=np.uint8)
+            if m.size != s.size:
+                raise ValueError("one seen flag per seed")
+        n = (int(c.max()) + 1 if c.size else 0) if n_classes is None else n_classes
+        res = C.c_void_p()
+        self._chk(self.lib.gg_reach_closure(self.ctx, csr.handle, ps, c.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)), s.size, n,
+                                            C.byref(res)))
+        return ReachClosure(self, res)
+
+    def debug_reach_visited(self, mode: int = 0, slots: int = 0):
+        """gg_reach_closure's visited set: 0 the budget decides, 1 bitmap, 2 hash set (first `slots` slots if != 0)."""
+        self._chk(self.lib.gg_debug_reach_visited(self.ctx, int(mode), int(slots)))
 
     # ---- graph-sharded BFS (one shard per GPU; see include/gg.h)
     def bfs_sharded_begin(self, shard: Csr, sources) -> "ShardedBfs":

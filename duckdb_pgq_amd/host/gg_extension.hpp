@@ -72,6 +72,8 @@ struct GGConnectionFlags {
 	bool rules = false;        // PRAGMA enable_gpu_graph / disable_gpu_graph
 	bool pinned_graphs = false; // PRAGMA gg_use_pinned_graphs / gg_ignore_pinned_graphs
 	bool joins = false;         // PRAGMA enable_gpu_joins / disable_gpu_joins: ANY single-key inner join over a table scan
+	bool recursive_union = false; // PRAGMA enable_gpu_recursive_union / disable_gpu_recursive_union: UNION recursive CTEs
+	                              // over one keyed table (GG_RECURSIVE_REACH; needs enable_gpu_graph too)
 };
 GGConnectionFlags GGGetConnectionFlags(ClientContext &context);
 void GGSetConnectionFlags(ClientContext &context, const GGConnectionFlags &flags);

@@ -111,6 +111,10 @@ struct GGWalkInput {
 	int max_levels = -1;    // from `counter < K` on the CTE side; -1: until a level is empty
 	vector<GGWalkColumn> columns;
 	string description;
+	// set by the table sink's Finalize: the id a NULL next (or anchor link) is staged as — no key, link or next — and
+	// whether any table row has a non-NULL key (without one the CSR holds only a dummy sentinel -> sentinel edge)
+	int64_t sentinel = 0;
+	bool has_edges = false;
 };
 
 //! Keeps the rows of the anchor (table_side false) or of the arm table on the host; the table side's Finalize stages
@@ -159,6 +163,38 @@ public:
 	}
 	string ParamsToString() const override;
 };
+
+//===--------------------------------------------------------------------===//
+// UNION recursion over one keyed table (gg_recursive_reach.cpp, rule: PlanRecursiveWalks in gg_plan_rule.cpp under
+// PRAGMA enable_gpu_recursive_union).  The same sinks and GGWalkInput; every column is CARRIED, CONSTANT or, at the
+// link's position, the TABLE's next column.
+//===--------------------------------------------------------------------===//
+//! Source: the distinct anchor rows, then every new (carried columns, next, constants) row of the reachability closure
+//! (gg_reach_closure) level by level
+class PhysicalGGRecursiveReach : public PhysicalOperator {
+public:
+	PhysicalGGRecursiveReach(vector<LogicalType> types, shared_ptr<GGGraph> graph, shared_ptr<GGWalkInput> input,
+	                         idx_t estimated_cardinality);
+	shared_ptr<GGGraph> graph;
+	shared_ptr<GGWalkInput> input;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_RECURSIVE_REACH";
+	}
+	string ParamsToString() const override;
+};
+
+//! column `col` of every row of `rows` as int64 (NULL: valid[r] = false) (gg_recursive_walks.cpp)
+void GGIntegerColumn(ChunkCollection &rows, idx_t col, vector<int64_t> &out, vector<bool> &valid);
+//! target[i] = column `col` of row row[i] of `rows`, i < n (gg_recursive_walks.cpp)
+void GGGatherRows(ChunkCollection &rows, idx_t col, const idx_t *row, idx_t n, Vector &target);
 
 //! true if a plan over `spec` can read its tables through pipeline sinks: the BuildPipelines rule is registered with
 //! the shim, every source is a plain table, and the connection did not ask for pinned graphs

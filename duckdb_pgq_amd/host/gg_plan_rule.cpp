@@ -2336,7 +2336,7 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 }
 
 //===--------------------------------------------------------------------===//
-// Recursive-CTE rule: UNION ALL recursion over one keyed table -> the walk closure
+// Recursive-CTE rule: UNION ALL recursion over one keyed table -> the walk closure; UNION -> the reach closure
 //===--------------------------------------------------------------------===//
 // benchmark/ldbc/queries/bi-9.sql (post_all) and interactive-short-6.sql (chain):
 //
@@ -2350,6 +2350,11 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 // counter).  The arm's column at the link's position must be a column of T (the next link).  A CTE-side predicate
 // `counter < K` (or <=) on a counter whose anchor value is a constant bounds the levels; any other CTE-side predicate
 // declines.  T and the anchor are planned by the reference's own planner and feed PhysicalGGWalkRowSinks.
+//
+// The same arm under UNION (union_all == false; reachability, interactive-complex-12.sql's extended_tags) becomes
+// GG_RECURSIVE_REACH (gg_recursive_reach.cpp) when the connection issued PRAGMA enable_gpu_recursive_union: every arm
+// column must then be carried, the next link, or a constant — no depth counter (its rows differ per level, so they
+// would never repeat), no other column of T, no CTE-side predicate.
 namespace {
 
 //! does the subtree read the CTE `index`?
@@ -2411,8 +2416,13 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	if (g_ctes_left_alone.erase(&op)) {
 		return trace("min(...) GROUP BY over it: the shortest-path rule's shape");
 	}
-	if (!op.union_all || op.children.size() != 2 || !g_plan_context || !g_plan_generator) {
-		return trace("not UNION ALL");
+	if (op.children.size() != 2 || !g_plan_context || !g_plan_generator) {
+		return trace("not a recursive CTE of two children");
+	}
+	// UNION (not ALL): the reachability closure, under its own switch
+	const bool reach = !op.union_all;
+	if (reach && !GGGetConnectionFlags(*g_plan_context).recursive_union) {
+		return trace("not UNION ALL (PRAGMA enable_gpu_recursive_union takes UNION)");
 	}
 	if (std::getenv("GG_NO_PIPELINE_SINKS") || !gg_pipeline_rule_registered() || !g_plan_generator->rec_ctes.empty()) {
 		return trace("no pipeline sinks, or inside another recursive CTE");
@@ -2495,6 +2505,9 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 				}
 				spec.kind = GGWalkColumn::CARRIED;
 			} else {
+				if (reach && c != link) {
+					return trace("UNION: a column of the table other than the next link");
+				}
 				spec.kind = GGWalkColumn::TABLE;
 				spec.index = column;
 			}
@@ -2510,6 +2523,9 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 			    !join_column(ref, child, column) || child != cte_child || column != c) {
 				return trace("an arm expression other than counter + constant");
 			}
+			if (reach) {
+				return trace("UNION: a depth counter (its rows differ per level)");
+			}
 			spec.kind = GGWalkColumn::COUNTER;
 			spec.step = step;
 		} else {
@@ -2520,6 +2536,9 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		return trace("the next link is not an integer column of the table");
 	}
 	input->next_column = input->columns[link].index;
+	if (reach && (!cte_filters.empty() || !join_filters.empty())) {
+		return trace("UNION: a CTE-side predicate");
+	}
 	// ---- CTE-side predicates: `counter < K` only
 	// (CTE column, predicate) pairs; the logical plan is only read here — the rule may still decline
 	vector<std::pair<idx_t, Expression *>> bounds;
@@ -2587,8 +2606,11 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	g_plan_generator = generator;
 	auto slot = make_shared<GGGraphSlot>();
 	auto scan = make_unique<PhysicalGGGraphScan>(
-	    types, "GG_RECURSIVE_WALKS", description, slot,
-	    [types, input, cardinality](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+	    types, reach ? "GG_RECURSIVE_REACH" : "GG_RECURSIVE_WALKS", description, slot,
+	    [types, input, cardinality, reach](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    if (reach) {
+			    return make_unique<PhysicalGGRecursiveReach>(types, move(graph), input, cardinality);
+		    }
 		    return make_unique<PhysicalGGRecursiveWalks>(types, move(graph), input, cardinality);
 	    },
 	    false, cardinality);
@@ -2967,6 +2989,18 @@ void PragmaDisableGpuJoins(ClientContext &context, const FunctionParameters &par
 	GGSetConnectionFlags(context, flags);
 }
 
+void PragmaEnableGpuRecursiveUnion(ClientContext &context, const FunctionParameters &parameters) {
+	auto flags = GGGetConnectionFlags(context);
+	flags.recursive_union = true;
+	GGSetConnectionFlags(context, flags);
+}
+
+void PragmaDisableGpuRecursiveUnion(ClientContext &context, const FunctionParameters &parameters) {
+	auto flags = GGGetConnectionFlags(context);
+	flags.recursive_union = false;
+	GGSetConnectionFlags(context, flags);
+}
+
 void PragmaUsePinnedGraphs(ClientContext &context, const FunctionParameters &parameters) {
 	auto flags = GGGetConnectionFlags(context);
 	flags.pinned_graphs = true;
@@ -3007,6 +3041,12 @@ void GGRegisterPlanRules(ClientContext &context) {
 	CreatePragmaFunctionInfo joins_off(PragmaFunction::PragmaStatement("disable_gpu_joins", PragmaDisableGpuJoins));
 	Catalog::GetCatalog(context).CreatePragmaFunction(context, &joins_on);
 	Catalog::GetCatalog(context).CreatePragmaFunction(context, &joins_off);
+	CreatePragmaFunctionInfo union_on(
+	    PragmaFunction::PragmaStatement("enable_gpu_recursive_union", PragmaEnableGpuRecursiveUnion));
+	CreatePragmaFunctionInfo union_off(
+	    PragmaFunction::PragmaStatement("disable_gpu_recursive_union", PragmaDisableGpuRecursiveUnion));
+	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_on);
+	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_off);
 
 	// A reference built with oracle/callout.patch exports the registration of its call-outs: the maintainers' route —
 	// no interposition, no access to private members (the BuildPipelines case and the write observation are then the

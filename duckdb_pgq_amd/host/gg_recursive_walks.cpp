@@ -27,10 +27,8 @@
 
 namespace duckdb {
 
-namespace {
-
 //! column `col` of every row of `rows` as int64 (NULL: valid[r] = false)
-void IntegerColumn(ChunkCollection &rows, idx_t col, vector<int64_t> &out, vector<bool> &valid) {
+void GGIntegerColumn(ChunkCollection &rows, idx_t col, vector<int64_t> &out, vector<bool> &valid) {
 	out.clear();
 	valid.clear();
 	out.reserve(rows.Count());
@@ -49,6 +47,8 @@ void IntegerColumn(ChunkCollection &rows, idx_t col, vector<int64_t> &out, vecto
 		}
 	}
 }
+
+namespace {
 
 class RowSinkState : public GlobalSinkState {};
 
@@ -78,13 +78,14 @@ SinkFinalizeType PhysicalGGWalkRowSink::Finalize(Pipeline &pipeline, Event &even
 	if (!table_side) {
 		return SinkFinalizeType::READY;
 	}
-	// the anchor's sink ran first (its pipeline is a dependency of this one): the sentinel avoids its links too
+	// the anchor's sink ran first (its pipeline is a dependency of this one): the sentinel avoids its links too, and the
+	// next values (GG_RECURSIVE_REACH emits the vertex a row reached, so a real next must never be the sentinel)
 	lock_guard<mutex> guard(input->lock);
 	vector<int64_t> key, next, link;
 	vector<bool> key_valid, next_valid, link_valid;
-	IntegerColumn(input->table, input->key_column, key, key_valid);
-	IntegerColumn(input->table, input->next_column, next, next_valid);
-	IntegerColumn(input->anchor, input->link_column, link, link_valid);
+	GGIntegerColumn(input->table, input->key_column, key, key_valid);
+	GGIntegerColumn(input->table, input->next_column, next, next_valid);
+	GGIntegerColumn(input->anchor, input->link_column, link, link_valid);
 	int64_t lo = std::numeric_limits<int64_t>::max(), hi = std::numeric_limits<int64_t>::min();
 	for (idx_t r = 0; r < key.size(); r++) {
 		if (key_valid[r]) {
@@ -96,6 +97,12 @@ SinkFinalizeType PhysicalGGWalkRowSink::Finalize(Pipeline &pipeline, Event &even
 		if (link_valid[r]) {
 			lo = std::min(lo, link[r]);
 			hi = std::max(hi, link[r]);
+		}
+	}
+	for (idx_t r = 0; r < next.size(); r++) {
+		if (next_valid[r]) {
+			lo = std::min(lo, next[r]);
+			hi = std::max(hi, next[r]);
 		}
 	}
 	int64_t sentinel = 0;
@@ -117,6 +124,8 @@ SinkFinalizeType PhysicalGGWalkRowSink::Finalize(Pipeline &pipeline, Event &even
 		dst.push_back(next_valid[r] ? next[r] : sentinel);
 		rowid.push_back((int64_t)r);
 	}
+	input->sentinel = sentinel;
+	input->has_edges = !src.empty();
 	if (src.empty()) { // a graph needs an edge: one that no seed reaches (the sentinel is no link)
 		src.push_back(sentinel);
 		dst.push_back(sentinel);
@@ -163,7 +172,7 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveWalks::GetGlobalSourceState(Cli
 	vector<bool> valid;
 	{
 		lock_guard<mutex> guard(input->lock);
-		IntegerColumn(input->anchor, input->link_column, link, valid);
+		GGIntegerColumn(input->anchor, input->link_column, link, valid);
 	}
 	vector<int64_t> seeds;
 	for (idx_t r = 0; r < link.size(); r++) {
@@ -202,10 +211,9 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveWalks::GetGlobalSourceState(Cli
 	return move(state);
 }
 
-namespace {
 //! target[i] = column `col` of row row[i] of `rows`, i < n: one vectorised copy per run of consecutive output rows whose
 //! source rows lie in one chunk of the collection (a chunk holds STANDARD_VECTOR_SIZE rows, ChunkCollection::LocateChunk)
-void GatherRows(ChunkCollection &rows, idx_t col, const idx_t *row, idx_t n, Vector &target) {
+void GGGatherRows(ChunkCollection &rows, idx_t col, const idx_t *row, idx_t n, Vector &target) {
 	SelectionVector sel(STANDARD_VECTOR_SIZE);
 	for (idx_t i = 0; i < n;) {
 		const idx_t chunk = row[i] / STANDARD_VECTOR_SIZE;
@@ -217,7 +225,6 @@ void GatherRows(ChunkCollection &rows, idx_t col, const idx_t *row, idx_t n, Vec
 		i = j;
 	}
 }
-} // namespace
 
 void PhysicalGGRecursiveWalks::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
                                        LocalSourceState &lstate) const {
@@ -242,17 +249,17 @@ void PhysicalGGRecursiveWalks::GetData(ExecutionContext &context, DataChunk &chu
 		auto &spec = input->columns[c];
 		switch (spec.kind) {
 		case GGWalkColumn::CARRIED:
-			GatherRows(input->anchor, c, anchor_row, n, chunk.data[c]);
+			GGGatherRows(input->anchor, c, anchor_row, n, chunk.data[c]);
 			break;
 		case GGWalkColumn::TABLE:
-			GatherRows(input->table, spec.index, table_row, n, chunk.data[c]);
+			GGGatherRows(input->table, spec.index, table_row, n, chunk.data[c]);
 			break;
 		case GGWalkColumn::CONSTANT:
 			chunk.data[c].Reference(spec.constant);
 			break;
 		case GGWalkColumn::COUNTER: { // the anchor's value + step x level, computed in BIGINT
 			Vector start(types[c]), wide(LogicalType::BIGINT);
-			GatherRows(input->anchor, c, anchor_row, n, start);
+			GGGatherRows(input->anchor, c, anchor_row, n, start);
 			VectorOperations::Cast(start, wide, n);
 			auto values = FlatVector::GetData<int64_t>(wide);
 			for (idx_t i = 0; i < n; i++) {

@@ -42,6 +42,10 @@
  *        <- PhysicalRecursiveCTE over a UNION ALL arm that joins the CTE with one table (the join rebuilt per level)
  *                                                               src/execution/operator/set/physical_recursive_cte.cpp:60-139
  *           (the post_all / chain reply trees of benchmark/ldbc/queries/bi-9.sql, interactive-short-6.sql)
+ *   gg_reach_closure / gg_reach_closure_levels / gg_reach_closure_fetch
+ *        <- PhysicalRecursiveCTE over a UNION arm that joins the CTE with one table: every produced row probed against
+ *           a hash table of the rows emitted so far     src/execution/operator/set/physical_recursive_cte.cpp:47-139
+ *           (reachability over knows, extended_tags of benchmark/ldbc/queries/interactive-complex-12.sql)
  *
  * Conventions
  *   - every int-returning function returns GG_OK (0) or a negative GG_ERR_*; the message is
@@ -330,6 +334,35 @@ int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_level, int c
 int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_index,
                           int64_t *edge_rowid, int32_t *level, uint32_t *n_out);
 
+/* Every (class, vertex) reachable from the seeds, each once — the rows a UNION recursive CTE adds to its anchor when its
+ * arm joins the CTE's link column with a table's key column, carries the table's next column as the new link and keeps
+ * every other column as the anchor row had it or sets it to a constant (reachability over a mirrored knows; extended_tags
+ * of benchmark/ldbc/queries/interactive-complex-12.sql).  The reference re-runs the arm's pipeline, hash-join build
+ * included, once per level, and probes every produced row against a GroupedAggregateHashTable of all rows emitted so
+ * far, keeping the new groups only (src/execution/operator/set/physical_recursive_cte.cpp:47-70 ProbeHT / Sink,
+ * :75-139 the loop).
+ * The table's rows are the CSR's edges key -> next (edge rowids are not needed).  Seed i is (seed_class[i], seed_ids[i]);
+ * its id is looked up as gg_csr_lookup does, and a seed that is not a vertex reaches nothing.  seed_seen[i] != 0 marks a
+ * seed whose anchor row equals an arm row: its (class, vertex) is visited from the start and is never a row; an unseen
+ * seed is expanded too, and is a row of the first level that reaches it again (seed_seen NULL: none is seen).  Duplicate
+ * seeds are allowed.  Level L's rows are the (class, w) of the level L - 1 rows' (level 0: the seeds') out-edges that are
+ * not visited yet, each once; the first level without a row ends the recursion, cycles included.
+ * One row per (class, vertex) pair reached: (class, vertex id, L).  Rows come by level; inside a level ascending by
+ * (class, the vertex's dense index in the CSR) — the same on every run and whichever visited set is used.
+ * The visited set is a bitmap of n_classes x V bits while that fits a budget, else a hash set of keys
+ * class << 32 | vertex (gg_debug_reach_visited forces either).  A level of 2^32 children or more fails with
+ * GG_ERR_TOO_LARGE, as do 2^32 seeds or more; a class >= n_classes with GG_ERR_INVALID_ARG; a shard CSR with
+ * GG_ERR_STATE.  The result answers gg_reach_closure_levels / gg_reach_closure_fetch (not gg_result_rows /
+ * gg_result_fetch, nor the walk closure's calls). */
+int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, const uint32_t *seed_class,
+                     const uint8_t *seed_seen, uint64_t n_seeds, uint32_t n_classes, gg_result **out_result);
+/* *n_levels = the deepest level L with rows; rows_per_level[L - 1] = rows of level L, for the first `capacity`. */
+int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
+/* Copy rows [offset, offset+max_rows) of the closure, in row order, into host arrays of >= max_rows entries (level may
+ * be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
+int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
+                           int64_t *vertex_id, int32_t *level, uint32_t *n_out);
+
 /* ---- graph-sharded 64-lane BFS (one shard of the graph per GPU) ------------------------------- */
 /* The layout north_star names for graphs that do not fit one GPU: `shard` comes from
  * gg_csr_build_shard; every rank holds the whole frontier (one uint64 of 64 lanes per vertex) and owns the
@@ -381,6 +414,10 @@ int gg_debug_scan_fault(gg_ctx *ctx, uint32_t spin_limit, uint64_t mute_tile);
  * runtime takes gridDim.x * blockDim.x in 32 bits, so a 3-hop expansion over more than ~1.3e10 2-hop rows runs
  * as several launches); 0 restores the hardware bound.  Results must not depend on it. */
 int gg_debug_max_grid_tiles(gg_ctx *ctx, uint64_t max_tiles);
+/* Testing knob: the visited set of gg_reach_closure.  mode 0: the budget decides, 1: the bitmap,
+ * 2: the hash set, first sized max(hash_initial_slots, 2 x seen seeds) slots when hash_initial_slots != 0 (a tiny size
+ * makes it grow by rebuilds).  Both forms must give identical rows in identical order. */
+int gg_debug_reach_visited(gg_ctx *ctx, int mode /* 0 auto, 1 bitmap, 2 hash */, uint64_t hash_initial_slots);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
