@@ -66,11 +66,6 @@ __global__ __launch_bounds__(256) void k_closure_emit(const uint2 *__restrict__ 
   }
 }
 
-dim3 stride_grid(gg_ctx *ctx, uint64_t n) {
-  const uint64_t want = (n + 255) / 256, cap = (uint64_t)ctx->num_cus * 32;
-  return dim3((unsigned)(want < cap ? (want ? want : 1) : cap));
-}
-
 }  // namespace
 
 extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, uint64_t n_seeds,
@@ -155,7 +150,7 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
 }
 
 extern "C" int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
-  if (!res || res->reach || !n_levels || (capacity > 0 && !rows_per_level) || res->k_min <= res->k_max)
+  if (!res || res->reach || res->level_sets || !n_levels || (capacity > 0 && !rows_per_level) || res->k_min <= res->k_max)
     return GG_ERR_INVALID_ARG;
   *n_levels = (int)res->level_rows.size();
   for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
@@ -164,7 +159,7 @@ extern "C" int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_l
 
 extern "C" int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_index,
                                      int64_t *edge_rowid, int32_t *level, uint32_t *n_out) {
-  if (!res || res->reach || !n_out || !seed_index || !edge_rowid || res->k_min <= res->k_max) return GG_ERR_INVALID_ARG;
+  if (!res || res->reach || res->level_sets || !n_out || !seed_index || !edge_rowid || res->k_min <= res->k_max) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = res->ctx;
   uint64_t total = 0;
   for (uint64_t m : res->level_rows) total += m;

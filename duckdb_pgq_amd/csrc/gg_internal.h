@@ -184,6 +184,8 @@ struct gg_ctx {
   uint64_t max_grid_tiles = 0;  // gg_debug_max_grid_tiles: workgroups per expansion launch (0: the hardware bound)
   int reach_visited_mode = 0;   // gg_debug_reach_visited: 0 the budget decides, 1 bitmap, 2 hash set (gg_reach.hip)
   uint64_t reach_hash_slots = 0;  // gg_debug_reach_visited: the hash set's first capacity (0: from the seed count)
+  int levels_set_mode = 0;      // gg_debug_level_sets: 0 the budget decides, 1 bitmap, 2 hash set (gg_levels.hip)
+  int levels_order_mode = 0;    // gg_debug_level_sets: 0 the byte model decides per level, 1 sort, 2 compact
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;
@@ -283,6 +285,8 @@ struct gg_result {
   // gg_reach_closure (reach: the same fields): level_rows[L - 1] new (class, vertex) rows of level L, walk_seed their
   // classes, walk_rowid their vertex ids
   bool reach = false;
+  // gg_level_sets (level_sets, reach false: the same fields): level_rows[L - 1] the members of level L
+  bool level_sets = false;
 };
 
 namespace gg {
@@ -554,5 +558,64 @@ __device__ __forceinline__ void load_window(uint64_t *s_foff, const OffT *__rest
     s_foff[t] = gi <= n_entries ? (uint64_t)foff[gi] : UINT64_MAX;
   }
 }
+
+// ---- sets of (class, vertex) pairs and the per-level steps gg_reach.hip and gg_levels.hip share
+constexpr unsigned long long REACH_EMPTY = ~0ull;  // no key: a vertex index is never INVALID_U32
+
+struct Visited {
+  uint32_t *bits = nullptr;           // bitmap form: bit class * V + vertex
+  uint64_t V = 0;
+  unsigned long long *slots = nullptr;  // hash form: cap slots of class << 32 | vertex
+  uint64_t cap = 0;
+};
+
+// true for the one caller that put (c, v) into the set.  Each form reads first and only does the atomic if the entry
+// may still be absent: on a mirrored graph most children are visited already.
+__device__ __forceinline__ bool claim(const Visited &vs, uint32_t c, uint32_t v) {
+  if (vs.bits) {
+    const uint64_t b = (uint64_t)c * vs.V + v;
+    const uint32_t mask = 1u << (b & 31);
+    if (__atomic_load_n(&vs.bits[b >> 5], __ATOMIC_RELAXED) & mask) return false;
+    return !(atomicOr(&vs.bits[b >> 5], mask) & mask);
+  }
+  const unsigned long long key = ((unsigned long long)c << 32) | v;
+  uint64_t s = __umul64hi(fmix64(key), vs.cap);
+  while (true) {
+    unsigned long long old = __atomic_load_n(&vs.slots[s], __ATOMIC_RELAXED);
+    if (old == REACH_EMPTY) old = atomicCAS(&vs.slots[s], REACH_EMPTY, key);
+    if (old == REACH_EMPTY) return true;
+    if (old == key) return false;
+    s = s + 1 == vs.cap ? 0 : s + 1;
+  }
+}
+
+inline dim3 stride_grid(gg_ctx *ctx, uint64_t n) {  // 256-thread workgroups for a kernel that strides over n items
+  const uint64_t want = (n + 255) / 256, cap = (uint64_t)ctx->num_cus * 32;
+  return dim3((unsigned)(want < cap ? (want ? want : 1) : cap));
+}
+inline int bits_for(uint64_t n) {  // bits of the largest value below n
+  int b = 1;
+  while (b < 64 && (1ull << b) < n) b++;
+  return b;
+}
+
+struct PairLevel {  // the rows of one level, device arrays, ascending by (class, vertex index)
+  uint32_t *cls, *vtx;
+  uint64_t n;
+};
+// foff[0..n_parent]: the exclusive prefix of the out-degrees of fvtx (INVALID_U32: 0), from the pool; *M = their sum
+// (one host round trip).  The caller frees *foff.  (gg_reach.hip)
+int frontier_offsets(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fvtx, uint64_t n_parent, uint64_t **foff, uint64_t *M);
+// one thread per child of the frontier claims (class, child) in vs; the winners, appended through `count` (a device
+// word) and sorted by (class, vertex index), are *out (n == 0: no array allocated)  (gg_reach.hip)
+int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, const uint32_t *fvtx, const uint64_t *foff,
+                        uint64_t n_parent, uint64_t M, const Visited &vs, uint32_t n_classes, uint32_t *count,
+                        PairLevel *out);
+// the levels' rows as the result's kept int64 columns (walk_seed: class, walk_rowid: vertex id); synchronises
+int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel> &levels, gg_result *res);
+// the bodies of gg_reach_closure_levels / _fetch and gg_level_sets_levels / _fetch (res is not NULL)
+int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
+int pair_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class, int64_t *vertex_id,
+                    int32_t *level, uint32_t *n_out);
 
 }  // namespace gg

@@ -37,35 +37,7 @@ namespace {
 // the bitmap form's budget: 2^33 bits = 1 GiB (and never more than a quarter of the free device memory); above it —
 // e.g. 10 M classes over 100 M vertices — the hash set, whose size follows the rows actually reached
 constexpr uint64_t REACH_BITMAP_MAX_BITS = 1ull << 33;
-constexpr unsigned long long REACH_EMPTY = ~0ull;  // no key: a vertex index is never INVALID_U32
 constexpr uint64_t REACH_MIN_SLOTS = 1024;
-
-struct Visited {
-  uint32_t *bits = nullptr;           // bitmap form: bit class * V + vertex
-  uint64_t V = 0;
-  unsigned long long *slots = nullptr;  // hash form: cap slots of class << 32 | vertex
-  uint64_t cap = 0;
-};
-
-// true for the one caller that put (c, v) into the set.  Each form reads first and only does the atomic if the entry
-// may still be absent: on a mirrored graph most children are visited already.
-__device__ __forceinline__ bool claim(const Visited &vs, uint32_t c, uint32_t v) {
-  if (vs.bits) {
-    const uint64_t b = (uint64_t)c * vs.V + v;
-    const uint32_t mask = 1u << (b & 31);
-    if (__atomic_load_n(&vs.bits[b >> 5], __ATOMIC_RELAXED) & mask) return false;
-    return !(atomicOr(&vs.bits[b >> 5], mask) & mask);
-  }
-  const unsigned long long key = ((unsigned long long)c << 32) | v;
-  uint64_t s = __umul64hi(fmix64(key), vs.cap);
-  while (true) {
-    unsigned long long old = __atomic_load_n(&vs.slots[s], __ATOMIC_RELAXED);
-    if (old == REACH_EMPTY) old = atomicCAS(&vs.slots[s], REACH_EMPTY, key);
-    if (old == REACH_EMPTY) return true;
-    if (old == key) return false;
-    s = s + 1 == vs.cap ? 0 : s + 1;
-  }
-}
 
 __global__ __launch_bounds__(256) void k_reach_deg(const uint32_t *__restrict__ off, const uint32_t *__restrict__ vtx,
                                                    uint64_t n, uint64_t *__restrict__ deg) {
@@ -127,21 +99,7 @@ __global__ __launch_bounds__(256) void k_reach_emit(const uint32_t *__restrict__
   }
 }
 
-dim3 stride_grid(gg_ctx *ctx, uint64_t n) {
-  const uint64_t want = (n + 255) / 256, cap = (uint64_t)ctx->num_cus * 32;
-  return dim3((unsigned)(want < cap ? (want ? want : 1) : cap));
-}
-
-int bits_for(uint64_t n) {  // bits of the largest value below n
-  int b = 1;
-  while (b < 64 && (1ull << b) < n) b++;
-  return b;
-}
-
-struct Level {
-  uint32_t *cls, *vtx;
-  uint64_t n;
-};
+using Level = PairLevel;
 
 // a hash set of `cap` slots holding the seen seeds and every level's rows so far
 int hash_build(gg_ctx *ctx, uint64_t cap, const uint32_t *seed_cls, const uint32_t *seed_dense, const uint8_t *seen,
@@ -161,6 +119,118 @@ int hash_build(gg_ctx *ctx, uint64_t cap, const uint32_t *seed_cls, const uint32
 }
 
 }  // namespace
+
+namespace gg {
+
+int frontier_offsets(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fvtx, uint64_t n_parent, uint64_t **foff_out,
+                     uint64_t *M) {
+  uint64_t *foff = nullptr, *total = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&foff, (n_parent + 1) * sizeof(uint64_t)));
+  GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
+  GG_LAUNCH(ctx, "reach_deg", k_reach_deg, stride_grid(ctx, n_parent), dim3(256), 0, csr->off, fvtx, n_parent, foff);
+  GG_TRY(scan_exclusive_u64(ctx, foff, foff, n_parent, total));
+  GG_HIP(hipMemcpyAsync(foff + n_parent, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+  GG_TRY(scan_error_fetch(ctx));
+  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  *M = ctx->pin_scratch[0];
+  GG_TRY(scan_error_test(ctx));
+  ctx->dev_free(total);
+  *foff_out = foff;
+  return GG_OK;
+}
+
+int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, const uint32_t *fvtx, const uint64_t *foff,
+                        uint64_t n_parent, uint64_t M, const Visited &vs, uint32_t n_classes, uint32_t *count,
+                        PairLevel *out) {
+  *out = PairLevel{nullptr, nullptr, 0};
+  uint32_t *tile_entry = nullptr;
+  uint64_t n_tiles = 0;
+  GG_TRY(make_tiles_u64(ctx, foff, n_parent, M, &tile_entry, &n_tiles));
+  uint32_t *new_cls = nullptr, *new_vtx = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&new_cls, M * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&new_vtx, M * sizeof(uint32_t)));
+  GG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
+  GG_LAUNCH(ctx, "reach_expand", k_reach_expand, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, fcls, fvtx,
+            foff, n_parent, M, tile_entry, vs, count, new_cls, new_vtx);
+  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  const uint64_t n_new = *(const uint32_t *)ctx->pin_scratch;
+  ctx->dev_free(tile_entry);
+  if (n_new == 0) {
+    ctx->dev_free(new_vtx);
+    ctx->dev_free(new_cls);
+    return GG_OK;
+  }
+  // (class, vertex index) ascending: by vertex, then stably by class
+  PairLevel l{nullptr, nullptr, n_new};
+  GG_TRY(ctx->dev_alloc((void **)&l.cls, n_new * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&l.vtx, n_new * sizeof(uint32_t)));
+  GG_TRY(sort_pairs_by_key(ctx, new_vtx, new_cls, n_new, bits_for(csr->V), l.vtx, l.cls));
+  if (n_classes > 1) {
+    GG_TRY(sort_pairs_by_key(ctx, l.cls, l.vtx, n_new, bits_for(n_classes), new_cls, new_vtx));
+    std::swap(l.cls, new_cls);
+    std::swap(l.vtx, new_vtx);
+  }
+  ctx->dev_free(new_vtx);
+  ctx->dev_free(new_cls);
+  *out = l;
+  return GG_OK;
+}
+
+int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel> &levels, gg_result *res) {
+  uint64_t n_rows = 0;
+  for (uint64_t m : res->level_rows) n_rows += m;
+  GG_TRY(ctx->dev_alloc((void **)&res->walk_seed, (n_rows ? n_rows : 1) * sizeof(int64_t)));
+  ctx->keep(res->walk_seed);
+  GG_TRY(ctx->dev_alloc((void **)&res->walk_rowid, (n_rows ? n_rows : 1) * sizeof(int64_t)));
+  ctx->keep(res->walk_rowid);
+  uint64_t at = 0;
+  for (const PairLevel &l : levels) {
+    GG_LAUNCH(ctx, "reach_emit", k_reach_emit, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx, l.n, csr->vid,
+              res->walk_seed + at, res->walk_rowid + at);
+    at += l.n;
+  }
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  return GG_OK;
+}
+
+int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
+  if (!n_levels || (capacity > 0 && !rows_per_level)) return GG_ERR_INVALID_ARG;
+  *n_levels = (int)res->level_rows.size();
+  for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
+  return GG_OK;
+}
+
+int pair_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class, int64_t *vertex_id,
+                    int32_t *level, uint32_t *n_out) {
+  if (!n_out || !seed_class || !vertex_id) return GG_ERR_INVALID_ARG;
+  gg_ctx *ctx = res->ctx;
+  uint64_t total = 0;
+  for (uint64_t m : res->level_rows) total += m;
+  if (offset >= total) {
+    *n_out = 0;
+    return GG_OK;
+  }
+  uint64_t take = total - offset;
+  if (take > max_rows) take = max_rows;
+  GG_HIP(hipSetDevice(ctx->device));
+  void *dst[2] = {seed_class, vertex_id};
+  const void *src[2] = {res->walk_seed + offset, res->walk_rowid + offset};
+  GG_TRY(ctx->fetch_columns(dst, src, 2, take * sizeof(int64_t)));
+  if (level) {  // the level of a row follows from the per-level row counts
+    uint64_t start = 0;
+    for (size_t l = 0; l < res->level_rows.size(); l++) {
+      const uint64_t end = start + res->level_rows[l];
+      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + take; r++) level[r - offset] = (int32_t)(l + 1);
+      start = end;
+    }
+  }
+  *n_out = (uint32_t)take;
+  return GG_OK;
+}
+
+}  // namespace gg
 
 extern "C" int gg_debug_reach_visited(gg_ctx *ctx, int mode, uint64_t hash_initial_slots) {
   if (!ctx || mode < 0 || mode > 2) return GG_ERR_INVALID_ARG;
@@ -230,17 +300,8 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
   const uint32_t *fcls = seed_cls, *fvtx = seed_dense;
   uint64_t n_parent = n_seeds;
   for (int level = 1; n_parent > 0; level++) {
-    uint64_t *foff = nullptr, *total = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&foff, (n_parent + 1) * sizeof(uint64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
-    GG_LAUNCH(ctx, "reach_deg", k_reach_deg, stride_grid(ctx, n_parent), dim3(256), 0, csr->off, fvtx, n_parent, foff);
-    GG_TRY(scan_exclusive_u64(ctx, foff, foff, n_parent, total));
-    GG_HIP(hipMemcpyAsync(foff + n_parent, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t M = ctx->pin_scratch[0];
-    GG_TRY(scan_error_test(ctx));
+    uint64_t *foff = nullptr, M = 0;
+    GG_TRY(frontier_offsets(ctx, csr, fvtx, n_parent, &foff, &M));
     if (M == 0) break;
     if (M >= (1ull << 32)) {
       set_error("gg_reach_closure: level %d has %llu children (2^32 or more)", level, (unsigned long long)M);
@@ -251,38 +312,11 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
     // forest the rebuilds took 6.0 ms of 48 when the table grew only to the bound, 3.4 of 41 at twice it)
     if (!bitmap && vs.cap < 2 * (visited + M))
       GG_TRY(hash_build(ctx, std::max(4 * (visited + M), 2 * vs.cap), seed_cls, seed_dense, seen, n_seeds, levels, &vs));
-    uint32_t *tile_entry = nullptr;
-    uint64_t n_tiles = 0;
-    GG_TRY(make_tiles_u64(ctx, foff, n_parent, M, &tile_entry, &n_tiles));
-    uint32_t *new_cls = nullptr, *new_vtx = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&new_cls, M * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&new_vtx, M * sizeof(uint32_t)));
-    GG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
-    GG_LAUNCH(ctx, "reach_expand", k_reach_expand, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, fcls, fvtx,
-              foff, n_parent, M, tile_entry, vs, count, new_cls, new_vtx);
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t n_new = *(const uint32_t *)ctx->pin_scratch;
-    ctx->dev_free(tile_entry);
-    ctx->dev_free(total);
+    Level l;
+    GG_TRY(expand_claim_sorted(ctx, csr, fcls, fvtx, foff, n_parent, M, vs, n_classes, count, &l));
     ctx->dev_free(foff);
-    if (n_new == 0) {
-      ctx->dev_free(new_vtx);
-      ctx->dev_free(new_cls);
-      break;
-    }
-    // (class, vertex index) ascending: by vertex, then stably by class
-    Level l{nullptr, nullptr, n_new};
-    GG_TRY(ctx->dev_alloc((void **)&l.cls, n_new * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&l.vtx, n_new * sizeof(uint32_t)));
-    GG_TRY(sort_pairs_by_key(ctx, new_vtx, new_cls, n_new, bits_for(csr->V), l.vtx, l.cls));
-    if (n_classes > 1) {
-      GG_TRY(sort_pairs_by_key(ctx, l.cls, l.vtx, n_new, bits_for(n_classes), new_cls, new_vtx));
-      std::swap(l.cls, new_cls);
-      std::swap(l.vtx, new_vtx);
-    }
-    ctx->dev_free(new_vtx);
-    ctx->dev_free(new_cls);
+    if (l.n == 0) break;
+    const uint64_t n_new = l.n;
     levels.push_back(l);
     res->level_rows.push_back(n_new);
     visited += n_new;
@@ -291,54 +325,18 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
     n_parent = n_new;
   }
 
-  uint64_t n_rows = 0;
-  for (uint64_t m : res->level_rows) n_rows += m;
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_seed, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_seed);
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_rowid, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_rowid);
-  uint64_t at = 0;
-  for (const Level &l : levels) {
-    GG_LAUNCH(ctx, "reach_emit", k_reach_emit, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx, l.n, csr->vid,
-              res->walk_seed + at, res->walk_rowid + at);
-    at += l.n;
-  }
-  GG_HIP(hipStreamSynchronize(ctx->stream));
+  GG_TRY(emit_pair_levels(ctx, csr, levels, res.get()));
   *out = res.release();
   return GG_OK;
 }
 
 extern "C" int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
-  if (!res || !res->reach || !n_levels || (capacity > 0 && !rows_per_level)) return GG_ERR_INVALID_ARG;
-  *n_levels = (int)res->level_rows.size();
-  for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
-  return GG_OK;
+  if (!res || !res->reach) return GG_ERR_INVALID_ARG;
+  return pair_rows_levels(res, rows_per_level, capacity, n_levels);
 }
 
 extern "C" int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
                                       int64_t *vertex_id, int32_t *level, uint32_t *n_out) {
-  if (!res || !res->reach || !n_out || !seed_class || !vertex_id) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  uint64_t total = 0;
-  for (uint64_t m : res->level_rows) total += m;
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  GG_HIP(hipSetDevice(ctx->device));
-  void *dst[2] = {seed_class, vertex_id};
-  const void *src[2] = {res->walk_seed + offset, res->walk_rowid + offset};
-  GG_TRY(ctx->fetch_columns(dst, src, 2, take * sizeof(int64_t)));
-  if (level) {  // the level of a row follows from the per-level row counts
-    uint64_t start = 0;
-    for (size_t l = 0; l < res->level_rows.size(); l++) {
-      const uint64_t end = start + res->level_rows[l];
-      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + take; r++) level[r - offset] = (int32_t)(l + 1);
-      start = end;
-    }
-  }
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  if (!res || !res->reach) return GG_ERR_INVALID_ARG;
+  return pair_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
 }

@@ -20,6 +20,7 @@ SYMBOLS = [
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
     "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_reach_visited",
+    "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
     "gg_result_filter_common_neighbour", "gg_staging_clear_edges", "gg_vertices_from_edges",
@@ -131,6 +132,10 @@ def load_library(path: str | None = None):
     lib.gg_walk_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.gg_reach_closure.argtypes = [P, P, i64p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), u64, C.c_uint32,
                                      C.POINTER(P)]
+    lib.gg_level_sets.argtypes = [P, P, i64p, C.POINTER(C.c_uint32), u64, C.c_uint32, C.c_int, C.POINTER(P)]
+    lib.gg_level_sets_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
+    lib.gg_level_sets_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.gg_bfs_sharded_begin.argtypes = [P, P, i64p, C.c_int, C.POINTER(P)]
@@ -318,6 +323,12 @@ class ReachClosure(WalkClosure):
     """Every (class, vertex) reachable from a seed list (gg_reach_closure), left in HBM.  fetch() gives (class int64,
     vertex id int64, level int32) by level, inside a level ascending by (class, dense vertex index)."""
     _levels_fn, _fetch_fn = "gg_reach_closure_levels", "gg_reach_closure_fetch"
+
+
+class LevelSets(ReachClosure):
+    """The level sets of a seed list (gg_level_sets), left in HBM.  fetch() gives (class int64, vertex id int64, level
+    int32): the members of level 1, then of level 2, ..., inside a level ascending by (class, dense vertex index)."""
+    _levels_fn, _fetch_fn = "gg_level_sets_levels", "gg_level_sets_fetch"
 
 
 class Csr:
@@ -730,6 +741,24 @@ class GG:
     def debug_reach_visited(self, mode: int = 0, slots: int = 0):
         """gg_reach_closure's visited set: 0 the budget decides, 1 bitmap, 2 hash set (first `slots` slots if != 0)."""
         self._chk(self.lib.gg_debug_reach_visited(self.ctx, int(mode), int(slots)))
+
+    def level_sets(self, csr: Csr, seeds, classes, n_classes: int | None = None, max_levels: int = -1) -> LevelSets:
+        """gg_level_sets: for L = 1, 2, ... the set of (class, vertex) that L edges lead to from the seeds (seed i in
+        class classes[i]); max_levels < 0: until a level is empty.  n_classes defaults to max(classes) + 1."""
+        s, ps = _i64(seeds)
+        c = np.ascontiguousarray(classes, dtype=np.uint32)
+        if c.size != s.size:
+            raise ValueError("one class per seed")
+        n = (int(c.max()) + 1 if c.size else 0) if n_classes is None else n_classes
+        res = C.c_void_p()
+        self._chk(self.lib.gg_level_sets(self.ctx, csr.handle, ps, c.ctypes.data_as(C.POINTER(C.c_uint32)), s.size, n,
+                                         int(max_levels), C.byref(res)))
+        return LevelSets(self, res)
+
+    def debug_level_sets(self, set_mode: int = 0, order_mode: int = 0):
+        """gg_level_sets' per-level set (0 the budget decides, 1 bitmap, 2 hash set) and order route (0 the byte model
+        decides, 1 claim and sort, 2 read the rows off the bitmap; not with the hash set)."""
+        self._chk(self.lib.gg_debug_level_sets(self.ctx, int(set_mode), int(order_mode)))
 
     # ---- graph-sharded BFS (one shard per GPU; see include/gg.h)
     def bfs_sharded_begin(self, shard: Csr, sources) -> "ShardedBfs":

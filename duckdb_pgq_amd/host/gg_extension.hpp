@@ -74,6 +74,8 @@ struct GGConnectionFlags {
 	bool joins = false;         // PRAGMA enable_gpu_joins / disable_gpu_joins: ANY single-key inner join over a table scan
 	bool recursive_union = false; // PRAGMA enable_gpu_recursive_union / disable_gpu_recursive_union: UNION recursive CTEs
 	                              // over one keyed table (GG_RECURSIVE_REACH; needs enable_gpu_graph too)
+	bool recursive_levels = false; // PRAGMA enable_gpu_recursive_levels / disable_gpu_recursive_levels: UNION recursive
+	                               // CTEs with a depth counter (GG_RECURSIVE_LEVELS; needs enable_gpu_graph too)
 };
 GGConnectionFlags GGGetConnectionFlags(ClientContext &context);
 void GGSetConnectionFlags(ClientContext &context, const GGConnectionFlags &flags);

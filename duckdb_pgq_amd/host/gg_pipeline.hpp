@@ -191,6 +191,50 @@ public:
 	string ParamsToString() const override;
 };
 
+//===--------------------------------------------------------------------===//
+// UNION recursion with a depth counter over one keyed table (gg_recursive_levels.cpp, rule: PlanRecursiveWalks in
+// gg_plan_rule.cpp under PRAGMA enable_gpu_recursive_levels).  The same sinks and GGWalkInput; every column is CARRIED,
+// CONSTANT, a COUNTER or, at the link's position, the TABLE's next column.
+//===--------------------------------------------------------------------===//
+//! Source: the distinct anchor rows, then level by level the members of the level sets (gg_level_sets) as (carried
+//! columns, next, constants, start + step x level)
+class PhysicalGGRecursiveLevels : public PhysicalOperator {
+public:
+	PhysicalGGRecursiveLevels(vector<LogicalType> types, shared_ptr<GGGraph> graph, shared_ptr<GGWalkInput> input,
+	                          idx_t estimated_cardinality);
+	shared_ptr<GGGraph> graph;
+	shared_ptr<GGWalkInput> input;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_RECURSIVE_LEVELS";
+	}
+	string ParamsToString() const override;
+};
+
+//! what GG_RECURSIVE_REACH and GG_RECURSIVE_LEVELS share (gg_recursive_reach.cpp), rows compared as the reference's
+//! hash table compares them (NULL equal to NULL):
+//! the distinct rows of `rows`, in their first occurrence's order
+void GGDistinctRows(ClientContext &context, ChunkCollection &rows, const vector<LogicalType> &types,
+                    ChunkCollection &distinct);
+//! row_class[r]: the class of row r, classes being the distinct values of the columns `carried` numbered in order of
+//! appearance (none carried: one class); class_row[c]: the first row of class c
+void GGRowClasses(ClientContext &context, ChunkCollection &rows, const vector<idx_t> &carried,
+                  const vector<LogicalType> &carried_types, vector<uint32_t> &row_class, vector<idx_t> &class_row);
+//! every (class, vertex id) row of a device result and its rows per level, through its levels / fetch calls
+typedef int (*GGPairLevelsFn)(const gg_result *, uint64_t *, int, int *);
+typedef int (*GGPairFetchFn)(const gg_result *, uint64_t, uint32_t, int64_t *, int64_t *, int32_t *, uint32_t *);
+void GGFetchPairRows(gg_result *res, GGPairLevelsFn levels_fn, GGPairFetchFn fetch_fn, const char *what,
+                     vector<int64_t> &row_class, vector<int64_t> &vertex, vector<uint64_t> &per_level);
+//! target[i] = vertex[i] cast to the target's type, the sentinel as NULL, i < n
+void GGLinkColumn(const int64_t *vertex, idx_t n, int64_t sentinel, Vector &target);
+
 //! column `col` of every row of `rows` as int64 (NULL: valid[r] = false) (gg_recursive_walks.cpp)
 void GGIntegerColumn(ChunkCollection &rows, idx_t col, vector<int64_t> &out, vector<bool> &valid);
 //! target[i] = column `col` of row row[i] of `rows`, i < n (gg_recursive_walks.cpp)

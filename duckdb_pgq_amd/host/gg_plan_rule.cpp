@@ -1832,6 +1832,28 @@ bool ReferenceIndex(Expression &expr, idx_t &index) {
 	return true;
 }
 
+//! bi-10's next link `CASE WHEN a = b THEN x ELSE y END` in an arm that joins on a = b: if a, b and y are each one of the
+//! two sides of the join condition (is_join_key), the check always holds and the CASE is its THEN column, returned in
+//! `then_column` (RemoveUnusedColumns may already have rewritten one side of the condition into the other).  `resolve`
+//! maps an expression to the caller's notion of a column.
+template <class COLUMN, class RESOLVE, class IS_JOIN_KEY>
+bool CaseOverJoinCondition(Expression &expr, RESOLVE resolve, IS_JOIN_KEY is_join_key, COLUMN &then_column) {
+	if (expr.GetExpressionClass() != ExpressionClass::BOUND_CASE) {
+		return false;
+	}
+	auto &bound_case = (BoundCaseExpression &)expr;
+	if (bound_case.check->type != ExpressionType::COMPARE_EQUAL) {
+		return false;
+	}
+	auto &check = (BoundComparisonExpression &)*bound_case.check;
+	COLUMN l, r, if_false;
+	if (!resolve(*check.left, l) || !resolve(*check.right, r) || !resolve(*bound_case.result_if_true, then_column) ||
+	    !resolve(*bound_case.result_if_false, if_false)) {
+		return false;
+	}
+	return is_join_key(l) && is_join_key(r) && is_join_key(if_false);
+}
+
 //! binding of a leaf -> PlanColumn (GET: table column id; CTE scan: column position)
 bool ResolvePlanColumn(StepInput &in, const ColumnBinding &binding, PlanColumn &out) {
 	if (in.cte && in.cte->table_index == binding.table_index) {
@@ -2203,23 +2225,12 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 				return nullptr;
 			}
 		} else if (expr.GetExpressionClass() == ExpressionClass::BOUND_CASE) {
-			auto &bound_case = (BoundCaseExpression &)expr;
-			if (bound_case.check->type != ExpressionType::COMPARE_EQUAL) {
-				return nullptr;
-			}
-			auto &check = (BoundComparisonExpression &)*bound_case.check;
-			PlanColumn l, r, if_true, if_false;
-			if (!column_of(*check.left, l) || !column_of(*check.right, r) || !column_of(*bound_case.result_if_true, if_true) ||
-			    !column_of(*bound_case.result_if_false, if_false)) {
-				return nullptr;
-			}
-			PlanColumn edge_src;
+			PlanColumn edge_src, if_true;
 			edge_src.table_index = edge_get->table_index;
 			edge_src.column = src;
 			// the check repeats the join condition, so it always holds and the CASE is its THEN branch
-			// (RemoveUnusedColumns may already have rewritten e.src into the equal f.friend)
 			auto is_join_key = [&](const PlanColumn &c) { return c == cte_friend || c == edge_src; };
-			if (!is_join_key(l) || !is_join_key(r) || !is_join_key(if_false) ||
+			if (!CaseOverJoinCondition(expr, column_of, is_join_key, if_true) ||
 			    if_true.table_index != edge_get->table_index || if_true.column == src ||
 			    (dst != INVALID_INDEX && dst != if_true.column)) {
 				return nullptr;
@@ -2355,6 +2366,13 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 // GG_RECURSIVE_REACH (gg_recursive_reach.cpp) when the connection issued PRAGMA enable_gpu_recursive_union: every arm
 // column must then be carried, the next link, or a constant — no depth counter (its rows differ per level, so they
 // would never repeat), no other column of T, no CTE-side predicate.
+//
+// The UNION arm WITH depth counters (bi-10's friends(startPerson, hopCount, friend) under any consumer but the
+// shortest-path rule's min) becomes GG_RECURSIVE_LEVELS (gg_recursive_levels.cpp) when the connection issued PRAGMA
+// enable_gpu_recursive_levels: at least one column is counter + positive constant with a constant anchor value, every
+// other column is carried, a constant or the next link — a column of T, or bi-10's CASE over the join condition
+// (CaseOverJoinCondition) — and the only CTE-side predicates are `counter < K` / `<= K`, which bound the levels; the
+// last level's counter must fit its type.
 namespace {
 
 //! does the subtree read the CTE `index`?
@@ -2383,6 +2401,23 @@ bool CteSide(LogicalOperator &op, idx_t index, vector<Expression *> &filters) {
 		return true;
 	}
 	return false;
+}
+
+//! CteSide, or (the level sets' rule only) a filter over it that projects — what the optimizer leaves of `counter < K`
+//! when the arm does not read every CTE column: column_map[j] is then the CTE column of the side's output column j
+//! (empty: the CTE's own layout)
+bool CteSideProjected(LogicalOperator &op, idx_t index, vector<Expression *> &filters, vector<idx_t> &column_map) {
+	if (op.type != LogicalOperatorType::LOGICAL_FILTER || ((LogicalFilter &)op).projection_map.empty()) {
+		return CteSide(op, index, filters);
+	}
+	if (op.children.size() != 1 || !CteSide(*op.children[0], index, filters)) {
+		return false;
+	}
+	for (auto &expr : op.expressions) {
+		filters.push_back(expr.get());
+	}
+	column_map = ((LogicalFilter &)op).projection_map;
+	return true;
 }
 
 bool IsIntegral(const LogicalType &type) {
@@ -2419,11 +2454,14 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	if (op.children.size() != 2 || !g_plan_context || !g_plan_generator) {
 		return trace("not a recursive CTE of two children");
 	}
-	// UNION (not ALL): the reachability closure, under its own switch
-	const bool reach = !op.union_all;
-	if (reach && !GGGetConnectionFlags(*g_plan_context).recursive_union) {
+	// UNION (not ALL): the reachability closure, or with a depth counter the level sets, each under its own switch
+	const bool set_union = !op.union_all;
+	const auto flags = GGGetConnectionFlags(*g_plan_context);
+	if (set_union && !flags.recursive_union && !flags.recursive_levels) {
 		return trace("not UNION ALL (PRAGMA enable_gpu_recursive_union takes UNION)");
 	}
+	bool reach = set_union; // until a depth counter is met under PRAGMA enable_gpu_recursive_levels
+	bool levels = false;
 	if (std::getenv("GG_NO_PIPELINE_SINKS") || !gg_pipeline_rule_registered() || !g_plan_generator->rec_ctes.empty()) {
 		return trace("no pipeline sinks, or inside another recursive CTE");
 	}
@@ -2455,10 +2493,15 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		return trace("not an inner join on one equality");
 	}
 	vector<Expression *> cte_filters; // over the CTE's columns
+	vector<idx_t> cte_column_map; // the CTE side's output column -> CTE column, if the side projects (levels only)
+	auto cte_side = [&](LogicalOperator &side) {
+		return set_union && flags.recursive_levels ? CteSideProjected(side, op.table_index, cte_filters, cte_column_map)
+		                                           : CteSide(side, op.table_index, cte_filters);
+	};
 	idx_t cte_child;
-	if (CteSide(*join.children[0], op.table_index, cte_filters)) {
+	if (cte_side(*join.children[0])) {
 		cte_child = 0;
-	} else if (CteSide(*join.children[1], op.table_index, cte_filters)) {
+	} else if (cte_side(*join.children[1])) {
 		cte_child = 1;
 	} else {
 		return trace("the join does not scan the CTE directly");
@@ -2475,9 +2518,21 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		const idx_t k = j < left_width ? j : j - left_width;
 		auto &map = child == 0 ? join.left_projection_map : join.right_projection_map;
 		column = map.empty() ? k : (k < map.size() ? map[k] : INVALID_INDEX);
-		return column < join.children[child]->types.size();
+		if (column >= join.children[child]->types.size()) {
+			return false;
+		}
+		if (child == cte_child && !cte_column_map.empty()) {
+			column = cte_column_map[column];
+		}
+		return true;
 	};
-	const idx_t link = ((BoundReferenceExpression &)*(cte_child == 0 ? join.conditions[0].left : join.conditions[0].right)).index;
+	idx_t link = ((BoundReferenceExpression &)*(cte_child == 0 ? join.conditions[0].left : join.conditions[0].right)).index;
+	if (!cte_column_map.empty()) {
+		if (link >= cte_column_map.size()) {
+			return trace("link or key is not an integer column");
+		}
+		link = cte_column_map[link];
+	}
 	const idx_t key = ((BoundReferenceExpression &)*(cte_child == 0 ? join.conditions[0].right : join.conditions[0].left)).index;
 	if (link >= n_cols || key >= table.types.size() || !IsIntegral(op.types[link]) || !IsIntegral(table.types[key])) {
 		return trace("link or key is not an integer column");
@@ -2505,7 +2560,7 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 				}
 				spec.kind = GGWalkColumn::CARRIED;
 			} else {
-				if (reach && c != link) {
+				if (set_union && c != link) {
 					return trace("UNION: a column of the table other than the next link");
 				}
 				spec.kind = GGWalkColumn::TABLE;
@@ -2523,11 +2578,35 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 			    !join_column(ref, child, column) || child != cte_child || column != c) {
 				return trace("an arm expression other than counter + constant");
 			}
-			if (reach) {
-				return trace("UNION: a depth counter (its rows differ per level)");
+			if (set_union) {
+				if (!flags.recursive_levels) {
+					return trace("UNION: a depth counter (its rows differ per level)");
+				}
+				if (step <= 0) { // rows of different levels could be equal
+					return trace("UNION: a depth counter whose step is not positive");
+				}
+				reach = false;
+				levels = true;
 			}
 			spec.kind = GGWalkColumn::COUNTER;
 			spec.step = step;
+		} else if (set_union && flags.recursive_levels && c == link &&
+		           expr.GetExpressionClass() == ExpressionClass::BOUND_CASE) {
+			// bi-10's CASE over the join condition: the table column in its THEN branch
+			typedef std::pair<idx_t, idx_t> JoinSide; // (child of the join, column of that child)
+			auto resolve = [&](Expression &e, JoinSide &out) {
+				return ReferenceIndex(e, ref) && join_column(ref, out.first, out.second);
+			};
+			auto is_join_key = [&](const JoinSide &side) {
+				return side == JoinSide(cte_child, link) || side == JoinSide(t_child, key);
+			};
+			JoinSide then_column;
+			if (!CaseOverJoinCondition(expr, resolve, is_join_key, then_column) || then_column.first != t_child ||
+			    then_column.second == key) {
+				return trace("a CASE at the link's position that is not over the join condition");
+			}
+			spec.kind = GGWalkColumn::TABLE;
+			spec.index = then_column.second;
 		} else {
 			return trace("an arm expression of another kind");
 		}
@@ -2536,6 +2615,9 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		return trace("the next link is not an integer column of the table");
 	}
 	input->next_column = input->columns[link].index;
+	if (set_union && !levels && !flags.recursive_union) {
+		return trace("UNION without a depth counter (PRAGMA enable_gpu_recursive_union takes it)");
+	}
 	if (reach && (!cte_filters.empty() || !join_filters.empty())) {
 		return trace("UNION: a CTE-side predicate");
 	}
@@ -2586,6 +2668,27 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		}
 		input->max_levels = input->max_levels < 0 ? (int)levels : std::min(input->max_levels, (int)levels);
 	}
+	if (levels) {
+		// every counter starts at a constant, so that a level's rows differ from every other level's, and
+		// start + step * max_levels fits its type: the reference would raise an overflow there, this plan must not run
+		auto &anchor = *op.children[0];
+		for (idx_t c = 0; c < n_cols; c++) {
+			if (input->columns[c].kind != GGWalkColumn::COUNTER) {
+				continue;
+			}
+			int64_t start;
+			if (anchor.type != LogicalOperatorType::LOGICAL_PROJECTION || c >= anchor.expressions.size() ||
+			    !IntegerConstant(*anchor.expressions[c], start)) {
+				return trace("a counter whose anchor value is not a constant");
+			}
+			if (input->max_levels > 0) {
+				const hugeint_t last = hugeint_t(start) + hugeint_t(input->columns[c].step) * hugeint_t(input->max_levels);
+				if (last > Value::MaximumValue(op.types[c]).GetValue<hugeint_t>()) {
+					return trace("UNION: a depth counter that overflows its type within the bound");
+				}
+			}
+		}
+	}
 	// ---- plan: the anchor and the table by the reference's planner, under the sinks
 	string description = "link=#" + std::to_string(link) + " key=#" + std::to_string(key) + " next=#" +
 	                     std::to_string(input->next_column) +
@@ -2606,8 +2709,11 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	g_plan_generator = generator;
 	auto slot = make_shared<GGGraphSlot>();
 	auto scan = make_unique<PhysicalGGGraphScan>(
-	    types, reach ? "GG_RECURSIVE_REACH" : "GG_RECURSIVE_WALKS", description, slot,
-	    [types, input, cardinality, reach](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+	    types, levels ? "GG_RECURSIVE_LEVELS" : (reach ? "GG_RECURSIVE_REACH" : "GG_RECURSIVE_WALKS"), description, slot,
+	    [types, input, cardinality, reach, levels](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    if (levels) {
+			    return make_unique<PhysicalGGRecursiveLevels>(types, move(graph), input, cardinality);
+		    }
 		    if (reach) {
 			    return make_unique<PhysicalGGRecursiveReach>(types, move(graph), input, cardinality);
 		    }
@@ -3001,6 +3107,18 @@ void PragmaDisableGpuRecursiveUnion(ClientContext &context, const FunctionParame
 	GGSetConnectionFlags(context, flags);
 }
 
+void PragmaEnableGpuRecursiveLevels(ClientContext &context, const FunctionParameters &parameters) {
+	auto flags = GGGetConnectionFlags(context);
+	flags.recursive_levels = true;
+	GGSetConnectionFlags(context, flags);
+}
+
+void PragmaDisableGpuRecursiveLevels(ClientContext &context, const FunctionParameters &parameters) {
+	auto flags = GGGetConnectionFlags(context);
+	flags.recursive_levels = false;
+	GGSetConnectionFlags(context, flags);
+}
+
 void PragmaUsePinnedGraphs(ClientContext &context, const FunctionParameters &parameters) {
 	auto flags = GGGetConnectionFlags(context);
 	flags.pinned_graphs = true;
@@ -3047,6 +3165,12 @@ void GGRegisterPlanRules(ClientContext &context) {
 	    PragmaFunction::PragmaStatement("disable_gpu_recursive_union", PragmaDisableGpuRecursiveUnion));
 	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_on);
 	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_off);
+	CreatePragmaFunctionInfo levels_on(
+	    PragmaFunction::PragmaStatement("enable_gpu_recursive_levels", PragmaEnableGpuRecursiveLevels));
+	CreatePragmaFunctionInfo levels_off(
+	    PragmaFunction::PragmaStatement("disable_gpu_recursive_levels", PragmaDisableGpuRecursiveLevels));
+	Catalog::GetCatalog(context).CreatePragmaFunction(context, &levels_on);
+	Catalog::GetCatalog(context).CreatePragmaFunction(context, &levels_off);
 
 	// A reference built with oracle/callout.patch exports the registration of its call-outs: the maintainers' route —
 	// no interposition, no access to private members (the BuildPipelines case and the write observation are then the

@@ -65,6 +65,90 @@ void Project(DataChunk &chunk, const vector<idx_t> &cols, const vector<LogicalTy
 
 } // namespace
 
+void GGDistinctRows(ClientContext &context, ChunkCollection &rows, const vector<LogicalType> &types,
+                    ChunkCollection &distinct) {
+	GroupedAggregateHashTable rows_ht(BufferManager::GetBufferManager(context), types);
+	Vector addresses(LogicalType::POINTER);
+	SelectionVector new_groups(STANDARD_VECTOR_SIZE);
+	for (idx_t c = 0; c < rows.ChunkCount(); c++) {
+		DataChunk chunk;
+		chunk.Initialize(types);
+		rows.GetChunk(c).Copy(chunk);
+		const idx_t n_new = rows_ht.FindOrCreateGroups(chunk, addresses, new_groups);
+		if (n_new > 0) {
+			chunk.Slice(new_groups, n_new);
+			distinct.Append(chunk);
+		}
+	}
+}
+
+void GGRowClasses(ClientContext &context, ChunkCollection &rows, const vector<idx_t> &carried,
+                  const vector<LogicalType> &carried_types, vector<uint32_t> &row_class, vector<idx_t> &class_row) {
+	row_class.assign(rows.Count(), 0);
+	class_row.clear();
+	if (carried.empty()) {
+		if (rows.Count() > 0) {
+			class_row.push_back(0);
+		}
+		return;
+	}
+	GroupedAggregateHashTable class_ht(BufferManager::GetBufferManager(context), carried_types);
+	std::unordered_map<uintptr_t, uint32_t> class_of;
+	Vector addresses(LogicalType::POINTER);
+	idx_t at = 0;
+	for (idx_t c = 0; c < rows.ChunkCount(); c++) {
+		auto &chunk = rows.GetChunk(c);
+		DataChunk groups;
+		Project(chunk, carried, carried_types, groups);
+		class_ht.FindOrCreateGroups(groups, addresses);
+		auto address = FlatVector::GetData<data_ptr_t>(addresses);
+		for (idx_t r = 0; r < chunk.size(); r++, at++) {
+			auto entry = class_of.emplace((uintptr_t)address[r], (uint32_t)class_row.size());
+			if (entry.second) {
+				class_row.push_back(at);
+			}
+			row_class[at] = entry.first->second;
+		}
+	}
+}
+
+void GGFetchPairRows(gg_result *res, GGPairLevelsFn levels_fn, GGPairFetchFn fetch_fn, const char *what,
+                     vector<int64_t> &row_class, vector<int64_t> &vertex, vector<uint64_t> &per_level) {
+	int n_levels = 0;
+	GGGraph::Check(levels_fn(res, nullptr, 0, &n_levels), what);
+	per_level.assign(MaxValue<int>(n_levels, 1), 0);
+	GGGraph::Check(levels_fn(res, per_level.data(), n_levels, &n_levels), what);
+	per_level.resize(n_levels);
+	uint64_t total = 0;
+	for (int l = 0; l < n_levels; l++) {
+		total += per_level[l];
+	}
+	row_class.resize(total);
+	vertex.resize(total);
+	for (uint64_t at = 0; at < total;) {
+		uint32_t got = 0;
+		const uint32_t want = (uint32_t)MinValue<uint64_t>(total - at, 1u << 24);
+		GGGraph::Check(fetch_fn(res, at, want, row_class.data() + at, vertex.data() + at, nullptr, &got), what);
+		if (got == 0) {
+			throw InternalException(string(what) + ": a fetch returned no rows");
+		}
+		at += got;
+	}
+}
+
+void GGLinkColumn(const int64_t *vertex, idx_t n, int64_t sentinel, Vector &target) {
+	Vector wide(LogicalType::BIGINT);
+	auto values = FlatVector::GetData<int64_t>(wide);
+	auto &validity = FlatVector::Validity(wide);
+	for (idx_t i = 0; i < n; i++) {
+		values[i] = vertex[i];
+		if (values[i] == sentinel) {
+			validity.SetInvalid(i);
+		}
+	}
+	VectorOperations::Cast(wide, target, n);
+}
+
 unique_ptr<GlobalSourceState> PhysicalGGRecursiveReach::GetGlobalSourceState(ClientContext &context) const {
 	auto state = make_unique<RecursiveReachState>();
 	auto &buffer_manager = BufferManager::GetBufferManager(context);
@@ -81,49 +165,12 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveReach::GetGlobalSourceState(Cli
 	}
 	lock_guard<mutex> guard(input->lock);
 	// ---- the distinct anchor rows: the groups a hash table over every column creates, in order
-	{
-		GroupedAggregateHashTable rows_ht(buffer_manager, types);
-		Vector addresses(LogicalType::POINTER);
-		SelectionVector new_groups(STANDARD_VECTOR_SIZE);
-		for (idx_t c = 0; c < input->anchor.ChunkCount(); c++) {
-			DataChunk chunk;
-			chunk.Initialize(types);
-			input->anchor.GetChunk(c).Copy(chunk);
-			const idx_t n_new = rows_ht.FindOrCreateGroups(chunk, addresses, new_groups);
-			if (n_new > 0) {
-				chunk.Slice(new_groups, n_new);
-				state->distinct.Append(chunk);
-			}
-		}
-	}
+	GGDistinctRows(context, input->anchor, types, state->distinct);
 	const idx_t n_distinct = state->distinct.Count();
 	// ---- classes (the group of C), seen flags (K equal to the arm's constants)
-	vector<uint32_t> seed_class(n_distinct, 0);
+	vector<uint32_t> seed_class;
 	vector<uint8_t> seen(n_distinct, 1);
-	if (carried.empty()) {
-		if (n_distinct > 0) {
-			state->class_row.push_back(0);
-		}
-	} else {
-		GroupedAggregateHashTable class_ht(buffer_manager, carried_types);
-		std::unordered_map<uintptr_t, uint32_t> class_of;
-		Vector addresses(LogicalType::POINTER);
-		idx_t at = 0;
-		for (idx_t c = 0; c < state->distinct.ChunkCount(); c++) {
-			auto &chunk = state->distinct.GetChunk(c);
-			DataChunk groups;
-			Project(chunk, carried, carried_types, groups);
-			class_ht.FindOrCreateGroups(groups, addresses);
-			auto address = FlatVector::GetData<data_ptr_t>(addresses);
-			for (idx_t r = 0; r < chunk.size(); r++, at++) {
-				auto entry = class_of.emplace((uintptr_t)address[r], (uint32_t)state->class_row.size());
-				if (entry.second) {
-					state->class_row.push_back(at);
-				}
-				seed_class[at] = entry.first->second;
-			}
-		}
-	}
+	GGRowClasses(context, state->distinct, carried, carried_types, seed_class, state->class_row);
 	if (!constants.empty()) {
 		GroupedAggregateHashTable constant_ht(buffer_manager, constant_types);
 		Vector addresses(LogicalType::POINTER);
@@ -165,27 +212,9 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveReach::GetGlobalSourceState(Cli
 	                                (uint32_t)state->class_row.size(), &res),
 	               "gg_reach_closure");
 	std::unique_ptr<gg_result, void (*)(gg_result *)> owner(res, gg_result_destroy);
-	int n_levels = 0;
-	GGGraph::Check(gg_reach_closure_levels(res, nullptr, 0, &n_levels), "gg_reach_closure_levels");
-	vector<uint64_t> per_level(MaxValue<int>(n_levels, 1));
-	GGGraph::Check(gg_reach_closure_levels(res, per_level.data(), n_levels, &n_levels), "gg_reach_closure_levels");
-	uint64_t total = 0;
-	for (int l = 0; l < n_levels; l++) {
-		total += per_level[l];
-	}
-	state->row_class.resize(total);
-	state->vertex.resize(total);
-	for (uint64_t at = 0; at < total;) {
-		uint32_t got = 0;
-		const uint32_t want = (uint32_t)MinValue<uint64_t>(total - at, 1u << 24);
-		GGGraph::Check(gg_reach_closure_fetch(res, at, want, state->row_class.data() + at, state->vertex.data() + at,
-		                                      nullptr, &got),
-		               "gg_reach_closure_fetch");
-		if (got == 0) {
-			throw InternalException("gg_reach_closure_fetch returned no rows");
-		}
-		at += got;
-	}
+	vector<uint64_t> per_level;
+	GGFetchPairRows(res, gg_reach_closure_levels, gg_reach_closure_fetch, "gg_reach_closure", state->row_class,
+	                state->vertex, per_level);
 	return move(state);
 }
 
@@ -214,19 +243,9 @@ void PhysicalGGRecursiveReach::GetData(ExecutionContext &context, DataChunk &chu
 		case GGWalkColumn::CONSTANT:
 			chunk.data[c].Reference(spec.constant);
 			break;
-		case GGWalkColumn::TABLE: { // the next link: the vertex reached, the sentinel as NULL
-			Vector wide(LogicalType::BIGINT);
-			auto values = FlatVector::GetData<int64_t>(wide);
-			auto &validity = FlatVector::Validity(wide);
-			for (idx_t i = 0; i < n; i++) {
-				values[i] = state.vertex[state.next_row + i];
-				if (values[i] == input->sentinel) {
-					validity.SetInvalid(i);
-				}
-			}
-			VectorOperations::Cast(wide, chunk.data[c], n);
+		case GGWalkColumn::TABLE: // the next link: the vertex reached, the sentinel as NULL
+			GGLinkColumn(state.vertex.data() + state.next_row, n, input->sentinel, chunk.data[c]);
 			break;
-		}
 		case GGWalkColumn::COUNTER:
 			throw InternalException("GG_RECURSIVE_REACH: a depth counter");
 		}

@@ -46,6 +46,10 @@
  *        <- PhysicalRecursiveCTE over a UNION arm that joins the CTE with one table: every produced row probed against
  *           a hash table of the rows emitted so far     src/execution/operator/set/physical_recursive_cte.cpp:47-139
  *           (reachability over knows, extended_tags of benchmark/ldbc/queries/interactive-complex-12.sql)
+ *   gg_level_sets / gg_level_sets_levels / gg_level_sets_fetch
+ *        <- PhysicalRecursiveCTE over a UNION arm with a depth counter: rows deduplicated inside a level only
+ *                                                               src/execution/operator/set/physical_recursive_cte.cpp:47-139
+ *           (the friends CTE of benchmark/ldbc/queries/bi-10-shortestpath.sql:8-25 under any consumer)
  *
  * Conventions
  *   - every int-returning function returns GG_OK (0) or a negative GG_ERR_*; the message is
@@ -363,6 +367,33 @@ int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int 
 int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
                            int64_t *vertex_id, int32_t *level, uint32_t *n_out);
 
+/* The level sets of the seeds — the rows a UNION recursive CTE adds to its anchor when its arm joins the CTE's link column
+ * with a table's key column, carries the table's next column as the new link and adds a positive constant to a depth
+ * counter (friends(startPerson, hopCount, friend) of benchmark/ldbc/queries/bi-10-shortestpath.sql:8-25).  A row of level
+ * L carries start + step * L and so never equals a row of another level: the reference's hash table of all rows so far
+ * (src/execution/operator/set/physical_recursive_cte.cpp:47-70) only ever removes duplicates inside a level.
+ * The table's rows are the CSR's edges key -> next (edge rowids are not needed).  Level 0 is the set of
+ * (seed_class[i], seed_ids[i]); a seed that is not a vertex contributes nothing and duplicate seeds collapse.  Level
+ * L >= 1 is the set of (c, w) with (c, u) in level L - 1 and u -> w an edge.  A vertex without out-edges (a NULL next's
+ * sentinel) is a member and is never expanded.
+ * One row (class, vertex id, L) per member of every level L >= 1.  Rows come by level; inside a level ascending by
+ * (class, the vertex's dense index in the CSR) — gg_reach_closure's order, the same on every run and on every route.
+ * max_levels >= 0: levels 1..max_levels; < 0: until a level is empty.  An unbounded run whose level V + 1 is not empty
+ * has met a cycle — the reference would never end — and fails with GG_ERR_STATE (after V + 1 levels: a caller that may
+ * meet cycles bounds max_levels).  A level of 2^32 children or more fails with GG_ERR_TOO_LARGE, as do 2^32 seeds or
+ * more; a class >= n_classes with GG_ERR_INVALID_ARG; a shard CSR with GG_ERR_STATE.
+ * The per-level set is a bitmap of n_classes x V bits within gg_reach_closure's budget, else a hash set sized from the
+ * level's child count; a level's rows are read off the bitmap in order or claimed and sorted (DESIGN.md 4.9;
+ * gg_debug_level_sets forces either).  The result answers gg_level_sets_levels / gg_level_sets_fetch only. */
+int gg_level_sets(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, const uint32_t *seed_class, uint64_t n_seeds,
+                  uint32_t n_classes, int max_levels, gg_result **out_result);
+/* *n_levels = the deepest level L with rows; rows_per_level[L - 1] = members of level L, for the first `capacity`. */
+int gg_level_sets_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
+/* Copy rows [offset, offset+max_rows), in row order, into host arrays of >= max_rows entries (level may be NULL).
+ * *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
+int gg_level_sets_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
+                        int64_t *vertex_id, int32_t *level, uint32_t *n_out);
+
 /* ---- graph-sharded 64-lane BFS (one shard of the graph per GPU) ------------------------------- */
 /* The layout north_star names for graphs that do not fit one GPU: `shard` comes from
  * gg_csr_build_shard; every rank holds the whole frontier (one uint64 of 64 lanes per vertex) and owns the
@@ -418,6 +449,11 @@ int gg_debug_max_grid_tiles(gg_ctx *ctx, uint64_t max_tiles);
  * 2: the hash set, first sized max(hash_initial_slots, 2 x seen seeds) slots when hash_initial_slots != 0 (a tiny size
  * makes it grow by rebuilds).  Both forms must give identical rows in identical order. */
 int gg_debug_reach_visited(gg_ctx *ctx, int mode /* 0 auto, 1 bitmap, 2 hash */, uint64_t hash_initial_slots);
+/* Testing knob: gg_level_sets' per-level set (0: the budget decides, 1: the bitmap, 2: the hash set) and order route
+ * (0: the byte model decides per level, 1: claim and sort, 2: read the rows off the bitmap).  The compact route needs a
+ * bitmap: set_mode 2 with order_mode 2 is GG_ERR_INVALID_ARG.  Every combination must give identical rows in identical
+ * order. */
+int gg_debug_level_sets(gg_ctx *ctx, int set_mode /* 0 auto, 1 bitmap, 2 hash */, int order_mode /* 0 auto, 1 sort, 2 compact */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
