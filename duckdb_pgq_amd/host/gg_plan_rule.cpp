@@ -1025,7 +1025,66 @@ GGGraphSpec GraphSpecOf(const WalkPattern &pattern) {
 	return spec;
 }
 
-//! PhysicalTableScan over the gg scan function for `hops`-hop walks of the pattern.
+//! The scan-function route of MakeGraphSource: a PhysicalTableScan over the gg scan function `function` (columns `names`,
+//! c0 ... cN where not given).  When the scan opens `build` makes the graph, and only then the factory runs, which may
+//! read more rows itself (the probe keys, the BFS seeds).
+using GraphBuilder = std::function<shared_ptr<GGGraph>(ClientContext &)>;
+unique_ptr<PhysicalOperator> MakeFunctionScan(GraphBuilder build, vector<LogicalType> types, const string &function,
+                                              const string &description, bool parallel_result,
+                                              PhysicalGGGraphScan::Factory factory, idx_t estimated_cardinality,
+                                              vector<string> names) {
+	auto data = make_unique<GGFunctionData>();
+	data->open = [build, factory](ClientContext &context, GGOpened &opened) {
+		opened.graph = build(context);
+		opened.source = factory(context, opened.graph);
+	};
+	data->description = description;
+	data->parallel_result = parallel_result;
+	vector<column_t> column_ids;
+	for (idx_t c = 0; c < types.size(); c++) {
+		column_ids.push_back(c);
+		if (names.size() <= c) {
+			names.push_back("c" + to_string(c));
+		}
+	}
+	return make_unique<PhysicalTableScan>(move(types), GGScanFunction(function), move(data), move(column_ids), move(names),
+	                                      nullptr, estimated_cardinality);
+}
+
+//! A rule's GPU scan on whichever route is available; every plan a rule takes over passes here once.  If the tables of
+//! `spec` can reach the device through pipeline sinks the reference's executor schedules (gg_pipeline.cpp; sinks_route
+//! false: the rule has no such route), a PhysicalGGGraphScan named `name` over them; otherwise the scan function
+//! `function`, which calls GGBuildGraph when it opens.  The one `factory` makes the source operator on both routes.
+unique_ptr<PhysicalOperator> MakeGraphSource(const GGGraphSpec &spec, vector<LogicalType> types, const string &function,
+                                             const string &name, const string &description, bool parallel_result,
+                                             PhysicalGGGraphScan::Factory factory, idx_t estimated_cardinality,
+                                             vector<string> names = {}, bool sinks_route = true) {
+	g_rules_fired++;
+	if (sinks_route && g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
+		return GGMakeGraphScan(spec, move(types), name, description, parallel_result, move(factory),
+		                       estimated_cardinality);
+	}
+	return MakeFunctionScan([spec](ClientContext &context) { return GGBuildGraph(context, spec); }, move(types), function,
+	                        description, parallel_result, move(factory), estimated_cardinality, move(names));
+}
+
+//! The same for a graph that takes several edge-table passes: `sinks` in build order (empty: pipeline sinks are not
+//! available), and the rule's own `build` of the same graph for the scan-function route.
+unique_ptr<PhysicalOperator> MakeGraphSource(const vector<GGSinkSpec> &sinks, GraphBuilder build,
+                                             vector<LogicalType> types, const string &function, const string &name,
+                                             const string &description, bool parallel_result,
+                                             PhysicalGGGraphScan::Factory factory, idx_t estimated_cardinality,
+                                             vector<string> names = {}) {
+	g_rules_fired++;
+	if (!sinks.empty()) {
+		return GGMakeGraphScan(sinks, move(types), name, description, parallel_result, move(factory),
+		                       estimated_cardinality);
+	}
+	return MakeFunctionScan(move(build), move(types), function, description, parallel_result, move(factory),
+	                        estimated_cardinality, move(names));
+}
+
+//! The GPU scan for `hops`-hop walks of the pattern.
 unique_ptr<PhysicalOperator> MakeExpandScan(const WalkPattern &pattern, bool count_only, idx_t estimated_cardinality) {
 	auto spec = GraphSpecOf(pattern);
 	const int hops = (int)pattern.hops;
@@ -1038,43 +1097,23 @@ unique_ptr<PhysicalOperator> MakeExpandScan(const WalkPattern &pattern, bool cou
 		// ranks inside one process, for a host with several GPUs; the rows of each shard cross its own PCIe link
 		spec.shards = GGGraph::ConfiguredParts();
 	}
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		// (the planner's count(*) needs the number of walks only: degrees, not the counting expansion's checksum)
-		opened.source = make_unique<PhysicalGGPathExpand>(opened.graph, hops, hops, count_only, sources, all_sources, 0,
-		                                                  count_only);
-	};
-	data->description = pattern.edge_table->name + ": " + pattern.edge_table->columns[pattern.src_column].name +
-	                    " -> " + pattern.edge_table->columns[pattern.dst_column].name + "\n" + to_string(hops) +
-	                    (hops == 1 ? " hop" : " hops") + "\nvertices: " +
-	                    (pattern.vertex_table ? pattern.vertex_table->name + "." +
-	                                                pattern.vertex_table->columns[pattern.vertex_key].name
-	                                          : string("endpoint ids")) +
-	                    (all_sources ? string() : "\nfrom " + to_string(sources[0])) +
-	                    (spec.shards > 1 ? "\nshards: " + to_string(spec.shards) : string());
-	data->parallel_result = !count_only;
-	auto types = PhysicalGGPathExpand::OutputTypes(hops, count_only);
-	if (g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
-		// the tables reach the device through pipeline sinks the reference's executor schedules (gg_pipeline.cpp)
-		g_rules_fired++;
-		return GGMakeGraphScan(
-		    spec, move(types), count_only ? "GG_PATH_COUNT" : "GG_PATH_EXPAND", data->description, !count_only,
-		    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    return make_unique<PhysicalGGPathExpand>(move(graph), hops, hops, count_only, sources, all_sources, 0,
-			                                             count_only);
-		    },
-		    estimated_cardinality);
-	}
-	vector<column_t> column_ids;
-	vector<string> names;
-	for (idx_t c = 0; c < types.size(); c++) {
-		column_ids.push_back(c);
-		names.push_back("c" + to_string(c));
-	}
-	g_rules_fired++;
-	return make_unique<PhysicalTableScan>(move(types), GGScanFunction(count_only ? "gg_path_count" : "gg_path_expand"),
-	                                      move(data), move(column_ids), move(names), nullptr, estimated_cardinality);
+	const auto description =
+	    pattern.edge_table->name + ": " + pattern.edge_table->columns[pattern.src_column].name + " -> " +
+	    pattern.edge_table->columns[pattern.dst_column].name + "\n" + to_string(hops) + (hops == 1 ? " hop" : " hops") +
+	    "\nvertices: " +
+	    (pattern.vertex_table ? pattern.vertex_table->name + "." + pattern.vertex_table->columns[pattern.vertex_key].name
+	                          : string("endpoint ids")) +
+	    (all_sources ? string() : "\nfrom " + to_string(sources[0])) +
+	    (spec.shards > 1 ? "\nshards: " + to_string(spec.shards) : string());
+	return MakeGraphSource(
+	    spec, PhysicalGGPathExpand::OutputTypes(hops, count_only), count_only ? "gg_path_count" : "gg_path_expand",
+	    count_only ? "GG_PATH_COUNT" : "GG_PATH_EXPAND", description, !count_only,
+	    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    // (the planner's count(*) needs the number of walks only: degrees, not the counting expansion's checksum)
+		    return make_unique<PhysicalGGPathExpand>(move(graph), hops, hops, count_only, sources, all_sources, 0,
+		                                             count_only);
+	    },
+	    estimated_cardinality);
 }
 
 
@@ -1375,40 +1414,38 @@ unique_ptr<PhysicalOperator> PlanSameNeighbourPaths(LogicalComparisonJoin &op, P
 	if (pattern.source_table) {
 		sources = TableColumns(pattern.source_table, {pattern.source_key});
 	}
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = make_shared<GGGraph>(0);
+	// the scan-function route reads the tables when the scan opens
+	auto build = [=](ClientContext &context) {
+		auto graph = make_shared<GGGraph>(0);
 		const vector<LogicalType> two = {LogicalType::BIGINT, LogicalType::BIGINT};
 		// vertex set = endpoint ids of both edge tables: the path table contributes its endpoints first ...
-		PhysicalGGEdgeSink endpoints(opened.graph, two, 0, false, true, false, false);
+		PhysicalGGEdgeSink endpoints(graph, two, 0, false, true, false, false);
 		GGRunSinkPipeline(context, path, endpoints);
 		// ... the filter table adds its own and builds the filter CSR over the union ...
-		PhysicalGGEdgeSink filter_sink(opened.graph, two, 0, true, true, true, true);
+		PhysicalGGEdgeSink filter_sink(graph, two, 0, true, true, true, true);
 		GGRunSinkPipeline(context, filter, filter_sink);
 		// ... and the path table comes back for its CSR over the same vertex numbering
-		GGGraph::Check(gg_staging_clear_edges(opened.graph->ctx), "gg_staging_clear_edges");
-		PhysicalGGEdgeSink path_sink(opened.graph, two, 0);
+		GGGraph::Check(gg_staging_clear_edges(graph->ctx), "gg_staging_clear_edges");
+		PhysicalGGEdgeSink path_sink(graph, two, 0);
 		GGRunSinkPipeline(context, path, path_sink);
-		vector<int64_t> source_ids;
-		if (sources.table) {
-			source_ids = GGScanInt64Column(context, sources);
-		}
-		opened.source = make_unique<PhysicalGGFilteredPaths>(opened.graph, hops, move(source_ids), 0, sources.table == nullptr);
+		return graph;
 	};
-	data->description = pattern.path_table->name + ": " + pattern.path_table->columns[pattern.path_src].name + " -> " +
-	                    pattern.path_table->columns[pattern.path_dst].name + "\n" + to_string(hops) +
-	                    (hops == 1 ? " hop" : " hops") + "\nall on one " + pattern.filter_table->name + "." +
-	                    pattern.filter_table->columns[pattern.filter_dst].name +
-	                    (pattern.source_table ? "\nfrom every " + pattern.source_table->name : string());
-	vector<LogicalType> types(hops + 2, LogicalType::BIGINT);
-	g_rules_fired++;
-	unique_ptr<PhysicalOperator> scan;
+	const auto description = pattern.path_table->name + ": " + pattern.path_table->columns[pattern.path_src].name +
+	                         " -> " + pattern.path_table->columns[pattern.path_dst].name + "\n" + to_string(hops) +
+	                         (hops == 1 ? " hop" : " hops") + "\nall on one " + pattern.filter_table->name + "." +
+	                         pattern.filter_table->columns[pattern.filter_dst].name +
+	                         (pattern.source_table ? "\nfrom every " + pattern.source_table->name : string());
+	vector<string> names = {"w"};
+	for (int v = 0; v <= hops; v++) {
+		names.push_back("v" + to_string(v));
+	}
+	vector<GGSinkSpec> sinks;
 	GGGraphSpec sinks_spec;  // (what GGPipelineSinksAvailable looks at: plain tables, no pinned graphs)
 	sinks_spec.edges = path;
 	if (g_plan_context && filter.table && GGPipelineSinksAvailable(*g_plan_context, sinks_spec)) {
 		// the three table passes as pipeline sinks the reference's executor schedules (gg_pipeline.cpp), in build order:
 		// endpoints of the path table, the filter table (its endpoints and its CSR), the path table's CSR
-		vector<GGSinkSpec> sinks(3);
+		sinks.resize(3);
 		sinks[0].rows = path;
 		sinks[0].options.first = true;
 		sinks[0].options.derive_vertices = true;
@@ -1418,26 +1455,18 @@ unique_ptr<PhysicalOperator> PlanSameNeighbourPaths(LogicalComparisonJoin &op, P
 		sinks[1].options.as_filter = sinks[1].options.derive_vertices = sinks[1].options.keep_vertices = true;
 		sinks[1].options.clear_edges_after = true;  // the path table's rows come back for its own CSR
 		sinks[2].rows = path;
-		scan = GGMakeGraphScan(
-		    sinks, move(types), "GG_SAME_NEIGHBOUR_WALKS", data->description, false /* one thread drains the result */,
-		    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    vector<int64_t> source_ids;
-			    if (sources.table) {
-				    source_ids = GGScanInt64Column(context, sources);
-			    }
-			    return make_unique<PhysicalGGFilteredPaths>(move(graph), hops, move(source_ids), 0, sources.table == nullptr);
-		    },
-		    op.estimated_cardinality);
-	} else {
-		vector<column_t> column_ids;
-		vector<string> names;
-		for (idx_t c = 0; c < types.size(); c++) {
-			column_ids.push_back(c);
-			names.push_back(c == 0 ? "w" : "v" + to_string(c - 1));
-		}
-		scan = make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_same_neighbour_walks"), move(data),
-		                                      move(column_ids), move(names), nullptr, op.estimated_cardinality);
 	}
+	auto scan = MakeGraphSource(
+	    sinks, build, vector<LogicalType>(hops + 2, LogicalType::BIGINT), "gg_same_neighbour_walks",
+	    "GG_SAME_NEIGHBOUR_WALKS", description, false /* one thread drains the result */,
+	    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    vector<int64_t> source_ids;
+		    if (sources.table) {
+			    source_ids = GGScanInt64Column(context, sources);
+		    }
+		    return make_unique<PhysicalGGFilteredPaths>(move(graph), hops, move(source_ids), 0, sources.table == nullptr);
+	    },
+	    op.estimated_cardinality, move(names));
 	auto projection = make_unique<PhysicalProjection>(op.types, move(select_list), op.estimated_cardinality);
 	projection->children.push_back(move(scan));
 	return move(projection);
@@ -1455,26 +1484,18 @@ unique_ptr<PhysicalOperator> MakeEdgeScan(const WalkPattern &pattern, const vect
 	const auto sources = pattern.sources;
 	const bool all_sources = pattern.all_sources;
 	auto edge_table = pattern.edge_table;
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		opened.source = make_unique<PhysicalGGPathEdges>(opened.graph, hops, sources, all_sources, edge_table, payload, 0);
-	};
-	data->description = pattern.edge_table->name + ": " + pattern.edge_table->columns[pattern.src_column].name + " -> " +
-	                    pattern.edge_table->columns[pattern.dst_column].name + "\n" + to_string(hops) +
-	                    (hops == 1 ? " hop" : " hops") + "\nwith " + to_string(payload.size()) +
-	                    (payload.size() == 1 ? " edge column by rowid" : " edge columns by rowid") +
-	                    (all_sources ? string() : "\nfrom " + to_string(sources[0]));
-	auto types = PhysicalGGPathEdges::OutputTypes(hops, *edge_table, payload);
-	vector<column_t> column_ids;
-	vector<string> names;
-	for (idx_t c = 0; c < types.size(); c++) {
-		column_ids.push_back(c);
-		names.push_back("c" + to_string(c));
-	}
-	g_rules_fired++;
-	return make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_path_edges"), move(data), move(column_ids),
-	                                      move(names), nullptr, estimated_cardinality);
+	const auto description = pattern.edge_table->name + ": " + pattern.edge_table->columns[pattern.src_column].name +
+	                         " -> " + pattern.edge_table->columns[pattern.dst_column].name + "\n" + to_string(hops) +
+	                         (hops == 1 ? " hop" : " hops") + "\nwith " + to_string(payload.size()) +
+	                         (payload.size() == 1 ? " edge column by rowid" : " edge columns by rowid") +
+	                         (all_sources ? string() : "\nfrom " + to_string(sources[0]));
+	return MakeGraphSource(
+	    spec, PhysicalGGPathEdges::OutputTypes(hops, *edge_table, payload), "gg_path_edges", "GG_PATH_EDGES", description,
+	    false,
+	    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    return make_unique<PhysicalGGPathEdges>(move(graph), hops, sources, all_sources, edge_table, payload, 0);
+	    },
+	    estimated_cardinality, {}, false /* the scan-function route only */);
 }
 
 unique_ptr<PhysicalOperator> PlanJoinChain(LogicalComparisonJoin &op) {
@@ -1595,34 +1616,15 @@ unique_ptr<PhysicalOperator> MakeKeyJoinCountScan(PatternInput &in) {
 	GGGraphSpec spec;
 	spec.edges = TableColumns(build_table, {b.column, b.column}); // (key -> key: only the degree of a key matters)
 	const auto probe = TableColumns(probe_table, {a.column});
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		opened.source = make_unique<PhysicalGGPathExpand>(opened.graph, 1, 1, true, GGScanInt64Column(context, probe), false,
-		                                                  0, true);
-	};
-	data->description = build_table->name + "." + build_table->columns[b.column].name + "\nprobed with " +
-	                    probe_table->name + "." + probe_table->columns[a.column].name + "\n1 hop";
-	data->parallel_result = false;
-	auto types = PhysicalGGPathExpand::OutputTypes(1, true);
-	g_rules_fired++;
-	if (g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
-		return GGMakeGraphScan(
-		    spec, move(types), "GG_JOIN_COUNT", data->description, false,
-		    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    return make_unique<PhysicalGGPathExpand>(move(graph), 1, 1, true, GGScanInt64Column(context, probe), false, 0,
-			                                             true);
-		    },
-		    1);
-	}
-	vector<column_t> column_ids;
-	vector<string> names;
-	for (idx_t c = 0; c < types.size(); c++) {
-		column_ids.push_back(c);
-		names.push_back("c" + to_string(c));
-	}
-	return make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_join_count"), move(data), move(column_ids),
-	                                      move(names), nullptr, 1);
+	const auto description = build_table->name + "." + build_table->columns[b.column].name + "\nprobed with " +
+	                         probe_table->name + "." + probe_table->columns[a.column].name + "\n1 hop";
+	return MakeGraphSource(
+	    spec, PhysicalGGPathExpand::OutputTypes(1, true), "gg_join_count", "GG_JOIN_COUNT", description, false,
+	    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    return make_unique<PhysicalGGPathExpand>(move(graph), 1, 1, true, GGScanInt64Column(context, probe), false, 0,
+		                                             true);
+	    },
+	    1);
 }
 
 //! Join rule 3 (PRAGMA enable_gpu_joins): ANY inner join on one equality of two integer columns whose build side —
@@ -2309,38 +2311,22 @@ unique_ptr<PhysicalOperator> PlanShortestPath(LogicalAggregate &op) {
 		}
 		return sources;
 	};
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		opened.source = make_unique<PhysicalGGShortestPath>(opened.graph, read_seeds(context), max_hops, 0, lone_sources);
-	};
-	data->description = edge_table->name + ": " + edge_table->columns[src].name + " -> " + edge_table->columns[dst].name +
-	                    "\nmin hops <= " + to_string(max_hops) + "\nvertices: " +
-	                    (validated ? vertex_table->name + "." + vertex_table->columns[vertex_key].name
-	                               : string("endpoint ids")) +
-	                    "\nfrom " +
-	                    (seed_predicates.empty() ? "every " + vertex_table->name
-	                     : all_vertices          ? vertex_table->name + " where " + seed_predicates[0]
-	                                             : to_string(seed_constants.size()) +
-	                                          (seed_constants.size() == 1 ? " id" : " ids"));
-	data->parallel_result = true;
-	vector<LogicalType> types = {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER};
-	vector<column_t> column_ids = {0, 1, 2};
-	vector<string> names = {"startPerson", "friend", "hopCount"};
-	g_rules_fired++;
-	unique_ptr<PhysicalOperator> scan;
-	if (g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
-		// the tables reach the device through pipeline sinks (gg_pipeline.cpp); the seeds are read when the graph exists
-		scan = GGMakeGraphScan(
-		    spec, move(types), "GG_SHORTEST_PATH_BFS", data->description, true,
-		    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    return make_unique<PhysicalGGShortestPath>(move(graph), read_seeds(context), max_hops, 0, lone_sources);
-		    },
-		    op.estimated_cardinality);
-	} else {
-		scan = make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_shortest_path_bfs"), move(data),
-		                                      move(column_ids), move(names), nullptr, op.estimated_cardinality);
-	}
+	const auto description =
+	    edge_table->name + ": " + edge_table->columns[src].name + " -> " + edge_table->columns[dst].name +
+	    "\nmin hops <= " + to_string(max_hops) + "\nvertices: " +
+	    (validated ? vertex_table->name + "." + vertex_table->columns[vertex_key].name : string("endpoint ids")) +
+	    "\nfrom " +
+	    (seed_predicates.empty() ? "every " + vertex_table->name
+	     : all_vertices          ? vertex_table->name + " where " + seed_predicates[0]
+	                             : to_string(seed_constants.size()) + (seed_constants.size() == 1 ? " id" : " ids"));
+	// (on either route the seeds are read when the graph exists)
+	auto scan = MakeGraphSource(
+	    spec, {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER}, "gg_shortest_path_bfs",
+	    "GG_SHORTEST_PATH_BFS", description, true,
+	    [=](ClientContext &context, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    return make_unique<PhysicalGGShortestPath>(move(graph), read_seeds(context), max_hops, 0, lone_sources);
+	    },
+	    op.estimated_cardinality, {"startPerson", "friend", "hopCount"});
 	auto projection = make_unique<PhysicalProjection>(op.types, move(select_list), op.estimated_cardinality);
 	projection->children.push_back(move(scan));
 	return move(projection);
@@ -2441,12 +2427,26 @@ struct RulesSuspended {
 	}
 };
 
-unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
+//! which closure a recursive CTE becomes: UNION ALL -> the walks; UNION -> the reached vertices, or with a depth counter
+//! (under PRAGMA enable_gpu_recursive_levels) the level sets
+enum class RecursiveKind { WALKS, REACH, LEVELS };
+
+//! What MatchRecursiveWalks read off the logical plan
+struct RecursiveMatch {
+	RecursiveKind kind = RecursiveKind::WALKS;
+	shared_ptr<GGWalkInput> input;
+	LogicalOperator *join = nullptr; // the arm's join ...
+	idx_t t_child = 0;               // ... and which child of it is the table
+};
+
+//! Only READS the logical plan and fills `match`: until it returns true the rule may still decline, so nothing is moved
+//! out of `op`.  The checks run in this order; the first one met names the reason in the rule trace.
+bool MatchRecursiveWalks(LogicalRecursiveCTE &op, RecursiveMatch &match) {
 	auto trace = [](const char *why) {
 		if (std::getenv("GG_RULE_TRACE")) {
 			fprintf(stderr, "[gg] recursive walks declined: %s\n", why);
 		}
-		return nullptr;
+		return false;
 	};
 	if (g_ctes_left_alone.erase(&op)) {
 		return trace("min(...) GROUP BY over it: the shortest-path rule's shape");
@@ -2460,8 +2460,8 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	if (set_union && !flags.recursive_union && !flags.recursive_levels) {
 		return trace("not UNION ALL (PRAGMA enable_gpu_recursive_union takes UNION)");
 	}
-	bool reach = set_union; // until a depth counter is met under PRAGMA enable_gpu_recursive_levels
-	bool levels = false;
+	auto &kind = match.kind;
+	kind = set_union ? RecursiveKind::REACH : RecursiveKind::WALKS; // REACH: until a depth counter is met (then LEVELS)
 	if (std::getenv("GG_NO_PIPELINE_SINKS") || !gg_pipeline_rule_registered() || !g_plan_generator->rec_ctes.empty()) {
 		return trace("no pipeline sinks, or inside another recursive CTE");
 	}
@@ -2585,8 +2585,7 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 				if (step <= 0) { // rows of different levels could be equal
 					return trace("UNION: a depth counter whose step is not positive");
 				}
-				reach = false;
-				levels = true;
+				kind = RecursiveKind::LEVELS;
 			}
 			spec.kind = GGWalkColumn::COUNTER;
 			spec.step = step;
@@ -2615,14 +2614,13 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		return trace("the next link is not an integer column of the table");
 	}
 	input->next_column = input->columns[link].index;
-	if (set_union && !levels && !flags.recursive_union) {
+	if (kind == RecursiveKind::REACH && !flags.recursive_union) {
 		return trace("UNION without a depth counter (PRAGMA enable_gpu_recursive_union takes it)");
 	}
-	if (reach && (!cte_filters.empty() || !join_filters.empty())) {
+	if (kind == RecursiveKind::REACH && (!cte_filters.empty() || !join_filters.empty())) {
 		return trace("UNION: a CTE-side predicate");
 	}
-	// ---- CTE-side predicates: `counter < K` only
-	// (CTE column, predicate) pairs; the logical plan is only read here — the rule may still decline
+	// ---- CTE-side predicates: `counter < K` only, as (CTE column, predicate) pairs
 	vector<std::pair<idx_t, Expression *>> bounds;
 	for (auto filter : cte_filters) {
 		idx_t column;
@@ -2641,6 +2639,13 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		}
 		bounds.emplace_back(column, filter);
 	}
+	// the anchor's value of a counter, which has to be an integer constant
+	auto counter_start = [&](idx_t column, int64_t &start) {
+		auto &anchor = *op.children[0];
+		return (anchor.type == LogicalOperatorType::LOGICAL_PROJECTION && column < anchor.expressions.size() &&
+		        IntegerConstant(*anchor.expressions[column], start)) ||
+		       trace("a counter whose anchor value is not a constant");
+	};
 	for (auto &entry : bounds) {
 		const idx_t column = entry.first;
 		auto filter = entry.second;
@@ -2655,31 +2660,27 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 		}
 		// the counter of a level-L row is start + step * L: it is expanded iff that is < K, so the deepest level is the
 		// first L where it is not
-		auto &anchor = *op.children[0];
-		if (anchor.type != LogicalOperatorType::LOGICAL_PROJECTION || column >= anchor.expressions.size() ||
-		    !IntegerConstant(*anchor.expressions[column], start)) {
-			return trace("a counter whose anchor value is not a constant");
+		if (!counter_start(column, start)) {
+			return false;
 		}
 		const int64_t limit = filter->type == ExpressionType::COMPARE_LESSTHAN ? bound : bound + 1;
 		const int64_t step = input->columns[column].step;
-		const int64_t levels = limit <= start ? 0 : (limit - start + step - 1) / step;
-		if (levels >= (1 << 30)) {
+		const int64_t deepest = limit <= start ? 0 : (limit - start + step - 1) / step;
+		if (deepest >= (1 << 30)) {
 			return trace("a level bound too large");
 		}
-		input->max_levels = input->max_levels < 0 ? (int)levels : std::min(input->max_levels, (int)levels);
+		input->max_levels = input->max_levels < 0 ? (int)deepest : std::min(input->max_levels, (int)deepest);
 	}
-	if (levels) {
+	if (kind == RecursiveKind::LEVELS) {
 		// every counter starts at a constant, so that a level's rows differ from every other level's, and
 		// start + step * max_levels fits its type: the reference would raise an overflow there, this plan must not run
-		auto &anchor = *op.children[0];
 		for (idx_t c = 0; c < n_cols; c++) {
 			if (input->columns[c].kind != GGWalkColumn::COUNTER) {
 				continue;
 			}
 			int64_t start;
-			if (anchor.type != LogicalOperatorType::LOGICAL_PROJECTION || c >= anchor.expressions.size() ||
-			    !IntegerConstant(*anchor.expressions[c], start)) {
-				return trace("a counter whose anchor value is not a constant");
+			if (!counter_start(c, start)) {
+				return false;
 			}
 			if (input->max_levels > 0) {
 				const hugeint_t last = hugeint_t(start) + hugeint_t(input->columns[c].step) * hugeint_t(input->max_levels);
@@ -2689,11 +2690,24 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 			}
 		}
 	}
-	// ---- plan: the anchor and the table by the reference's planner, under the sinks
-	string description = "link=#" + std::to_string(link) + " key=#" + std::to_string(key) + " next=#" +
+	input->description = "link=#" + std::to_string(link) + " key=#" + std::to_string(key) + " next=#" +
 	                     std::to_string(input->next_column) +
 	                     (input->max_levels >= 0 ? " max_levels=" + std::to_string(input->max_levels) : string());
-	input->description = description;
+	match.input = input;
+	match.join = &join;
+	match.t_child = t_child;
+	return true;
+}
+
+//! The plan: the anchor and the table by the reference's planner, under the sinks of a scan of the match's kind.  From
+//! here on the logical plan is spent (its children move into the generator): the rule can no longer decline.
+unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
+	RecursiveMatch match;
+	if (!MatchRecursiveWalks(op, match)) {
+		return nullptr;
+	}
+	const auto kind = match.kind;
+	const auto input = match.input;
 	const auto types = op.types;
 	const auto cardinality = op.estimated_cardinality;
 	// Both are planned with every gg rule suspended: their plans run under the walk sinks, whose pipelines are built by
@@ -2704,20 +2718,25 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 	{
 		RulesSuspended suspended;
 		anchor_plan = generator->CreatePlan(move(op.children[0]));
-		table_plan = generator->CreatePlan(move(join.children[t_child]));
+		table_plan = generator->CreatePlan(move(match.join->children[match.t_child]));
 	}
 	g_plan_generator = generator;
 	auto slot = make_shared<GGGraphSlot>();
 	auto scan = make_unique<PhysicalGGGraphScan>(
-	    types, levels ? "GG_RECURSIVE_LEVELS" : (reach ? "GG_RECURSIVE_REACH" : "GG_RECURSIVE_WALKS"), description, slot,
-	    [types, input, cardinality, reach, levels](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-		    if (levels) {
+	    types,
+	    kind == RecursiveKind::LEVELS  ? "GG_RECURSIVE_LEVELS"
+	    : kind == RecursiveKind::REACH ? "GG_RECURSIVE_REACH"
+	                                   : "GG_RECURSIVE_WALKS",
+	    input->description, slot,
+	    [types, input, cardinality, kind](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    switch (kind) {
+		    case RecursiveKind::LEVELS:
 			    return make_unique<PhysicalGGRecursiveLevels>(types, move(graph), input, cardinality);
-		    }
-		    if (reach) {
+		    case RecursiveKind::REACH:
 			    return make_unique<PhysicalGGRecursiveReach>(types, move(graph), input, cardinality);
+		    default:
+			    return make_unique<PhysicalGGRecursiveWalks>(types, move(graph), input, cardinality);
 		    }
-		    return make_unique<PhysicalGGRecursiveWalks>(types, move(graph), input, cardinality);
 	    },
 	    false, cardinality);
 	auto anchor_sink = make_unique<PhysicalGGWalkRowSink>(input, slot, false, anchor_plan->types,
@@ -2752,90 +2771,79 @@ unique_ptr<PhysicalOperator> PlanRecursiveWalks(LogicalRecursiveCTE &op) {
 //! (src/execution/physical_plan/plan_distinct.cpp:12-78) is the SET IMAGE of h hops from the source: gg_walk_endpoints
 //! keeps, per vertex, a flag for every walk length that ends there; the rule keeps the vertices whose flag h is set
 //! (and that pass the predicates the statement puts on the end vertex).
-unique_ptr<PhysicalOperator> PlanDistinctEndpoints(LogicalDistinct &op) {
-	if (op.children.size() != 1 || op.types.size() != 1 || op.children[0]->type != LogicalOperatorType::LOGICAL_PROJECTION) {
-		return nullptr;
+//! What both rules ask of a branch `SELECT <end vertex> FROM <walk>`: a projection of one column over a join tree that
+//! is a walk of h edges over one edge table, pinned at its first vertex (one source, no vertex table, no payload
+//! predicates) with predicates on the end vertex only, the projected column that end vertex, NOT NULL and of the
+//! DISTINCT's type.  (`in` owns filters the pattern's residual points to: it has to live until the plan is built.)
+bool SolvePinnedWalkEnd(LogicalOperator &branch, const LogicalType &type, PatternInput &in, WalkPattern &pattern) {
+	if (branch.type != LogicalOperatorType::LOGICAL_PROJECTION || branch.children.size() != 1 ||
+	    branch.expressions.size() != 1 || branch.expressions[0]->type != ExpressionType::BOUND_REF ||
+	    branch.children[0]->type != LogicalOperatorType::LOGICAL_COMPARISON_JOIN) {
+		return false;
 	}
-	if (op.distinct_targets.size() > 1 ||
-	    (op.distinct_targets.size() == 1 && (op.distinct_targets[0]->type != ExpressionType::BOUND_REF ||
-	                                         ((BoundReferenceExpression &)*op.distinct_targets[0]).index != 0))) {
-		return nullptr;
+	auto &join = *branch.children[0];
+	if (!CollectJoinTree(join, in) || !SolveWalkPattern(in, pattern) || pattern.all_sources ||
+	    pattern.sources.size() != 1 || pattern.vertex_table || !pattern.payload_filters.empty()) {
+		return false;
 	}
-	auto &projection_op = *op.children[0];
-	if (projection_op.children.size() != 1 || projection_op.expressions.size() != 1 ||
-	    projection_op.expressions[0]->type != ExpressionType::BOUND_REF ||
-	    projection_op.children[0]->type != LogicalOperatorType::LOGICAL_COMPARISON_JOIN) {
-		return nullptr;
-	}
-	auto &join = *projection_op.children[0];
-	PatternInput in;
-	WalkPattern pattern;
-	if (!CollectJoinTree(join, in) || !SolveWalkPattern(in, pattern) || pattern.hops < 2 || pattern.hops > GG_MAX_HOPS ||
-	    pattern.all_sources || pattern.sources.size() != 1 || pattern.vertex_table || !pattern.payload_filters.empty()) {
-		return nullptr;
-	}
-	const idx_t hops = pattern.hops;
 	for (auto &entry : pattern.residual) {
-		if (entry.first != hops) {
-			return nullptr; // a predicate on an inner vertex changes which walks exist
+		if (entry.first != pattern.hops) {
+			return false; // a predicate on an inner vertex changes which walks exist
 		}
 	}
-	{
-		auto bindings = join.GetColumnBindings();
-		const auto index = ((BoundReferenceExpression &)*projection_op.expressions[0]).index;
-		LeafColumn column;
-		if (index >= bindings.size() || !ResolveLeafColumn(in, bindings[index], column) ||
-		    pattern.edge_position[column.leaf] != hops || column.column != pattern.dst_column) {
-			return nullptr;
-		}
+	auto bindings = join.GetColumnBindings();
+	const auto index = ((BoundReferenceExpression &)*branch.expressions[0]).index;
+	LeafColumn column;
+	if (index >= bindings.size() || !ResolveLeafColumn(in, bindings[index], column) ||
+	    pattern.edge_position[column.leaf] != pattern.hops || column.column != pattern.dst_column) {
+		return false;
 	}
+	// a NULL endpoint is a row of the reference's DISTINCT; the vertex set has no NULL
 	auto &table = *pattern.edge_table;
-	if (!ColumnIsNotNull(table, pattern.dst_column) || table.columns[pattern.dst_column].type != op.types[0]) {
-		return nullptr; // a NULL endpoint is a row of the reference's DISTINCT; the vertex set has no NULL
+	return ColumnIsNotNull(table, pattern.dst_column) && table.columns[pattern.dst_column].type == type;
+}
+
+//! a DISTINCT over its child's one column
+bool DistinctOfOneColumn(LogicalDistinct &op) {
+	if (op.children.size() != 1 || op.types.size() != 1 || op.distinct_targets.size() > 1) {
+		return false;
 	}
-	const auto spec = GraphSpecOf(pattern);
-	const auto sources = pattern.sources;
-	const int k_max = (int)hops;
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		opened.source = make_unique<PhysicalGGWalkEndpoints>(opened.graph, sources, k_max, 0);
-	};
-	data->description = table.name + ": " + table.columns[pattern.src_column].name + " -> " +
-	                    table.columns[pattern.dst_column].name + "\ndistinct endpoints of " + to_string(hops) +
-	                    " hops\nfrom " + to_string(sources[0]);
-	auto types = PhysicalGGWalkEndpoints::OutputTypes(k_max);
-	g_rules_fired++;
-	unique_ptr<PhysicalOperator> scan;
-	if (g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
-		scan = GGMakeGraphScan(
-		    spec, move(types), "GG_WALK_ENDPOINTS", data->description, false,
-		    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    return make_unique<PhysicalGGWalkEndpoints>(move(graph), sources, k_max, 0);
-		    },
-		    op.estimated_cardinality);
-	} else {
-		vector<column_t> column_ids;
-		vector<string> names;
-		for (idx_t c = 0; c < types.size(); c++) {
-			column_ids.push_back(c);
-			names.push_back("c" + to_string(c));
-		}
-		scan = make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_walk_endpoints"), move(data),
-		                                      move(column_ids), move(names), nullptr, op.estimated_cardinality);
-	}
-	// scan columns: (id, h1, ..., hk).  keep: hk = 1 AND the statement's predicates on the end vertex
-	unique_ptr<Expression> keep = make_unique<BoundComparisonExpression>(
-	    ExpressionType::COMPARE_EQUAL, make_unique<BoundReferenceExpression>(LogicalType::BIGINT, hops),
+	return op.distinct_targets.empty() || (op.distinct_targets[0]->type == ExpressionType::BOUND_REF &&
+	                                       ((BoundReferenceExpression &)*op.distinct_targets[0]).index == 0);
+}
+
+//! Over the endpoint scan's columns (id, h1, ..., hk): h_hop = 1, ANDed with the pattern's predicates on the end vertex
+unique_ptr<Expression> EndsAfter(idx_t hop, const WalkPattern *pattern = nullptr) {
+	unique_ptr<Expression> flag = make_unique<BoundComparisonExpression>(
+	    ExpressionType::COMPARE_EQUAL, make_unique<BoundReferenceExpression>(LogicalType::BIGINT, hop),
 	    make_unique<BoundConstantExpression>(Value::BIGINT(1)));
-	if (!pattern.residual.empty()) {
-		auto both = make_unique<BoundConjunctionExpression>(ExpressionType::CONJUNCTION_AND);
-		both->children.push_back(move(keep));
-		for (auto &entry : pattern.residual) {
-			both->children.push_back(FilterToExpression(*entry.second, 0));
-		}
-		keep = move(both);
+	if (!pattern || pattern->residual.empty()) {
+		return flag;
 	}
+	auto both = make_unique<BoundConjunctionExpression>(ExpressionType::CONJUNCTION_AND);
+	both->children.push_back(move(flag));
+	for (auto &entry : pattern->residual) {
+		both->children.push_back(FilterToExpression(*entry.second, 0));
+	}
+	return move(both);
+}
+
+//! The plan of both rules: the endpoints of walks of up to `hops` edges from the pattern's source (`lengths`: the walk
+//! lengths asked for, as EXPLAIN words them), the filter `keep` on them, the id in the DISTINCT's type
+unique_ptr<PhysicalOperator> MakeDistinctEndpoints(LogicalDistinct &op, const WalkPattern &pattern, int hops,
+                                                   const string &lengths, unique_ptr<Expression> keep) {
+	auto &table = *pattern.edge_table;
+	const auto sources = pattern.sources;
+	const auto description = table.name + ": " + table.columns[pattern.src_column].name + " -> " +
+	                         table.columns[pattern.dst_column].name + "\ndistinct endpoints of " + lengths +
+	                         " hops\nfrom " + to_string(sources[0]);
+	auto scan = MakeGraphSource(
+	    GraphSpecOf(pattern), PhysicalGGWalkEndpoints::OutputTypes(hops), "gg_walk_endpoints", "GG_WALK_ENDPOINTS",
+	    description, false,
+	    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
+		    return make_unique<PhysicalGGWalkEndpoints>(move(graph), sources, hops, 0);
+	    },
+	    op.estimated_cardinality);
 	vector<unique_ptr<Expression>> predicates;
 	predicates.push_back(move(keep));
 	auto filter = make_unique<PhysicalFilter>(scan->types, move(predicates), op.estimated_cardinality);
@@ -2851,16 +2859,22 @@ unique_ptr<PhysicalOperator> PlanDistinctEndpoints(LogicalDistinct &op) {
 	return move(projection);
 }
 
+unique_ptr<PhysicalOperator> PlanDistinctEndpoints(LogicalDistinct &op) {
+	PatternInput in;
+	WalkPattern pattern;
+	if (!DistinctOfOneColumn(op) || !SolvePinnedWalkEnd(*op.children[0], op.types[0], in, pattern) || pattern.hops < 2) {
+		return nullptr;
+	}
+	// keep: hk = 1 AND the statement's predicates on the end vertex
+	return MakeDistinctEndpoints(op, pattern, (int)pattern.hops, to_string(pattern.hops),
+	                             EndsAfter(pattern.hops, &pattern));
+}
+
 unique_ptr<PhysicalOperator> PlanDistinctUnion(LogicalDistinct &op) {
 	if (op.children.size() == 1 && op.children[0]->type == LogicalOperatorType::LOGICAL_PROJECTION) {
 		return PlanDistinctEndpoints(op);
 	}
-	if (op.children.size() != 1 || op.types.size() != 1 || op.children[0]->type != LogicalOperatorType::LOGICAL_UNION) {
-		return nullptr;
-	}
-	if (op.distinct_targets.size() > 1 ||
-	    (op.distinct_targets.size() == 1 && (op.distinct_targets[0]->type != ExpressionType::BOUND_REF ||
-	                                         ((BoundReferenceExpression &)*op.distinct_targets[0]).index != 0))) {
+	if (!DistinctOfOneColumn(op) || op.children[0]->type != LogicalOperatorType::LOGICAL_UNION) {
 		return nullptr;
 	}
 	auto &setop = *op.children[0];
@@ -2870,8 +2884,7 @@ unique_ptr<PhysicalOperator> PlanDistinctUnion(LogicalDistinct &op) {
 	// which branch is the join?
 	LogicalOperator *one = nullptr, *two = nullptr;
 	for (auto &child : setop.children) {
-		if (child->type != LogicalOperatorType::LOGICAL_PROJECTION || child->children.size() != 1 ||
-		    child->expressions.size() != 1 || child->expressions[0]->type != ExpressionType::BOUND_REF) {
+		if (child->type != LogicalOperatorType::LOGICAL_PROJECTION || child->children.size() != 1) {
 			return nullptr;
 		}
 		(child->children[0]->type == LogicalOperatorType::LOGICAL_COMPARISON_JOIN ? two : one) = child.get();
@@ -2879,33 +2892,19 @@ unique_ptr<PhysicalOperator> PlanDistinctUnion(LogicalDistinct &op) {
 	if (!one || !two) {
 		return nullptr;
 	}
-	// the 2-hop branch: a walk of two edges over one edge table, pinned at its first vertex, endpoint projected
+	// the 2-hop branch
 	PatternInput in2;
 	WalkPattern pattern;
-	auto &join = *two->children[0];
-	if (!CollectJoinTree(join, in2) || !SolveWalkPattern(in2, pattern) || pattern.hops != 2 || pattern.all_sources ||
-	    pattern.sources.size() != 1 || pattern.vertex_table || !pattern.payload_filters.empty()) {
+	if (!SolvePinnedWalkEnd(*two, op.types[0], in2, pattern) || pattern.hops != 2) {
 		return nullptr;
-	}
-	for (auto &entry : pattern.residual) {
-		if (entry.first != 2) {
-			return nullptr; // a predicate on the middle vertex changes which walks exist
-		}
-	}
-	{
-		auto bindings = join.GetColumnBindings();
-		const auto index = ((BoundReferenceExpression &)*two->expressions[0]).index;
-		LeafColumn column;
-		if (index >= bindings.size() || !ResolveLeafColumn(in2, bindings[index], column) ||
-		    pattern.edge_position[column.leaf] != 2 || column.column != pattern.dst_column) {
-			return nullptr;
-		}
 	}
 	// the 1-hop branch: the same table, source and endpoint columns, the same constant, nothing else
 	PatternInput in1;
-	if (!CollectJoinTree(*one, in1) || in1.leaves.size() != 1 || in1.leaves[0].table != pattern.edge_table ||
-	    !in1.filters.empty() || !in1.other_filters.empty() || in1.constants.size() != 1 || in1.constants[0].column.column != pattern.src_column ||
-	    in1.constants[0].value != pattern.sources[0] || in1.aliases.empty()) {
+	if (one->expressions.size() != 1 || one->expressions[0]->type != ExpressionType::BOUND_REF ||
+	    !CollectJoinTree(*one, in1) || in1.leaves.size() != 1 || in1.leaves[0].table != pattern.edge_table ||
+	    !in1.filters.empty() || !in1.other_filters.empty() || in1.constants.size() != 1 ||
+	    in1.constants[0].column.column != pattern.src_column || in1.constants[0].value != pattern.sources[0] ||
+	    in1.aliases.empty()) {
 		return nullptr;
 	}
 	{
@@ -2915,72 +2914,11 @@ unique_ptr<PhysicalOperator> PlanDistinctUnion(LogicalDistinct &op) {
 			return nullptr;
 		}
 	}
-	auto &table = *pattern.edge_table;
-	if (!ColumnIsNotNull(table, pattern.dst_column) || table.columns[pattern.dst_column].type != op.types[0]) {
-		return nullptr; // a NULL endpoint is a row of the reference's UNION; the vertex set has no NULL
-	}
-
-	const auto spec = GraphSpecOf(pattern);
-	const auto sources = pattern.sources;
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &context, GGOpened &opened) {
-		opened.graph = GGBuildGraph(context, spec);
-		opened.source = make_unique<PhysicalGGWalkEndpoints>(opened.graph, sources, 2, 0);
-	};
-	data->description = table.name + ": " + table.columns[pattern.src_column].name + " -> " +
-	                    table.columns[pattern.dst_column].name + "\ndistinct endpoints of 1..2 hops\nfrom " +
-	                    to_string(sources[0]);
-	auto types = PhysicalGGWalkEndpoints::OutputTypes(2);
-	g_rules_fired++;
-	unique_ptr<PhysicalOperator> scan;
-	if (g_plan_context && GGPipelineSinksAvailable(*g_plan_context, spec)) {
-		scan = GGMakeGraphScan(
-		    spec, move(types), "GG_WALK_ENDPOINTS", data->description, false,
-		    [=](ClientContext &, shared_ptr<GGGraph> graph) -> unique_ptr<PhysicalOperator> {
-			    return make_unique<PhysicalGGWalkEndpoints>(move(graph), sources, 2, 0);
-		    },
-		    op.estimated_cardinality);
-	} else {
-		vector<column_t> column_ids;
-		vector<string> names;
-		for (idx_t c = 0; c < types.size(); c++) {
-			column_ids.push_back(c);
-			names.push_back("c" + to_string(c));
-		}
-		scan = make_unique<PhysicalTableScan>(move(types), GGScanFunction("gg_walk_endpoints"), move(data),
-		                                      move(column_ids), move(names), nullptr, op.estimated_cardinality);
-	}
-	// scan columns: (id, h1, h2).  keep: h1 = 1 OR (h2 = 1 AND the second branch's predicates on the endpoint)
-	auto flag = [](idx_t column) {
-		return make_unique<BoundComparisonExpression>(ExpressionType::COMPARE_EQUAL,
-		                                              make_unique<BoundReferenceExpression>(LogicalType::BIGINT, column),
-		                                              make_unique<BoundConstantExpression>(Value::BIGINT(1)));
-	};
-	unique_ptr<Expression> second = flag(2);
-	if (!pattern.residual.empty()) {
-		auto both = make_unique<BoundConjunctionExpression>(ExpressionType::CONJUNCTION_AND);
-		both->children.push_back(move(second));
-		for (auto &entry : pattern.residual) {
-			both->children.push_back(FilterToExpression(*entry.second, 0));
-		}
-		second = move(both);
-	}
+	// keep: h1 = 1 OR (h2 = 1 AND the second branch's predicates on the endpoint)
 	auto keep = make_unique<BoundConjunctionExpression>(ExpressionType::CONJUNCTION_OR);
-	keep->children.push_back(flag(1));
-	keep->children.push_back(move(second));
-	vector<unique_ptr<Expression>> predicates;
-	predicates.push_back(move(keep));
-	auto filter = make_unique<PhysicalFilter>(scan->types, move(predicates), op.estimated_cardinality);
-	filter->children.push_back(move(scan));
-	vector<unique_ptr<Expression>> select_list;
-	unique_ptr<Expression> ref = make_unique<BoundReferenceExpression>(LogicalType::BIGINT, 0);
-	if (op.types[0] != LogicalType::BIGINT) {
-		ref = make_unique<BoundCastExpression>(move(ref), op.types[0]);
-	}
-	select_list.push_back(move(ref));
-	auto projection = make_unique<PhysicalProjection>(op.types, move(select_list), op.estimated_cardinality);
-	projection->children.push_back(move(filter));
-	return move(projection);
+	keep->children.push_back(EndsAfter(1));
+	keep->children.push_back(EndsAfter(2, &pattern));
+	return MakeDistinctEndpoints(op, pattern, 2, "1..2", move(keep));
 }
 
 //! `min(x) GROUP BY a, b` directly over a recursive CTE that the shortest-path rule declined (bi-10's shape with UNION
@@ -3071,65 +3009,30 @@ unique_ptr<PhysicalOperator> CalloutEntry(ClientContext &context, PhysicalPlanGe
 	return plan;
 }
 
-void PragmaEnableGpuGraph(ClientContext &context, const FunctionParameters &parameters) {
+//! PRAGMA <name>: one switch of the issuing connection set to VALUE
+template <bool GGConnectionFlags::*FLAG, bool VALUE>
+void PragmaSetFlag(ClientContext &context, const FunctionParameters &parameters) {
 	auto flags = GGGetConnectionFlags(context);
-	flags.rules = true;
+	flags.*FLAG = VALUE;
 	GGSetConnectionFlags(context, flags);
 }
 
-void PragmaDisableGpuGraph(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.rules = false;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaEnableGpuJoins(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.joins = true;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaDisableGpuJoins(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.joins = false;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaEnableGpuRecursiveUnion(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.recursive_union = true;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaDisableGpuRecursiveUnion(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.recursive_union = false;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaEnableGpuRecursiveLevels(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.recursive_levels = true;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaDisableGpuRecursiveLevels(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.recursive_levels = false;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaUsePinnedGraphs(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.pinned_graphs = true;
-	GGSetConnectionFlags(context, flags);
-}
-
-void PragmaIgnorePinnedGraphs(ClientContext &context, const FunctionParameters &parameters) {
-	auto flags = GGGetConnectionFlags(context);
-	flags.pinned_graphs = false;
-	GGSetConnectionFlags(context, flags);
-}
+// same style as the reference's enable_profiling / disable_profiling (pragma_functions.cpp:280-345)
+const struct {
+	const char *name;
+	pragma_function_t function;
+} PRAGMAS[] = {
+    {"enable_gpu_graph", PragmaSetFlag<&GGConnectionFlags::rules, true>},
+    {"disable_gpu_graph", PragmaSetFlag<&GGConnectionFlags::rules, false>},
+    {"gg_use_pinned_graphs", PragmaSetFlag<&GGConnectionFlags::pinned_graphs, true>},
+    {"gg_ignore_pinned_graphs", PragmaSetFlag<&GGConnectionFlags::pinned_graphs, false>},
+    {"enable_gpu_joins", PragmaSetFlag<&GGConnectionFlags::joins, true>},
+    {"disable_gpu_joins", PragmaSetFlag<&GGConnectionFlags::joins, false>},
+    {"enable_gpu_recursive_union", PragmaSetFlag<&GGConnectionFlags::recursive_union, true>},
+    {"disable_gpu_recursive_union", PragmaSetFlag<&GGConnectionFlags::recursive_union, false>},
+    {"enable_gpu_recursive_levels", PragmaSetFlag<&GGConnectionFlags::recursive_levels, true>},
+    {"disable_gpu_recursive_levels", PragmaSetFlag<&GGConnectionFlags::recursive_levels, false>},
+};
 
 //! INSERT / DELETE / UPDATE about to be planned: drop the graphs pinned on the target table (never takes the
 //! plan over)
@@ -3145,32 +3048,10 @@ int WriteObserver(void *ret_slot, void *generator, void *logical_operator) {
 } // namespace
 
 void GGRegisterPlanRules(ClientContext &context) {
-	// same style as the reference's enable_profiling / disable_profiling (pragma_functions.cpp:280-345)
-	CreatePragmaFunctionInfo enable(PragmaFunction::PragmaStatement("enable_gpu_graph", PragmaEnableGpuGraph));
-	CreatePragmaFunctionInfo disable(PragmaFunction::PragmaStatement("disable_gpu_graph", PragmaDisableGpuGraph));
-	CreatePragmaFunctionInfo use_pins(PragmaFunction::PragmaStatement("gg_use_pinned_graphs", PragmaUsePinnedGraphs));
-	CreatePragmaFunctionInfo no_pins(
-	    PragmaFunction::PragmaStatement("gg_ignore_pinned_graphs", PragmaIgnorePinnedGraphs));
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &enable);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &disable);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &use_pins);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &no_pins);
-	CreatePragmaFunctionInfo joins_on(PragmaFunction::PragmaStatement("enable_gpu_joins", PragmaEnableGpuJoins));
-	CreatePragmaFunctionInfo joins_off(PragmaFunction::PragmaStatement("disable_gpu_joins", PragmaDisableGpuJoins));
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &joins_on);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &joins_off);
-	CreatePragmaFunctionInfo union_on(
-	    PragmaFunction::PragmaStatement("enable_gpu_recursive_union", PragmaEnableGpuRecursiveUnion));
-	CreatePragmaFunctionInfo union_off(
-	    PragmaFunction::PragmaStatement("disable_gpu_recursive_union", PragmaDisableGpuRecursiveUnion));
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_on);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &union_off);
-	CreatePragmaFunctionInfo levels_on(
-	    PragmaFunction::PragmaStatement("enable_gpu_recursive_levels", PragmaEnableGpuRecursiveLevels));
-	CreatePragmaFunctionInfo levels_off(
-	    PragmaFunction::PragmaStatement("disable_gpu_recursive_levels", PragmaDisableGpuRecursiveLevels));
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &levels_on);
-	Catalog::GetCatalog(context).CreatePragmaFunction(context, &levels_off);
+	for (auto &pragma : PRAGMAS) {
+		CreatePragmaFunctionInfo info(PragmaFunction::PragmaStatement(pragma.name, pragma.function));
+		Catalog::GetCatalog(context).CreatePragmaFunction(context, &info);
+	}
 
 	// A reference built with oracle/callout.patch exports the registration of its call-outs: the maintainers' route —
 	// no interposition, no access to private members (the BuildPipelines case and the write observation are then the
