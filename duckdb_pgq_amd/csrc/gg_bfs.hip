@@ -495,7 +495,8 @@ __global__ __launch_bounds__(256) void k_endpoint_fill(const uint32_t *__restric
 template <typename DistT>
 static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops, const int64_t *dst_ids,
                    uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats, bool *overflow,
-                   gg_result *pairs = nullptr /* filled with (source, vertex, distance) rows if non-null */) {
+                   gg_result *pairs = nullptr /* filled with (source, vertex, distance) rows if non-null */,
+                   const PathsRequest *paths = nullptr /* the paths of these pairs into paths->res if non-null */) {
   constexpr int MAX_LEVEL = sizeof(DistT) == 1 ? 254 : 65534;
   ApiScope scope(ctx);  // (per run: an 8-bit run's blocks are back in the pool before the 16-bit rerun)
   *overflow = false;
@@ -621,6 +622,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
     for (int c = 0; c < ncols; c++) ctx->keep(pairs->cols[table][c]);
     pairs->rows[table] = reached;
   }
+  if (paths && !*overflow) GG_TRY(paths_emit(ctx, csr, dist8, sizeof(DistT), *paths));
   if (out_dist && !*overflow) {
     uint32_t *dst_dense = nullptr;
     int32_t *out_dev = nullptr;
@@ -637,7 +639,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
 
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
-                        gg_result *pairs);
+                        gg_result *pairs, const PathsRequest *paths = nullptr);
 
 extern "C" int gg_bfs64(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats) {
@@ -668,9 +670,40 @@ static int bfs_pairs(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int
   return GG_OK;
 }
 
+extern "C" int gg_bfs64_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
+                              const uint32_t *pair_lane, const int64_t *pair_dst_ids, uint64_t n_pairs, int want_edges,
+                              gg_bfs_stats *stats, gg_result **out_result) {
+  if (!out_result) return GG_ERR_INVALID_ARG;
+  *out_result = nullptr;
+  if (!ctx || !csr || csr->ctx != ctx || (n_pairs && (!pair_lane || !pair_dst_ids))) return GG_ERR_INVALID_ARG;
+  if (csr->n_parts > 1) {
+    set_error("gg_bfs64_paths needs a whole CSR, not a shard");
+    return GG_ERR_STATE;
+  }
+  if (want_edges && !csr->has_rowid) {
+    set_error("gg_bfs64_paths with edges needs a CSR built with edge rowids (gg_ctx_set_edge_rowid(ctx, 1))");
+    return GG_ERR_STATE;
+  }
+  if (n_pairs >= (1ull << 32)) {
+    set_error("gg_bfs64_paths: %llu pairs do not fit a 32-bit pair index", (unsigned long long)n_pairs);
+    return GG_ERR_TOO_LARGE;
+  }
+  for (uint64_t i = 0; i < n_pairs; i++)
+    if (n_src < 0 || pair_lane[i] >= (uint32_t)n_src) {
+      set_error("gg_bfs64_paths: pair %llu names source %u of %d", (unsigned long long)i, pair_lane[i], n_src);
+      return GG_ERR_INVALID_ARG;
+    }
+  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
+  res->paths = true;
+  const PathsRequest rq{pair_lane, pair_dst_ids, n_pairs, want_edges != 0, res.get()};
+  GG_TRY(bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, nullptr, &rq));
+  *out_result = res.release();
+  return GG_OK;
+}
+
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
-                        gg_result *pairs) {
+                        gg_result *pairs, const PathsRequest *paths) {
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
   if (!ctx || !csr || csr->ctx != ctx || n_src < 0 || n_src > GG_BFS_LANES || (n_src && !src_ids) ||
       (n_dst && !dst_ids)) {
@@ -683,9 +716,9 @@ static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids
   }
   // one byte per (vertex, lane) covers 254 levels; deeper searches (max_hops < 0 or > 254 only) rerun with two-byte cells
   bool overflow = false;
-  GG_TRY(bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs));
+  GG_TRY(bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths));
   if (!overflow) return GG_OK;
-  GG_TRY(bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs));
+  GG_TRY(bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths));
   if (overflow) {
     set_error("gg_bfs64: search deeper than 65534 levels is not supported");
     return GG_ERR_TOO_LARGE;

@@ -654,6 +654,7 @@ extern "C" void gg_csr_destroy(gg_csr *csr) {
     ctx->dev_free(csr->roff);
     ctx->dev_free(csr->rnbr);
     ctx->dev_free(csr->rrow);
+    ctx->dev_free(csr->rnbr_by_src);
     ctx->dev_free(csr->pin_off);
     ctx->dev_free(csr->pin_nbr);
   }

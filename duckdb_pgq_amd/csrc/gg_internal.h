@@ -261,11 +261,14 @@ struct gg_csr {
   bool ht_built = false;       // filled at build time only if the densification needed it; else on first use (ensure_ht)
   uint64_t ht_cap = 0;         // slots; slot = mulhi(key * GOLD, ht_cap)
   int64_t ht_min_idx = -1;     // dense index of the vertex whose id == HT_EMPTY, if any
-  // reverse CSR (in-neighbours), built lazily by ensure_reverse(): row x lists the sources u of
-  // every edge u->x in ascending (u, rowid) order
+  // reverse CSR (in-neighbours): row x lists the sources u of every edge u->x — in ascending (u, rowid) order when
+  // ensure_reverse() built it lazily, in rowid order when the bucketed build made it (gg_csr_fast.hip)
   uint32_t *roff = nullptr;    // V+1
   uint32_t *rnbr = nullptr;    // E   source u of the reverse entry
   uint32_t *rrow = nullptr;    // E   destination x of the reverse entry (COO view, sorted by x)
+  // the reverse rows again with their sources ascending (gg_paths.hip: ensure_reverse_by_source, whole CSRs, on first
+  // use): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
+  uint32_t *rnbr_by_src = nullptr;  // E
   // the reverse entries grouped by SOURCE (gg_bfs.hip: ensure_push_in, shards only, on first use): row u lists
   // the owned destinations of u's edges, so a shard can push a light frontier into the words it owns
   uint32_t *pin_off = nullptr; // V+1
@@ -287,6 +290,9 @@ struct gg_result {
   bool reach = false;
   // gg_level_sets (level_sets, reach false: the same fields): level_rows[L - 1] the members of level L
   bool level_sets = false;
+  // gg_bfs64_paths (paths: k_min > k_max too): cols[gg::PATHS_TABLE] = pair index, vertex id, step (int32 cells), and
+  // the edge rowid if edges were asked for; rows[gg::PATHS_TABLE] their number
+  bool paths = false;
 };
 
 namespace gg {
@@ -617,5 +623,17 @@ int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel
 int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
 int pair_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class, int64_t *vertex_id,
                     int32_t *level, uint32_t *n_out);
+
+// ---- shortest paths off a finished BFS batch (gg_paths.hip; called by bfs_run in gg_bfs.hip)
+constexpr int PATHS_TABLE = 3;  // the gg_result table that holds the path rows
+struct PathsRequest {
+  const uint32_t *pair_lane;    // host, n_pairs: the pair's source as an index into the batch's source list
+  const int64_t *pair_dst_ids;  // host, n_pairs
+  uint64_t n_pairs;
+  bool want_edges;
+  gg_result *res;
+};
+// dist: the batch's [V][64] distance cells of cell_bytes (1 or 2) each, on the device.  Fills rq.res; synchronises.
+int paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, const PathsRequest &rq);
 
 }  // namespace gg

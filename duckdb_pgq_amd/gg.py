@@ -24,7 +24,8 @@ SYMBOLS = [
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
     "gg_result_filter_common_neighbour", "gg_staging_clear_edges", "gg_vertices_from_edges",
-    "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
+    "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_bfs64_paths", "gg_bfs64_paths_rows", "gg_bfs64_paths_fetch",
+    "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
@@ -126,6 +127,10 @@ def load_library(path: str | None = None):
     lib.gg_csr_lookup.argtypes = [P, P, i64p, u64, C.POINTER(C.c_uint32)]
     lib.gg_bfs64_pairs.argtypes = [P, P, i64p, C.c_int, C.c_int, C.POINTER(BfsStats), C.POINTER(P)]
     lib.gg_bfs64_pairs_packed.argtypes = [P, P, i64p, C.c_int, C.c_int, C.POINTER(BfsStats), C.POINTER(P)]
+    lib.gg_bfs64_paths.argtypes = [P, P, i64p, C.c_int, C.c_int, C.POINTER(C.c_uint32), i64p, u64, C.c_int,
+                                   C.POINTER(BfsStats), C.POINTER(P)]
+    lib.gg_bfs64_paths_rows.argtypes = [P, C.POINTER(u64)]
+    lib.gg_bfs64_paths_fetch.argtypes = [P, u64, C.c_uint32, i64p, C.POINTER(C.c_int32), i64p, i64p, C.POINTER(C.c_uint32)]
     lib.gg_walk_endpoints.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
     lib.gg_walk_closure.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
     lib.gg_walk_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
@@ -689,6 +694,62 @@ class GG:
             self.lib.gg_result_destroy(res)
         return out.T.copy(), {"levels": st.levels, "traversed_edges": st.traversed_edges,
                               "active_vertices": st.active_vertices, "reached_pairs": st.reached_pairs}
+
+    def bfs64_paths(self, csr: Csr, sources, pair_lane, pair_dst, max_hops: int = -1, edges: bool = True):
+        """gg_bfs64_paths: the pinned shortest path of each (sources[pair_lane[i]], pair_dst[i]) of one <=64-source batch,
+        unnested: (pair_index int64, step int32, vertex int64, edge int64) arrays ascending by (pair, step), and the
+        BFS's statistics."""
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        s, ps = _i64(sources)
+        d, pd = _i64(pair_dst)
+        lane = np.ascontiguousarray(pair_lane, dtype=np.uint32)
+        if lane.size != d.size:
+            raise ValueError("one source lane per target")
+        st, res = BfsStats(), C.c_void_p()
+        self._chk(self.lib.gg_bfs64_paths(self.ctx, csr.handle, ps, s.size, int(max_hops),
+                                          lane.ctypes.data_as(C.POINTER(C.c_uint32)), pd, d.size, 1 if edges else 0,
+                                          C.byref(st), C.byref(res)))
+        try:
+            n = C.c_uint64()
+            self._chk(self.lib.gg_bfs64_paths_rows(res, C.byref(n)))
+            n = int(n.value)
+            pair, step = np.empty(n, np.int64), np.empty(n, np.int32)
+            vtx, edge = np.empty(n, np.int64), np.empty(n, np.int64)
+            done = 0
+            while done < n:
+                got = C.c_uint32()
+                self._chk(self.lib.gg_bfs64_paths_fetch(
+                    res, done, min(n - done, 1 << 30), pair[done:].ctypes.data_as(i64p), step[done:].ctypes.data_as(i32p),
+                    vtx[done:].ctypes.data_as(i64p), edge[done:].ctypes.data_as(i64p), C.byref(got)))
+                assert got.value
+                done += got.value
+        finally:
+            self.lib.gg_result_destroy(res)
+        return (pair, step, vtx, edge), {"levels": st.levels, "traversed_edges": st.traversed_edges,
+                                         "active_vertices": st.active_vertices, "reached_pairs": st.reached_pairs}
+
+    def shortest_paths(self, csr: Csr, src, dst, max_hops: int = -1, edges: bool = True):
+        """The pinned shortest path (include/gg.h, gg_bfs64_paths) of every pair (src[i], dst[i]), unnested: arrays
+        (pair_index int64, step int32, vertex int64, edge int64), one row per step 0..d of every pair that has a path of at
+        most max_hops edges (max_hops < 0: of any length), ascending by (pair index, step); edge is the rowid of the edge
+        into the step's vertex, -1 at step 0 (and everywhere with edges=False).  Any number of pairs: they are grouped by
+        source into device batches of at most 64 distinct sources."""
+        s, _ = _i64(src)
+        d, _ = _i64(dst)
+        if s.size != d.size:
+            raise ValueError("one target per source")
+        uniq, inv = np.unique(s, return_inverse=True)
+        parts = []
+        for b0 in range(0, uniq.size, GG_BFS_LANES):
+            members = np.flatnonzero((inv >= b0) & (inv < b0 + GG_BFS_LANES))  # ascending pair index
+            (pair, step, vtx, edge), _ = self.bfs64_paths(csr, uniq[b0:b0 + GG_BFS_LANES], inv[members] - b0, d[members],
+                                                          max_hops, edges)
+            parts.append((members[pair], step, vtx, edge))
+        if not parts:
+            return np.empty(0, np.int64), np.empty(0, np.int32), np.empty(0, np.int64), np.empty(0, np.int64)
+        pair, step, vtx, edge = (np.concatenate([p[c] for p in parts]) for c in range(4))
+        order = np.argsort(pair, kind="stable")  # batches interleave; inside a pair the steps already ascend
+        return pair[order], step[order], vtx[order], edge[order]
 
     def walk_endpoints(self, csr: Csr, sources, k_max: int):
         """gg_walk_endpoints: (vertex ids, masks) — bit h of a mask: the vertex ends a walk of exactly h edges

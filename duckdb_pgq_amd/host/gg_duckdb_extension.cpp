@@ -12,6 +12,8 @@
 //        -> (hops INTEGER, rows BIGINT, digest BIGINT, traversed_edges BIGINT)
 //   gg_shortest_path(vertex_table, vertex_key, edge_table, src_col, dst_col, sources_sql, max_hops)
 //        -> (startPerson BIGINT, friend BIGINT, hopCount INTEGER)
+//   gg_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
+//        -> (src BIGINT, dst BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT)   the paths, unnested
 //   gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //                           filter_table, filter_src, filter_dst, hops)
 //        -> (w BIGINT, v0 BIGINT, ..., v{hops} BIGINT)      Train Benchmark ConnectedSegments
@@ -105,6 +107,9 @@ struct PinnedGraph {
 	column_t vertex_key, src, dst;
 	idx_t vertex_rows, edge_rows;
 	shared_ptr<GGGraph> graph;
+	//! the same tables built WITH the edge table's rowids, for gg_shortest_path_rows: made by the first such statement
+	//! that finds this pin and kept with it (a pin builds without the rowid payload, like every plan that returns no edge)
+	shared_ptr<GGGraph> graph_rowids;
 };
 static mutex g_pinned_lock;
 static vector<PinnedGraph> g_pinned;
@@ -168,6 +173,40 @@ shared_ptr<GGGraph> GGBuildGraph(ClientContext &context, const GGGraphSpec &spec
 		return pinned;
 	}
 	return BuildGraphNow(context, spec);
+}
+
+//! The graph of `spec` (whose edge source ends in the rowid) with edge rowids: where this connection would get a pinned
+//! graph for the same tables, the rowid-carrying companion of that pin — built on first use, dropped with the pin.
+static shared_ptr<GGGraph> BuildGraphWithRowids(ClientContext &context, const GGGraphSpec &spec) {
+	auto plain = spec;
+	if (plain.edges.table && plain.edges.columns.size() == 3) {
+		plain.edges.columns.pop_back();
+	}
+	PinnedGraph key;
+	const bool pinnable = PinKey(plain, key);
+	if (!pinnable || !FindPinned(context, plain)) {
+		return BuildGraphNow(context, spec);
+	}
+	auto same = [&](const PinnedGraph &p) {
+		return p.vertex_oid == key.vertex_oid && p.edge_oid == key.edge_oid && p.vertex_key == key.vertex_key &&
+		       p.src == key.src && p.dst == key.dst && p.vertex_rows == key.vertex_rows && p.edge_rows == key.edge_rows;
+	};
+	{
+		lock_guard<mutex> guard(g_pinned_lock);
+		for (auto &p : g_pinned) {
+			if (same(p) && p.graph_rowids) {
+				return p.graph_rowids;
+			}
+		}
+	}
+	auto graph = BuildGraphNow(context, spec);
+	lock_guard<mutex> guard(g_pinned_lock);
+	for (auto &p : g_pinned) {
+		if (same(p) && !p.graph_rowids) {
+			p.graph_rowids = graph;
+		}
+	}
+	return graph;
 }
 
 void GGDropPinsOfTable(idx_t table_oid) {
@@ -460,6 +499,53 @@ static unique_ptr<FunctionData> ShortestBind(ClientContext &context, vector<Valu
 	return move(data);
 }
 
+//! the two integer columns of a statement as (src, dst) pairs; a row with a NULL is no pair
+static void QueryInt64Pairs(ClientContext &context, const string &sql, const char *what, vector<int64_t> &src,
+                            vector<int64_t> &dst) {
+	Connection con(*context.db);
+	auto result = con.Query(sql);
+	if (!result->success) {
+		throw BinderException(string(what) + " query failed: " + result->error);
+	}
+	if (result->types.size() != 2 || !result->types[0].IsIntegral() || !result->types[1].IsIntegral()) {
+		throw BinderException(string(what) + " query must yield two integer columns");
+	}
+	for (idx_t r = 0; r < result->collection.Count(); r++) {
+		auto s = result->GetValue(0, r), d = result->GetValue(1, r);
+		if (!s.is_null && !d.is_null) {
+			src.push_back(s.GetValue<int64_t>());
+			dst.push_back(d.GetValue<int64_t>());
+		}
+	}
+}
+
+//! gg_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
+static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<Value> &inputs,
+                                                 unordered_map<string, Value> &named_parameters,
+                                                 vector<LogicalType> &input_table_types,
+                                                 vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                 vector<string> &names) {
+	const GraphArguments graph(inputs);
+	const string pairs_sql = inputs[5].ToString();
+	const auto max_hops = inputs[6].GetValue<int64_t>();
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec;
+		spec.vertices = GGTableSource(ctx, graph.vertex_table, {graph.vertex_key}, false);
+		spec.edges = GGTableSource(ctx, graph.edge_table, {graph.edge_src, graph.edge_dst}, true);
+		spec.edges_with_rowid = true;
+		opened.graph = BuildGraphWithRowids(ctx, spec);
+		vector<int64_t> src, dst;
+		QueryInt64Pairs(ctx, pairs_sql, "gg_shortest_path_rows: pairs", src, dst);
+		opened.source = make_unique<PhysicalGGShortestPathRows>(opened.graph, move(src), move(dst),
+		                                                        max_hops < 0 ? -1 : (int)max_hops, 0);
+	};
+	data->parallel_result = true;
+	return_types = PhysicalGGShortestPathRows::OutputTypes();
+	names = {"src", "dst", "step", "vertex", "edge_rowid"};
+	return move(data);
+}
+
 //! gg_graph_pin(vertex_table, vertex_key, edge_table, src_col, dst_col) -> (vertices, edges, build_ms);
 //! vertex_table = '' pins the edge-only form (vertex set = endpoint ids).  gg_graph_unpin() drops all.
 struct PinResultData : public TableFunctionData {
@@ -579,6 +665,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	auto khop = GGScanFunction("gg_khop", khop_args, KhopBind);
 	auto khop_count = GGScanFunction("gg_khop_count", khop_args, KhopCountBind);
 	auto shortest = GGScanFunction("gg_shortest_path", sp_args, ShortestBind);
+	auto shortest_rows = GGScanFunction("gg_shortest_path_rows", sp_args, ShortestRowsBind);
 	auto filtered = GGScanFunction("gg_same_neighbour_paths",
 	                               {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
 	                                LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
@@ -587,7 +674,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	TableFunction pin("gg_graph_pin", graph_args, GraphPinFunction, GraphPinBind);
 	TableFunction unpin("gg_graph_unpin", {}, GraphUnpinFunction, GraphUnpinBind);
 	TableFunction pins("gg_graph_pins", {}, GraphUnpinFunction, GraphPinsBind);
-	CreateTableFunctionInfo khop_info(khop), khop_count_info(khop_count), shortest_info(shortest),
+	CreateTableFunctionInfo khop_info(khop), khop_count_info(khop_count), shortest_info(shortest), shortest_rows_info(shortest_rows),
 	    filtered_info(filtered), pin_info(pin), unpin_info(unpin), pins_info(pins);
 
 	Connection con(db);
@@ -596,6 +683,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &khop_info);
 	catalog.CreateTableFunction(*con.context, &khop_count_info);
 	catalog.CreateTableFunction(*con.context, &shortest_info);
+	catalog.CreateTableFunction(*con.context, &shortest_rows_info);
 	catalog.CreateTableFunction(*con.context, &filtered_info);
 	catalog.CreateTableFunction(*con.context, &pin_info);
 	catalog.CreateTableFunction(*con.context, &unpin_info);

@@ -11,6 +11,7 @@
 //   PhysicalGGPathExpand                         <->  the chain of PhysicalHashJoin::Execute probes
 //        (physical_hash_join.cpp:217-254) of a k-hop pattern; a source that emits the walks.
 //   PhysicalGGShortestPath                       <->  PhysicalRecursiveCTE + min(hop) aggregate
+//   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
 // Compiled against the reference's headers; duckdb symbols are resolved by the hosting libduckdb at
@@ -384,6 +385,40 @@ public:
 	}
 	string GetName() const override {
 		return "GG_SHORTEST_PATH";
+	}
+};
+
+//! Source: (src BIGINT, dst BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT) — the pinned shortest path of every
+//! (src[i], dst[i]) unnested, one row per step 0..d, edge_rowid NULL at step 0 (include/gg.h, gg_bfs64_paths).  The graph
+//! must have been built with the edge table's rowids.  Pairs are grouped by source into batches of 64 bit lanes; pairs
+//! without a path of at most max_hops edges (max_hops < 0: of any length) yield no row.
+class PhysicalGGShortestPathRows : public PhysicalOperator {
+public:
+	PhysicalGGShortestPathRows(shared_ptr<GGGraph> graph, vector<int64_t> src, vector<int64_t> dst, int max_hops,
+	                           idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes();
+
+	//! BFS + trace of the next batch (batches run one at a time, when the previous one is drained)
+	void RunBatch(GlobalSourceState &gstate) const;
+
+	shared_ptr<GGGraph> graph;
+	vector<int64_t> src, dst;
+	int max_hops;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_SHORTEST_PATH_ROWS";
 	}
 };
 

@@ -1,0 +1,216 @@
+// gg_shortest_paths.cpp — the shortest paths themselves as rows: (src, dst, step, vertex, edge_rowid).
+//
+// The reference has no relation for this: benchmark/ldbc/queries/bi-10-shortestpath.sql:26-31 stops at min(hopCount).
+// With its operators a path is read backwards by one hash join of friends_shortest with knows per step
+// (PhysicalHashJoin::Execute, src/execution/operator/join/physical_hash_join.cpp:217-254) under a min(rowid) aggregate
+// (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266).  Here gg_bfs64_paths reads the paths off the
+// distances of a 64-source BFS batch while they are still on the device (include/gg.h pins WHICH shortest path: the
+// predecessor with the smallest vertex-table position, among parallel edges the one appended first).
+//
+// Pairs are grouped by source, 64 distinct sources to a batch, in the order the sources first occur; one batch's rows are
+// resident at a time and the pipeline's threads drain them together, each through its own page-locked slab — the
+// protocol of PhysicalGGShortestPath.  Rows of one pair arrive in step order inside a slab, pairs in no promised order.
+#include "duckdb.hpp"
+#include "duckdb/common/exception.hpp"
+#include "duckdb/main/client_context.hpp"
+
+#include <atomic>
+#include <thread>
+#include <unordered_map>
+
+#include "gg_extension.hpp"
+#include "gg_operators.hpp"
+
+namespace duckdb {
+
+namespace {
+
+class ShortestPathRowsState : public GlobalSourceState {
+public:
+	~ShortestPathRowsState() override {
+		if (result) {
+			gg_result_destroy(result);
+		}
+	}
+	idx_t MaxThreads() override {
+		return max_threads;
+	}
+	vector<int64_t> uniq;            // distinct sources, in first-occurrence order; batch b holds uniq[64 b ..]
+	vector<vector<idx_t>> members;   // per batch: the pairs (indices into src / dst) of its sources, ascending
+	vector<vector<uint32_t>> lanes;  // per batch and member: the source's lane
+	idx_t batch = 0;                 // the batch whose rows are in `result`
+	gg_result *result = nullptr;     // its path rows, in HBM
+	idx_t rows = 0;                  // ... and how many
+	idx_t offset = 0;                // next unclaimed row of the current batch
+	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result`
+	mutex lock;
+	idx_t max_threads = 1;
+};
+
+//! a fetch in flight on the current batch's result (the batch is not replaced under it)
+struct FetchGuard {
+	std::atomic<idx_t> &counter;
+	explicit FetchGuard(std::atomic<idx_t> &counter_p) : counter(counter_p) {
+	}
+	~FetchGuard() {
+		counter--;
+	}
+};
+
+} // namespace
+
+PhysicalGGShortestPathRows::PhysicalGGShortestPathRows(shared_ptr<GGGraph> graph_p, vector<int64_t> src_p,
+                                                       vector<int64_t> dst_p, int max_hops_p,
+                                                       idx_t estimated_cardinality)
+    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), estimated_cardinality), graph(move(graph_p)),
+      src(move(src_p)), dst(move(dst_p)), max_hops(max_hops_p) {
+	D_ASSERT(src.size() == dst.size());
+}
+
+vector<LogicalType> PhysicalGGShortestPathRows::OutputTypes() {
+	return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER, LogicalType::BIGINT, LogicalType::BIGINT};
+}
+
+//! Trace the pairs of batch state.batch; the rows stay on the device until the pipeline threads have fetched them.
+void PhysicalGGShortestPathRows::RunBatch(GlobalSourceState &gstate_p) const {
+	auto &state = (ShortestPathRowsState &)gstate_p;
+	if (state.result) {
+		gg_result_destroy(state.result);
+		state.result = nullptr;
+	}
+	const idx_t base = state.batch * GG_BFS_LANES;
+	const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - base);
+	auto &members = state.members[state.batch];
+	vector<int64_t> targets(members.size());
+	for (idx_t i = 0; i < members.size(); i++) {
+		targets[i] = dst[members[i]];
+	}
+	GGGraph::Check(gg_bfs64_paths(graph->ctx, graph->csr, state.uniq.data() + base, n, max_hops,
+	                              state.lanes[state.batch].data(), targets.data(), targets.size(), 1, nullptr,
+	                              &state.result),
+	               "gg_bfs64_paths");
+	uint64_t rows = 0;
+	GGGraph::Check(gg_bfs64_paths_rows(state.result, &rows), "gg_bfs64_paths_rows");
+	state.rows = rows;
+	state.offset = 0;
+}
+
+unique_ptr<GlobalSourceState> PhysicalGGShortestPathRows::GetGlobalSourceState(ClientContext &context) const {
+	auto state = make_unique<ShortestPathRowsState>();
+	lock_guard<mutex> guard(graph->lock);
+	if (!graph->csr) {
+		throw InternalException("GG_SHORTEST_PATH_ROWS scheduled before the CSR was built");
+	}
+	std::unordered_map<int64_t, idx_t> position; // source id -> index into uniq
+	for (idx_t p = 0; p < src.size(); p++) {
+		auto found = position.find(src[p]);
+		idx_t at;
+		if (found == position.end()) {
+			at = state->uniq.size();
+			position.emplace(src[p], at);
+			state->uniq.push_back(src[p]);
+			if (at % GG_BFS_LANES == 0) {
+				state->members.emplace_back();
+				state->lanes.emplace_back();
+			}
+		} else {
+			at = found->second;
+		}
+		state->members[at / GG_BFS_LANES].push_back(p);
+		state->lanes[at / GG_BFS_LANES].push_back((uint32_t)(at % GG_BFS_LANES));
+	}
+	if (!state->members.empty()) {
+		RunBatch(*state);
+	}
+	// the first batch's size is the only estimate there is of how much the threads will have to drain
+	state->max_threads = MaxValue<idx_t>(1, state->rows * state->members.size() / GGResultSlab::SLAB_ROWS);
+	return move(state);
+}
+
+unique_ptr<LocalSourceState> PhysicalGGShortestPathRows::GetLocalSourceState(ExecutionContext &context,
+                                                                             GlobalSourceState &gstate) const {
+	return make_unique<GGResultSlab>(graph);
+}
+
+void PhysicalGGShortestPathRows::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+                                         LocalSourceState &lstate) const {
+	auto &gstate = (ShortestPathRowsState &)gstate_p;
+	auto &slab = (GGResultSlab &)lstate;
+	if (context.client.interrupted) {
+		throw InterruptException();
+	}
+	if (slab.pos >= slab.rows) {
+		idx_t offset, want;
+		gg_result *result;
+		{
+			lock_guard<mutex> guard(gstate.lock);
+			while (gstate.offset >= gstate.rows) { // current batch claimed completely: run the next one
+				if (gstate.batch + 1 >= gstate.members.size()) {
+					return;
+				}
+				if (context.client.interrupted) {
+					throw InterruptException();
+				}
+				// Fetches still reading the batch that is about to go: they end without taking this lock, so the wait
+				// is bounded.  The lock stays held through RunBatch on purpose — the other threads have nothing to
+				// claim until the next batch's rows exist (as in PhysicalGGShortestPath).
+				while (gstate.fetching.load() != 0) {
+					if (context.client.interrupted) {
+						throw InterruptException();
+					}
+					std::this_thread::yield();
+				}
+				gstate.batch++;
+				lock_guard<mutex> device_guard(graph->lock);
+				RunBatch(gstate);
+			}
+			offset = gstate.offset;
+			want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, gstate.rows - offset);
+			gstate.offset += want;
+			result = gstate.result;
+			slab.table = (int)gstate.batch; // pair i of these rows is members[batch][i]
+			gstate.fetching++;
+		}
+		uint32_t got = 0;
+		int rc;
+		{
+			FetchGuard claim(gstate.fetching);
+			// columns 0..2: pair, vertex, edge rowid; column 3's memory holds the int32 steps
+			auto columns = slab.Columns(4);
+			rc = gg_bfs64_paths_fetch(result, offset, (uint32_t)want, columns[0], (int32_t *)columns[3], columns[1],
+			                          columns[2], &got);
+		}
+		GGGraph::Check(rc, "gg_bfs64_paths_fetch");
+		slab.rows = got;
+		slab.pos = 0;
+		if (got == 0) {
+			return;
+		}
+	}
+	const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
+	auto out_src = FlatVector::GetData<int64_t>(chunk.data[0]);
+	auto out_dst = FlatVector::GetData<int64_t>(chunk.data[1]);
+	auto out_step = FlatVector::GetData<int32_t>(chunk.data[2]);
+	auto out_vertex = FlatVector::GetData<int64_t>(chunk.data[3]);
+	auto out_edge = FlatVector::GetData<int64_t>(chunk.data[4]);
+	auto &edge_validity = FlatVector::Validity(chunk.data[4]);
+	auto &members = gstate.members[slab.table]; // (filled before the first batch ran; never changed afterwards)
+	const int64_t *pair = slab.column[0] + slab.pos, *vertex = slab.column[1] + slab.pos;
+	const int64_t *edge = slab.column[2] + slab.pos;
+	const int32_t *step = (const int32_t *)slab.column[3] + slab.pos;
+	for (idx_t i = 0; i < n; i++) {
+		const idx_t p = members[(idx_t)pair[i]];
+		out_src[i] = src[p];
+		out_dst[i] = dst[p];
+		out_step[i] = step[i];
+		out_vertex[i] = vertex[i];
+		out_edge[i] = edge[i];
+		if (step[i] == 0) { // no edge leads into the path's first vertex
+			edge_validity.SetInvalid(i);
+		}
+	}
+	slab.pos += n;
+	chunk.SetCardinality(n);
+}
+
+} // namespace duckdb

@@ -28,6 +28,11 @@
  *                                                               src/execution/aggregate_hashtable.cpp:367-504,
  *                                                               src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266
  *           (the friends/friends_shortest CTE pair of benchmark/ldbc/queries/bi-10-shortestpath.sql:8-31)
+ *   gg_bfs64_paths / gg_bfs64_paths_rows / gg_bfs64_paths_fetch
+ *        <- no relation of the reference: bi-10-shortestpath.sql:26-31 stops at min(hopCount).  With its operators a path
+ *           is one more hash join of friends_shortest with knows per step under a min(rowid) aggregate
+ *                                                               physical_hash_join.cpp:217-254, join_hashtable.cpp:304-476,
+ *                                                               physical_hash_aggregate.cpp:152-266
  *   gg_walk_endpoints
  *        <- PhysicalUnion + the hash-aggregate dedupe above it (friends UNION friends of friends)
  *                                                               src/execution/physical_plan/plan_distinct.cpp:12-78,
@@ -300,6 +305,38 @@ int gg_bfs64_pairs(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n
  * the source list and the vertex ids (gg_csr_export) themselves. */
 int gg_bfs64_pairs_packed(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
                           gg_bfs_stats *stats, gg_result **out_result);
+
+/* The shortest paths themselves (ANY SHORTEST), read backwards off the distances of one gg_bfs64 batch while they are
+ * still on the device.  The batch is gg_bfs64(src_ids, n_src <= 64, max_hops); pair i asks for the path from
+ * src_ids[pair_lane[i]] to pair_dst_ids[i].  Which of the shortest paths is pinned: for a source s and a vertex x at
+ * distance d >= 1,
+ *     pred(s, x) = the in-neighbour of x at distance d - 1 from s with the smallest dense index (vertex-table
+ *                  position);
+ *     edge(s, x) = the first entry of pred(s, x)'s forward row, in CSR order (gg_csr_export), whose destination is x —
+ *                  among parallel edges the one appended first; reported as the rowid the Sink passed with the edge row,
+ *                  or its append position if it passed none;
+ * and the path of (s, t) is p_d = t, p_{i-1} = pred(s, p_i), p_0 = s.  One row per step i = 0..d:
+ *     (pair index, step i, vertex id p_i, rowid of the edge p_{i-1} -> p_i; -1 at step 0),
+ * ascending by (pair index, step).  s == t and s a vertex: the one row of step 0.  No path of at most max_hops edges
+ * (max_hops < 0: of any length), or s or t not a vertex: no rows.  Duplicate pairs each get their rows.
+ * want_edges == 0: the edge column is not computed (gg_bfs64_paths_fetch reports -1).  want_edges != 0 on a CSR built
+ * without edge rowids fails with GG_ERR_STATE, as gg_expand_khop_edges does; a shard CSR with GG_ERR_STATE; a
+ * pair_lane >= n_src with GG_ERR_INVALID_ARG; 2^32 rows or more in one call with GG_ERR_TOO_LARGE (ask for fewer pairs).
+ * Should a reached vertex have no in-neighbour one level closer, the distances and the CSR disagree: GG_ERR_STATE, never
+ * a loop.
+ * Pairs are traced in parallel, the steps of one pair one after the other — per step a piece of a reverse row, one
+ * distance cell per entry looked at and a piece of a forward row: a path of 10^5 steps (a chain) is 10^5 dependent
+ * steps of one lane group, slow and correct.  stats: those of the BFS.
+ * The first call on a CSR sorts a copy of its reverse rows by source (4 bytes per edge, kept with the CSR).
+ * The result answers gg_bfs64_paths_rows / gg_bfs64_paths_fetch only. */
+int gg_bfs64_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
+                   const uint32_t *pair_lane, const int64_t *pair_dst_ids, uint64_t n_pairs, int want_edges,
+                   gg_bfs_stats *stats, gg_result **out_result);
+int gg_bfs64_paths_rows(const gg_result *res, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows), in row order, into host arrays of >= max_rows entries (edge_rowid may be NULL).
+ * *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
+int gg_bfs64_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index, int32_t *step,
+                         int64_t *vertex_id, int64_t *edge_rowid, uint32_t *n_out);
 
 /* Distinct endpoints of the walks of 1..k_max edges that start at any of the given sources — the device form of
  *   SELECT dst FROM e WHERE src = C  UNION  SELECT e2.dst FROM e e1, e e2 WHERE e1.src = C AND e1.dst = e2.src
