@@ -847,6 +847,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   csr->ht_built = !fast || hs.dict_mode == DICT_WIDE16;
   csr->E = hs.kept;
   csr->E_rev = hs.kept_rev;
+  csr->rev_derived = fast && hs.rev_derived != 0;
   csr->owned_vertices = shard ? hs.owned : V;
   csr->dropped = shard ? 0 : E - hs.kept;  // a shard cannot tell dropped edges from other shards' edges
   for (void *p : {(void *)csr->off, (void *)csr->nbr, (void *)csr->row, (void *)csr->epos, (void *)csr->eid,
@@ -1660,5 +1661,28 @@ extern "C" int gg_csr_export(const gg_csr *csr, int64_t *off, int64_t *nbr, int6
     }
   }
   if (vid && csr->V) GG_HIP(hipMemcpy(vid, csr->vid, csr->V * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return GG_OK;
+}
+
+extern "C" int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, int64_t *rrow, int *derived) {
+  if (!csr) return GG_ERR_INVALID_ARG;
+  gg_ctx *ctx = csr->ctx;
+  ApiScope scope(ctx);
+  if (derived) *derived = csr->rev_derived ? 1 : 0;
+  if (!roff && !rnbr && !rrow) return GG_OK;
+  GG_HIP(hipSetDevice(ctx->device));
+  GG_TRY(ensure_reverse(ctx, csr));  // (the multi-pass build of a whole graph leaves the reverse CSR to its first use)
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  auto fetch = [&](int64_t *out, const uint32_t *dev, uint64_t n) -> int {
+    if (!out || !n) return GG_OK;
+    std::vector<uint32_t> h(n);
+    GG_HIP(hipMemcpy(h.data(), dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (uint64_t i = 0; i < n; i++) out[i] = (int64_t)h[i];
+    return GG_OK;
+  };
+  GG_TRY(fetch(roff, csr->roff, csr->V + 1));
+  const uint64_t n_rev = csr->n_parts > 1 ? csr->E_rev : csr->E;
+  GG_TRY(fetch(rnbr, csr->rnbr, n_rev));
+  GG_TRY(fetch(rrow, csr->rrow, n_rev));
   return GG_OK;
 }

@@ -91,7 +91,23 @@ struct FastGeom {
   uint32_t rank_atomic;  // 1: stable ranks straight from ds_add_rtn (lds_order_ok), 0: from match masks
   uint32_t h;         // mirrored halves (whole builds): floor(E / 2), row i + h is expected to be row i reversed;
   uint32_t nt1;       // tiles of the first half [0, h).  0 and 0: one run of tiles from row 0
+  uint32_t derive;    // 1: E = 2 h and the vertex-sorted form: the reverse CSR is derived from the forward rows if the
+                      // device finds every pair mirrored (reverse_derivable; "Derived reverse" below)
 };
+
+// Derived reverse.  Where EVERY row i + h is row i with source and destination swapped (E = 2 h), the reverse CSR holds
+// nothing new: with A / B the entries of x's forward row that come from first- / second-half rows (the row is A ++ B
+// in rowid order), roff == off, rrow is the row-index expansion of off, and x's reverse row in rowid order is B ++ A —
+// the forward row rotated by |A|.  The build then partitions and chunk-sorts the E forward entries only, first-half
+// tiles into part_f and second-half tiles into part_r (the second set of nb columns, chunks and offset rows means
+// "forward entries of second-half tiles" instead of "reverse entries"), and k_vrows writes both CSRs from them.
+// The decision is made on the device: the sampled rows chose the paired densification, which sees every pair and
+// raises tally[2] at the first one that is not mirrored.  Final once k_densify_pairs is done: k_col_partial reads it
+// there, k_col_scan leaves it in BuildStatus::rev_derived for the kernels behind it and for the host.  Both forms of
+// those kernels are launched and the unused one returns at once, as with the two densifications.
+__device__ __forceinline__ bool reverse_derivable(uint32_t derive, const uint32_t *__restrict__ tally) {
+  return derive && mirror_pays(tally) && tally[2] == 0;
+}
 
 // Rows [*r0, *r1) of a tile of D and A.  Tiles stay in rowid order; with h > 0 the first nt1 tiles cover [0, h) (the
 // last of them may be partial) and the rest start at h, so no tile straddles h and second-half tile nt1 + t holds,
@@ -316,7 +332,8 @@ __device__ __forceinline__ void densify_tile_pairs(const int64_t *__restrict__ s
                                                    const uint32_t *__restrict__ dir,
                                                    const unsigned long long *__restrict__ tab,
                                                    const DirectMap *__restrict__ dm, u32x2 *__restrict__ pairs,
-                                                   uint32_t low, uint32_t nb, uint32_t *hist) {
+                                                   uint32_t low, uint32_t nb, uint32_t *hist,
+                                                   uint32_t *__restrict__ unmirrored) {
   constexpr int B = GG_FB_DB;  // row pairs per batch: the first probes of 2*B lookups in flight per lane
   const int64_t min_id = dm->min_id, max_id = dm->max_id;
   PkGeom pk;
@@ -377,6 +394,7 @@ __device__ __forceinline__ void densify_tile_pairs(const int64_t *__restrict__ s
       }
     }
     if (__ballot(any2) == 0) continue;  // (uniform) every pair of the wave mirrored
+    if (any2) *unmirrored = 1u;         // the table is not fully mirrored: its reverse CSR cannot be derived
     probe_batch<MODE, B, true>(ps, pd, two, ht, cap, min_idx, dir, tab, min_id, max_id, pk, us, vs);
 #pragma unroll
     for (int j = 0; j < B; j++) {
@@ -409,7 +427,8 @@ __global__ __launch_bounds__(FB_THREADS) GG_FB_DATTR void k_densify_pairs(
     const int64_t *__restrict__ src, const int64_t *__restrict__ dst, uint64_t E, const HtSlot *__restrict__ ht,
     uint64_t cap, const BuildStatus *__restrict__ st, const uint32_t *__restrict__ dir,
     const unsigned long long *__restrict__ tab, const DirectMap *__restrict__ dm, u32x2 *__restrict__ pairs,
-    FastGeom g, uint64_t nblocks, uint32_t *__restrict__ counts, const uint32_t *__restrict__ mirror_tally) {
+    FastGeom g, uint64_t nblocks, uint32_t *__restrict__ counts, const uint32_t *__restrict__ mirror_tally,
+    uint32_t *__restrict__ unmirrored /* the tally's third word */) {
   constexpr uint32_t NH = PAIRED ? 4 : 2;  // LDS histograms: forward and reverse of each tile
   __shared__ uint32_t hist[NH << FB_MAX_HB];
   if (g.h && mirror_pays(mirror_tally) != PAIRED) return;  // (uniform over the grid) the other form's work
@@ -424,7 +443,8 @@ __global__ __launch_bounds__(FB_THREADS) GG_FB_DATTR void k_densify_pairs(
   auto run = [&](auto mode_tag) {
     constexpr int M = decltype(mode_tag)::value;
     if (PAIRED)
-      densify_tile_pairs<M>(src, dst, a0, a1, b0, b1, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, nb, hist);
+      densify_tile_pairs<M>(src, dst, a0, a1, b0, b1, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, nb, hist,
+                            unmirrored);
     else
       densify_tile<M>(src, dst, b0, b1, ht, cap, st->min_idx, dir, tab, dm, pairs, g.low, g.part, g.n_parts, hist,
                       hist + nb);
@@ -448,12 +468,16 @@ __global__ __launch_bounds__(FB_THREADS) GG_FB_DATTR void k_densify_pairs(
 // ---- A: two stable bucket partitions from one read of the pairs ---------------------------------------------
 // Element order inside a tile: wave w owns rows [w * FB_WTILE, (w + 1) * FB_WTILE), 64 consecutive rows per
 // step.  PACK: output word = low(key) << key_bits | payload; otherwise the pair (low(key), payload).
-template <bool PACK, bool ROWID, int STOP = 0>  // STOP > 0: timing probes that write nothing (GG_FB_A_PROBE builds)
+// MIRROR: the derived-reverse form (an instantiation of its own: the kernel sits at two workgroups per CU), ONE stable
+// partition by bucket(u) of (low(u), v): first-half tiles into out_f, second-half tiles into out_r, whose positions are
+// the second set of nb columns of the tile's row of bases.  With g.derive both forms are launched, one returns at once.
+template <bool PACK, bool ROWID, int STOP = 0, bool MIRROR = false>  // STOP > 0: timing probes that write nothing (GG_FB_A_PROBE builds)
 __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
     const u32x2 *__restrict__ pairs, uint64_t E, FastGeom g, uint64_t nblocks, const uint32_t *__restrict__ bases,
     const BuildStatus *__restrict__ st, uint32_t *__restrict__ out_f, uint32_t *__restrict__ out_r,
     uint32_t *__restrict__ epos_f) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
   const uint32_t nb = 1u << g.hb;
   uint32_t *xw = lds;                                   // staged words (PACK) or low keys
   uint32_t *xp = xw + FB_TILE;                          // staged payloads (!PACK)
@@ -497,7 +521,8 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
   }
 
 #pragma unroll 1
-  for (int dir = 0; dir < 2; dir++) {
+  for (int dir = 0; dir < (MIRROR ? 1 : 2); dir++) {
+    const uint32_t col = MIRROR ? (tile >= g.nt1 ? 1u : 0u) : (uint32_t)dir;  // the set of nb columns, and the output
     for (uint32_t i = threadIdx.x; i < FB_WAVES * nb; i += FB_THREADS) hw[i] = 0;
     __syncthreads();
     // (decided once per wave and direction, on its first 64 rows: the table's order does not change in between)
@@ -550,7 +575,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
       for (uint32_t q = 0; q < dpt; q++) {
         const uint32_t d = threadIdx.x * dpt + q;
         if (d < nb) {
-          gb[d] = bases[tile * 2 * nb + (uint64_t)dir * nb + d] - ex;
+          gb[d] = bases[tile * 2 * nb + (uint64_t)col * nb + d] - ex;
 #pragma unroll
           for (int w = 0; w < FB_WAVES; w++) hw[w * nb + d] += ex;  // ... + the bucket's first staged slot
           ex += tot[q];
@@ -621,7 +646,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
     if (STOP == 3) continue;  // timing probe: no write-out
     // write out: consecutive staged slots of one bucket -> consecutive global positions
     const uint32_t nvalid = misc[FB_WAVES];
-    uint32_t *out = dir ? out_r : out_f;
+    uint32_t *out = col ? out_r : out_f;
 #pragma unroll
     for (int it = 0; it < FB_ITEMS; it++) {
       const uint32_t i = (uint32_t)it * FB_THREADS + threadIdx.x;
@@ -677,21 +702,33 @@ constexpr int LEAF_MAXS = GG_FB_LEAF_MAXS;  // 64-entry steps a wave of k_leaf_r
 //   k_col_scan     (one workgroup) partial[g][c] <- bucket start + sums of the earlier groups; bucket starts, chunk
 //                  table and kept-edge count on the way (every figure the kernels below need)
 //   k_col_apply    counts[tile][c] <- partial[g][c] + counts of the group's earlier tiles, in place
+// Derived reverse: column set 0 takes the FORWARD counts of the first-half tiles, set 1 the FORWARD counts of the
+// second-half tiles (col_live); a tile counts nothing in the other set and its base there is not written.
 // Every access is a coalesced row.  (The first version kept the counters bucket-major for a chained scan: D wrote
 // and A read 1024 separate lines per tile, as many bytes again as A's payload.)
 //   bstart[dir * (nb + 1) + j]   first position of bucket j in that direction's partitioned array
 //   cstart[i], i = dir * nb + j  first chunk of bucket i (cstart[2 nb] = number of chunks)
 //   part_of[p]                   chunk p: {first entry, end, bucket i} (one load in k_sub_sort instead of a chain)
+__device__ __forceinline__ bool col_live(uint64_t tile, uint32_t c, uint32_t nb, uint32_t nt1) {
+  return (c >= nb) == (tile >= nt1);
+}
 __global__ __launch_bounds__(1024) void k_col_partial(const uint32_t *__restrict__ counts, uint64_t nblocks,
                                                      uint32_t ncol, uint32_t gsz, uint32_t *__restrict__ partial,
-                                                     uint32_t *__restrict__ coltot /* [ncol], zeroed */) {
+                                                     uint32_t *__restrict__ coltot /* [ncol], zeroed */, uint32_t derive,
+                                                     uint32_t nt1, const uint32_t *__restrict__ tally) {
+  const bool mirror = reverse_derivable(derive, tally);  // uniform over the grid
+  const uint32_t nb = ncol / 2;
   const uint64_t t0 = (uint64_t)blockIdx.x * gsz, t1 = t0 + gsz < nblocks ? t0 + gsz : nblocks;
   for (uint32_t c = threadIdx.x; c < ncol; c += 1024) {
     uint32_t sum = 0;
     for (uint64_t tb = t0; tb < t1; tb += 16) {
       uint32_t v[16];
 #pragma unroll
-      for (int q = 0; q < 16; q++) v[q] = tb + q < t1 ? counts[(tb + q) * ncol + c] : 0u;
+      for (int q = 0; q < 16; q++) {
+        v[q] = 0u;
+        if (tb + q < t1 && (!mirror || col_live(tb + q, c, nb, nt1)))
+          v[q] = counts[(tb + q) * ncol + (mirror ? c & (nb - 1u) : c)];
+      }
 #pragma unroll
       for (int q = 0; q < 16; q++) sum += v[q];
     }
@@ -704,7 +741,8 @@ __global__ __launch_bounds__(1024) void k_col_partial(const uint32_t *__restrict
 __global__ __launch_bounds__(1024) void k_col_scan(uint32_t *__restrict__ coltot /* in: totals, out: starts */,
                                                    uint32_t nb, uint32_t *__restrict__ bstart,
                                                    uint32_t *__restrict__ cstart, uint4 *__restrict__ part_of,
-                                                   BuildStatus *__restrict__ st) {
+                                                   BuildStatus *__restrict__ st, uint32_t derive,
+                                                   const uint32_t *__restrict__ tally) {
   __shared__ uint32_t s_b[2 * ((1 << FB_MAX_HB) + 1)];  // bucket starts, both directions
   __shared__ uint32_t s_w[2][16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -749,8 +787,11 @@ __global__ __launch_bounds__(1024) void k_col_scan(uint32_t *__restrict__ coltot
       s_b[dir * (nb + 1) + nb] = all[dir];
       bstart[dir * (nb + 1) + nb] = all[dir];
     }
-    st->kept = all[0];  // both directions count the same rows
-    st->kept_rev = all[1];
+    // (derived reverse: the two column sets are the two halves of the forward entries)
+    const bool mirror = reverse_derivable(derive, tally);
+    st->rev_derived = mirror ? 1ULL : 0ULL;
+    st->kept = mirror ? all[0] + all[1] : all[0];  // both directions count the same rows
+    st->kept_rev = mirror ? all[0] + all[1] : all[1];
   }
   __syncthreads();
   // chunks per bucket, exclusive scan over the 2 nb buckets (consecutive buckets per thread), chunk -> bucket table
@@ -792,7 +833,10 @@ __global__ __launch_bounds__(1024) void k_col_scan(uint32_t *__restrict__ coltot
 // partial rows of the groups before it (L2-resident: the whole matrix is ~1 MB) instead of waiting for a scan.
 __global__ __launch_bounds__(1024) void k_col_apply(uint32_t *__restrict__ counts, uint64_t nblocks, uint32_t ncol,
                                                     uint32_t gsz, const uint32_t *__restrict__ partial,
-                                                    const uint32_t *__restrict__ colstart) {
+                                                    const uint32_t *__restrict__ colstart, uint32_t nt1,
+                                                    const BuildStatus *__restrict__ st) {
+  const bool mirror = st->rev_derived != 0;  // uniform over the grid
+  const uint32_t nb = ncol / 2;
   const uint64_t t0 = (uint64_t)blockIdx.x * gsz, t1 = t0 + gsz < nblocks ? t0 + gsz : nblocks;
   for (uint32_t c = threadIdx.x; c < ncol; c += 1024) {
     uint32_t run = colstart[c];
@@ -808,10 +852,15 @@ __global__ __launch_bounds__(1024) void k_col_apply(uint32_t *__restrict__ count
     uint32_t v[16];
     for (uint64_t tb = t0; tb < t1; tb += 16) {
 #pragma unroll
-      for (int q = 0; q < 16; q++) v[q] = tb + q < t1 ? counts[(tb + q) * ncol + c] : 0u;
+      for (int q = 0; q < 16; q++) {
+        v[q] = 0u;
+        if (tb + q < t1 && (!mirror || col_live(tb + q, c, nb, nt1)))
+          v[q] = counts[(tb + q) * ncol + (mirror ? c & (nb - 1u) : c)];
+      }
 #pragma unroll
       for (int q = 0; q < 16; q++) {
-        if (tb + q < t1) counts[(tb + q) * ncol + c] = run;
+        // (derived reverse: column nb + j of a second-half tile READS the tile's word j, which nobody writes)
+        if (tb + q < t1 && (!mirror || col_live(tb + q, c, nb, nt1))) counts[(tb + q) * ncol + c] = run;
         run += v[q];
       }
     }
@@ -1472,18 +1521,25 @@ __global__ __launch_bounds__(FB_THREADS) void k_vsort_pipe(uint32_t *__restrict_
 }
 
 // where the rows of every group of VG vertices start: one wave per bucket, lane = group (at most 64 groups)
+// mirror (derived reverse, nb workgroups): bucket j's rows take the entries of BOTH half-buckets j and nb + j
 __global__ __launch_bounds__(64) void k_vgroups(const uint16_t *__restrict__ offs, const uint32_t *__restrict__ bstart,
                                                 const uint32_t *__restrict__ cstart, FastGeom g,
-                                                uint32_t *__restrict__ gstart /* [2 nb][64] */) {
+                                                uint32_t *__restrict__ gstart /* [2 nb][64] */, uint32_t mirror,
+                                                const BuildStatus *__restrict__ st) {
+  if (g.derive && (st->rev_derived != 0) != (mirror != 0)) return;  // (uniform over the grid) the other form's work
   const uint32_t nb = 1u << g.hb, nk = 1u << g.low, i = blockIdx.x, dir = i / nb, j = i % nb;
   const uint32_t vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG, groups = nk / vg;
   const int lane = threadIdx.x;
-  const uint32_t p0 = cstart[i], p1 = cstart[i + 1], k0 = (uint32_t)lane * vg;
-  uint32_t tot = 0;
-  if ((uint32_t)lane < groups)
-    for (uint32_t p = p0; p < p1; p++) tot += (uint32_t)offs[(uint64_t)p * g.ss + k0 + vg] - offs[(uint64_t)p * g.ss + k0];
+  const uint32_t k0 = (uint32_t)lane * vg;
+  uint32_t tot = 0, b0 = bstart[dir * (nb + 1) + j];
+  for (uint32_t half = 0; half < (mirror ? 2u : 1u); half++) {
+    const uint32_t ih = i + half * nb, p0 = cstart[ih], p1 = cstart[ih + 1];
+    if (half) b0 += bstart[nb + 1 + j];
+    if ((uint32_t)lane < groups)
+      for (uint32_t p = p0; p < p1; p++) tot += (uint32_t)offs[(uint64_t)p * g.ss + k0 + vg] - offs[(uint64_t)p * g.ss + k0];
+  }
   const uint32_t incl = wave_scan_incl(tot);  // (DPP moves, gg_internal.h)
-  gstart[(uint64_t)i * 64 + lane] = bstart[dir * (nb + 1) + j] + incl - tot;
+  gstart[(uint64_t)i * 64 + lane] = b0 + incl - tot;
 }
 
 // One wave per (direction, bucket, group of VG vertices).  Chunks are taken FB_VCG at a time: for chunk c the lanes
@@ -1498,12 +1554,12 @@ __global__ __launch_bounds__(64) void k_vgroups(const uint16_t *__restrict__ off
 #ifndef GG_FB_VCAP
 #define GG_FB_VCAP 1536  // entries of a wave's stage in k_vrows
 #endif
-__global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
-                                              const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
-                                              const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
-                                              FastGeom g, uint64_t V, uint32_t *__restrict__ off,
-                                              uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
-                                              uint32_t *__restrict__ rnbr, uint32_t *__restrict__ rrow) {
+__device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
+                                            const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
+                                            const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
+                                            FastGeom g, uint64_t V, uint32_t *__restrict__ off,
+                                            uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
+                                            uint32_t *__restrict__ rnbr, uint32_t *__restrict__ rrow) {
   __shared__ uint32_t s_delta[FB_VCG * FB_VG];
   __shared__ uint32_t s_run[2 * FB_VCG];  // [c]: first entry of the run inside chunk c, [FB_VCG + c]: its length
   __shared__ uint32_t s_stage[GG_FB_VCAP];
@@ -1649,6 +1705,202 @@ __global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f
   }
 }
 
+// Derived reverse: one wave per (bucket j, group of VG vertices), nb buckets.  The group's entries are the runs of the
+// chunks of half-bucket j (A: from first-half rows, in part_f) followed by those of half-bucket nb + j (B: from
+// second-half rows, in part_r); walking the chunks in that order, the running row positions put A then B into every
+// forward row exactly as above.  The offset rows of the two halves give |A| and |B| per vertex on the way, and the
+// reverse row is the forward row rotated by |A|: an A entry at forward position p lies at p + |B| in rnbr, a B entry
+// at p - |A|.  roff = off; rrow[p] is the vertex whose row holds p, in either CSR.  The staged path reads the rotated
+// entry back from the stage, so all three arrays go out as whole lines; large groups store each entry twice.
+__device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
+                                             const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
+                                             const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
+                                             FastGeom g, uint64_t V, uint32_t *__restrict__ off,
+                                             uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
+                                             uint32_t *__restrict__ rnbr, uint32_t *__restrict__ rrow) {
+  __shared__ uint32_t s_delta[FB_VCG * FB_VG];
+  __shared__ uint32_t s_run[2 * FB_VCG];  // [c]: first entry of the run inside chunk c, [FB_VCG + c]: its length
+  __shared__ uint32_t s_vt[3 * FB_VG];    // per vertex of the group: row start inside the group, |A|, |B|
+  __shared__ uint32_t s_stage[GG_FB_VCAP];
+  const uint32_t nb = 1u << g.hb, nk = 1u << g.low;
+  const uint32_t vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG, groups = nk / vg;  // (powers of two)
+  const uint32_t unit = blockIdx.x, j = unit / groups, gi = unit % groups, k0 = gi * vg;
+  const int lane = threadIdx.x;
+  const uint64_t v0 = ((uint64_t)j << g.low) + k0;  // first vertex of the group
+  if (j >= nb || v0 >= V) return;                   // (the table ends before this group: uniform)
+  const uint32_t bA = bstart[j], bB = bstart[nb + 1 + j];
+  const uint32_t pA = cstart[j], nA = cstart[j + 1] - pA, pB = cstart[nb + j], nB = cstart[nb + j + 1] - pB;
+  const uint32_t nch = nA + nB;  // chunk c of the group: chunk c of A, or chunk c - nA of B
+  const uint32_t gs = gstart[(uint64_t)j * 64 + gi];
+  const uint32_t pay_mask = (1u << g.key_bits) - 1u;
+  const uint32_t keep_mask = (vg << g.key_bits) - 1u;  // payload and the vertex inside the group
+  // the vertices' |A| and |B| (sums over the chunks' offset rows of either half), the row offsets of both CSRs
+  uint32_t degA = 0, degB = 0;
+#pragma unroll 1
+  for (uint32_t c0 = 0; c0 < nch; c0 += 8) {
+    uint32_t sv[8];
+#pragma unroll
+    for (int q = 0; q < 8; q++) {  // eight loads in flight
+      const uint32_t c = c0 + q;
+      sv[q] = 0;
+      if (c < nch && (uint32_t)lane <= vg) sv[q] = offs[(uint64_t)(c < nA ? pA + c : pB + (c - nA)) * g.ss + k0 + lane];
+    }
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const uint32_t c = c0 + q;
+      if (c >= nch) continue;  // uniform
+      const uint32_t nxt = (uint32_t)__shfl_down((int)sv[q], 1, 64);  // (by the whole wave: lane vg feeds lane vg - 1)
+      if ((uint32_t)lane < vg) {
+        if (c < nA)  // uniform
+          degA += nxt - sv[q];
+        else
+          degB += nxt - sv[q];
+      }
+      if (c < (uint32_t)FB_VCG) {
+        if ((uint32_t)lane < vg) s_delta[c * vg + lane] = sv[q];
+        if (lane == 0) s_run[c] = sv[q];
+        if ((uint32_t)lane == vg) s_run[FB_VCG + c] = sv[q];  // (the END of the run for now)
+      }
+    }
+  }
+  const uint32_t deg = degA + degB;
+  const uint32_t dincl = wave_scan_incl(deg);  // (DPP moves, gg_internal.h)
+  uint32_t base = gs + dincl - deg;            // lane d < vg: row position of vertex d's next entry; lane vg: the end
+  {
+    const uint64_t vv = v0 + (uint32_t)lane;
+    if ((uint32_t)lane <= vg && vv <= V) {
+      off[vv] = base;
+      roff[vv] = base;
+    }
+  }
+  const uint32_t t0 = gs;
+  const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)dincl, 63);  // entries of the group
+  const bool staged = n <= (uint32_t)GG_FB_VCAP;  // uniform
+  if ((uint32_t)lane < vg) {
+    s_vt[lane] = base - t0;
+    s_vt[vg + lane] = degA;
+    s_vt[2 * vg + lane] = degB;
+  }
+  if (staged) base -= t0;  // positions inside the stage
+#pragma unroll 1
+  for (uint32_t cg = 0; cg < nch; cg += FB_VCG) {
+    const uint32_t ncg = nch - cg < (uint32_t)FB_VCG ? nch - cg : (uint32_t)FB_VCG;
+    const uint32_t nAr = nA > cg ? nA - cg : 0u;  // chunks of this round below nAr are A's
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (uint32_t c = 0; c < ncg; c++) {  // chunk c of the round, lane d < vg: where vertex d starts in it
+      uint32_t sv = 0, first, end;
+      if (cg == 0) {  // parked above
+        if ((uint32_t)lane < vg) sv = s_delta[c * vg + lane];
+        first = s_run[c];
+        end = s_run[FB_VCG + c];
+      } else {
+        const uint32_t cc = cg + c;
+        if ((uint32_t)lane <= vg) sv = offs[(uint64_t)(cc < nA ? pA + cc : pB + (cc - nA)) * g.ss + k0 + lane];
+        first = (uint32_t)__builtin_amdgcn_readlane((int)sv, 0);
+        end = (uint32_t)__builtin_amdgcn_readlane((int)sv, (int)vg);
+      }
+      uint32_t nxt = (uint32_t)__shfl_down((int)sv, 1, 64);
+      if ((uint32_t)lane + 1 == vg) nxt = end;
+      if ((uint32_t)lane < vg) {
+        s_delta[c * vg + lane] = base - (sv - first);
+        base += nxt - sv;
+      }
+      if (lane == 0) {
+        s_run[c] = first;
+        s_run[FB_VCG + c] = end - first;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    // lane c holds chunk c's run; a run is walked in 64-entry steps
+    uint32_t so = 0, len = 0;
+    if ((uint32_t)lane < ncg) {
+      so = s_run[lane];
+      len = s_run[FB_VCG + lane];
+    }
+    const uint32_t cl = cg + (uint32_t)lane;
+    const uint32_t src = (cl < nA ? bA + cl * FB_TILE : bB + (cl - nA) * FB_TILE) + so;  // the run's first entry
+    const uint32_t st_c = (len + 63) / 64;
+    const uint32_t sincl = wave_scan_incl(st_c);  // (DPP moves, gg_internal.h)
+    const uint32_t sexcl = sincl - st_c;
+    const uint32_t T = (uint32_t)__builtin_amdgcn_readlane((int)sincl, 63);
+#pragma unroll 1
+    for (uint32_t r = 0; r < T; r += FB_VSTEPS) {
+      uint32_t kw[FB_VSTEPS], kx[FB_VSTEPS];
+      uint32_t have = 0;
+#pragma unroll
+      for (int q = 0; q < FB_VSTEPS; q++) {  // all loads of the round issue back to back
+        const uint32_t t = r + q;
+        kw[q] = 0;
+        kx[q] = 0;
+        if (t < T) {  // uniform
+          const int cc = __popcll(__ballot(sincl <= t));  // the run this step belongs to (< 64: t < T)
+          const uint32_t kidx = (t - (uint32_t)__builtin_amdgcn_readlane((int)sexcl, cc)) * 64 + lane;
+          const uint32_t run_src = (uint32_t)__builtin_amdgcn_readlane((int)src, cc);
+          const uint32_t run_len = (uint32_t)__builtin_amdgcn_readlane((int)len, cc);
+          const uint32_t *__restrict__ buf = (uint32_t)cc < nAr ? buf_f : buf_r;  // uniform
+          if (kidx < run_len) {
+            have |= 1u << q;
+            kw[q] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(buf + run_src), 0, (int)(run_len * 4u),
+                                                  0x00020000),
+                kidx * 4u, 0, 0);
+            kx[q] = kidx | ((uint32_t)cc << 24);  // index inside the run (< 8192), run number
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < FB_VSTEPS; q++) {
+        if (r + q >= T) continue;  // uniform
+        if ((have >> q) & 1u) {
+          const uint32_t d = (kw[q] >> g.key_bits) & (vg - 1u);
+          const uint32_t pos = s_delta[(kx[q] >> 24) * vg + d] + (kx[q] & 0xFFFFFFu);
+          if (staged) {
+            s_stage[pos] = kw[q] & keep_mask;
+          } else {
+            const uint32_t pay = kw[q] & pay_mask;
+            nbr[pos] = pay;
+            rrow[pos] = (uint32_t)v0 + d;
+            rnbr[(kx[q] >> 24) < nAr ? pos + s_vt[2 * vg + d] : pos - s_vt[vg + d]] = pay;
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the tables are rewritten by the next round of chunks
+  }
+  if (staged) {
+    // written from the 128-byte line the group's first entry lies in: every store instruction covers whole lines
+    // (the first and the last are shared with the neighbouring groups)
+    const uint32_t hd = GG_FB_ALIGNW ? (t0 & 31u) : 0u;
+    for (uint32_t x0 = 0; x0 < n + hd; x0 += 64) {
+      const uint32_t x = x0 + lane - hd;  // (wraps below zero for the lanes before the first entry)
+      if (x < n) {
+        const uint32_t sw = s_stage[x], d = sw >> g.key_bits;
+        const uint32_t rs = s_vt[d], a = s_vt[vg + d], b = s_vt[2 * vg + d], i = x - rs;  // entry i of d's row
+        nbr[t0 + x] = sw & pay_mask;
+        rrow[t0 + x] = (uint32_t)v0 + d;
+        rnbr[t0 + x] = s_stage[rs + (i < b ? a + i : i - b)] & pay_mask;  // B ++ A
+      }
+    }
+  }
+}
+
+// MIRROR: the derived-reverse form.  With g.derive both forms are launched and one returns at once.
+template <bool MIRROR>
+__global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
+                                              const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
+                                              const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
+                                              FastGeom g, uint64_t V, const BuildStatus *__restrict__ st,
+                                              uint32_t *__restrict__ off, uint32_t *__restrict__ nbr,
+                                              uint32_t *__restrict__ roff, uint32_t *__restrict__ rnbr,
+                                              uint32_t *__restrict__ rrow) {
+  if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
+  if (MIRROR)
+    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rnbr, rrow);
+  else
+    vrows_plain(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rnbr, rrow);
+}
+
 static int bits_of(uint64_t v) {  // bits needed for values 0..v
   int b = 0;
   while (b < 64 && (v >> b)) b++;
@@ -1697,6 +1949,8 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   const uint64_t h = ctx->mirror_pairs && csr->n_parts <= 1 && E >= 2 ? E / 2 : 0;
   g.h = (uint32_t)h;
   g.nt1 = (uint32_t)((h + FB_TILE - 1) / FB_TILE);
+  // derived reverse: possible where every row has a partner (E = 2 h) in the vertex-sorted form; the device decides
+  g.derive = vsort && h && E == 2 * h && ctx->mirror_reverse ? 1u : 0u;
   *taken = 1;
   const uint32_t nb = 1u << hb;
   const bool rowid = ctx->keep_edge_rowid && csr->n_parts <= 1;  // a shard only serves 2-hop counting and BFS: no rowids
@@ -1729,9 +1983,10 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   while ((nblocks64 + gsz - 1) / gsz > 512) gsz *= 2;
   const uint32_t ngroups = (uint32_t)((nblocks64 + gsz - 1) / gsz);
   uint32_t *partial = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&partial, (((uint64_t)ngroups + 1) * ncol + 2) * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&partial, (((uint64_t)ngroups + 1) * ncol + 3) * sizeof(uint32_t)));
   uint32_t *coltot = partial + (uint64_t)ngroups * ncol;  // column totals, then column (= bucket) starts
-  uint32_t *mirror_tally = coltot + ncol;                   // [2] rows sampled / mirrored (h > 0), zeroed with coltot
+  uint32_t *mirror_tally = coltot + ncol;                   // [3] rows sampled / mirrored (h > 0), != 0: the paired
+                                                            // densification met a pair that is not mirrored; zeroed with coltot
   {
     uint64_t span = csr->ht_cap > 2 * npairs ? csr->ht_cap : 2 * npairs;
     if (span < DIRECT_MAX_RANGE) span = DIRECT_MAX_RANGE;
@@ -1739,7 +1994,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "dict_init", k_dict_init, dim3((unsigned)((span + 255) / 256)), dim3(256), 0,
               (const int64_t *)ctx->c_vid.dev, V, csr->ht,
               csr->ht_cap, tab, 2 * npairs, dir, dm, st, (uint32_t)csr->part, (uint32_t)csr->n_parts, csr->vid, coltot,
-              ncol + 2);
+              ncol + 3);
     GG_LAUNCH(ctx, "dict_insert", k_dict_insert, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, csr->vid, V, csr->ht,
               csr->ht_cap, tab, dir, dm, idx_bits, (uint32_t)npairs, st, (const int64_t *)ctx->c_src.dev,
               (const int64_t *)ctx->c_dst.dev, h, mirror_tally);
@@ -1763,11 +2018,11 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "densify_pairs", (k_densify_pairs<false, true>), dim3((unsigned)(nblocks64 - g.nt1)), dim3(FB_THREADS),
               0, ctx->c_src.dev, ctx->c_dst.dev, E, csr->ht, csr->ht_cap, st, (const uint32_t *)dir,
               (const unsigned long long *)tab, (const DirectMap *)dm, pairs, g, nblocks64, counts,
-              (const uint32_t *)mirror_tally);
+              (const uint32_t *)mirror_tally, mirror_tally + 2);
   GG_LAUNCH(ctx, h ? "densify_unpaired" : "densify_pairs", (k_densify_pairs<false, false>), dim3(nblocks),
             dim3(FB_THREADS), 0, ctx->c_src.dev, ctx->c_dst.dev, E, csr->ht, csr->ht_cap, st, (const uint32_t *)dir,
             (const unsigned long long *)tab, (const DirectMap *)dm, pairs, g, nblocks64, counts,
-            (const uint32_t *)mirror_tally);
+            (const uint32_t *)mirror_tally, mirror_tally + 2);
   const uint64_t pmax = 2 * (nblocks64 + nb);  // chunks: every bucket may end in a partial one
   uint4 *part_of = nullptr;
   uint32_t *cstart = nullptr, *offs = nullptr, *substart = nullptr;
@@ -1776,8 +2031,9 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&offs, pmax * g.ss * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&substart, (uint64_t)2 * nb * (g.ss < 64 ? 64 : g.ss) * sizeof(uint32_t)));
   GG_LAUNCH(ctx, "col_partial", k_col_partial, dim3(ngroups), dim3(1024), 0, (const uint32_t *)counts, nblocks64, ncol, gsz,
-            partial, coltot);
-  GG_LAUNCH(ctx, "col_scan", k_col_scan, dim3(1), dim3(1024), 0, coltot, nb, bstart, cstart, part_of, st);
+            partial, coltot, g.derive, g.nt1, (const uint32_t *)mirror_tally);
+  GG_LAUNCH(ctx, "col_scan", k_col_scan, dim3(1), dim3(1024), 0, coltot, nb, bstart, cstart, part_of, st, g.derive,
+            (const uint32_t *)mirror_tally);
   if (!rowid) {
     // every status word is final now (duplicate ids: k_dict_insert; dictionary mode: k_dict_wide; kept entries: the
     // column scan) and no kernel below reports an error: the host gets its copy here and waits for THIS, with two
@@ -1788,7 +2044,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     ctx->status_early = true;
   }
   GG_LAUNCH(ctx, "col_apply", k_col_apply, dim3(ngroups), dim3(1024), 0, counts, nblocks64, ncol, gsz,
-            (const uint32_t *)partial, (const uint32_t *)coltot);
+            (const uint32_t *)partial, (const uint32_t *)coltot, g.nt1, (const BuildStatus *)st);
 
   // ---- A ----------------------------------------------------------------------------------------------------
   const size_t words = g.pack ? 1 : 2;
@@ -1803,20 +2059,25 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
                            sizeof(uint32_t) +
                        (size_t)FB_TILE * sizeof(uint16_t) + 16 + (0 ? (size_t)FB_WAVES * nb * 8 : 0);
   const unsigned grid_a = (unsigned)(((nblocks64 + 7) / 8) * 8);
-#define GG_FB_LAUNCH_A(P, R)                                                                                        \
-  GG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_partition_dual<P, R>),                                 \
+#define GG_FB_LAUNCH_A(NAME, P, R, M)                                                                               \
+  GG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_partition_dual<P, R, 0, M>),                           \
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));                                \
-  GG_LAUNCH(ctx, "partition_dual", (k_partition_dual<P, R>), dim3(grid_a), dim3(FB_THREADS), lds_a,                  \
+  GG_LAUNCH(ctx, NAME, (k_partition_dual<P, R, 0, M>), dim3(grid_a), dim3(FB_THREADS), lds_a,                        \
             (const u32x2 *)pairs, E, g, nblocks64, (const uint32_t *)counts, (const BuildStatus *)st, part_f, part_r, \
             epos_f)
-  if (g.pack && rowid) {
-    GG_FB_LAUNCH_A(true, true);
+  // g.derive: the derived-reverse form and the plain one, one of which returns at once.  The plain launches are timed
+  // under "<name>_plain" then, so that each name's time per launch is one form's (as with "densify_unpaired")
+  if (g.derive) {
+    GG_FB_LAUNCH_A("partition_dual", true, false, true);
+    GG_FB_LAUNCH_A("partition_dual_plain", true, false, false);
+  } else if (g.pack && rowid) {
+    GG_FB_LAUNCH_A("partition_dual", true, true, false);
   } else if (g.pack) {
-    GG_FB_LAUNCH_A(true, false);
+    GG_FB_LAUNCH_A("partition_dual", true, false, false);
   } else if (rowid) {
-    GG_FB_LAUNCH_A(false, true);
+    GG_FB_LAUNCH_A("partition_dual", false, true, false);
   } else {
-    GG_FB_LAUNCH_A(false, false);
+    GG_FB_LAUNCH_A("partition_dual", false, false, false);
   }
 #undef GG_FB_LAUNCH_A
 
@@ -1853,12 +2114,22 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     uint32_t *gstart = substart;                            // [2 nb][64]
     GG_LAUNCH(ctx, "sub_sort", k_vsort_pipe, dim3(grid_p), dim3(FB_THREADS), lds_v, part_f, part_r,
               (const uint32_t *)cstart, (const uint4 *)part_of, g, offs16);
-    GG_LAUNCH(ctx, "sub_totals", k_vgroups, dim3(2 * nb), dim3(64), 0, (const uint16_t *)offs16,
-              (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart);
     const uint32_t nk = 1u << low, vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG;
-    GG_LAUNCH(ctx, "leaf_rows", k_vrows, dim3((unsigned)(2ull * nb * (nk / vg))), dim3(64), 0, (const uint32_t *)part_f,
-              (const uint32_t *)part_r, (const uint32_t *)bstart, (const uint32_t *)cstart, (const uint16_t *)offs16,
-              (const uint32_t *)gstart, g, V, csr->off, csr->nbr, csr->roff, csr->rnbr, csr->rrow);
+    if (g.derive) {  // (the derived-reverse forms: nb buckets of both halves' entries)
+      GG_LAUNCH(ctx, "sub_totals", k_vgroups, dim3(nb), dim3(64), 0, (const uint16_t *)offs16,
+                (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, 1u, (const BuildStatus *)st);
+      GG_LAUNCH(ctx, "leaf_rows", k_vrows<true>, dim3((unsigned)((uint64_t)nb * (nk / vg))), dim3(64), 0,
+                (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart, (const uint32_t *)cstart,
+                (const uint16_t *)offs16, (const uint32_t *)gstart, g, V, (const BuildStatus *)st, csr->off, csr->nbr,
+                csr->roff, csr->rnbr, csr->rrow);
+    }
+    GG_LAUNCH(ctx, g.derive ? "sub_totals_plain" : "sub_totals", k_vgroups, dim3(2 * nb), dim3(64), 0,
+              (const uint16_t *)offs16, (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, 0u,
+              (const BuildStatus *)st);
+    GG_LAUNCH(ctx, g.derive ? "leaf_rows_plain" : "leaf_rows", k_vrows<false>, dim3((unsigned)(2ull * nb * (nk / vg))),
+              dim3(64), 0, (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart,
+              (const uint32_t *)cstart, (const uint16_t *)offs16, (const uint32_t *)gstart, g, V,
+              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr, csr->rrow);
   } else if (g.pack && rowid) {
     GG_FB_LAUNCH_B2(true, true);
   } else if (g.pack && g.rank_atomic && GG_FB_SUBPIPE) {

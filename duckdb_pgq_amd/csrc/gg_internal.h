@@ -74,6 +74,8 @@ struct BuildStatus {  // device-side status block of a CSR build, copied back on
   unsigned long long owned;        // vertices owned by this shard
   unsigned long long scan_error;   // !=0: a chained scan gave up waiting for a predecessor tile (gg_runtime.hip)
   unsigned long long dict_mode;    // bucketed build: DictMode the edge densification used (DICT_WIDE16: csr->ht is built)
+  unsigned long long rev_derived;  // bucketed build: !=0: every row i + E/2 mirrors row i and the reverse CSR was derived
+                                   // from the forward rows (gg_csr_fast.hip "Derived reverse"); final behind k_col_scan
 };
 
 // id -> dense index dictionary used while densifying edge rows, chosen on the device from the vertex ids'
@@ -181,6 +183,8 @@ struct gg_ctx {
   bool keep_edge_rowid = true;  // gg_ctx_set_edge_rowid
   bool mirror_pairs = true;     // GG_MIRROR_PAIRS=0 at context creation: whole builds and the endpoint set never pair row i
                                 // with row i + E/2 (gg_csr_fast.hip, k_set_insert2); results are the same either way
+  bool mirror_reverse = true;   // GG_MIRROR_REVERSE=0 at context creation (GG_MIRROR_PAIRS=0 implies it): the bucketed build
+                                // never derives the reverse CSR of a fully mirrored table from its forward rows
   uint64_t max_grid_tiles = 0;  // gg_debug_max_grid_tiles: workgroups per expansion launch (0: the hardware bound)
   int reach_visited_mode = 0;   // gg_debug_reach_visited: 0 the budget decides, 1 bitmap, 2 hash set (gg_reach.hip)
   uint64_t reach_hash_slots = 0;  // gg_debug_reach_visited: the hash set's first capacity (0: from the seed count)
@@ -266,6 +270,7 @@ struct gg_csr {
   uint32_t *roff = nullptr;    // V+1
   uint32_t *rnbr = nullptr;    // E   source u of the reverse entry
   uint32_t *rrow = nullptr;    // E   destination x of the reverse entry (COO view, sorted by x)
+  bool rev_derived = false;    // the bucketed build derived roff / rnbr / rrow from the forward rows (fully mirrored table)
   // the reverse rows again with their sources ascending (gg_paths.hip: ensure_reverse_by_source, whole CSRs, on first
   // use): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
   uint32_t *rnbr_by_src = nullptr;  // E

@@ -503,6 +503,7 @@ extern "C" int gg_ctx_create(int device, gg_ctx **out) {
     ctx->fetch_lanes_used = atoi(e) >= 1 && atoi(e) <= gg_ctx::FETCH_LANES ? (uint32_t)atoi(e) : gg_ctx::FETCH_LANES;
   if (const char *e = getenv("GG_PLACE_PROBES")) ctx->place_probes = atoi(e) > 0 ? (atoi(e) < 16 ? atoi(e) : 16) : 1;
   if (const char *e = getenv("GG_MIRROR_PAIRS")) ctx->mirror_pairs = atoi(e) != 0;
+  if (const char *e = getenv("GG_MIRROR_REVERSE")) ctx->mirror_reverse = atoi(e) != 0;
   for (int i = 0; i < 2; i++) {
     GG_HIP(hipHostMalloc((void **)&ctx->pin_v[i], gg_ctx::STAGE_ROWS * sizeof(int64_t), hipHostMallocDefault));
     GG_HIP(hipEventCreateWithFlags(&ctx->pin_v_free[i], hipEventDisableTiming));

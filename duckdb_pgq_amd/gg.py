@@ -19,6 +19,7 @@ SYMBOLS = [
     "gg_ctx_set_edge_rowid", "gg_csr_build", "gg_csr_build_shard", "gg_csr_destroy", "gg_csr_info", "gg_csr_export",
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
+    "gg_debug_csr_reverse",
     "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_reach_visited",
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
@@ -104,6 +105,7 @@ def load_library(path: str | None = None):
     lib.gg_debug_force_frontier.argtypes = [P, C.c_int]
     lib.gg_debug_force_legacy_build.argtypes = [P, C.c_int]
     lib.gg_debug_rank_mode.argtypes = [P, C.c_int]
+    lib.gg_debug_csr_reverse.argtypes = [P, i64p, i64p, i64p, C.POINTER(C.c_int)]
     lib.gg_debug_scan_fault.argtypes = [P, C.c_uint32, u64]
     lib.gg_debug_max_grid_tiles.argtypes = [P, u64]
     lib.gg_debug_reset.argtypes = [P]
@@ -351,6 +353,23 @@ class Csr:
         p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
         self.gg._chk(self.gg.lib.gg_csr_export(self.handle, p(off), p(nbr), p(eid), p(vid)))
         return off, nbr, eid, vid
+
+    @property
+    def reverse_derived(self) -> int:
+        """1 if the build derived the reverse CSR from the forward rows (a fully mirrored edge table)."""
+        d = C.c_int()
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, None, None, None, C.byref(d)))
+        return d.value
+
+    def export_reverse(self):
+        """(roff, rnbr, rrow) of the reverse CSR as int64 arrays (gg_debug_csr_reverse)."""
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
+        roff = np.empty(self.V + 1, np.int64)
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, p(roff), None, None, None))
+        rnbr = np.empty(int(roff[-1]), np.int64)  # (a shard keeps the edges whose DESTINATION it owns here)
+        rrow = np.empty(int(roff[-1]), np.int64)
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, None, p(rnbr), p(rrow), None))
+        return roff, rnbr, rrow
 
     def close(self):
         if self.handle:

@@ -473,6 +473,14 @@ int gg_debug_force_legacy_build(gg_ctx *ctx, int on);
  * ds_add_rtn serves colliding lanes in lane order and use it if so; 1: use it; 2: match masks by ballots.  Both
  * must export identical arrays. */
 int gg_debug_rank_mode(gg_ctx *ctx, int mode);
+/* Testing hook: the reverse CSR (in-neighbours) as int64 arrays — roff[V + 1], and rnbr / rrow (source / destination
+ * of every reverse entry) with as many entries as the CSR keeps edges (a shard: the edges whose destination it owns);
+ * any of the three may be NULL.  Row x lists its sources in edge-rowid order where the bucketed build made the reverse
+ * CSR, in ascending (source, rowid) order where the multi-pass build of a whole graph left it to this call.
+ * *derived (may be NULL): 1 if the build derived the reverse CSR from the forward rows of a fully mirrored edge table
+ * (row i + E/2 = row i with source and destination swapped, for every i), which must give the same arrays as sorting;
+ * GG_MIRROR_REVERSE=0 in the environment at gg_ctx_create (or GG_MIRROR_PAIRS=0) switches that off. */
+int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, int64_t *rrow, int *derived);
 /* Testing knob (fault injection): tile `mute_tile` of every chained prefix scan never publishes its sum and the
  * tiles behind it give up after `spin_limit` polls instead of 2^24; the call that ran the scan must then
  * fail with GG_ERR_HIP instead of returning a wrong result.  spin_limit 0 and mute_tile UINT64_MAX restore
