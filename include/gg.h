@@ -364,7 +364,8 @@ int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, ui
  * fails with GG_ERR_STATE.  That test costs V + 1 levels, each a few launches and one host round trip: on a graph of many
  * vertices a reachable cycle is a long run before the error (or a level of 2^32 walks, or the pool running out, comes
  * first) — a caller that may meet cycles bounds max_levels.  A level of 2^32 walks or more fails with GG_ERR_TOO_LARGE;
- * a shard CSR with GG_ERR_STATE.
+ * a shard CSR with GG_ERR_STATE; a CSR built without edge rowids with GG_ERR_STATE too, whichever build made it (no
+ * rows without their rowid column), and the context stays usable.
  * The result answers gg_walk_closure_levels / gg_walk_closure_fetch (not gg_result_rows / gg_result_fetch). */
 int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, uint64_t n_seeds, int max_levels,
                     gg_result **out_result);
