@@ -190,6 +190,7 @@ struct gg_ctx {
   uint64_t reach_hash_slots = 0;  // gg_debug_reach_visited: the hash set's first capacity (0: from the seed count)
   int levels_set_mode = 0;      // gg_debug_level_sets: 0 the budget decides, 1 bitmap, 2 hash set (gg_levels.hip)
   int levels_order_mode = 0;    // gg_debug_level_sets: 0 the byte model decides per level, 1 sort, 2 compact
+  uint32_t tri_lds_entries = 0; // gg_debug_triangle_tile: entries of an in-row gg_triangles may stage in LDS (0: the default)
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;
@@ -272,7 +273,7 @@ struct gg_csr {
   uint32_t *rrow = nullptr;    // E   destination x of the reverse entry (COO view, sorted by x)
   bool rev_derived = false;    // the bucketed build derived roff / rnbr / rrow from the forward rows (fully mirrored table)
   // the reverse rows again with their sources ascending (gg_paths.hip: ensure_reverse_by_source, whole CSRs, on first
-  // use): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
+  // use by gg_bfs64_paths or gg_triangles): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
   uint32_t *rnbr_by_src = nullptr;  // E
   // the reverse entries grouped by SOURCE (gg_bfs.hip: ensure_push_in, shards only, on first use): row u lists
   // the owned destinations of u's edges, so a shard can push a light frontier into the words it owns
@@ -397,6 +398,8 @@ int grow_column(gg_ctx *ctx, Column &c, size_t live_rows, size_t need_rows);
 void staging_trace_print();
 // build csr->roff / csr->rnbr if absent (gg_csr.hip)
 int ensure_reverse(gg_ctx *ctx, gg_csr *csr);
+// build csr->rnbr_by_src if absent: the reverse rows with their sources ascending, under csr->roff (gg_paths.hip)
+int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr);
 // fill csr->ht from csr->vid if the build did not need it (gg_csr.hip); every ht_lookup user calls this first
 int ensure_ht(gg_ctx *ctx, gg_csr *csr);
 // bucketed two-level build of forward + reverse CSR (gg_csr_fast.hip); *taken = 0 if the graph is outside

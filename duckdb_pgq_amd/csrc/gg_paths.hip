@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void k_entry_rows(const uint32_t *__restrict__
 // sorts them by source; a BFS pull does not care, the trace does: with the sources ascending, the FIRST entry one level
 // closer is the predecessor with the smallest dense index and a step ends at the first hit.  One stable sort of the
 // forward entries by destination, once per CSR (first gg_bfs64_paths call), 4 E bytes kept with it.
-static int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr) {
+int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr) {
   if (csr->rnbr_by_src) return GG_OK;
   if (!csr->roff) GG_TRY(ensure_reverse(ctx, csr));  // (a search of zero levels never built it)
   const uint64_t V = csr->V, E = csr->E;

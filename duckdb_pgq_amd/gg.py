@@ -30,6 +30,7 @@ SYMBOLS = [
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
+    "gg_triangles", "gg_debug_triangle_tile",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -56,6 +57,10 @@ class BfsStats(C.Structure):
         ("active_vertices", C.c_uint64),
         ("reached_pairs", C.c_uint64),
     ]
+
+
+class TriStats(C.Structure):
+    _fields_ = [("rows", C.c_uint64), ("digest", C.c_uint64), ("wedges", C.c_uint64)]
 
 
 _lib = None
@@ -153,6 +158,8 @@ def load_library(path: str | None = None):
     lib.gg_bfs_sharded_levels.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
     lib.gg_bfs_sharded_end.argtypes = [P]
     lib.gg_bfs_sharded_end.restype = None
+    lib.gg_triangles.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.POINTER(TriStats), C.POINTER(P)]
+    lib.gg_debug_triangle_tile.argtypes = [P, C.c_uint32]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
     lib.gg_profile_reset.argtypes = [P]
@@ -839,6 +846,29 @@ class GG:
         """gg_level_sets' per-level set (0 the budget decides, 1 bitmap, 2 hash set) and order route (0 the byte model
         decides, 1 claim and sort, 2 read the rows off the bitmap; not with the hash set)."""
         self._chk(self.lib.gg_debug_level_sets(self.ctx, int(set_mode), int(order_mode)))
+
+    # ---- triangles
+    def triangles(self, csr: Csr, sources=None, ordered: bool = False, materialise: bool = False):
+        """gg_triangles: the closed 3-edge walks (a, b, c) with a from `sources` (None: every vertex); ordered: only
+        id(a) < id(b) < id(c).  Returns {"rows", "digest", "wedges"}; with materialise, (that dict, KhopResult whose
+        table 2 holds the rows — the caller closes it)."""
+        st, res = TriStats(), C.c_void_p()
+        if sources is None:
+            sp, ns = None, 0
+        else:
+            a, sp = _i64(sources)
+            ns = a.size
+            if ns == 0:  # an empty list, not "every vertex": a non-NULL pointer with n_src = 0
+                sp = C.cast((C.c_int64 * 1)(), C.POINTER(C.c_int64))
+        self._chk(self.lib.gg_triangles(self.ctx, csr.handle, sp, ns, int(ordered), int(materialise), C.byref(st),
+                                        C.byref(res)))
+        d = {"rows": int(st.rows), "digest": int(st.digest), "wedges": int(st.wedges)}
+        return (d, KhopResult(self, res, d)) if materialise else d
+
+    def debug_triangle_tile(self, n: int = 0):
+        """gg_triangles stages at most n entries of an in-row in LDS (0: the default); longer rows are searched in
+        global memory."""
+        self._chk(self.lib.gg_debug_triangle_tile(self.ctx, int(n)))
 
     # ---- graph-sharded BFS (one shard per GPU; see include/gg.h)
     def bfs_sharded_begin(self, shard: Csr, sources) -> "ShardedBfs":

@@ -14,6 +14,10 @@
 //        -> (startPerson BIGINT, friend BIGINT, hopCount INTEGER)
 //   gg_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
 //        -> (src BIGINT, dst BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT)   the paths, unnested
+//   gg_triangle_count(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered)
+//        -> (rows BIGINT, digest BIGINT, wedges BIGINT)          closed 3-edge walks (gg_triangles.cpp)
+//   gg_triangles(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered)
+//        -> (v0 BIGINT, v1 BIGINT, v2 BIGINT)
 //   gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //                           filter_table, filter_src, filter_dst, hops)
 //        -> (w BIGINT, v0 BIGINT, ..., v{hops} BIGINT)      Train Benchmark ConnectedSegments
@@ -688,6 +692,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &pin_info);
 	catalog.CreateTableFunction(*con.context, &unpin_info);
 	catalog.CreateTableFunction(*con.context, &pins_info);
+	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();
 }

@@ -88,6 +88,9 @@ vector<int64_t> GGQueryInt64Column(ClientContext &context, const string &sql, co
 //! "identifier" with embedded quotes doubled
 string GGQuote(const string &ident);
 
+//! gg_triangles.cpp: registers gg_triangles / gg_triangle_count (inside the caller's transaction)
+void GGRegisterTriangleFunctions(ClientContext &context);
+
 //! gg_plan_rule.cpp: hand the planner rules to the interposition shim if it is loaded; registers
 //! `PRAGMA enable_gpu_graph` / `PRAGMA disable_gpu_graph`.
 void GGRegisterPlanRules(ClientContext &context);

@@ -10,6 +10,8 @@
 //        <=1024-row DataChunks, Finalize once.
 //   PhysicalGGPathExpand                         <->  the chain of PhysicalHashJoin::Execute probes
 //        (physical_hash_join.cpp:217-254) of a k-hop pattern; a source that emits the walks.
+//   PhysicalGGTriangles                          <->  three PhysicalHashJoin probes, the last on two conditions
+//        (physical_hash_join.cpp:217-254) of the cyclic pattern a -> b -> c -> a (benchmark/ldbc/queries/bi-11.sql:22-33).
 //   PhysicalGGShortestPath                       <->  PhysicalRecursiveCTE + min(hop) aggregate
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
@@ -419,6 +421,35 @@ public:
 	}
 	string GetName() const override {
 		return "GG_SHORTEST_PATH_ROWS";
+	}
+};
+
+//! Source: the triangle rows (closed 3-edge walks, include/gg.h gg_triangles) of the graph from every vertex.
+//! Output: (v0 BIGINT, v1 BIGINT, v2 BIGINT), one row per triple of edge rows v0->v1, v1->v2, v2->v0; ordered: only
+//! id(v0) < id(v1) < id(v2).  count_only: the one row (rows BIGINT, digest BIGINT, wedges BIGINT).
+class PhysicalGGTriangles : public PhysicalOperator {
+public:
+	PhysicalGGTriangles(shared_ptr<GGGraph> graph, bool ordered, bool count_only, idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes(bool count_only);
+
+	shared_ptr<GGGraph> graph;
+	bool ordered;
+	bool count_only;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_TRIANGLES";
 	}
 };
 

@@ -1,0 +1,180 @@
+// gg_triangles.cpp — triangle rows (closed 3-edge walks) over one edge table, as two table functions:
+//
+//   gg_triangle_count(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered BOOLEAN)
+//        -> (rows BIGINT, digest BIGINT, wedges BIGINT)                      one row
+//   gg_triangles(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered BOOLEAN)
+//        -> (v0 BIGINT, v1 BIGINT, v2 BIGINT)                                the rows, order unspecified
+//
+// What they stand for in the reference: `edge k1, edge k2, edge k3 WHERE k1.dst = k2.src AND k2.dst = k3.src AND
+// k3.dst = k1.src` with every endpoint in the vertex table — three hash joins, the last on two conditions
+// (PhysicalHashJoin::Execute, src/execution/operator/join/physical_hash_join.cpp:217-254; JoinHashTable::Probe +
+// ScanStructure::NextInnerJoin, src/execution/join_hashtable.cpp:304-476).  ordered adds id(v0) < id(v1) < id(v2):
+// "Friend triangles", benchmark/ldbc/queries/bi-11.sql:22-33, is
+//   gg_triangle_count('persons_of_country', 'personid', 'knows', 'k_person1id', 'k_person2id', true).
+// No planner rule recognises the cyclic chain by itself: the reference plans the closing condition as a two-condition
+// join or as a filter depending on cardinalities.
+//
+// The graph comes from GGBuildGraph — the sink / finalize machinery of every other scan, without the rowid payload,
+// or the pinned graph of these tables if the connection asked for pinned graphs.  The rows stay on the device
+// (gg_triangles, include/gg.h) and the pipeline's threads drain them together, each through its own page-locked slab.
+#include "duckdb.hpp"
+#include "duckdb/catalog/catalog.hpp"
+#include "duckdb/common/exception.hpp"
+#include "duckdb/main/client_context.hpp"
+#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
+
+#include <atomic>
+
+#include "gg_extension.hpp"
+#include "gg_operators.hpp"
+
+namespace duckdb {
+
+namespace {
+
+class TrianglesState : public GlobalSourceState {
+public:
+	~TrianglesState() override {
+		if (result) {
+			gg_result_destroy(result);
+		}
+	}
+	idx_t MaxThreads() override {
+		return max_threads;
+	}
+	gg_tri_stats stats {};
+	gg_result *result = nullptr; // the rows, in HBM (count_only: none)
+	idx_t offset = 0;            // next unclaimed row
+	bool counted = false;        // count_only: the one row went out
+	mutex lock;
+	idx_t max_threads = 1;
+};
+
+} // namespace
+
+PhysicalGGTriangles::PhysicalGGTriangles(shared_ptr<GGGraph> graph_p, bool ordered_p, bool count_only_p,
+                                         idx_t estimated_cardinality)
+    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(count_only_p), estimated_cardinality),
+      graph(move(graph_p)), ordered(ordered_p), count_only(count_only_p) {
+}
+
+vector<LogicalType> PhysicalGGTriangles::OutputTypes(bool count_only) {
+	return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT};
+}
+
+unique_ptr<GlobalSourceState> PhysicalGGTriangles::GetGlobalSourceState(ClientContext &context) const {
+	auto state = make_unique<TrianglesState>();
+	lock_guard<mutex> guard(graph->lock);
+	if (!graph->csr) {
+		throw InternalException("GG_TRIANGLES scheduled before the CSR was built");
+	}
+	GGGraph::Check(gg_triangles(graph->ctx, graph->csr, nullptr, 0, ordered ? 1 : 0, count_only ? 0 : 1, &state->stats,
+	                            count_only ? nullptr : &state->result),
+	               "gg_triangles");
+	state->max_threads = MaxValue<idx_t>(1, state->stats.rows / GGResultSlab::SLAB_ROWS);
+	return move(state);
+}
+
+unique_ptr<LocalSourceState> PhysicalGGTriangles::GetLocalSourceState(ExecutionContext &context,
+                                                                      GlobalSourceState &gstate) const {
+	return make_unique<GGResultSlab>(graph);
+}
+
+void PhysicalGGTriangles::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+                                  LocalSourceState &lstate) const {
+	auto &gstate = (TrianglesState &)gstate_p;
+	if (count_only) {
+		lock_guard<mutex> guard(gstate.lock);
+		if (gstate.counted) {
+			return;
+		}
+		gstate.counted = true;
+		FlatVector::GetData<int64_t>(chunk.data[0])[0] = (int64_t)gstate.stats.rows;
+		FlatVector::GetData<int64_t>(chunk.data[1])[0] = (int64_t)gstate.stats.digest;
+		FlatVector::GetData<int64_t>(chunk.data[2])[0] = (int64_t)gstate.stats.wedges;
+		chunk.SetCardinality(1);
+		return;
+	}
+	if (context.client.interrupted) {
+		throw InterruptException();
+	}
+	auto &slab = (GGResultSlab &)lstate;
+	if (slab.pos >= slab.rows) { // claim the next rows; the result lives as long as the global state
+		idx_t offset, want;
+		{
+			lock_guard<mutex> guard(gstate.lock);
+			if (gstate.offset >= gstate.stats.rows) {
+				return;
+			}
+			offset = gstate.offset;
+			want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, gstate.stats.rows - offset);
+			gstate.offset += want;
+		}
+		uint32_t got = 0;
+		GGGraph::Check(gg_result_fetch(gstate.result, 2, offset, (uint32_t)want, slab.Columns(3), &got),
+		               "gg_result_fetch");
+		slab.rows = got;
+		slab.pos = 0;
+		if (got == 0) {
+			return;
+		}
+	}
+	const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
+	for (idx_t c = 0; c < 3; c++) {
+		memcpy(FlatVector::GetData<int64_t>(chunk.data[c]), slab.column[c] + slab.pos, n * sizeof(int64_t));
+	}
+	slab.pos += n;
+	chunk.SetCardinality(n);
+}
+
+static unique_ptr<FunctionData> TrianglesBindInternal(vector<Value> &inputs, vector<LogicalType> &return_types,
+                                                      vector<string> &names, bool count_only) {
+	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
+	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+	const bool ordered = !inputs[5].is_null && inputs[5].GetValue<bool>();
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
+		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
+		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
+		opened.graph = GGBuildGraph(ctx, spec);
+		opened.source = make_unique<PhysicalGGTriangles>(opened.graph, ordered, count_only, 0);
+	};
+	data->parallel_result = !count_only;
+	data->description = string(ordered ? "ordered " : "") + "triangles of " + edge_table;
+	return_types = PhysicalGGTriangles::OutputTypes(count_only);
+	if (count_only) {
+		names = {"rows", "digest", "wedges"};
+	} else {
+		names = {"v0", "v1", "v2"};
+	}
+	return move(data);
+}
+
+static unique_ptr<FunctionData> TrianglesBind(ClientContext &context, vector<Value> &inputs,
+                                              unordered_map<string, Value> &named_parameters,
+                                              vector<LogicalType> &input_table_types, vector<string> &input_table_names,
+                                              vector<LogicalType> &return_types, vector<string> &names) {
+	return TrianglesBindInternal(inputs, return_types, names, false);
+}
+
+static unique_ptr<FunctionData> TriangleCountBind(ClientContext &context, vector<Value> &inputs,
+                                                  unordered_map<string, Value> &named_parameters,
+                                                  vector<LogicalType> &input_table_types,
+                                                  vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                  vector<string> &names) {
+	return TrianglesBindInternal(inputs, return_types, names, true);
+}
+
+void GGRegisterTriangleFunctions(ClientContext &context) {
+	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
+	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BOOLEAN};
+	auto rows = GGScanFunction("gg_triangles", args, TrianglesBind);
+	auto count = GGScanFunction("gg_triangle_count", args, TriangleCountBind);
+	CreateTableFunctionInfo rows_info(rows), count_info(count);
+	auto &catalog = Catalog::GetCatalog(context);
+	catalog.CreateTableFunction(context, &rows_info);
+	catalog.CreateTableFunction(context, &count_info);
+}
+
+} // namespace duckdb

@@ -55,6 +55,11 @@
  *        <- PhysicalRecursiveCTE over a UNION arm with a depth counter: rows deduplicated inside a level only
  *                                                               src/execution/operator/set/physical_recursive_cte.cpp:47-139
  *           (the friends CTE of benchmark/ldbc/queries/bi-10-shortestpath.sql:8-25 under any consumer)
+ *   gg_triangles
+ *        <- the chain of three hash joins whose last join carries two conditions (k2.dst = k3.src AND k3.dst = k1.src):
+ *           PhysicalHashJoin::Execute -> JoinHashTable::Probe + ScanStructure::NextInnerJoin
+ *                                                               physical_hash_join.cpp:217-254, join_hashtable.cpp:304-476
+ *           ("Friend triangles", benchmark/ldbc/queries/bi-11.sql:22-33)
  *
  * Conventions
  *   - every int-returning function returns GG_OK (0) or a negative GG_ERR_*; the message is
@@ -274,6 +279,40 @@ int gg_staging_clear_edges(gg_ctx *ctx);
  * gg_staging_clear_edges, stage the next, derive again with keep).  Computed on the device (hash set +
  * radix sort); *n_vertices (nullable) receives the number of distinct ids. */
 int gg_vertices_from_edges(gg_ctx *ctx, int keep_staged_vertices, uint64_t *n_vertices);
+
+/* ---- triangles (closed 3-edge walks) --------------------------------------------------------- */
+typedef struct gg_tri_stats {
+  uint64_t rows;     /* triangle rows */
+  uint64_t digest;   /* sum of the low 32 bits of the gg row hash of (a,b,c) as a 2-hop row, mod 2^32 */
+  uint64_t wedges;   /* 2-hop walks a->b->c whose closing edge was looked for */
+} gg_tri_stats;
+/* The rows of
+ *   knows k1, knows k2, knows k3 WHERE k1.dst = k2.src AND k2.dst = k3.src AND k3.dst = k1.src
+ * with every endpoint in the vertex table: a triangle row is a triple of kept edge rows e1: a->b, e2: b->c, e3: c->a,
+ * reported as (a, b, c).  The reference runs this as three hash joins, the last on two conditions
+ * (src/execution/operator/join/physical_hash_join.cpp:217-254, src/execution/join_hashtable.cpp:304-476
+ * Probe + NextInnerJoin); benchmark/ldbc/queries/bi-11.sql:22-33 is this chain under count(*).
+ * These are closed WALKS, not simple cycles: parallel edge rows multiply (a row per choice of e1, e2, e3); a self-loop
+ * a->a is the one row (a, a, a); a 2-cycle a<->b with a self-loop on a contributes (a, a, b), (a, b, a), (b, a, a) as
+ * well; and every rotation of a directed 3-cycle is a row of its own.
+ * order = 0: every row.  order = 1: only rows with id(a) < id(b) < id(c), the int64 vertex ids compared as signed
+ * integers (not the dense indices) — bi-11's filter for counting each triangle once.  On a simple undirected graph stored
+ * mirrored, order = 0 gives 6 rows per triangle and order = 1 gives 1.
+ * src_ids == NULL: every vertex may be a.  Otherwise a ranges over the list, with multiplicity; ids that are not vertices
+ * contribute nothing (as in gg_expand_khop).
+ * stats->wedges: the 2-hop walks a->b->c the call looked at — order = 0: all those of the sources; order = 1: those with
+ * id(a) < id(b) < id(c), the rest is pruned before any search.
+ * materialise == 0: count and digest only (out_result may be NULL); 64-bit counters, no size limit.
+ * materialise != 0: the rows are table 2 of *out_result — three int64 id columns a, b, c for gg_result_rows /
+ * gg_result_fetch / gg_result_digest (whose digest equals stats->digest).  Row order is unspecified, but the rows are
+ * placed by count, scan, write — no atomics-ordered append — so it is the same on every run.  2^32 rows or more fail with
+ * GG_ERR_TOO_LARGE (count them, or pass source lists).
+ * A shard CSR fails with GG_ERR_STATE, an order outside {0, 1} with GG_ERR_INVALID_ARG.  Edge rowids are not needed: a CSR
+ * built without them is accepted.  The edges' rowids, cycles longer than 3 and shards are not served.
+ * The first call on a CSR sorts a copy of its reverse rows by source (gg_bfs64_paths' copy: 4 bytes per edge, kept with
+ * the CSR); order = 1 ranks the vertex ids and filters both row sets once per call. */
+int gg_triangles(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int order, int materialise,
+                 gg_tri_stats *stats, gg_result **out_result);
 
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {
@@ -500,6 +539,10 @@ int gg_debug_reach_visited(gg_ctx *ctx, int mode /* 0 auto, 1 bitmap, 2 hash */,
  * bitmap: set_mode 2 with order_mode 2 is GG_ERR_INVALID_ARG.  Every combination must give identical rows in identical
  * order. */
 int gg_debug_level_sets(gg_ctx *ctx, int set_mode /* 0 auto, 1 bitmap, 2 hash */, int order_mode /* 0 auto, 1 sort, 2 compact */);
+/* Testing knob: gg_triangles stages at most `lds_entries` entries of a vertex's sorted in-row in LDS and searches
+ * longer in-rows in global memory (the route of hub vertices), so that route runs on small graphs; 0 restores the
+ * default, the kernel's own budget is the upper bound.  Results must not depend on it. */
+int gg_debug_triangle_tile(gg_ctx *ctx, uint32_t lds_entries /* 0: default */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
