@@ -14,20 +14,6 @@
 
 namespace duckdb {
 
-//! A slab fetch in flight: the counter was raised under the state's lock when the range was claimed; it comes
-//! down when the fetch is over — also when it ends in an exception, or the next claimer would wait for ever.
-struct FetchClaim {
-	std::atomic<idx_t> &counter;
-	FetchClaim(std::atomic<idx_t> &counter_p, bool already_counted) : counter(counter_p) {
-		if (!already_counted) {
-			counter++;
-		}
-	}
-	~FetchClaim() {
-		counter--;
-	}
-};
-
 //===--------------------------------------------------------------------===//
 // GGGraph
 //===--------------------------------------------------------------------===//
@@ -244,6 +230,64 @@ int64_t **GGResultSlab::Columns(idx_t columns) {
 		column[c] = memory + c * SLAB_ROWS;
 	}
 	return column;
+}
+
+idx_t GGResultSlab::Emit(DataChunk &chunk, idx_t first, idx_t columns) {
+	const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, rows - pos);
+	for (idx_t c = 0; c < columns; c++) {
+		memcpy(FlatVector::GetData<int64_t>(chunk.data[first + c]), column[c] + pos, n * sizeof(int64_t));
+	}
+	pos += n;
+	chunk.SetCardinality(n);
+	return n;
+}
+
+void GGResultDrain::Replace(ClientContext &context, int table_p, const produce_t &produce) {
+	// the fetches still reading the result that is about to go end without taking `lock`: the wait is bounded
+	while (fetching.load() != 0) {
+		if (context.interrupted) {
+			throw InterruptException();
+		}
+		std::this_thread::yield();
+	}
+	result.reset();
+	rows = offset = 0; // (nothing to claim if the device call throws)
+	idx_t n = 0;
+	result = produce(n);
+	Open(table_p, n);
+}
+
+bool GGResultDrain::Refill(GGResultSlab &slab, const advance_t &advance, const fetch_t &fetch) {
+	//! A slab fetch in flight: the counter was raised under the lock when the range was claimed; it comes down when the
+	//! fetch is over — also when it ends in an exception, or the next Replace would wait for ever.
+	struct InFlight {
+		std::atomic<idx_t> &counter;
+		explicit InFlight(std::atomic<idx_t> &counter_p) : counter(counter_p) {
+		}
+		~InFlight() {
+			counter--;
+		}
+	};
+	gg_result *claimed;
+	idx_t at, want;
+	{
+		lock_guard<mutex> guard(lock);
+		while (offset >= rows) {
+			if (!advance()) {
+				return false;
+			}
+		}
+		claimed = result.get();
+		at = offset;
+		want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, rows - offset);
+		offset += want;
+		slab.table = table;
+		fetching++;
+	}
+	InFlight in_flight(fetching);
+	slab.rows = fetch(claimed, slab.table, at, (uint32_t)want, slab);
+	slab.pos = 0;
+	return slab.rows > 0;
 }
 
 //===--------------------------------------------------------------------===//
@@ -491,26 +535,15 @@ SinkFinalizeType PhysicalGGEdgeSink::Finalize(Pipeline &pipeline, Event &event, 
 //! ownership-sharded one (GG_DEVICES) one per part — the pipeline's threads drain them side by side, each stream's
 //! rows crossing its own device's PCIe link.
 struct GGExpandStream {
-	~GGExpandStream() {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
 	int graph_part = 0;
 	bool by_middle = false;        // ranges are middle-vertex ranges (gg_expand_khop_mid_result), else source ranges / slices
 	gg_khop_stats stats;           // of the part that is materialised right now
-	gg_result *result = nullptr;   // walks of the current part, in HBM
 	// A result too large for the device-memory budget is produced part by part, one materialised at a time.
 	// parts[i] = [first, last): middle vertices, source vertices (all sources) or positions of the source list.
 	vector<std::pair<uint64_t, uint64_t>> parts;
 	idx_t part = 0;
-	bool started = false, done = false;
-	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result` (it may not be freed under them)
-	// scan position: (current hop length, next row of it nobody has claimed); pipeline threads claim
-	// GGResultSlab::SLAB_ROWS rows at a time under the lock and fetch them into their own slab
-	mutex lock;
-	int hop = 0;
-	idx_t offset = 0;
+	bool started = false;
+	GGResultDrain drain; // walks of the current part; its tables are the hop lengths
 };
 
 class GGExpandGlobalState : public GlobalSourceState {
@@ -588,36 +621,32 @@ static uint64_t ResultBudgetBytes() {
 	return MaxValue<uint64_t>(mb, 1) << 20;
 }
 
-//! Materialise the walks of stream.parts[stream.part] (caller holds the stream's lock or is single-threaded).
-void PhysicalGGPathExpand::MaterialisePart(GGExpandStream &stream) const {
-	if (stream.result) {
-		gg_result_destroy(stream.result);
-		stream.result = nullptr;
-	}
+//! Materialise the walks of stream.parts[stream.part] (caller holds the stream's lock; the previous part is gone).
+GGResultPtr PhysicalGGPathExpand::MaterialisePart(GGExpandStream &stream, idx_t &rows) const {
 	auto &part = graph->Part(stream.graph_part);
 	lock_guard<mutex> device_guard(part.lock);
 	const auto range = stream.parts[stream.part];
+	GGResultPtr owner;
 	if (stream.by_middle) {
 		// (no stats: the counting expansion in front of the rows would only produce a digest nobody reads here)
 		GGGraph::Check(gg_expand_khop_mid_result(part.ctx, part.csr, range.first, range.second, k_min, nullptr,
-		                                         &stream.result),
+		                                         GGResultOut(owner)),
 		               "gg_expand_khop_mid_result");
 		memset(&stream.stats, 0, sizeof(stream.stats));
 		for (int h = k_min; h <= 2; h++) {
-			GGGraph::Check(gg_result_rows(stream.result, h, &stream.stats.rows[h]), "gg_result_rows");
+			GGGraph::Check(gg_result_rows(owner.get(), h, &stream.stats.rows[h]), "gg_result_rows");
 		}
 	} else if (all_sources) {
 		GGGraph::Check(gg_expand_khop_range(part.ctx, part.csr, range.first, range.second, k_min, k_max, 1,
-		                                    &stream.stats, &stream.result),
+		                                    &stream.stats, GGResultOut(owner)),
 		               "gg_expand_khop_range");
 	} else {
 		GGGraph::Check(gg_expand_khop(part.ctx, part.csr, sources.data() + range.first, range.second - range.first,
-		                              k_min, k_max, 1, &stream.stats, &stream.result),
+		                              k_min, k_max, 1, &stream.stats, GGResultOut(owner)),
 		               "gg_expand_khop");
 	}
-	stream.hop = k_min;
-	stream.offset = 0;
-	stream.started = true;
+	rows = stream.stats.rows[k_min];
+	return owner;
 }
 
 unique_ptr<GlobalSourceState> PhysicalGGPathExpand::GetGlobalSourceState(ClientContext &context) const {
@@ -671,7 +700,7 @@ unique_ptr<GlobalSourceState> PhysicalGGPathExpand::GetGlobalSourceState(ClientC
 				total += per_part[p].rows[h];
 			}
 		}
-		state->max_threads = MaxValue<idx_t>(1, total / GGResultSlab::SLAB_ROWS);
+		state->max_threads = GGResultSlab::ThreadsFor(total);
 		return move(state);
 	}
 	if (rows_only) {
@@ -729,7 +758,7 @@ unique_ptr<GlobalSourceState> PhysicalGGPathExpand::GetGlobalSourceState(ClientC
 		}
 	}
 	state->streams.push_back(move(stream));
-	state->max_threads = MaxValue<idx_t>(1, total / GGResultSlab::SLAB_ROWS);
+	state->max_threads = GGResultSlab::ThreadsFor(total);
 	return move(state);
 }
 
@@ -796,67 +825,39 @@ void PhysicalGGPathExpand::GetData(ExecutionContext &context, DataChunk &chunk, 
 			return; // every part of every stream handed out
 		}
 		auto &stream = *gstate.streams[slab.stream];
-		idx_t offset, want;
-		gg_result *result = nullptr;
-		{
-			lock_guard<mutex> guard(stream.lock);
-			while (!stream.done) {
-				if (!stream.started) {
-					if (stream.parts.empty()) {
-						stream.done = true;
-						break;
-					}
-					MaterialisePart(stream);
+		auto &drain = stream.drain;
+		auto materialise = [&](idx_t &rows) { return MaterialisePart(stream, rows); };
+		auto advance = [&]() -> bool {
+			if (!stream.started) {
+				if (stream.parts.empty()) {
+					return false;
 				}
-				while (stream.hop <= k_max && stream.offset >= stream.stats.rows[stream.hop]) {
-					stream.hop++;
-					stream.offset = 0;
-				}
-				if (stream.hop <= k_max) {
-					break;
-				}
-				if (stream.part + 1 >= stream.parts.size()) {
-					stream.done = true;
-					break;
-				}
-				// this part is claimed completely: wait for the fetches still reading it, then replace it
-				while (stream.fetching.load() != 0) {
-					std::this_thread::yield();
-				}
-				stream.part++;
-				MaterialisePart(stream);
+				stream.started = true;
+			} else if (drain.Table() < k_max) { // the next hop-length table of this part
+				drain.Open(drain.Table() + 1, stream.stats.rows[drain.Table() + 1]);
+				return true;
+			} else if (stream.part + 1 >= stream.parts.size()) {
+				return false;
+			} else {
+				stream.part++; // this part is claimed completely
 			}
-			if (!stream.done) {
-				slab.table = stream.hop;
-				offset = stream.offset;
-				want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, stream.stats.rows[stream.hop] - stream.offset);
-				stream.offset += want;
-				result = stream.result;
-				stream.fetching++;
-			}
-		}
-		if (!result) { // this stream has nothing left: try the next one
+			drain.Replace(context.client, k_min, materialise);
+			return true;
+		};
+		auto fetch = [](gg_result *result, int hop, idx_t offset, uint32_t want, GGResultSlab &slab) {
+			uint32_t got = 0;
+			GGGraph::Check(gg_result_fetch(result, hop, offset, want, slab.Columns(hop + 1), &got), "gg_result_fetch");
+			return got;
+		};
+		if (drain.Refill(slab, advance, fetch)) {
+			exhausted = 0;
+		} else { // this stream has nothing left: try the next one
 			slab.stream = (slab.stream + 1) % n_streams;
 			exhausted++;
-			continue;
 		}
-		exhausted = 0;
-		uint32_t got = 0;
-		int rc;
-		{
-			FetchClaim claim(stream.fetching, true); // released also when slab.Columns() throws (pinned allocation)
-			rc = gg_result_fetch(result, slab.table, offset, (uint32_t)want, slab.Columns(slab.table + 1), &got);
-		}
-		GGGraph::Check(rc, "gg_result_fetch");
-		slab.rows = got;
-		slab.pos = 0;
 	}
 	const int hop = slab.table;
-	const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
-	for (int c = 0; c <= hop; c++) {
-		memcpy(FlatVector::GetData<int64_t>(chunk.data[1 + c]), slab.column[c] + slab.pos, n * sizeof(int64_t));
-	}
-	slab.pos += n;
+	const idx_t n = slab.Emit(chunk, 1, hop + 1);
 	auto hops = FlatVector::GetData<int32_t>(chunk.data[0]);
 	for (idx_t i = 0; i < n; i++) {
 		hops[i] = hop;
@@ -865,7 +866,6 @@ void PhysicalGGPathExpand::GetData(ExecutionContext &context, DataChunk &chunk, 
 		chunk.data[1 + c].SetVectorType(VectorType::CONSTANT_VECTOR);
 		ConstantVector::SetNull(chunk.data[1 + c], true);
 	}
-	chunk.SetCardinality(n);
 }
 
 //===--------------------------------------------------------------------===//
@@ -880,12 +880,7 @@ public:
 
 class GGKeyJoinOperatorState : public OperatorState {
 public:
-	~GGKeyJoinOperatorState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
-	gg_result *result = nullptr; // matches of the probe chunk in hand: (position among its valid keys, build rowid)
+	GGResultPtr result; // matches of the probe chunk in hand: (position among its valid keys, build rowid)
 	idx_t matches = 0, offset = 0;
 	vector<sel_t> valid_rows;     // position among the valid keys -> row of the probe chunk
 	vector<vector<int64_t>> scratch;
@@ -976,14 +971,13 @@ OperatorResultType PhysicalGGKeyJoin::Execute(ExecutionContext &context, DataChu
 		{
 			lock_guard<mutex> guard(graph.lock); // (device calls on one context are serialised, gg.h)
 			GGGraph::Check(gg_join_probe(graph.ctx, graph.csr, state.scratch[0].data(), state.scratch[0].size(), &matches,
-			                             &state.result),
+			                             GGResultOut(state.result)),
 			               "gg_join_probe");
 		}
 		state.matches = matches;
 		state.offset = 0;
 		if (matches == 0) {
-			gg_result_destroy(state.result);
-			state.result = nullptr;
+			state.result.reset();
 			return OperatorResultType::NEED_MORE_INPUT;
 		}
 	}
@@ -997,7 +991,7 @@ OperatorResultType PhysicalGGKeyJoin::Execute(ExecutionContext &context, DataChu
 	uint32_t n = 0;
 	{
 		lock_guard<mutex> guard(graph.lock);
-		GGGraph::Check(gg_result_fetch(state.result, 1, state.offset, STANDARD_VECTOR_SIZE, cols, &n), "gg_result_fetch");
+		GGGraph::Check(gg_result_fetch(state.result.get(), 1, state.offset, STANDARD_VECTOR_SIZE, cols, &n), "gg_result_fetch");
 	}
 	state.offset += n;
 	SelectionVector sel(STANDARD_VECTOR_SIZE);
@@ -1051,8 +1045,7 @@ OperatorResultType PhysicalGGKeyJoin::Execute(ExecutionContext &context, DataChu
 	}
 	chunk.SetCardinality(n);
 	if (state.offset >= state.matches) {
-		gg_result_destroy(state.result);
-		state.result = nullptr;
+		state.result.reset();
 		return OperatorResultType::NEED_MORE_INPUT;
 	}
 	return OperatorResultType::HAVE_MORE_OUTPUT;
@@ -1063,12 +1056,7 @@ OperatorResultType PhysicalGGKeyJoin::Execute(ExecutionContext &context, DataChu
 //===--------------------------------------------------------------------===//
 class GGFilteredGlobalState : public GlobalSourceState {
 public:
-	~GGFilteredGlobalState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
-	gg_result *result = nullptr;
+	GGResultPtr result;
 	idx_t rows = 0;
 	idx_t offset = 0;
 };
@@ -1090,15 +1078,17 @@ unique_ptr<GlobalSourceState> PhysicalGGFilteredPaths::GetGlobalSourceState(Clie
 		throw InternalException("GG_FILTERED_PATHS scheduled before both CSRs were built");
 	}
 	gg_khop_stats stats;
-	gg_result *paths = nullptr;
-	GGGraph::Check(gg_expand_khop_result(graph->ctx, graph->csr, all_sources ? nullptr : SourceIds(sources),
-	                                     all_sources ? 0 : sources.size(), hops, hops, &stats, &paths),
-	               "gg_expand_khop_result");
-	int rc = gg_result_filter_common_neighbour(graph->ctx, paths, hops, graph->filter_csr, &state->result);
-	gg_result_destroy(paths);
-	GGGraph::Check(rc, "gg_result_filter_common_neighbour");
+	{
+		GGResultPtr paths; // (gone once filtered)
+		GGGraph::Check(gg_expand_khop_result(graph->ctx, graph->csr, all_sources ? nullptr : SourceIds(sources),
+		                                     all_sources ? 0 : sources.size(), hops, hops, &stats, GGResultOut(paths)),
+		               "gg_expand_khop_result");
+		GGGraph::Check(gg_result_filter_common_neighbour(graph->ctx, paths.get(), hops, graph->filter_csr,
+		                                                 GGResultOut(state->result)),
+		               "gg_result_filter_common_neighbour");
+	}
 	uint64_t n = 0;
-	GGGraph::Check(gg_result_rows(state->result, hops + 1, &n), "gg_result_rows");
+	GGGraph::Check(gg_result_rows(state->result.get(), hops + 1, &n), "gg_result_rows");
 	state->rows = n;
 	return move(state);
 }
@@ -1116,7 +1106,7 @@ void PhysicalGGFilteredPaths::GetData(ExecutionContext &context, DataChunk &chun
 	uint32_t n = 0;
 	{
 		lock_guard<mutex> guard(graph->lock);
-		GGGraph::Check(gg_result_fetch(gstate.result, hops + 1, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n),
+		GGGraph::Check(gg_result_fetch(gstate.result.get(), hops + 1, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n),
 		               "gg_result_fetch");
 	}
 	gstate.offset += n;
@@ -1151,12 +1141,7 @@ PhysicalGGPathEdges::PhysicalGGPathEdges(shared_ptr<GGGraph> graph_p, int hops_p
 //! part — slices of the source list (all sources: of the vertex ids) expanded, handed out and freed in turn.
 class GGPathEdgesGlobalState : public GlobalSourceState {
 public:
-	~GGPathEdgesGlobalState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
-	gg_result *result = nullptr;
+	GGResultPtr result;
 	idx_t rows = 0;
 	idx_t offset = 0;
 	vector<int64_t> ids; // the sources the parts slice (all sources: every vertex id)
@@ -1166,18 +1151,15 @@ public:
 
 void PhysicalGGPathEdges::MaterialisePart(GlobalSourceState &gstate_p) const {
 	auto &state = (GGPathEdgesGlobalState &)gstate_p;
-	if (state.result) {
-		gg_result_destroy(state.result);
-		state.result = nullptr;
-	}
+	state.result.reset(); // (before the next part is made: one is resident at a time)
 	gg_khop_stats stats;
 	const auto range = state.parts[state.part];
 	const bool whole = all_sources && state.parts.size() == 1;
 	GGGraph::Check(gg_expand_khop_edges(graph->ctx, graph->csr, whole ? nullptr : state.ids.data() + range.first,
-	                                    whole ? 0 : range.second - range.first, hops, &stats, &state.result),
+	                                    whole ? 0 : range.second - range.first, hops, &stats, GGResultOut(state.result)),
 	               "gg_expand_khop_edges");
 	uint64_t n = 0;
-	GGGraph::Check(gg_result_rows(state.result, hops, &n), "gg_result_rows");
+	GGGraph::Check(gg_result_rows(state.result.get(), hops, &n), "gg_result_rows");
 	state.rows = n;
 	state.offset = 0;
 }
@@ -1255,8 +1237,8 @@ void PhysicalGGPathEdges::GetData(ExecutionContext &context, DataChunk &chunk, G
 	uint32_t n = 0, ne = 0;
 	{
 		lock_guard<mutex> guard(graph->lock);
-		GGGraph::Check(gg_result_fetch(gstate.result, hops, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n), "gg_result_fetch");
-		GGGraph::Check(gg_result_fetch_edges(gstate.result, hops, gstate.offset, STANDARD_VECTOR_SIZE, ecols, &ne),
+		GGGraph::Check(gg_result_fetch(gstate.result.get(), hops, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n), "gg_result_fetch");
+		GGGraph::Check(gg_result_fetch_edges(gstate.result.get(), hops, gstate.offset, STANDARD_VECTOR_SIZE, ecols, &ne),
 		               "gg_result_fetch_edges");
 	}
 	if (n != ne) {
@@ -1320,10 +1302,11 @@ unique_ptr<GlobalSourceState> PhysicalGGWalkEndpoints::GetGlobalSourceState(Clie
 	if (!graph->csr) {
 		throw InternalException("GG_WALK_ENDPOINTS scheduled before the CSR was built");
 	}
-	GGGraph::Check(gg_walk_endpoints(graph->ctx, graph->csr, sources.data(), sources.size(), k_max, &state->result),
+	GGGraph::Check(gg_walk_endpoints(graph->ctx, graph->csr, sources.data(), sources.size(), k_max,
+	                                 GGResultOut(state->result)),
 	               "gg_walk_endpoints");
 	uint64_t n = 0;
-	GGGraph::Check(gg_result_rows(state->result, 1, &n), "gg_result_rows");
+	GGGraph::Check(gg_result_rows(state->result.get(), 1, &n), "gg_result_rows");
 	state->rows = n;
 	return move(state);
 }
@@ -1339,7 +1322,7 @@ void PhysicalGGWalkEndpoints::GetData(ExecutionContext &context, DataChunk &chun
 	uint32_t n = 0;
 	{
 		lock_guard<mutex> guard(graph->lock);
-		GGGraph::Check(gg_result_fetch(gstate.result, 1, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n),
+		GGGraph::Check(gg_result_fetch(gstate.result.get(), 1, gstate.offset, STANDARD_VECTOR_SIZE, cols, &n),
 		               "gg_result_fetch");
 	}
 	for (int h = 1; h <= k_max; h++) {
@@ -1357,25 +1340,16 @@ void PhysicalGGWalkEndpoints::GetData(ExecutionContext &context, DataChunk &chun
 //===--------------------------------------------------------------------===//
 class GGShortestGlobalState : public GlobalSourceState {
 public:
-	~GGShortestGlobalState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
 	idx_t MaxThreads() override {
 		return max_threads;
 	}
 	vector<int64_t> uniq;            // the sources, deduplicated, in 64-lane batches
 	shared_ptr<const vector<int64_t>> vid; // vertex ids by dense index (the rows come back packed, see RunBatch)
-	idx_t batch_base = 0;            // first source of the batch whose rows are in `result`
-	gg_result *result = nullptr;     // packed (lane, distance, dense vertex) rows of the current batch, in HBM
-	idx_t rows = 0;                  // ... and how many
-	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result`
+	//! packed (lane, distance, dense vertex) rows of the current batch; its table is the batch's first source
+	GGResultDrain drain;
 	//! seed rows of sources that are not vertices of the graph (lone_sources): served once, at the end
 	vector<int64_t> lone;
-	mutex lock;
-	idx_t offset = 0; // next unclaimed row of the current batch
-	idx_t lone_offset = 0;
+	idx_t lone_offset = 0; // (under drain.lock)
 	idx_t max_threads = 1;
 };
 
@@ -1386,25 +1360,22 @@ PhysicalGGShortestPath::PhysicalGGShortestPath(shared_ptr<GGGraph> graph_p, vect
       graph(move(graph_p)), sources(move(sources_p)), max_hops(max_hops_p), lone_sources(lone_sources_p) {
 }
 
-//! Run the 64-lane BFS of the batch starting at batch_base; its reached (source, vertex, distance) rows are
+//! Run the 64-lane BFS of the batch starting at source batch_base; its reached (source, vertex, distance) rows are
 //! compacted on the device and stay there until the pipeline threads have fetched them.  One batch is
 //! resident at a time: "every person" as seeds at SF100 is 7 000 batches of up to 0.7 GB of rows each.
-void PhysicalGGShortestPath::RunBatch(GlobalSourceState &gstate_p) const {
+GGResultPtr PhysicalGGShortestPath::RunBatch(GlobalSourceState &gstate_p, idx_t batch_base, idx_t &rows) const {
 	auto &state = (GGShortestGlobalState &)gstate_p;
-	if (state.result) {
-		gg_result_destroy(state.result);
-		state.result = nullptr;
-	}
-	const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - state.batch_base);
+	const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - batch_base);
 	// one 8-byte word per row (lane << 58 | distance << 32 | dense vertex): a third of the bytes of three
 	// id columns over PCIe; the pipeline threads turn lane and dense index back into ids as they unpack
-	GGGraph::Check(gg_bfs64_pairs_packed(graph->ctx, graph->csr, state.uniq.data() + state.batch_base, n, max_hops,
-	                                     nullptr, &state.result),
+	GGResultPtr owner;
+	GGGraph::Check(gg_bfs64_pairs_packed(graph->ctx, graph->csr, state.uniq.data() + batch_base, n, max_hops, nullptr,
+	                                     GGResultOut(owner)),
 	               "gg_bfs64_pairs_packed");
-	uint64_t rows = 0;
-	GGGraph::Check(gg_result_rows(state.result, 0, &rows), "gg_result_rows");
-	state.rows = rows;
-	state.offset = 0;
+	uint64_t n_rows = 0;
+	GGGraph::Check(gg_result_rows(owner.get(), 0, &n_rows), "gg_result_rows");
+	rows = n_rows;
+	return owner;
 }
 
 unique_ptr<GlobalSourceState> PhysicalGGShortestPath::GetGlobalSourceState(ClientContext &context) const {
@@ -1435,11 +1406,11 @@ unique_ptr<GlobalSourceState> PhysicalGGShortestPath::GetGlobalSourceState(Clien
 	}
 	if (!state->uniq.empty()) {
 		state->vid = graph->VertexIds();
-		RunBatch(*state);
+		state->drain.Replace(context, 0, [&](idx_t &rows) { return RunBatch(*state, 0, rows); });
 	}
 	// the first batch's size is the only estimate there is of how much the threads will have to drain
 	const idx_t batches = (state->uniq.size() + GG_BFS_LANES - 1) / GG_BFS_LANES;
-	state->max_threads = MaxValue<idx_t>(1, state->rows * batches / GGResultSlab::SLAB_ROWS);
+	state->max_threads = GGResultSlab::ThreadsFor(state->drain.Rows() * batches);
 	return move(state);
 }
 
@@ -1456,50 +1427,35 @@ void PhysicalGGShortestPath::GetData(ExecutionContext &context, DataChunk &chunk
 		throw InterruptException();
 	}
 	if (slab.pos >= slab.rows) {
-		idx_t offset, want;
-		gg_result *result;
-		{
-			lock_guard<mutex> guard(gstate.lock);
-			while (gstate.offset >= gstate.rows) { // current batch claimed completely: run the next one
-				if (gstate.batch_base + GG_BFS_LANES >= gstate.uniq.size()) {
-					if (gstate.uniq.empty() || gstate.lone_offset >= gstate.lone.size()) {
-						return;
-					}
-					// last: the seed rows of the sources that are not vertices
-					const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, gstate.lone.size() - gstate.lone_offset);
-					for (idx_t i = 0; i < n; i++) {
-						FlatVector::GetData<int64_t>(chunk.data[0])[i] = gstate.lone[gstate.lone_offset + i];
-						FlatVector::GetData<int64_t>(chunk.data[1])[i] = gstate.lone[gstate.lone_offset + i];
-						FlatVector::GetData<int32_t>(chunk.data[2])[i] = 0;
-					}
-					gstate.lone_offset += n;
-					chunk.SetCardinality(n);
-					return;
-				}
-				while (gstate.fetching.load() != 0) { // fetches still reading the batch that is about to go
-					std::this_thread::yield();
-				}
-				gstate.batch_base += GG_BFS_LANES;
-				lock_guard<mutex> device_guard(graph->lock);
-				RunBatch(gstate);
+		auto &drain = gstate.drain;
+		auto advance = [&]() -> bool { // current batch claimed completely: run the next one
+			const idx_t next = (idx_t)drain.Table() + GG_BFS_LANES;
+			if (next < gstate.uniq.size()) {
+				// (the drain's lock stays held through the BFS on purpose: the other threads have nothing to claim
+				// until the next batch's rows exist)
+				drain.Replace(context.client, (int)next, [&](idx_t &rows) {
+					lock_guard<mutex> device_guard(graph->lock);
+					return RunBatch(gstate, next, rows);
+				});
+				return true;
 			}
-			offset = gstate.offset;
-			want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, gstate.rows - offset);
-			gstate.offset += want;
-			result = gstate.result;
-			slab.table = (int)gstate.batch_base; // lane i of these rows is source uniq[batch_base + i]
-			gstate.fetching++;
-		}
-		uint32_t got = 0;
-		int rc;
-		{
-			FetchClaim claim(gstate.fetching, true);
-			rc = gg_result_fetch(result, 0, offset, (uint32_t)want, slab.Columns(1), &got);
-		}
-		GGGraph::Check(rc, "gg_result_fetch");
-		slab.rows = got;
-		slab.pos = 0;
-		if (got == 0) {
+			// last, and still under the lock: the seed rows of the sources that are not vertices
+			const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, gstate.lone.size() - gstate.lone_offset);
+			for (idx_t i = 0; i < n; i++) {
+				FlatVector::GetData<int64_t>(chunk.data[0])[i] = gstate.lone[gstate.lone_offset + i];
+				FlatVector::GetData<int64_t>(chunk.data[1])[i] = gstate.lone[gstate.lone_offset + i];
+				FlatVector::GetData<int32_t>(chunk.data[2])[i] = 0;
+			}
+			gstate.lone_offset += n;
+			chunk.SetCardinality(n);
+			return false;
+		};
+		auto fetch = [](gg_result *result, int, idx_t offset, uint32_t want, GGResultSlab &slab) {
+			uint32_t got = 0;
+			GGGraph::Check(gg_result_fetch(result, 0, offset, want, slab.Columns(1), &got), "gg_result_fetch");
+			return got;
+		};
+		if (!drain.Refill(slab, advance, fetch)) { // (lane i of a slab's rows is source uniq[slab.table + i])
 			return;
 		}
 	}

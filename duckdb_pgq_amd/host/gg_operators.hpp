@@ -16,6 +16,9 @@
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
+// The four sources whose rows stay on the device (path expansion, triangles, the two shortest-path ones) hand them to
+// the pipeline's threads through one helper, GGResultDrain + GGResultSlab below: claim under a lock, fetch without one.
+//
 // Compiled against the reference's headers; duckdb symbols are resolved by the hosting libduckdb at
 // load time (the library is loaded as an extension: gg_duckdb_extension.cpp).
 #pragma once
@@ -80,22 +83,53 @@ idx_t GGExtractKeys(DataChunk &input, const vector<idx_t> &cols, vector<vector<i
 idx_t GGKeyColumns(DataChunk &input, const vector<idx_t> &cols, vector<vector<int64_t>> &scratch,
                    vector<const int64_t *> &keys);
 
+//! Owner of a device-resident result (gg.h): destroyed with its owner, or when another result takes its place.
+struct GGResultDestroy {
+	void operator()(gg_result *result) const {
+		gg_result_destroy(result);
+	}
+};
+typedef std::unique_ptr<gg_result, GGResultDestroy> GGResultPtr;
+//! The `gg_result **out` argument of a C-ABI call that fills `owner`: GGGraph::Check(gg_x(..., GGResultOut(owner)), ..).
+//! What the call left in the slot is the owner's when the statement ends, also when Check throws.
+class GGResultOut {
+public:
+	explicit GGResultOut(GGResultPtr &owner_p) : owner(owner_p) {
+	}
+	~GGResultOut() {
+		owner.reset(slot);
+	}
+	operator gg_result **() {
+		return &slot;
+	}
+
+private:
+	GGResultPtr &owner;
+	gg_result *slot = nullptr;
+};
+
 //! A thread's window onto a device-resident result table: up to SLAB_ROWS rows of up to GG_MAX_HOPS+1
 //! int64 columns in page-locked host memory (gg_host_alloc), refilled with one copy per column and served
 //! to the pipeline in <=1024-row DataChunks.  This is the LocalSourceState of the GG sources, so several
-//! pipeline threads drain one result concurrently, each through its own slab.
+//! pipeline threads drain one result concurrently, each through its own slab (GGResultDrain::Refill).
 class GGResultSlab : public LocalSourceState {
 public:
 	//! 2 MB per column and fetch: a result drains at 44 GB/s in copies of that size over the library's fetch lanes
 	//! (36 at 1 MB, 48 at 4 MB, 51 at 8 MB — scripts/bench_fetch.py, profiles/r04_bench_fetch.txt; 22-29 GB/s before
 	//! the lanes) against twice / four times the page-locked memory per thread
 	static constexpr idx_t SLAB_ROWS = 1u << 18;
+	//! pipeline threads worth starting on a result of `rows` rows: one per slab of it
+	static idx_t ThreadsFor(idx_t rows) {
+		return MaxValue<idx_t>(1, rows / SLAB_ROWS);
+	}
 
 	explicit GGResultSlab(shared_ptr<GGGraph> graph);
 	~GGResultSlab() override;
 
 	//! make room for `columns` columns; returns the column base pointers
 	int64_t **Columns(idx_t columns);
+	//! serve the next <=1024 rows: the first `columns` columns as they are, into chunk.data[first ..]; sets the cardinality
+	idx_t Emit(DataChunk &chunk, idx_t first, idx_t columns);
 
 	shared_ptr<GGGraph> graph;
 	int64_t *memory = nullptr;
@@ -103,6 +137,57 @@ public:
 	int64_t *column[GG_MAX_HOPS + 1];
 	idx_t rows = 0, pos = 0; // filled rows, next row to serve
 	int table = 0;           // which table of the result the slab holds (hop length / batch)
+};
+
+//! The scan position the pipeline threads of a source share, and the one place where the protocol between them is
+//! written down: the result that stands in HBM right now, the table of it that is being handed out (hop length /
+//! batch), and the next row of that table nobody has claimed.
+//!   - A thread claims up to SLAB_ROWS rows under `lock` and fetches them into its own slab with NO lock held (the
+//!     library's fetch lanes rely on that); `fetching` counts the claims whose fetch has not ended.  It is raised under
+//!     the lock at claim time and lowered on every exit from the fetch, an exception included.
+//!   - The result is replaced only under `lock` and only once `fetching` is 0: never under a fetch that reads it.
+//!   - Lock order: `lock`, then GGGraph::lock.  `lock` stays held through the device call that makes the next part or
+//!     batch — the other threads have nothing to claim until its rows exist.
+//!   - The slab carries the table it was claimed from (GGResultSlab::table): rows are emitted by that tag, never by
+//!     the table the drain has moved on to.
+class GGResultDrain {
+public:
+	//! the device call that makes the next result (taking the GGGraph::lock it needs) and says how many rows its first
+	//! table has
+	typedef std::function<GGResultPtr(idx_t &rows)> produce_t;
+	//! called under `lock` when the current table is claimed completely: move to the next table (Open), part or batch
+	//! (Replace); false: nothing is left
+	typedef std::function<bool()> advance_t;
+	//! copies rows [offset, offset + want) of `table` into the slab (slab.Columns(n) in here: a pinned allocation that
+	//! throws must not leave `fetching` raised); returns the rows copied
+	typedef std::function<uint32_t(gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab)> fetch_t;
+
+	//! Caller holds `lock` (or is single-threaded).  Waits for the fetches in flight (polling the interrupt flag),
+	//! destroys the current result — one is resident at a time — and installs the one `produce` makes, open at `table`.
+	void Replace(ClientContext &context, int table, const produce_t &produce);
+	//! Caller holds `lock`.  Another table of the same result: hand out its `rows` rows from the first.
+	void Open(int table_p, idx_t rows_p) {
+		table = table_p;
+		rows = rows_p;
+		offset = 0;
+	}
+	//! Claim the next rows and fetch them into the slab; false: the slab has no rows (nothing is left to claim).
+	bool Refill(GGResultSlab &slab, const advance_t &advance, const fetch_t &fetch);
+
+	int Table() const {
+		return table;
+	}
+	idx_t Rows() const {
+		return rows;
+	}
+
+	std::mutex lock;
+
+private:
+	GGResultPtr result;              // in HBM
+	int table = 0;                   // the table of it being handed out
+	idx_t rows = 0, offset = 0;      // rows of that table, next unclaimed one
+	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result` (it may not be freed under them)
 };
 
 class PhysicalGGVertexSink : public PhysicalOperator {
@@ -185,7 +270,7 @@ public:
 
 	static vector<LogicalType> OutputTypes(int k_max, bool count_only);
 	//! expand the current part of a stream of a result that is produced part by part (see GetGlobalSourceState)
-	void MaterialisePart(GGExpandStream &stream) const;
+	GGResultPtr MaterialisePart(GGExpandStream &stream, idx_t &rows) const;
 	void PlanMiddleParts(GGExpandStream &stream, GGGraph &part, const gg_khop_stats &stats) const;
 
 	shared_ptr<GGGraph> graph;
@@ -365,8 +450,9 @@ public:
 	PhysicalGGShortestPath(shared_ptr<GGGraph> graph, vector<int64_t> sources, int max_hops,
 	                       idx_t estimated_cardinality, bool lone_sources = false);
 
-	//! BFS of the next 64-source batch (batches run one at a time, when the previous one is drained)
-	void RunBatch(GlobalSourceState &gstate) const;
+	//! BFS of the 64-source batch starting at source `batch_base` (batches run one at a time, when the previous one
+	//! is drained); caller holds graph->lock
+	GGResultPtr RunBatch(GlobalSourceState &gstate, idx_t batch_base, idx_t &rows) const;
 
 	shared_ptr<GGGraph> graph;
 	vector<int64_t> sources;
@@ -400,8 +486,9 @@ public:
 	                           idx_t estimated_cardinality);
 	static vector<LogicalType> OutputTypes();
 
-	//! BFS + trace of the next batch (batches run one at a time, when the previous one is drained)
-	void RunBatch(GlobalSourceState &gstate) const;
+	//! BFS + trace of batch `batch` (batches run one at a time, when the previous one is drained); caller holds
+	//! graph->lock
+	GGResultPtr RunBatch(GlobalSourceState &gstate, idx_t batch, idx_t &rows) const;
 
 	shared_ptr<GGGraph> graph;
 	vector<int64_t> src, dst;

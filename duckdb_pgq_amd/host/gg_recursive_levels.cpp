@@ -89,11 +89,11 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveLevels::GetGlobalSourceState(Cl
 		seeds[i] = pairs[i].second;
 	}
 	lock_guard<std::mutex> graph_guard(graph->lock);
-	gg_result *res = nullptr;
+	GGResultPtr owner;
 	GGGraph::Check(gg_level_sets(graph->ctx, graph->csr, seeds.data(), seed_class.data(), seeds.size(),
-	                             (uint32_t)state->class_row.size(), input->max_levels, &res),
+	                             (uint32_t)state->class_row.size(), input->max_levels, GGResultOut(owner)),
 	               "gg_level_sets");
-	std::unique_ptr<gg_result, void (*)(gg_result *)> owner(res, gg_result_destroy);
+	gg_result *res = owner.get();
 	GGFetchPairRows(res, gg_level_sets_levels, gg_level_sets_fetch, "gg_level_sets", state->row_class, state->vertex,
 	                state->level_end);
 	for (idx_t l = 1; l < state->level_end.size(); l++) {

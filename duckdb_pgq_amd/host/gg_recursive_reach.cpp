@@ -207,11 +207,11 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveReach::GetGlobalSourceState(Cli
 		}
 	}
 	lock_guard<std::mutex> graph_guard(graph->lock);
-	gg_result *res = nullptr;
+	GGResultPtr owner;
 	GGGraph::Check(gg_reach_closure(graph->ctx, graph->csr, seeds.data(), seed_class.data(), seen.data(), seeds.size(),
-	                                (uint32_t)state->class_row.size(), &res),
+	                                (uint32_t)state->class_row.size(), GGResultOut(owner)),
 	               "gg_reach_closure");
-	std::unique_ptr<gg_result, void (*)(gg_result *)> owner(res, gg_result_destroy);
+	gg_result *res = owner.get();
 	vector<uint64_t> per_level;
 	GGFetchPairRows(res, gg_reach_closure_levels, gg_reach_closure_fetch, "gg_reach_closure", state->row_class,
 	                state->vertex, per_level);

@@ -182,10 +182,11 @@ unique_ptr<GlobalSourceState> PhysicalGGRecursiveWalks::GetGlobalSourceState(Cli
 		}
 	}
 	lock_guard<std::mutex> guard(graph->lock);
-	gg_result *res = nullptr;
-	GGGraph::Check(gg_walk_closure(graph->ctx, graph->csr, seeds.data(), seeds.size(), input->max_levels, &res),
+	GGResultPtr owner;
+	GGGraph::Check(gg_walk_closure(graph->ctx, graph->csr, seeds.data(), seeds.size(), input->max_levels,
+	                               GGResultOut(owner)),
 	               "gg_walk_closure");
-	std::unique_ptr<gg_result, void (*)(gg_result *)> owner(res, gg_result_destroy);
+	gg_result *res = owner.get();
 	int n_levels = 0;
 	GGGraph::Check(gg_walk_closure_levels(res, nullptr, 0, &n_levels), "gg_walk_closure_levels");
 	vector<uint64_t> per_level(MaxValue<int>(n_levels, 1));

@@ -8,14 +8,12 @@
 // predecessor with the smallest vertex-table position, among parallel edges the one appended first).
 //
 // Pairs are grouped by source, 64 distinct sources to a batch, in the order the sources first occur; one batch's rows are
-// resident at a time and the pipeline's threads drain them together, each through its own page-locked slab — the
-// protocol of PhysicalGGShortestPath.  Rows of one pair arrive in step order inside a slab, pairs in no promised order.
+// resident at a time and the pipeline's threads drain them together, each through its own page-locked slab
+// (GGResultDrain, gg_operators.hpp).  Rows of one pair arrive in step order inside a slab, pairs in no promised order.
 #include "duckdb.hpp"
 #include "duckdb/common/exception.hpp"
 #include "duckdb/main/client_context.hpp"
 
-#include <atomic>
-#include <thread>
 #include <unordered_map>
 
 #include "gg_extension.hpp"
@@ -27,34 +25,14 @@ namespace {
 
 class ShortestPathRowsState : public GlobalSourceState {
 public:
-	~ShortestPathRowsState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
 	idx_t MaxThreads() override {
 		return max_threads;
 	}
 	vector<int64_t> uniq;            // distinct sources, in first-occurrence order; batch b holds uniq[64 b ..]
 	vector<vector<idx_t>> members;   // per batch: the pairs (indices into src / dst) of its sources, ascending
 	vector<vector<uint32_t>> lanes;  // per batch and member: the source's lane
-	idx_t batch = 0;                 // the batch whose rows are in `result`
-	gg_result *result = nullptr;     // its path rows, in HBM
-	idx_t rows = 0;                  // ... and how many
-	idx_t offset = 0;                // next unclaimed row of the current batch
-	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result`
-	mutex lock;
+	GGResultDrain drain;             // the path rows of the current batch; its table is the batch
 	idx_t max_threads = 1;
-};
-
-//! a fetch in flight on the current batch's result (the batch is not replaced under it)
-struct FetchGuard {
-	std::atomic<idx_t> &counter;
-	explicit FetchGuard(std::atomic<idx_t> &counter_p) : counter(counter_p) {
-	}
-	~FetchGuard() {
-		counter--;
-	}
 };
 
 } // namespace
@@ -71,28 +49,25 @@ vector<LogicalType> PhysicalGGShortestPathRows::OutputTypes() {
 	return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER, LogicalType::BIGINT, LogicalType::BIGINT};
 }
 
-//! Trace the pairs of batch state.batch; the rows stay on the device until the pipeline threads have fetched them.
-void PhysicalGGShortestPathRows::RunBatch(GlobalSourceState &gstate_p) const {
+//! Trace the pairs of a batch; the rows stay on the device until the pipeline threads have fetched them.
+GGResultPtr PhysicalGGShortestPathRows::RunBatch(GlobalSourceState &gstate_p, idx_t batch, idx_t &rows) const {
 	auto &state = (ShortestPathRowsState &)gstate_p;
-	if (state.result) {
-		gg_result_destroy(state.result);
-		state.result = nullptr;
-	}
-	const idx_t base = state.batch * GG_BFS_LANES;
+	const idx_t base = batch * GG_BFS_LANES;
 	const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - base);
-	auto &members = state.members[state.batch];
+	auto &members = state.members[batch];
 	vector<int64_t> targets(members.size());
 	for (idx_t i = 0; i < members.size(); i++) {
 		targets[i] = dst[members[i]];
 	}
+	GGResultPtr owner;
 	GGGraph::Check(gg_bfs64_paths(graph->ctx, graph->csr, state.uniq.data() + base, n, max_hops,
-	                              state.lanes[state.batch].data(), targets.data(), targets.size(), 1, nullptr,
-	                              &state.result),
+	                              state.lanes[batch].data(), targets.data(), targets.size(), 1, nullptr,
+	                              GGResultOut(owner)),
 	               "gg_bfs64_paths");
-	uint64_t rows = 0;
-	GGGraph::Check(gg_bfs64_paths_rows(state.result, &rows), "gg_bfs64_paths_rows");
-	state.rows = rows;
-	state.offset = 0;
+	uint64_t n_rows = 0;
+	GGGraph::Check(gg_bfs64_paths_rows(owner.get(), &n_rows), "gg_bfs64_paths_rows");
+	rows = n_rows;
+	return owner;
 }
 
 unique_ptr<GlobalSourceState> PhysicalGGShortestPathRows::GetGlobalSourceState(ClientContext &context) const {
@@ -120,10 +95,10 @@ unique_ptr<GlobalSourceState> PhysicalGGShortestPathRows::GetGlobalSourceState(C
 		state->lanes[at / GG_BFS_LANES].push_back((uint32_t)(at % GG_BFS_LANES));
 	}
 	if (!state->members.empty()) {
-		RunBatch(*state);
+		state->drain.Replace(context, 0, [&](idx_t &rows) { return RunBatch(*state, 0, rows); });
 	}
 	// the first batch's size is the only estimate there is of how much the threads will have to drain
-	state->max_threads = MaxValue<idx_t>(1, state->rows * state->members.size() / GGResultSlab::SLAB_ROWS);
+	state->max_threads = GGResultSlab::ThreadsFor(state->drain.Rows() * state->members.size());
 	return move(state);
 }
 
@@ -140,50 +115,33 @@ void PhysicalGGShortestPathRows::GetData(ExecutionContext &context, DataChunk &c
 		throw InterruptException();
 	}
 	if (slab.pos >= slab.rows) {
-		idx_t offset, want;
-		gg_result *result;
-		{
-			lock_guard<mutex> guard(gstate.lock);
-			while (gstate.offset >= gstate.rows) { // current batch claimed completely: run the next one
-				if (gstate.batch + 1 >= gstate.members.size()) {
-					return;
-				}
-				if (context.client.interrupted) {
-					throw InterruptException();
-				}
-				// Fetches still reading the batch that is about to go: they end without taking this lock, so the wait
-				// is bounded.  The lock stays held through RunBatch on purpose — the other threads have nothing to
-				// claim until the next batch's rows exist (as in PhysicalGGShortestPath).
-				while (gstate.fetching.load() != 0) {
-					if (context.client.interrupted) {
-						throw InterruptException();
-					}
-					std::this_thread::yield();
-				}
-				gstate.batch++;
-				lock_guard<mutex> device_guard(graph->lock);
-				RunBatch(gstate);
+		auto &drain = gstate.drain;
+		auto advance = [&]() -> bool { // current batch claimed completely: run the next one
+			const idx_t next = (idx_t)drain.Table() + 1;
+			if (next >= gstate.members.size()) {
+				return false;
 			}
-			offset = gstate.offset;
-			want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, gstate.rows - offset);
-			gstate.offset += want;
-			result = gstate.result;
-			slab.table = (int)gstate.batch; // pair i of these rows is members[batch][i]
-			gstate.fetching++;
-		}
-		uint32_t got = 0;
-		int rc;
-		{
-			FetchGuard claim(gstate.fetching);
+			if (context.client.interrupted) {
+				throw InterruptException();
+			}
+			// (the drain's lock stays held through RunBatch on purpose: the other threads have nothing to claim until
+			// the next batch's rows exist)
+			drain.Replace(context.client, (int)next, [&](idx_t &rows) {
+				lock_guard<mutex> device_guard(graph->lock);
+				return RunBatch(gstate, next, rows);
+			});
+			return true;
+		};
+		auto fetch = [](gg_result *result, int, idx_t offset, uint32_t want, GGResultSlab &slab) {
 			// columns 0..2: pair, vertex, edge rowid; column 3's memory holds the int32 steps
 			auto columns = slab.Columns(4);
-			rc = gg_bfs64_paths_fetch(result, offset, (uint32_t)want, columns[0], (int32_t *)columns[3], columns[1],
-			                          columns[2], &got);
-		}
-		GGGraph::Check(rc, "gg_bfs64_paths_fetch");
-		slab.rows = got;
-		slab.pos = 0;
-		if (got == 0) {
+			uint32_t got = 0;
+			GGGraph::Check(gg_bfs64_paths_fetch(result, offset, want, columns[0], (int32_t *)columns[3], columns[1],
+			                                    columns[2], &got),
+			               "gg_bfs64_paths_fetch");
+			return got;
+		};
+		if (!drain.Refill(slab, advance, fetch)) { // (pair i of a slab's rows is members[slab.table][i])
 			return;
 		}
 	}

@@ -16,14 +16,13 @@
 //
 // The graph comes from GGBuildGraph — the sink / finalize machinery of every other scan, without the rowid payload,
 // or the pinned graph of these tables if the connection asked for pinned graphs.  The rows stay on the device
-// (gg_triangles, include/gg.h) and the pipeline's threads drain them together, each through its own page-locked slab.
+// (gg_triangles, include/gg.h) and the pipeline's threads drain them together, each through its own page-locked slab
+// (GGResultDrain, gg_operators.hpp: one result, one table).
 #include "duckdb.hpp"
 #include "duckdb/catalog/catalog.hpp"
 #include "duckdb/common/exception.hpp"
 #include "duckdb/main/client_context.hpp"
 #include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
-#include <atomic>
 
 #include "gg_extension.hpp"
 #include "gg_operators.hpp"
@@ -34,19 +33,12 @@ namespace {
 
 class TrianglesState : public GlobalSourceState {
 public:
-	~TrianglesState() override {
-		if (result) {
-			gg_result_destroy(result);
-		}
-	}
 	idx_t MaxThreads() override {
 		return max_threads;
 	}
 	gg_tri_stats stats {};
-	gg_result *result = nullptr; // the rows, in HBM (count_only: none)
-	idx_t offset = 0;            // next unclaimed row
-	bool counted = false;        // count_only: the one row went out
-	mutex lock;
+	GGResultDrain drain;  // the rows (count_only: none)
+	bool counted = false; // count_only: the one row went out (under drain.lock)
 	idx_t max_threads = 1;
 };
 
@@ -68,10 +60,16 @@ unique_ptr<GlobalSourceState> PhysicalGGTriangles::GetGlobalSourceState(ClientCo
 	if (!graph->csr) {
 		throw InternalException("GG_TRIANGLES scheduled before the CSR was built");
 	}
-	GGGraph::Check(gg_triangles(graph->ctx, graph->csr, nullptr, 0, ordered ? 1 : 0, count_only ? 0 : 1, &state->stats,
-	                            count_only ? nullptr : &state->result),
-	               "gg_triangles");
-	state->max_threads = MaxValue<idx_t>(1, state->stats.rows / GGResultSlab::SLAB_ROWS);
+	state->drain.Replace(context, 2, [&](idx_t &rows) {
+		GGResultPtr owner;
+		GGGraph::Check(gg_triangles(graph->ctx, graph->csr, nullptr, 0, ordered ? 1 : 0, count_only ? 0 : 1,
+		                            &state->stats,
+		                            count_only ? nullptr : static_cast<gg_result **>(GGResultOut(owner))),
+		               "gg_triangles");
+		rows = count_only ? 0 : state->stats.rows;
+		return owner;
+	});
+	state->max_threads = GGResultSlab::ThreadsFor(state->stats.rows);
 	return move(state);
 }
 
@@ -84,7 +82,7 @@ void PhysicalGGTriangles::GetData(ExecutionContext &context, DataChunk &chunk, G
                                   LocalSourceState &lstate) const {
 	auto &gstate = (TrianglesState &)gstate_p;
 	if (count_only) {
-		lock_guard<mutex> guard(gstate.lock);
+		lock_guard<mutex> guard(gstate.drain.lock);
 		if (gstate.counted) {
 			return;
 		}
@@ -99,32 +97,17 @@ void PhysicalGGTriangles::GetData(ExecutionContext &context, DataChunk &chunk, G
 		throw InterruptException();
 	}
 	auto &slab = (GGResultSlab &)lstate;
-	if (slab.pos >= slab.rows) { // claim the next rows; the result lives as long as the global state
-		idx_t offset, want;
-		{
-			lock_guard<mutex> guard(gstate.lock);
-			if (gstate.offset >= gstate.stats.rows) {
-				return;
-			}
-			offset = gstate.offset;
-			want = MinValue<idx_t>(GGResultSlab::SLAB_ROWS, gstate.stats.rows - offset);
-			gstate.offset += want;
-		}
-		uint32_t got = 0;
-		GGGraph::Check(gg_result_fetch(gstate.result, 2, offset, (uint32_t)want, slab.Columns(3), &got),
-		               "gg_result_fetch");
-		slab.rows = got;
-		slab.pos = 0;
-		if (got == 0) {
+	if (slab.pos >= slab.rows) {
+		auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
+			uint32_t got = 0;
+			GGGraph::Check(gg_result_fetch(result, table, offset, want, slab.Columns(3), &got), "gg_result_fetch");
+			return got;
+		};
+		if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
 			return;
 		}
 	}
-	const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
-	for (idx_t c = 0; c < 3; c++) {
-		memcpy(FlatVector::GetData<int64_t>(chunk.data[c]), slab.column[c] + slab.pos, n * sizeof(int64_t));
-	}
-	slab.pos += n;
-	chunk.SetCardinality(n);
+	slab.Emit(chunk, 0, 3);
 }
 
 static unique_ptr<FunctionData> TrianglesBindInternal(vector<Value> &inputs, vector<LogicalType> &return_types,
