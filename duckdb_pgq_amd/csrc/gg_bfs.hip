@@ -576,7 +576,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
     }
     launched = upto;
     GG_HIP(hipMemcpyAsync(host_steps.data(), steps, (size_t)(launched + 1) * sizeof(BfsStep), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
+    GG_TRY(sync_checked(ctx));
     // level L ran iff the frontier it started from (steps[L - 1]) was not empty
     int ran = 0;
     while (ran < launched && host_steps[ran].n_active != 0) ran++;
@@ -616,9 +616,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
       GG_LAUNCH(ctx, "bfs_pairs_fill", (k_bfs_pairs_fill<DistT>), dim3(vgrid), dim3(256), 0, (const DistT *)dist8, V, n_src,
                 (const uint32_t *)counts, (const int64_t *)ids_dev, (const int64_t *)csr->vid, pairs->cols[2][0],
                 pairs->cols[2][1], pairs->cols[2][2]);
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipStreamSynchronize(s));
-    GG_TRY(scan_error_test(ctx));
+    GG_TRY(sync_checked(ctx));
     for (int c = 0; c < ncols; c++) ctx->keep(pairs->cols[table][c]);
     pairs->rows[table] = reached;
   }
@@ -631,7 +629,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
     GG_LAUNCH(ctx, "bfs_widen", (k_bfs_widen<DistT>), dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0,
               (const DistT *)dist8, V, n_src, (const uint32_t *)dst_dense, n_out, out_dev);
     GG_HIP(hipMemcpyAsync(out_dist, out_dev, (uint64_t)n_src * n_out * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
+    GG_TRY(sync_checked(ctx));
   }
   if (stats) *stats = st;
   return GG_OK;
@@ -792,9 +790,7 @@ static int ensure_push_in(gg_ctx *ctx, gg_csr *csr) {
   if (n)
     GG_LAUNCH(ctx, "pin_fill", k_pin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr, csr->rrow, n, cnt,
               pin_nbr);
-  GG_TRY(scan_error_fetch(ctx));
-  GG_HIP(hipStreamSynchronize(s));
-  GG_TRY(scan_error_test(ctx));
+  GG_TRY(sync_checked(ctx));
   ctx->dev_free(cnt);
   csr->pin_off = pin_off;
   csr->pin_nbr = pin_nbr;
@@ -870,7 +866,9 @@ extern "C" void gg_bfs_sharded_end(gg_bfs_run *run) {
   if (!run) return;
   gg_ctx *ctx = run->ctx;
   (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
+  // (a teardown has nobody to report to: a scan error still pending here is cleared and dropped on purpose, so
+  // that it does not fail the next, unrelated call)
+  (void)sync_checked(ctx);
   for (void *p : {(void *)run->ids_dev, (void *)run->front, (void *)run->next, (void *)run->seen, (void *)run->dist8,
                   (void *)run->acc, (void *)run->lv})
     ctx->dev_free(p);
@@ -920,7 +918,7 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
   if (csr->V)
     GG_LAUNCH(ctx, "bfs_seed", (k_bfs_seed<uint8_t>), dim3(1), dim3(64), 0, src_dense, n_src, csr->off, run->front,
               run->seen, run->dist8, run->lv, (const int64_t *)csr->vid, (uint32_t)csr->part, (uint32_t)csr->n_parts);
-  GG_HIP(hipStreamSynchronize(s));
+  GG_TRY(sync_checked(ctx));
   *out = run.release();
   return GG_OK;
 }
@@ -959,11 +957,9 @@ extern "C" int gg_bfs_sharded_expand(gg_bfs_run *run, void **next_words_dev, uin
               run->lv + 1, E_rev, run->front, run->next, run->acc, run->seen, V, run->level, csr->off, csr->roff, csr->rnbr,
               run->dist8, run->lv, ugrid);
   }
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, run->lv, 2 * sizeof(BfsLevel), hipMemcpyDeviceToHost, s));
-  GG_HIP(hipStreamSynchronize(s));  // the words are complete in memory: the caller's collective may read them
-  BfsLevel h, st;
-  memcpy(&h, ctx->pin_scratch, sizeof(h));
-  memcpy(&st, (const char *)ctx->pin_scratch + sizeof(h), sizeof(st));
+  BfsLevel lv[2];  // synchronises: the words are complete in memory, the caller's collective may read them
+  GG_TRY(read_back(ctx, {{run->lv, sizeof(lv), lv}}));
+  const BfsLevel &h = lv[0], &st = lv[1];
   if (V) (st.te * GG_BFS_PULL_FACTOR <= csr->E_rev ? run->levels_push : run->levels_pull)++;
   if (next_words_dev) *next_words_dev = run->next;
   if (n_words) *n_words = V;
@@ -987,8 +983,7 @@ extern "C" int gg_bfs_sharded_words(gg_bfs_run *run, uint64_t *host_words, int w
     GG_HIP(hipMemcpyAsync(run->next, host_words, bytes, hipMemcpyHostToDevice, ctx->stream));
   else
     GG_HIP(hipMemcpyAsync(host_words, run->next, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  return GG_OK;
+  return sync_checked(ctx);
 }
 
 extern "C" int gg_bfs_sharded_commit(gg_bfs_run *run) {
@@ -1006,23 +1001,16 @@ extern "C" int gg_bfs_sharded_pairs(gg_bfs_run *run, gg_result **out_result) {
   gg_csr *csr = run->csr;
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   const uint64_t V = csr->V;
   ResultOwner res = make_result(ctx, 2, 2);
   if (V) {
     uint32_t *counts = nullptr;
-    uint64_t *total = nullptr;
+    uint64_t rows = 0;
     GG_TRY(ctx->dev_alloc((void **)&counts, V * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
     const unsigned vgrid = (unsigned)((V + 255) / 256);
     GG_LAUNCH(ctx, "bfs_pairs_count", (k_bfs_pairs_count<uint8_t>), dim3(vgrid), dim3(256), 0,
               (const uint8_t *)run->dist8, V, run->n_src, counts);
-    GG_TRY(scan_exclusive_u32(ctx, counts, counts, V, total));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipStreamSynchronize(s));
-    GG_TRY(scan_error_test(ctx));
-    const uint64_t rows = ctx->pin_scratch[0];
+    GG_TRY(scan_total_u32(ctx, counts, counts, V, &rows));
     if (rows) {
       for (int c = 0; c < 3; c++) GG_TRY(ctx->dev_alloc((void **)&res->cols[2][c], rows * sizeof(int64_t)));
       GG_LAUNCH(ctx, "bfs_pairs_fill", (k_bfs_pairs_fill<uint8_t>), dim3(vgrid), dim3(256), 0, (const uint8_t *)run->dist8,
@@ -1032,7 +1020,7 @@ extern "C" int gg_bfs_sharded_pairs(gg_bfs_run *run, gg_result **out_result) {
       res->rows[2] = rows;
     }
   }
-  GG_HIP(hipStreamSynchronize(s));
+  GG_TRY(sync_checked(ctx));
   *out_result = res.release();
   return GG_OK;
 }
@@ -1058,10 +1046,9 @@ extern "C" int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
   if (V && n_src) {
     const uint64_t words = (V + 31) / 32;
     uint32_t *dense = nullptr, *bits = nullptr, *counts = nullptr;
-    uint64_t *total = nullptr;
+    uint64_t rows = 0;
     GG_TRY(ctx->dev_alloc((void **)&bits, (uint64_t)(k_max + 1) * words * sizeof(uint32_t)));
     GG_TRY(ctx->dev_alloc((void **)&counts, V * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
     GG_HIP(hipMemsetAsync(bits, 0, (uint64_t)(k_max + 1) * words * sizeof(uint32_t), s));
     GG_TRY(upload_ids(ctx, csr, src_ids, n_src, &dense));
     GG_LAUNCH(ctx, "set_seed", k_set_seed, dim3((unsigned)((n_src + 255) / 256)), dim3(256), 0, (const uint32_t *)dense, n_src,
@@ -1072,17 +1059,12 @@ extern "C" int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
                 (const uint32_t *)(bits + (uint64_t)(h - 1) * words), bits + (uint64_t)h * words, V);
     GG_LAUNCH(ctx, "endpoint_count", k_endpoint_count, dim3(vgrid), dim3(256), 0, (const uint32_t *)bits, words, k_max, V,
               counts);
-    GG_TRY(scan_exclusive_u32(ctx, counts, counts, V, total));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipStreamSynchronize(s));
-    GG_TRY(scan_error_test(ctx));
-    const uint64_t rows = ctx->pin_scratch[0];
+    GG_TRY(scan_total_u32(ctx, counts, counts, V, &rows));
     if (rows) {
       for (int c = 0; c < 2; c++) GG_TRY(ctx->dev_alloc((void **)&res->cols[1][c], rows * sizeof(int64_t)));
       GG_LAUNCH(ctx, "endpoint_fill", k_endpoint_fill, dim3(vgrid), dim3(256), 0, (const uint32_t *)bits, words, k_max, V,
                 (const uint32_t *)counts, (const int64_t *)csr->vid, res->cols[1][0], res->cols[1][1]);
-      GG_HIP(hipStreamSynchronize(s));
+      GG_TRY(sync_checked(ctx));
       for (int c = 0; c < 2; c++) ctx->keep(res->cols[1][c]);
       res->rows[1] = rows;
     }

@@ -58,7 +58,9 @@ __global__ __launch_bounds__(XT) void k_closure_expand(const uint32_t *__restric
 // rows of one level -> the result's int64 columns at their offset
 __global__ __launch_bounds__(256) void k_closure_emit(const uint2 *__restrict__ rows, uint64_t n,
                                                       const int64_t *__restrict__ eid, const uint32_t *__restrict__ epos,
-                                                      int64_t *__restrict__ seed_out, int64_t *__restrict__ rowid_out) {
+                                                      int64_t *__restrict__ seed_out, int64_t *__restrict__ rowid_out,
+                                                      const unsigned long long *__restrict__ err) {
+  if (*err) return;  // a level's rows were placed by the offsets of a chained scan: not valid once one gave up
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
     const uint2 row = rows[r];
     seed_out[r] = (int64_t)row.x;
@@ -91,19 +93,12 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
   const uint2 *prow = nullptr;
   uint64_t n_parent = n_seeds;
   for (int level = 1; n_parent > 0 && (max_levels < 0 || level <= max_levels); level++) {
-    uint64_t *foff = nullptr, *total = nullptr;
+    uint64_t *foff = nullptr, M = 0;
     GG_TRY(ctx->dev_alloc((void **)&foff, (n_parent + 1) * sizeof(uint64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
     const uint32_t *dense = level == 1 ? seed_dense : nullptr;
     GG_LAUNCH(ctx, "closure_deg", k_closure_deg, stride_grid(ctx, n_parent), dim3(256), 0, csr->off, csr->nbr, dense,
               prow, n_parent, foff);
-    GG_TRY(scan_exclusive_u64(ctx, foff, foff, n_parent, total));
-    GG_HIP(hipMemcpyAsync(foff + n_parent, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    const uint64_t M = ctx->pin_scratch[0];
-    GG_TRY(scan_error_test(ctx));
+    GG_TRY(offsets_from_deg(ctx, foff, n_parent, &M));
     if (M == 0) break;
     if (M >= (1ull << 32)) {
       set_error("gg_walk_closure: level %d holds %llu walks (2^32 or more)", level, (unsigned long long)M);
@@ -123,7 +118,6 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
     GG_LAUNCH(ctx, "closure_expand", k_closure_expand, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, dense,
               prow, foff, n_parent, M, tile_entry, rows);
     ctx->dev_free(tile_entry);
-    ctx->dev_free(total);
     ctx->dev_free(foff);
     levels.push_back(rows);
     res->level_rows.push_back(M);
@@ -141,10 +135,10 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
   for (size_t l = 0; l < levels.size(); l++) {
     const uint64_t m = res->level_rows[l];
     GG_LAUNCH(ctx, "closure_emit", k_closure_emit, stride_grid(ctx, m), dim3(256), 0, levels[l], m, csr->eid, csr->epos,
-              res->walk_seed + at, res->walk_rowid + at);
+              res->walk_seed + at, res->walk_rowid + at, (const unsigned long long *)ctx->dev_err);
     at += m;
   }
-  GG_HIP(hipStreamSynchronize(ctx->stream));
+  GG_TRY(sync_checked(ctx));
   *out = res.release();
   return GG_OK;
 }

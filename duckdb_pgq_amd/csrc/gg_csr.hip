@@ -818,18 +818,19 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
 
   // status back to the host (the only synchronisation of the build): duplicate check, sentinel
   // vertex, kept-edge count
-  // (the bucketed build runs no chained scan; k_gather_rowid still does nothing while the word is set — an earlier
-  // call that failed may have left it — so a build with explicit rowids reports it rather than an unwritten column)
+  // (the multi-pass build's chained scans are checked by read_back itself, which fails with the scans' own message.
+  // The bucketed build runs no chained scan, so read_back does not look at the word; k_gather_rowid still does
+  // nothing while it is set — an earlier call that failed may have left it — so a bucketed build with explicit
+  // rowids carries the word in its status and reports it rather than an unwritten column)
+  BuildStatus hs;
   if (fast && ctx->status_early && !csr->eid) {
     GG_HIP(hipEventSynchronize(ctx->status_ev));  // (the status left the device behind the column scan)
+    memcpy(&hs, ctx->pin_scratch, sizeof(hs));
   } else {
-    if (!fast || csr->eid)
+    if (fast && csr->eid)
       GG_HIP(hipMemcpyAsync(&st->scan_error, ctx->dev_err, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, st, sizeof(BuildStatus), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
+    GG_TRY(read_back(ctx, {{st, sizeof(hs), &hs}}));
   }
-  BuildStatus hs;
-  memcpy(&hs, ctx->pin_scratch, sizeof(hs));
   ctx->dev_free(st);
   ctx->dev_free(kept_dev);
   ctx->dev_free(kept_rev_dev);
@@ -873,16 +874,14 @@ int ensure_ht(gg_ctx *ctx, gg_csr *csr) {
   BuildStatus *st = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&st, sizeof(BuildStatus)));
   BuildStatus init{0ULL, -1LL, 0ULL, 0ULL, 0ULL, 0ULL, 0ULL};
-  memcpy(ctx->pin_scratch + 16, &init, sizeof(init));
+  memcpy(ctx->pin_scratch + 16, &init, sizeof(init));  // (words 16..: read_back below lands hs in the first ones)
   GG_HIP(hipMemcpyAsync(st, ctx->pin_scratch + 16, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
   GG_LAUNCH(ctx, "ht_init", k_ht_init, dim3((unsigned)((csr->ht_cap + 255) / 256)), dim3(256), 0, csr->ht, csr->ht_cap);
   if (csr->V)
     GG_LAUNCH(ctx, "ht_insert", k_ht_insert, dim3((unsigned)((csr->V + 255) / 256)), dim3(256), 0,
               (const int64_t *)csr->vid, csr->V, csr->ht, csr->ht_cap, st, 0u, 1u);
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 16, st, sizeof(BuildStatus), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
   BuildStatus hs;
-  memcpy(&hs, ctx->pin_scratch + 16, sizeof(hs));
+  GG_TRY(read_back(ctx, {{st, sizeof(hs), &hs}}));
   ctx->dev_free(st);
   csr->ht_min_idx = hs.min_idx;
   csr->ht_built = true;
@@ -916,9 +915,7 @@ int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
   }
   GG_LAUNCH(ctx, "row_offsets", k_row_offsets, dim3((unsigned)(((E ? E : 1) + 1023) / 1024)), dim3(256), 0, rkey, E,
             (const unsigned long long *)nullptr, V, csr->roff, (const unsigned long long *)ctx->dev_err);
-  GG_TRY(scan_error_fetch(ctx));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  GG_TRY(scan_error_test(ctx));
+  GG_TRY(sync_checked(ctx));
   csr->rrow = rkey;
   ctx->keep(csr->roff);
   ctx->keep(csr->rnbr);
@@ -1075,9 +1072,7 @@ static int vertices_from_edges_general(gg_ctx *ctx, int keep_staged_vertices, ui
               dim3(256), 0,
               ctx->c_src.dev, ctx->c_dst.dev, E, (const int64_t *)ctx->c_vid.dev, n_old, set, cap,
               cannot_fill ? ~0ULL : cap / 2, cannot_fill ? 0xFFFFFFFFu : 4096u, st);
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, st, sizeof(SetStatus), hipMemcpyDeviceToHost, s));
-    GG_HIP(hipStreamSynchronize(s));
-    memcpy(&host, ctx->pin_scratch, sizeof(SetStatus));
+    GG_TRY(read_back(ctx, {{st, sizeof(host), &host}}));
     if (!host.overflow) break;
     ctx->dev_free(set);
     cap <<= 3;
@@ -1116,9 +1111,7 @@ static int vertices_from_edges_general(gg_ctx *ctx, int keep_staged_vertices, ui
     memcpy(ctx->pin_scratch, &only, sizeof(only));
     GG_HIP(hipMemcpyAsync(ctx->c_vid.dev, ctx->pin_scratch, sizeof(only), hipMemcpyHostToDevice, s));
   }
-  GG_TRY(scan_error_fetch(ctx));
-  GG_HIP(hipStreamSynchronize(s));
-  GG_TRY(scan_error_test(ctx));
+  GG_TRY(sync_checked(ctx));
   ctx->n_vertices = V;
   if (n_vertices) *n_vertices = V;
   return GG_OK;
@@ -1587,10 +1580,8 @@ extern "C" int gg_vertices_from_edges(gg_ctx *ctx, int keep_staged_vertices, uin
   GG_LAUNCH(ctx, "set_bucket_hist", k_set_bucket_hist, dim3(SET_WG), dim3(1024), 0, (const int64_t *)keys,
             (const SetStatus2 *)st, B, hist, base);
   GG_LAUNCH(ctx, "set_bucket_scan", k_set_bucket_scan, dim3(1), dim3(1024), 0, (const uint32_t *)hist, B, start, st);
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, st, sizeof(SetStatus2), hipMemcpyDeviceToHost, s));
-  GG_HIP(hipStreamSynchronize(s));
   SetStatus2 host;
-  memcpy(&host, ctx->pin_scratch, sizeof(SetStatus2));
+  GG_TRY(read_back(ctx, {{st, sizeof(host), &host}}));
   const bool second = host.overflow[0] != 0;
   if ((second && host.overflow[1]) || host.max_bucket > SET_BUCKET_CAP) {
     // more ids than both tables hold, or ids too clustered for the bucket sort: the general path
@@ -1617,7 +1608,7 @@ extern "C" int gg_vertices_from_edges(gg_ctx *ctx, int keep_staged_vertices, uin
     const int64_t only = HT_EMPTY;  // has_min with nothing else
     memcpy(ctx->pin_scratch, &only, sizeof(only));
     GG_HIP(hipMemcpyAsync(ctx->c_vid.dev, ctx->pin_scratch, sizeof(only), hipMemcpyHostToDevice, s));
-    GG_HIP(hipStreamSynchronize(s));  // (pin_scratch is reused by the next call)
+    GG_TRY(sync_checked(ctx));  // (pin_scratch is reused by the next call)
   }
   // no synchronisation: the build that follows is queued on the same stream behind these kernels
   ctx->n_vertices = V;
@@ -1638,7 +1629,7 @@ extern "C" int gg_csr_export(const gg_csr *csr, int64_t *off, int64_t *nbr, int6
   if (!csr) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = csr->ctx;
   GG_HIP(hipSetDevice(ctx->device));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
+  GG_TRY(gg::sync_checked(ctx));
   if (off) {
     std::vector<uint32_t> h(csr->V + 1);
     GG_HIP(hipMemcpy(h.data(), csr->off, (csr->V + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1672,7 +1663,7 @@ extern "C" int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, i
   if (!roff && !rnbr && !rrow) return GG_OK;
   GG_HIP(hipSetDevice(ctx->device));
   GG_TRY(ensure_reverse(ctx, csr));  // (the multi-pass build of a whole graph leaves the reverse CSR to its first use)
-  GG_HIP(hipStreamSynchronize(ctx->stream));
+  GG_TRY(sync_checked(ctx));
   auto fetch = [&](int64_t *out, const uint32_t *dev, uint64_t n) -> int {
     if (!out || !n) return GG_OK;
     std::vector<uint32_t> h(n);

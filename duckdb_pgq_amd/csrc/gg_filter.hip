@@ -85,19 +85,13 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
   uint64_t total = 0;
   if (n_rows) {
     GG_TRY(ensure_ht(ctx, const_cast<gg_csr *>(filter)));
-    uint64_t *counts = nullptr, *tot = nullptr;
+    uint64_t *counts = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&counts, (n_rows + 1) * sizeof(uint64_t)));
-    GG_TRY(ctx->dev_alloc((void **)&tot, sizeof(uint64_t)));
     const unsigned grid = (unsigned)((n_rows + 255) / 256);
     GG_LAUNCH(ctx, "filter_count", (k_filter<false>), dim3(grid), dim3(256), 0, in, ncols, n_rows, filter->ht,
               filter->ht_cap, filter->ht_min_idx, filter->off, filter->nbr, filter->vid, counts,
               (const uint64_t *)nullptr, oc);
-    GG_TRY(scan_exclusive_u64(ctx, counts, counts, n_rows, tot));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tot, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    GG_TRY(scan_error_test(ctx));
-    total = ctx->pin_scratch[0];
+    GG_TRY(scan_total_u64(ctx, counts, counts, n_rows, &total));
     for (int c = 0; c <= ncols; c++) {
       GG_TRY(ctx->dev_alloc((void **)&o->cols[hops + 1][c], (total ? total : 1) * sizeof(int64_t)));
       ctx->keep(o->cols[hops + 1][c]);
@@ -107,7 +101,7 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
       GG_LAUNCH(ctx, "filter_fill", (k_filter<true>), dim3(grid), dim3(256), 0, in, ncols, n_rows, filter->ht,
                 filter->ht_cap, filter->ht_min_idx, filter->off, filter->nbr, filter->vid,
                 (uint64_t *)nullptr, (const uint64_t *)counts, oc);
-    GG_HIP(hipStreamSynchronize(ctx->stream));
+    GG_TRY(sync_checked(ctx));
   } else {
     for (int c = 0; c <= ncols; c++) {
       GG_TRY(ctx->dev_alloc((void **)&o->cols[hops + 1][c], sizeof(int64_t)));

@@ -8,6 +8,7 @@
 #include <cstring>
 #include <atomic>
 #include <condition_variable>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -199,13 +200,15 @@ struct gg_ctx {
   std::vector<hipEvent_t> prof_event_pool;   // events are reused: creating two per launch costs more than timing
   std::vector<std::string> prof_selected;    // gg_profile_select: time only these kernels (empty: all)
 
-  // small pinned scratch for D2H of counters
-  uint64_t *pin_scratch = nullptr;  // 64 x u64 (word 63: copy of dev_err, see scan_error_fetch)
+  // small pinned scratch for D2H of counters: 64 x u64, laid out per call by gg::read_back (word 63: copy of dev_err).
+  // The only other users are the multi-pass build's H2D seeds (gg_csr.hip) and the bucketed build's early status below.
+  uint64_t *pin_scratch = nullptr;
   // the bucketed build's status words are final long before its last kernel: copied to pin_scratch behind the
   // column scan, status_ev recorded behind the copy — gg_csr_build waits for that, not for the stream
   hipEvent_t status_ev = nullptr;
   bool status_early = false;
   unsigned long long *dev_err = nullptr;  // device word: != 0 after a chained scan gave up waiting
+  bool scan_pending = false;              // a chained scan was launched since dev_err was last fetched (gg::read_back)
   uint32_t scan_spin_limit = 1u << 24;    // polls per predecessor before a scan tile gives up
   uint64_t scan_mute_tile = ~0ull;        // gg_debug_scan_fault: this scan tile never publishes (tests)
 
@@ -309,8 +312,10 @@ namespace gg {
 //
 // The rules of an entry point: every launch goes through GG_LAUNCH; caller ids reach the device through upload_ids;
 // a result (or any other C-ABI object) under construction is held by an Owner and release()d only on success;
-// failures return at once through GG_TRY / GG_HIP, and the ApiScope frees the pool blocks.  An explicit dev_free is
-// only worth writing where it lowers the pool's peak, i.e. before a later allocation in the same call.
+// failures return at once through GG_TRY / GG_HIP, and the ApiScope frees the pool blocks; every host synchronisation
+// of a compute call is read_back / sync_checked, which test the chained scans' error word whenever a scan ran.  An
+// explicit dev_free is only worth writing where it lowers the pool's peak, i.e. before a later allocation in the same
+// call.
 struct ApiScope {
   gg_ctx *ctx;
   uint64_t mark;
@@ -373,11 +378,33 @@ int check_whole_csr(gg_ctx *ctx, const gg_csr *csr);
 // total (as uint64) to *total_dev if non-null.  One hand-written kernel, tiles chained by decoupled
 // look-back (gg_runtime.hip).
 int scan_exclusive_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *total_dev);
-// the error word of the chained scans: enqueue the fetch before a synchronisation, test after it
-int scan_error_fetch(gg_ctx *ctx);
-int scan_error_test(gg_ctx *ctx);
 // exclusive scan of n uint64 values
 int scan_exclusive_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_dev);
+
+// The host synchronisation of a compute call: the items' D2H copies (through consecutive 8-byte-aligned words of
+// ctx->pin_scratch) are queued on ctx->stream, the stream is synchronised ONCE, and the words are copied to each `host`.
+// If a chained scan ran since the last such synchronisation, its error word travels along and a scan that gave up makes
+// this GG_ERR_HIP.  More bytes than the scratch holds below the error word are refused (GG_ERR_STATE).
+struct ReadBack {
+  const void *dev;
+  size_t bytes;
+  void *host;
+};
+int read_back(gg_ctx *ctx, const ReadBack *items, size_t n_items);
+inline int read_back(gg_ctx *ctx, std::initializer_list<ReadBack> items) {
+  return read_back(ctx, items.begin(), items.size());
+}
+inline int sync_checked(gg_ctx *ctx) { return read_back(ctx, nullptr, 0); }
+// scan_exclusive_* with the grand total read back to *total_host (one read_back, `extra` items riding on it);
+// append_total: out has n + 1 entries and out[n] = the total
+int scan_total_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *total_host);
+int scan_total_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_host,
+                   bool append_total = false, std::initializer_list<ReadBack> extra = {});
+// degrees (u64, n entries) -> exclusive offsets (n + 1 entries) in place, *total_host their sum
+inline int offsets_from_deg(gg_ctx *ctx, uint64_t *deg_then_off /* n+1 */, uint64_t n, uint64_t *total_host,
+                            std::initializer_list<ReadBack> extra = {}) {
+  return scan_total_u64(ctx, deg_then_off, deg_then_off, n, total_host, true, extra);
+}
 
 // id -> dense lookup of n device ids; writes dense (uint32, INVALID_U32 if absent) to out_dev
 int lookup_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids_dev, uint64_t n, uint32_t *out_dev);

@@ -995,27 +995,6 @@ void free_frontier(gg_ctx *ctx, DevFrontier &f) {
   f = DevFrontier();
 }
 
-// read one u64 from device memory (synchronises the stream)
-int read_u64(gg_ctx *ctx, const uint64_t *dev, uint64_t *host) {
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, dev, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  *host = ctx->pin_scratch[0];
-  return GG_OK;
-}
-
-// degrees (u64, n entries) -> exclusive offsets (n+1 entries), returns total
-int offsets_from_deg(gg_ctx *ctx, uint64_t *deg_then_off /* n+1 */, uint64_t n, uint64_t *total_host) {
-  uint64_t *tot = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&tot, sizeof(uint64_t)));
-  GG_TRY(scan_exclusive_u64(ctx, deg_then_off, deg_then_off, n, tot));
-  GG_HIP(hipMemcpyAsync(deg_then_off + n, tot, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-  GG_TRY(scan_error_fetch(ctx));
-  GG_TRY(read_u64(ctx, tot, total_host));
-  GG_TRY(scan_error_test(ctx));
-  ctx->dev_free(tot);
-  return GG_OK;
-}
-
 template <typename OffT>
 int make_tiles(gg_ctx *ctx, const OffT *foff, uint64_t n_entries, uint64_t M, uint32_t **tile_entry,
                uint64_t *n_tiles) {
@@ -1174,11 +1153,11 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
                 (int)(j + 1 >= k_min), partial + t0 * 4, t0, (const uint64_t *)fqs, j);
     }
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tmp, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    digests[j + 1] = ctx->pin_scratch[0];
-    digests[j + 2] = ctx->pin_scratch[1];
-    walks[j + 2] = ctx->pin_scratch[2];
+    uint64_t h[3];
+    GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
+    digests[j + 1] = h[0];
+    digests[j + 2] = h[1];
+    walks[j + 2] = h[2];
     for (void *b : {(void *)fv, (void *)qlo, (void *)qhi, (void *)sv, (void *)slo, (void *)shi, (void *)froff, (void *)fqs,
                     (void *)foff2, (void *)tile_entry, (void *)partial, (void *)tmp})
       ctx->dev_free(b);
@@ -1226,11 +1205,11 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     GG_LAUNCH(ctx, "expand_front", k_expand_front, dim3((unsigned)f_tiles), dim3(XT), 0, csr->off, csr->nbr,
               (const uint32_t *)sv, (const uint32_t *)sq, M, partial);
     GG_TRY(reduce_partials(ctx, partial, f_tiles, tmp + 3));  // [1] digest of the last hop
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tmp, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    digests[j + 1] = ctx->pin_scratch[0];
-    walks[j + 2] = ctx->pin_scratch[2];
-    digests[j + 2] = ctx->pin_scratch[4];
+    uint64_t h[6];
+    GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
+    digests[j + 1] = h[0];
+    walks[j + 2] = h[2];
+    digests[j + 2] = h[4];
     for (void *b : {(void *)partial, (void *)tmp, (void *)pv, (void *)pq, (void *)sv, (void *)sq}) ctx->dev_free(b);
   } else if (M > 0) {
     uint32_t *tile_entry = nullptr;
@@ -1270,14 +1249,14 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     unsigned long long *tmp = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tmp, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
+    uint64_t h[3];
+    GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
     if (remaining == 2) {
-      digests[j + 1] = ctx->pin_scratch[0];
-      digests[j + 2] = ctx->pin_scratch[1];
-      walks[j + 2] = ctx->pin_scratch[2];
+      digests[j + 1] = h[0];
+      digests[j + 2] = h[1];
+      walks[j + 2] = h[2];
     } else {
-      digests[j + 1] = ctx->pin_scratch[1];
+      digests[j + 1] = h[1];
     }
     ctx->dev_free(tmp);
     ctx->dev_free(partial);
@@ -1285,10 +1264,9 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
   }
   // digests of the materialised intermediate hops
   if (j > 0) {
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, sums, (GG_MAX_HOPS + 1) * 3 * sizeof(unsigned long long),
-                          hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    for (int h = 1; h <= j; h++) digests[h] = ctx->pin_scratch[h * 3];
+    uint64_t hs[(GG_MAX_HOPS + 1) * 3];
+    GG_TRY(read_back(ctx, {{sums, sizeof(hs), hs}}));
+    for (int h = 1; h <= j; h++) digests[h] = hs[h * 3];
   }
   ctx->dev_free(sums);
   if (own_cur) free_frontier(ctx, cur);
@@ -1330,12 +1308,8 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
   uint64_t M = csr->E_rev, fbase = 0;
   if (!(mid_lo == 0 && mid_hi == csr->V)) {
     uint32_t ends[2] = {0, 0};
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, csr->roff + mid_lo, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 1, csr->roff + mid_hi, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(&ends[0], ctx->pin_scratch, sizeof(uint32_t));
-    memcpy(&ends[1], ctx->pin_scratch + 1, sizeof(uint32_t));
+    GG_TRY(read_back(ctx, {{csr->roff + mid_lo, sizeof(uint32_t), &ends[0]},
+                          {csr->roff + mid_hi, sizeof(uint32_t), &ends[1]}}));
     M = (uint64_t)ends[1] - ends[0];
     fbase = ends[0];
   }
@@ -1365,11 +1339,11 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
     GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, csr->rrow,
               csr->rnbr, fbase, M, (int)(k_min <= 1), partial, tmp);
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tmp, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    dig1 = ctx->pin_scratch[0];
-    dig2 = ctx->pin_scratch[1];
-    rows2 = ctx->pin_scratch[2];
+    uint64_t h[3];
+    GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
+    dig1 = h[0];
+    dig2 = h[1];
+    rows2 = h[2];
     ctx->dev_free(tmp);
     ctx->dev_free(partial);
   }
@@ -1400,9 +1374,7 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
     GG_LAUNCH(ctx, "mid3_prepare", k_mid3_prepare, dim3((unsigned)nb1), dim3(256), 0, csr->roff, csr->rrow, csr->rnbr,
               E, foff2, partial);
     GG_TRY(reduce_partials(ctx, partial, nb1, tmp));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 8, tmp, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    GG_TRY(offsets_from_deg(ctx, foff2, E, &M2));  // (synchronises: pin_scratch[8] is the 1-hop digest)
-    dig1 = ctx->pin_scratch[8];
+    GG_TRY(offsets_from_deg(ctx, foff2, E, &M2, {{tmp, sizeof(uint64_t), &dig1}}));  // (the 1-hop digest rides on its sync)
     ctx->dev_free(partial);
     partial = nullptr;
     if (M2) {
@@ -1425,11 +1397,11 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
                   (int)(k_min <= 2), partial + t0 * 4, t0, (const uint64_t *)nullptr, 0);
       }
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
-      GG_HIP(hipMemcpyAsync(ctx->pin_scratch, tmp, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-      GG_HIP(hipStreamSynchronize(ctx->stream));
-      dig2 = ctx->pin_scratch[0];
-      dig3 = ctx->pin_scratch[1];
-      rows3 = ctx->pin_scratch[2];
+      uint64_t h[3];
+      GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
+      dig2 = h[0];
+      dig3 = h[1];
+      rows3 = h[2];
       ctx->dev_free(tile_entry);
       ctx->dev_free(partial);
     }
@@ -1826,13 +1798,9 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
   GG_TRY(ensure_reverse(ctx, csr));
   uint64_t e0 = 0, n = csr->E_rev;
   if (!(mid_lo == 0 && mid_hi == csr->V)) {
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, csr->roff + mid_lo, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 1, csr->roff + mid_hi, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    uint32_t ends[2];
-    memcpy(&ends[0], ctx->pin_scratch, sizeof(uint32_t));
-    memcpy(&ends[1], ctx->pin_scratch + 1, sizeof(uint32_t));
+    uint32_t ends[2] = {0, 0};
+    GG_TRY(read_back(ctx, {{csr->roff + mid_lo, sizeof(uint32_t), &ends[0]},
+                          {csr->roff + mid_hi, sizeof(uint32_t), &ends[1]}}));
     e0 = ends[0];
     n = (uint64_t)ends[1] - ends[0];
   }
@@ -1959,7 +1927,7 @@ int khop_materialise(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fv0, uint64
         if (!epos_prev.empty())
           GG_HIP(hipMemcpyAsync(e_in, epos_prev.data(), epos_prev.size() * sizeof(void *), hipMemcpyHostToDevice,
                                 ctx->stream));
-        GG_HIP(hipStreamSynchronize(ctx->stream));
+        GG_TRY(sync_checked(ctx));
         GG_LAUNCH(ctx, "mat_rows_edges", (k_mat_rows_edges<uint64_t>), dim3((unsigned)n_tiles), dim3(XT), 0, csr->off,
                   csr->nbr, csr->vid, (const int64_t *)csr->eid, (const uint32_t *)csr->epos, (const uint64_t *)foff, n_prev, M,
                   (const uint32_t *)tile_entry, h - 1, d_in, e_in, ec);
@@ -1971,7 +1939,7 @@ int khop_materialise(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fv0, uint64
       } else if (M) {
         GG_HIP(hipMemcpyAsync(d_in, cols_prev.data(), cols_prev.size() * sizeof(void *), hipMemcpyHostToDevice,
                               ctx->stream));
-        GG_HIP(hipStreamSynchronize(ctx->stream));
+        GG_TRY(sync_checked(ctx));
         GG_LAUNCH(ctx, "mat_last", k_mat_last, dim3((unsigned)((n_prev + XT - 1) / XT)), dim3(XT), 0, csr->off, csr->nbr,
                   csr->vid, foff, n_prev, h - 1, d_in, oc);
       }
@@ -1999,7 +1967,7 @@ int khop_materialise(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fv0, uint64
         GG_HIP(hipMemcpyAsync(e_out, epos_cur.data(), epos_cur.size() * sizeof(void *), hipMemcpyHostToDevice,
                               ctx->stream));
       }
-      GG_HIP(hipStreamSynchronize(ctx->stream));  // host vectors are reused below
+      GG_TRY(sync_checked(ctx));  // host vectors are reused below
       GG_LAUNCH(ctx, "mat_fill", (k_mat_fill<uint64_t>), dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr,
                 foff, n_prev, M, tile_entry, h - 1, d_in, d_out, noff, with_edges ? e_in : (const uint32_t **)nullptr,
                 with_edges ? e_out : (uint32_t **)nullptr);
@@ -2032,8 +2000,7 @@ int khop_materialise(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fv0, uint64
   ctx->dev_free(d_out);
   ctx->dev_free(e_in);
   ctx->dev_free(e_out);
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  return GG_OK;
+  return sync_checked(ctx);
 }
 
 // ---- probe of a batch of keys (the device side of a generic single-key inner join) ---------------------------------
@@ -2161,10 +2128,9 @@ int khop_count_rows(gg_ctx *ctx, gg_csr *csr, const uint32_t *dense_src, uint64_
         GG_LAUNCH(ctx, "wc_dot", k_wc_dot, dim3(dot_grid), dim3(256), 0, csr->off, (const uint32_t *)nullptr, w, V, out + h);
     }
   }
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, out, (GG_MAX_HOPS + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  for (int h = k_min; h <= k_max; h++) rows[h] = ctx->pin_scratch[h];
+  uint64_t hr[GG_MAX_HOPS + 1];
+  GG_TRY(read_back(ctx, {{out, sizeof(hr), hr}}));
+  for (int h = k_min; h <= k_max; h++) rows[h] = hr[h];
   if (all && k_min <= 1) rows[1] = csr->n_parts > 1 ? csr->E_rev : csr->E;
   ctx->dev_free(out);
   ctx->dev_free(wa);
@@ -2205,7 +2171,7 @@ int frontier_from_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64
   if (n) {
     GG_LAUNCH(ctx, "compact_sources", k_compact_sources, dim3((unsigned)((n + 1023) / 1024)), dim3(256), 0, dense, n,
               f->fv, f->fq, f->foff, csr->off, cursor);
-    GG_TRY(read_u64(ctx, (const uint64_t *)cursor, &f->n));
+    GG_TRY(read_back(ctx, {{cursor, sizeof(uint64_t), &f->n}}));
   }
   return GG_OK;
 }
@@ -2249,12 +2215,8 @@ extern "C" int gg_expand_khop_range(gg_ctx *ctx, const gg_csr *csr, uint64_t src
   uint64_t M1 = csr->E;
   if (!all) {
     uint32_t ends[2] = {0, 0};
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, csr->off + src_lo, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 1, csr->off + src_hi, sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(&ends[0], ctx->pin_scratch, sizeof(uint32_t));
-    memcpy(&ends[1], ctx->pin_scratch + 1, sizeof(uint32_t));
+    GG_TRY(read_back(ctx, {{csr->off + src_lo, sizeof(uint32_t), &ends[0]},
+                          {csr->off + src_hi, sizeof(uint32_t), &ends[1]}}));
     M1 = (uint64_t)ends[1] - ends[0];
   }
   if (k_max == 2 && all && (ctx->force_frontier == 0 || csr->n_parts > 1)) {
@@ -2633,14 +2595,14 @@ extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result 
     GG_LAUNCH(ctx, "result_digest", k_result_digest, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, cols,
               hops, n, (const HtSlot *)csr->ht, csr->ht_cap, csr->ht_min_idx, out);
   }
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, out, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->pin_scratch[1]) {
-    set_error("gg_result_digest: %llu rows hold an id that is not a vertex", (unsigned long long)ctx->pin_scratch[1]);
+  uint64_t h[2];  // digest, bad ids
+  GG_TRY(read_back(ctx, {{out, sizeof(h), h}}));
+  if (h[1]) {
+    set_error("gg_result_digest: %llu rows hold an id that is not a vertex", (unsigned long long)h[1]);
     return GG_ERR_STATE;
   }
   if (n_rows) *n_rows = n;
-  *digest = ctx->pin_scratch[0];
+  *digest = h[0];
   return GG_OK;
 }
 

@@ -225,22 +225,15 @@ extern "C" int gg_level_sets(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed
       ctx->dev_free(foff);
     } else {
       uint32_t *tile_entry = nullptr, *group_at = nullptr;
-      uint64_t n_tiles = 0, *total = nullptr;
+      uint64_t n_tiles = 0;
       GG_TRY(make_tiles_u64(ctx, foff, n_parent, M, &tile_entry, &n_tiles));
       GG_LAUNCH(ctx, "levels_mark", k_levels_mark, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, fcls, fvtx,
                 foff, n_parent, M, tile_entry, vs.bits, vs.V);
       GG_TRY(ctx->dev_alloc((void **)&group_at, n_groups * sizeof(uint32_t)));
-      GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
       GG_LAUNCH(ctx, "levels_count", k_levels_count, stride_grid(ctx, n_groups), dim3(256), 0, (const uint4 *)vs.bits,
                 n_groups, group_at);
-      GG_TRY(scan_exclusive_u32(ctx, group_at, group_at, n_groups, total));
-      GG_TRY(scan_error_fetch(ctx));
-      GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-      GG_HIP(hipStreamSynchronize(ctx->stream));
-      l.n = ctx->pin_scratch[0];  // (>= 1: M > 0 children were marked)
-      GG_TRY(scan_error_test(ctx));
+      GG_TRY(scan_total_u32(ctx, group_at, group_at, n_groups, &l.n));  // (>= 1: M > 0 children were marked)
       ctx->dev_free(tile_entry);
-      ctx->dev_free(total);
       ctx->dev_free(foff);
       GG_TRY(ctx->dev_alloc((void **)&l.cls, l.n * sizeof(uint32_t)));
       GG_TRY(ctx->dev_alloc((void **)&l.vtx, l.n * sizeof(uint32_t)));

@@ -79,7 +79,7 @@ int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr) {
     }
     GG_TRY(ctx->dev_alloc((void **)&key_out, E * sizeof(uint32_t)));
     GG_TRY(sort_pairs_by_key(ctx, csr->nbr, row, E, bits_for(V < 2 ? 2 : V), key_out, sorted));
-    GG_HIP(hipStreamSynchronize(ctx->stream));
+    GG_TRY(sync_checked(ctx));
   }
   ctx->keep(sorted);
   csr->rnbr_by_src = sorted;
@@ -200,23 +200,17 @@ static int paths_emit_t(gg_ctx *ctx, const gg_csr *csr, const DistT *dist, const
   const uint64_t n = rq.n_pairs;
   hipStream_t s = ctx->stream;
   uint32_t *lane_dev = nullptr, *dst_dense = nullptr, *len = nullptr, *base = nullptr, *bad = nullptr;
-  uint64_t *total_dev = nullptr;
+  uint64_t rows = 0;
   GG_TRY(ctx->dev_alloc((void **)&lane_dev, n * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&len, n * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&base, n * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&total_dev, sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&bad, sizeof(uint32_t)));
   GG_HIP(hipMemcpyAsync(lane_dev, rq.pair_lane, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
   GG_HIP(hipMemsetAsync(bad, 0, sizeof(uint32_t), s));
   GG_TRY(upload_ids(ctx, csr, rq.pair_dst_ids, n, &dst_dense));
   GG_LAUNCH(ctx, "path_len", (k_path_len<DistT>), stride_grid(ctx, n), dim3(256), 0, dist, (const uint32_t *)lane_dev,
             (const uint32_t *)dst_dense, n, len);
-  GG_TRY(scan_exclusive_u32(ctx, len, base, n, total_dev));
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total_dev, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-  GG_TRY(scan_error_fetch(ctx));
-  GG_HIP(hipStreamSynchronize(s));
-  GG_TRY(scan_error_test(ctx));
-  const uint64_t rows = ctx->pin_scratch[0];
+  GG_TRY(scan_total_u32(ctx, len, base, n, &rows));
   if (rows >= (1ull << 32)) {  // (the bases are 32-bit and have wrapped: nothing is traced)
     set_error("gg_bfs64_paths: %llu path rows in one batch (2^32 or more)", (unsigned long long)rows);
     return GG_ERR_TOO_LARGE;
@@ -235,9 +229,9 @@ static int paths_emit_t(gg_ctx *ctx, const gg_csr *csr, const DistT *dist, const
             (const uint32_t *)csr->roff, (const uint32_t *)csr->rnbr_by_src, (const int64_t *)csr->vid,
             res->cols[PATHS_TABLE][0], reinterpret_cast<int32_t *>(res->cols[PATHS_TABLE][2]), res->cols[PATHS_TABLE][1],
             rq.want_edges ? res->cols[PATHS_TABLE][3] : (int64_t *)nullptr, bad);
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  GG_HIP(hipStreamSynchronize(s));
-  if (*(const uint32_t *)ctx->pin_scratch) {
+  uint32_t n_bad = 0;
+  GG_TRY(read_back(ctx, {{bad, sizeof(uint32_t), &n_bad}}));
+  if (n_bad) {
     set_error("gg_bfs64_paths: a reached vertex has no in-neighbour one level closer (distances and CSR disagree)");
     for (int c = 0; c < ncols; c++) res->cols[PATHS_TABLE][c] = nullptr;  // (not kept: the caller's ApiScope frees them)
     return GG_ERR_STATE;

@@ -92,7 +92,9 @@ __global__ __launch_bounds__(XT) void k_reach_expand(const uint32_t *__restrict_
 // rows of one level -> the result's int64 columns at their offset
 __global__ __launch_bounds__(256) void k_reach_emit(const uint32_t *__restrict__ cls, const uint32_t *__restrict__ vtx,
                                                     uint64_t n, const int64_t *__restrict__ vid,
-                                                    int64_t *__restrict__ cls_out, int64_t *__restrict__ vid_out) {
+                                                    int64_t *__restrict__ cls_out, int64_t *__restrict__ vid_out,
+                                                    const unsigned long long *__restrict__ err) {
+  if (*err) return;  // the rows of a level are not all written after a scan error (see k_radix_scatter)
   for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
     cls_out[r] = (int64_t)cls[r];
     vid_out[r] = vid[vtx[r]];
@@ -124,18 +126,10 @@ namespace gg {
 
 int frontier_offsets(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fvtx, uint64_t n_parent, uint64_t **foff_out,
                      uint64_t *M) {
-  uint64_t *foff = nullptr, *total = nullptr;
+  uint64_t *foff = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&foff, (n_parent + 1) * sizeof(uint64_t)));
-  GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
   GG_LAUNCH(ctx, "reach_deg", k_reach_deg, stride_grid(ctx, n_parent), dim3(256), 0, csr->off, fvtx, n_parent, foff);
-  GG_TRY(scan_exclusive_u64(ctx, foff, foff, n_parent, total));
-  GG_HIP(hipMemcpyAsync(foff + n_parent, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-  GG_TRY(scan_error_fetch(ctx));
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  *M = ctx->pin_scratch[0];
-  GG_TRY(scan_error_test(ctx));
-  ctx->dev_free(total);
+  GG_TRY(offsets_from_deg(ctx, foff, n_parent, M));
   *foff_out = foff;
   return GG_OK;
 }
@@ -153,9 +147,8 @@ int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, co
   GG_HIP(hipMemsetAsync(count, 0, sizeof(uint32_t), ctx->stream));
   GG_LAUNCH(ctx, "reach_expand", k_reach_expand, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, fcls, fvtx,
             foff, n_parent, M, tile_entry, vs, count, new_cls, new_vtx);
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch, count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  const uint64_t n_new = *(const uint32_t *)ctx->pin_scratch;
+  uint32_t n_new = 0;
+  GG_TRY(read_back(ctx, {{count, sizeof(uint32_t), &n_new}}));
   ctx->dev_free(tile_entry);
   if (n_new == 0) {
     ctx->dev_free(new_vtx);
@@ -188,11 +181,10 @@ int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel
   uint64_t at = 0;
   for (const PairLevel &l : levels) {
     GG_LAUNCH(ctx, "reach_emit", k_reach_emit, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx, l.n, csr->vid,
-              res->walk_seed + at, res->walk_rowid + at);
+              res->walk_seed + at, res->walk_rowid + at, (const unsigned long long *)ctx->dev_err);
     at += l.n;
   }
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  return GG_OK;
+  return sync_checked(ctx);
 }
 
 int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {

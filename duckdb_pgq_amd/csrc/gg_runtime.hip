@@ -446,6 +446,7 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));
     GG_HIP(hipMemsetAsync(ctx->dev_err, 0, sizeof(unsigned long long), ctx->stream));
+    ctx->scan_pending = false;
   }
   return GG_OK;
 }
@@ -987,7 +988,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_chained(const TIn *__rest
           w = __hip_atomic_load(&status[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } while ((w >> 62) == 0 && ++spins < spin_limit);  // predecessors hold lower tickets: they are running
         // gave up (a predecessor never published): the prefix is wrong from here on — say so, the host turns
-        // the flag into GG_ERR_HIP at its next synchronisation (scan_error_fetch / scan_error_test)
+        // the flag into GG_ERR_HIP at its next synchronisation (read_back)
         if ((w >> 62) == 0) atomicOr(err, 1ULL);
       }
       const unsigned long long is_prefix = __ballot((w >> 62) == 2);
@@ -1031,23 +1032,9 @@ static int scan_impl(gg_ctx *ctx, const TIn *in, TOut *out, uint64_t n, uint64_t
   GG_HIP(hipMemsetAsync(status, 0, (nb + 1) * sizeof(unsigned long long), ctx->stream));
   GG_LAUNCH(ctx, "scan_chained", (k_scan_chained<TIn, TOut>), dim3((unsigned)nb), dim3(SCAN_THREADS), 0, in, out, n, nb,
             status, total_dev, ctx->dev_err, ctx->scan_spin_limit, ctx->scan_mute_tile);
+  ctx->scan_pending = true;
   ctx->dev_free(status);  // stream-ordered reuse: later work on the same stream runs after this kernel
   return GG_OK;
-}
-
-// A chained scan that gave up waiting sets ctx->dev_err.  Callers enqueue scan_error_fetch before a
-// synchronisation they do anyway and call scan_error_test after it.
-int scan_error_fetch(gg_ctx *ctx) {
-  GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 63, ctx->dev_err, sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  return GG_OK;
-}
-int scan_error_test(gg_ctx *ctx) {
-  if (ctx->pin_scratch[63] == 0) return GG_OK;
-  ctx->pin_scratch[63] = 0;
-  GG_HIP(hipMemsetAsync(ctx->dev_err, 0, sizeof(unsigned long long), ctx->stream));
-  set_error("a chained prefix scan gave up waiting for a predecessor tile: the result of this call is not valid");
-  return GG_ERR_HIP;
 }
 
 int scan_exclusive_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *total_dev) {
@@ -1055,6 +1042,71 @@ int scan_exclusive_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t 
 }
 int scan_exclusive_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_dev) {
   return scan_impl<uint64_t, uint64_t, uint64_t>(ctx, in, out, n, total_dev);
+}
+
+// A chained scan that gave up waiting sets ctx->dev_err, and scan_impl sets ctx->scan_pending when it launches one:
+// read_back fetches the word before its synchronisation and tests it after it, whenever a scan is pending.
+constexpr size_t PIN_ERR_WORD = 63;  // of pin_scratch's 64
+static int scan_error_fetch(gg_ctx *ctx) {
+  GG_HIP(hipMemcpyAsync(ctx->pin_scratch + PIN_ERR_WORD, ctx->dev_err, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                        ctx->stream));
+  return GG_OK;
+}
+static int scan_error_test(gg_ctx *ctx) {
+  ctx->scan_pending = false;
+  if (ctx->pin_scratch[PIN_ERR_WORD] == 0) return GG_OK;
+  ctx->pin_scratch[PIN_ERR_WORD] = 0;
+  GG_HIP(hipMemsetAsync(ctx->dev_err, 0, sizeof(unsigned long long), ctx->stream));
+  set_error("a chained prefix scan gave up waiting for a predecessor tile: the result of this call is not valid");
+  return GG_ERR_HIP;
+}
+
+int read_back(gg_ctx *ctx, const ReadBack *items, size_t n_items) {
+  size_t words = 0;
+  for (size_t i = 0; i < n_items; i++) words += (items[i].bytes + 7) / 8;
+  if (words > PIN_ERR_WORD) {
+    set_error("internal: a read-back of %zu words does not fit the pinned scratch", words);
+    return GG_ERR_STATE;
+  }
+  size_t at = 0;
+  for (size_t i = 0; i < n_items; i++) {
+    GG_HIP(hipMemcpyAsync(ctx->pin_scratch + at, items[i].dev, items[i].bytes, hipMemcpyDeviceToHost, ctx->stream));
+    at += (items[i].bytes + 7) / 8;
+  }
+  const bool check = ctx->scan_pending;
+  if (check) GG_TRY(scan_error_fetch(ctx));
+  GG_HIP(hipStreamSynchronize(ctx->stream));
+  at = 0;
+  for (size_t i = 0; i < n_items; i++) {
+    memcpy(items[i].host, ctx->pin_scratch + at, items[i].bytes);
+    at += (items[i].bytes + 7) / 8;
+  }
+  return check ? scan_error_test(ctx) : GG_OK;
+}
+
+template <typename T>
+static int scan_total(gg_ctx *ctx, const T *in, T *out, uint64_t n, uint64_t *total_host, uint64_t *append_at,
+                      std::initializer_list<ReadBack> extra) {
+  ReadBack items[4];  // (the total and at most three riders: no call has more than one today)
+  if (extra.size() >= sizeof(items) / sizeof(items[0])) {
+    set_error("internal: %zu extra read-back items ride on one scan total", extra.size());
+    return GG_ERR_STATE;
+  }
+  uint64_t *total = nullptr;  // (never freed explicitly: an 8-byte word does not lower the pool's peak)
+  GG_TRY(ctx->dev_alloc((void **)&total, sizeof(uint64_t)));
+  GG_TRY((scan_impl<T, T, uint64_t>(ctx, in, out, n, total)));
+  if (append_at) GG_HIP(hipMemcpyAsync(append_at, total, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+  size_t n_items = 0;
+  for (const ReadBack &e : extra) items[n_items++] = e;
+  items[n_items++] = {total, sizeof(uint64_t), total_host};
+  return read_back(ctx, items, n_items);
+}
+int scan_total_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *total_host) {
+  return scan_total<uint32_t>(ctx, in, out, n, total_host, nullptr, {});
+}
+int scan_total_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_host, bool append_total,
+                   std::initializer_list<ReadBack> extra) {
+  return scan_total<uint64_t>(ctx, in, out, n, total_host, append_total ? out + n : nullptr, extra);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1094,6 +1146,5 @@ extern "C" int gg_csr_lookup(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids,
   uint32_t *out_dev = nullptr;
   GG_TRY(gg::upload_ids(ctx, csr, ids, n, &out_dev));
   GG_HIP(hipMemcpyAsync(dense_out, out_dev, n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  GG_HIP(hipStreamSynchronize(ctx->stream));
-  return GG_OK;
+  return gg::sync_checked(ctx);
 }

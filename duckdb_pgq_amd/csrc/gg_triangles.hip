@@ -356,11 +356,9 @@ extern "C" int gg_triangles(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src
               args.foff, args.fnbr, eoff, toff);
     GG_TRY(scan_exclusive_u64(ctx, eoff, eoff, n_src + 1, totals));
     GG_TRY(scan_exclusive_u64(ctx, toff, toff, n_src + 1, totals + 1));
-    GG_HIP(hipMemcpyAsync(ctx->pin_scratch, totals, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    GG_TRY(scan_error_fetch(ctx));
-    GG_HIP(hipStreamSynchronize(st));
-    GG_TRY(scan_error_test(ctx));
-    const uint64_t n_ent = ctx->pin_scratch[0], n_tiles = ctx->pin_scratch[1];
+    uint64_t h[2];
+    GG_TRY(read_back(ctx, {{totals, sizeof(h), h}}));
+    const uint64_t n_ent = h[0], n_tiles = h[1];
     if (n_tiles) {
       uint32_t *ent_b = nullptr;
       uint64_t *woff = nullptr, *tile_rows = nullptr;
@@ -376,14 +374,9 @@ extern "C" int gg_triangles(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src
       args.stats = (unsigned long long *)(totals + 2);
       args.tile_rows = tile_rows;
       GG_TRY(tri_launch<false>(ctx, args, n_tiles));
-      GG_HIP(hipMemcpyAsync(ctx->pin_scratch, totals + 2, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      GG_HIP(hipMemcpyAsync(ctx->pin_scratch + 2, woff + n_ent, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-      GG_TRY(scan_error_fetch(ctx));
-      GG_HIP(hipStreamSynchronize(st));
-      GG_TRY(scan_error_test(ctx));
-      stats->rows = ctx->pin_scratch[0];
-      stats->digest = (uint64_t)(uint32_t)ctx->pin_scratch[1];
-      stats->wedges = ctx->pin_scratch[2];
+      GG_TRY(read_back(ctx, {{totals + 2, sizeof(h), h}, {woff + n_ent, sizeof(uint64_t), &stats->wedges}}));
+      stats->rows = h[0];
+      stats->digest = (uint64_t)(uint32_t)h[1];
       if (materialise && stats->rows) {
         if (stats->rows >= (1ull << 32)) {
           set_error("gg_triangles: %llu rows to materialise (2^32 or more); count them, or pass source lists",
@@ -402,9 +395,7 @@ extern "C" int gg_triangles(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src
           for (int c = 0; c < 3; c++) res->cols[2][c] = nullptr;  // (not kept: the ApiScope frees them)
           return rc;
         }
-        GG_TRY(scan_error_fetch(ctx));
-        GG_HIP(hipStreamSynchronize(st));
-        GG_TRY(scan_error_test(ctx));
+        GG_TRY(sync_checked(ctx));
       }
     }
   }
