@@ -655,6 +655,7 @@ extern "C" void gg_csr_destroy(gg_csr *csr) {
     ctx->dev_free(csr->rnbr);
     ctx->dev_free(csr->rrow);
     ctx->dev_free(csr->rnbr_by_src);
+    ctx->dev_free(csr->rpos_by_src);
     ctx->dev_free(csr->pin_off);
     ctx->dev_free(csr->pin_nbr);
   }

@@ -278,6 +278,9 @@ struct gg_csr {
   // the reverse rows again with their sources ascending (gg_paths.hip: ensure_reverse_by_source, whole CSRs, on first
   // use by gg_bfs64_paths or gg_triangles): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
   uint32_t *rnbr_by_src = nullptr;  // E
+  // the forward CSR position of every entry of rnbr_by_src (gg_paths.hip: ensure_reverse_pos_by_source, on first use by
+  // gg_triangles_edges only): equal sources of a row stand in ascending forward position, which is append order
+  uint32_t *rpos_by_src = nullptr;  // E
   // the reverse entries grouped by SOURCE (gg_bfs.hip: ensure_push_in, shards only, on first use): row u lists
   // the owned destinations of u's edges, so a shard can push a light frontier into the words it owns
   uint32_t *pin_off = nullptr; // V+1
@@ -302,6 +305,8 @@ struct gg_result {
   // gg_bfs64_paths (paths: k_min > k_max too): cols[gg::PATHS_TABLE] = pair index, vertex id, step (int32 cells), and
   // the edge rowid if edges were asked for; rows[gg::PATHS_TABLE] their number
   bool paths = false;
+  // gg_triangles_edges: ecols[2][0..2] = rowids of e1: a -> b, e2: b -> c, e3: c -> a (gg_triangles_fetch_edges)
+  bool tri_edges = false;
 };
 
 namespace gg {
@@ -427,6 +432,8 @@ void staging_trace_print();
 int ensure_reverse(gg_ctx *ctx, gg_csr *csr);
 // build csr->rnbr_by_src if absent: the reverse rows with their sources ascending, under csr->roff (gg_paths.hip)
 int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr);
+// build csr->rpos_by_src if absent: the same sort carrying the forward CSR position (gg_paths.hip)
+int ensure_reverse_pos_by_source(gg_ctx *ctx, gg_csr *csr);
 // fill csr->ht from csr->vid if the build did not need it (gg_csr.hip); every ht_lookup user calls this first
 int ensure_ht(gg_ctx *ctx, gg_csr *csr);
 // bucketed two-level build of forward + reverse CSR (gg_csr_fast.hip); *taken = 0 if the graph is outside

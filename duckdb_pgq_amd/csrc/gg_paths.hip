@@ -86,6 +86,33 @@ int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr) {
   return GG_OK;
 }
 
+__global__ __launch_bounds__(256) void k_entry_positions(uint64_t E, uint32_t *__restrict__ pos) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < E; i += (uint64_t)gridDim.x * blockDim.x)
+    pos[i] = (uint32_t)i;
+}
+
+// csr->rpos_by_src: the forward CSR position of every entry of rnbr_by_src — the same stable sort of the forward
+// entries by destination, carrying the position instead of the source.  Equal sources c of a's row therefore stand in
+// ascending forward position, i.e. in append order (forward rows are in append order on every build), which is the
+// order gg_triangles_edges lists parallel closing rows c -> a in.  Once per CSR, on the first gg_triangles_edges call;
+// 4 E bytes kept with it.  gg_bfs64_paths and gg_triangles never build it.
+int ensure_reverse_pos_by_source(gg_ctx *ctx, gg_csr *csr) {
+  if (csr->rpos_by_src) return GG_OK;
+  const uint64_t V = csr->V, E = csr->E;
+  uint32_t *pos = nullptr, *key_out = nullptr, *sorted = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&sorted, (E ? E : 1) * sizeof(uint32_t)));
+  if (E) {
+    GG_TRY(ctx->dev_alloc((void **)&pos, E * sizeof(uint32_t)));
+    GG_TRY(ctx->dev_alloc((void **)&key_out, E * sizeof(uint32_t)));
+    GG_LAUNCH(ctx, "tri_entry_positions", k_entry_positions, stride_grid(ctx, E), dim3(256), 0, E, pos);
+    GG_TRY(sort_pairs_by_key(ctx, csr->nbr, pos, E, bits_for(V < 2 ? 2 : V), key_out, sorted));
+    GG_TRY(sync_checked(ctx));
+  }
+  ctx->keep(sorted);
+  csr->rpos_by_src = sorted;
+  return GG_OK;
+}
+
 // One lane group per pair (grid-strided).  A group is in one of two phases: looking through the reverse row of x, its
 // sources ascending (rnbr_by_src), for the first in-neighbour one level closer (phase 0), or through that neighbour's
 // forward row for the first entry that leads to x (phase 1: forward rows are in append order on every build).  Each

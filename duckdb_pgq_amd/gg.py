@@ -30,7 +30,7 @@ SYMBOLS = [
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
-    "gg_triangles", "gg_debug_triangle_tile",
+    "gg_triangles", "gg_triangles_edges", "gg_triangles_fetch_edges", "gg_debug_triangle_tile",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -159,6 +159,8 @@ def load_library(path: str | None = None):
     lib.gg_bfs_sharded_end.argtypes = [P]
     lib.gg_bfs_sharded_end.restype = None
     lib.gg_triangles.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.POINTER(TriStats), C.POINTER(P)]
+    lib.gg_triangles_edges.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(TriStats), C.POINTER(P)]
+    lib.gg_triangles_fetch_edges.argtypes = [P, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
     lib.gg_debug_triangle_tile.argtypes = [P, C.c_uint32]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
@@ -265,6 +267,14 @@ class KhopResult:
         ptrs = (C.POINTER(C.c_int64) * h)(*[b.ctypes.data_as(C.POINTER(C.c_int64)) for b in bufs])
         got = C.c_uint32()
         self.gg._chk(self.gg.lib.gg_result_fetch_edges(self.handle, h, offset, min(max_rows, GG_CHUNK_ROWS), ptrs, C.byref(got)))
+        return np.stack([b[: got.value] for b in bufs], axis=1)
+
+    def fetch_triangle_edges(self, offset: int, max_rows: int = GG_CHUNK_ROWS) -> np.ndarray:
+        """Edge rowids e1, e2, e3 of rows [offset, offset + max_rows) (results of triangles_edges): [n, 3] int64."""
+        bufs = [np.empty(GG_CHUNK_ROWS, np.int64) for _ in range(3)]
+        ptrs = (C.POINTER(C.c_int64) * 3)(*[b.ctypes.data_as(C.POINTER(C.c_int64)) for b in bufs])
+        got = C.c_uint32()
+        self.gg._chk(self.gg.lib.gg_triangles_fetch_edges(self.handle, offset, min(max_rows, GG_CHUNK_ROWS), ptrs, C.byref(got)))
         return np.stack([b[: got.value] for b in bufs], axis=1)
 
     def digest(self, csr, h: int):
@@ -864,6 +874,25 @@ class GG:
                                         C.byref(res)))
         d = {"rows": int(st.rows), "digest": int(st.digest), "wedges": int(st.wedges)}
         return (d, KhopResult(self, res, d)) if materialise else d
+
+    def triangles_edges(self, csr: Csr, sources=None, ordered: bool = False):
+        """gg_triangles_edges: triangles(..., materialise=True) whose result also holds the rowids e1: a -> b, e2: b -> c,
+        e3: c -> a of every row (KhopResult.fetch_triangle_edges).  Returns (stats dict, KhopResult — the caller closes
+        it)."""
+        st, res = TriStats(), C.c_void_p()
+        keep, sp, ns = self._triangle_sources(sources)  # (keep: the array sp points into)
+        self._chk(self.lib.gg_triangles_edges(self.ctx, csr.handle, sp, ns, int(ordered), C.byref(st), C.byref(res)))
+        d = {"rows": int(st.rows), "digest": int(st.digest), "wedges": int(st.wedges)}
+        return d, KhopResult(self, res, d)
+
+    @staticmethod
+    def _triangle_sources(sources):
+        if sources is None:
+            return None, None, 0
+        a, sp = _i64(sources)
+        if a.size == 0:  # an empty list, not "every vertex": a non-NULL pointer with n_src = 0
+            sp = C.cast((C.c_int64 * 1)(), C.POINTER(C.c_int64))
+        return a, sp, a.size
 
     def debug_triangle_tile(self, n: int = 0):
         """gg_triangles stages at most n entries of an in-row in LDS (0: the default); longer rows are searched in

@@ -111,7 +111,7 @@ struct PinnedGraph {
 	column_t vertex_key, src, dst;
 	idx_t vertex_rows, edge_rows;
 	shared_ptr<GGGraph> graph;
-	//! the same tables built WITH the edge table's rowids, for gg_shortest_path_rows: made by the first such statement
+	//! the same tables built WITH the edge table's rowids, for gg_shortest_path_rows and gg_triangle_edges: made by the first such statement
 	//! that finds this pin and kept with it (a pin builds without the rowid payload, like every plan that returns no edge)
 	shared_ptr<GGGraph> graph_rowids;
 };
@@ -180,8 +180,9 @@ shared_ptr<GGGraph> GGBuildGraph(ClientContext &context, const GGGraphSpec &spec
 }
 
 //! The graph of `spec` (whose edge source ends in the rowid) with edge rowids: where this connection would get a pinned
-//! graph for the same tables, the rowid-carrying companion of that pin — built on first use, dropped with the pin.
-static shared_ptr<GGGraph> BuildGraphWithRowids(ClientContext &context, const GGGraphSpec &spec) {
+//! graph for the same tables, the rowid-carrying companion of that pin — built on first use, dropped with the pin
+//! (gg_shortest_path_rows here, gg_triangle_edges in gg_triangles.cpp).
+shared_ptr<GGGraph> GGBuildGraphWithRowids(ClientContext &context, const GGGraphSpec &spec) {
 	auto plain = spec;
 	if (plain.edges.table && plain.edges.columns.size() == 3) {
 		plain.edges.columns.pop_back();
@@ -538,7 +539,7 @@ static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<
 		spec.vertices = GGTableSource(ctx, graph.vertex_table, {graph.vertex_key}, false);
 		spec.edges = GGTableSource(ctx, graph.edge_table, {graph.edge_src, graph.edge_dst}, true);
 		spec.edges_with_rowid = true;
-		opened.graph = BuildGraphWithRowids(ctx, spec);
+		opened.graph = GGBuildGraphWithRowids(ctx, spec);
 		vector<int64_t> src, dst;
 		QueryInt64Pairs(ctx, pairs_sql, "gg_shortest_path_rows: pairs", src, dst);
 		opened.source = make_unique<PhysicalGGShortestPathRows>(opened.graph, move(src), move(dst),

@@ -65,6 +65,10 @@ GGScanSource GGTableSource(ClientContext &context, const string &table_name, con
 //! Builds the graph — or hands back the pinned one for exactly these tables and columns (gg_graph_pin), if this
 //! connection asked for pinned graphs (PRAGMA gg_use_pinned_graphs) and its transaction has changed nothing.
 shared_ptr<GGGraph> GGBuildGraph(ClientContext &context, const GGGraphSpec &spec);
+//! The graph of `spec` (whose edge source ends in the rowid) built with edge rowids.  A pinned graph carries none and is
+//! not used as it is: where this connection would get one for the same tables, its rowid-carrying companion is — built
+//! on first use, kept and dropped with the pin.
+shared_ptr<GGGraph> GGBuildGraphWithRowids(ClientContext &context, const GGGraphSpec &spec);
 
 //! Per-connection switches (the reference's pragmas act on one ClientContext, client_context.hpp:61-95; so do
 //! ours).  Entries die with their connection: they are held by weak_ptr.

@@ -513,15 +513,19 @@ public:
 
 //! Source: the triangle rows (closed 3-edge walks, include/gg.h gg_triangles) of the graph from every vertex.
 //! Output: (v0 BIGINT, v1 BIGINT, v2 BIGINT), one row per triple of edge rows v0->v1, v1->v2, v2->v0; ordered: only
-//! id(v0) < id(v1) < id(v2).  count_only: the one row (rows BIGINT, digest BIGINT, wedges BIGINT).
+//! id(v0) < id(v1) < id(v2).  count_only: the one row (rows BIGINT, digest BIGINT, wedges BIGINT).  with_edges
+//! (gg_triangles_edges; the graph carries edge rowids): three more columns (e1 BIGINT, e2 BIGINT, e3 BIGINT), the rowids
+//! of those three edge rows.
 class PhysicalGGTriangles : public PhysicalOperator {
 public:
-	PhysicalGGTriangles(shared_ptr<GGGraph> graph, bool ordered, bool count_only, idx_t estimated_cardinality);
-	static vector<LogicalType> OutputTypes(bool count_only);
+	PhysicalGGTriangles(shared_ptr<GGGraph> graph, bool ordered, bool count_only, bool with_edges,
+	                    idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes(bool count_only, bool with_edges);
 
 	shared_ptr<GGGraph> graph;
 	bool ordered;
 	bool count_only;
+	bool with_edges;
 
 public:
 	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;

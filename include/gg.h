@@ -308,11 +308,36 @@ typedef struct gg_tri_stats {
  * placed by count, scan, write — no atomics-ordered append — so it is the same on every run.  2^32 rows or more fail with
  * GG_ERR_TOO_LARGE (count them, or pass source lists).
  * A shard CSR fails with GG_ERR_STATE, an order outside {0, 1} with GG_ERR_INVALID_ARG.  Edge rowids are not needed: a CSR
- * built without them is accepted.  The edges' rowids, cycles longer than 3 and shards are not served.
+ * built without them is accepted (the rows with the rowids of their three edges: gg_triangles_edges).  Cycles longer than
+ * 3 and shards are not served.
  * The first call on a CSR sorts a copy of its reverse rows by source (gg_bfs64_paths' copy: 4 bytes per edge, kept with
  * the CSR); order = 1 ranks the vertex ids and filters both row sets once per call. */
 int gg_triangles(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int order, int materialise,
                  gg_tri_stats *stats, gg_result **out_result);
+/* gg_triangles(..., materialise = 1, ...) with the ROWID of the three edge rows of every triangle row: same arguments
+ * (sources with multiplicity, ids that are not vertices contribute nothing, order 0 or 1), same stats (rows, digest and
+ * wedges equal gg_triangles' for the same arguments), same errors and limits (a shard CSR: GG_ERR_STATE; an order outside
+ * {0, 1}: GG_ERR_INVALID_ARG; 2^32 rows or more: GG_ERR_TOO_LARGE), and like gg_expand_khop_edges it needs a CSR built
+ * with edge rowids kept (GG_ERR_STATE otherwise).  This is what a late join with the payload columns of k1, k2, k3 needs:
+ * the reference gathers build-side columns per match (ScanStructure::GatherResult in NextInnerJoin,
+ * src/execution/join_hashtable.cpp:442-476), and two parallel rows c -> a give two result rows that are equal as ids.
+ * Table 2 of the result holds the id columns a, b, c exactly as gg_triangles materialises them — the same rows at the same
+ * positions — for gg_result_rows / gg_result_fetch / gg_result_digest, and three int64 edge columns: e1 the rowid of the
+ * edge row a -> b, e2 of b -> c, e3 of c -> a (the rowid the Sink passed with the row, or its append position — counting
+ * rows dropped as dangling — if it passed none).  The rows are exactly the distinct triples (e1, e2, e3) of kept edge rows
+ * that close, one row per triple (order = 1: those with id(a) < id(b) < id(c)).  The rows of a wedge a -> b -> c with
+ * several parallel closing rows c -> a are consecutive and their e3 ascends in append order; otherwise the row order is
+ * unspecified and the same on every run.  gg_result_fetch_edges(res, 2, ...) hands back e1, e2, the edges of the 2-hop
+ * walk a -> b -> c.
+ * The first call on a CSR sorts the forward positions of its entries by destination (4 bytes per edge, kept with the
+ * CSR); gg_triangles and gg_bfs64_paths never build that array. */
+int gg_triangles_edges(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int order,
+                       gg_tri_stats *stats, gg_result **out_result);
+/* Copy rows [offset, offset+max_rows) of the edge columns e1, e2, e3 of a gg_triangles_edges result into ecols[0..2]
+ * (gg_result_fetch's conventions: *n_out = 0 past the end; gg_host_alloc destinations go over the fetch lanes).  A NULL
+ * result, ecols or n_out: GG_ERR_INVALID_ARG; a result without triangle edge columns: GG_ERR_STATE. */
+int gg_triangles_fetch_edges(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *const *ecols /* 3 */,
+                             uint32_t *n_out);
 
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {

@@ -5,8 +5,12 @@ Per workload (default sf10 and sf100) and per `order` (0: every closed 3-edge wa
     count      gg_triangles, count + digest only
     rows       gg_triangles materialising (a, b, c) in HBM, nothing fetched — skipped where the rows would not fit the
                2^32-row limit or `--max-rows`
+    edges      gg_triangles_edges: the rows with the rowids (e1, e2, e3) of their edge rows, same CSR, nothing fetched;
+               timed ALTERNATING with the ids-only materialisation (one call of each per round), so that both medians
+               come from the same run, with the k_tri_write_edges kernel time
 each the median wall time over `--runs` calls after a warm-up, with wedges/s, rows/s and the kernels' times from
-gg_profile_*.  Two yardsticks that do not depend on the code under test are recorded next to them:
+gg_profile_*.  The first gg_triangles_edges call on a CSR also sorts the forward positions by destination
+(csr->rpos_by_src): that one-time cost is reported per workload as `rpos_by_src_build`, apart from the steady state.  Two yardsticks that do not depend on the code under test are recorded next to them:
     khop3      gg_expand_khop(3..3, count) on the same CSR: it expands the same wedges and then all their leaves, where
                the triangle count does one search per wedge
     reference  the compiled reference's own plan of the three-join statement under count(*) (no planner rule), on the
@@ -32,6 +36,27 @@ def median_ms(call, runs):
         call()
         ms.append((time.perf_counter() - t0) * 1e3)
     return statistics.median(ms), ms
+
+
+def alternated_ms(call_a, call_b, runs):
+    """medians of two calls timed in turns (a, b, a, b, ...) after a warm-up of each: drift hits both alike"""
+    call_a()
+    call_b()
+    a, b = [], []
+    for _ in range(runs):
+        for call, ms in ((call_a, a), (call_b, b)):
+            t0 = time.perf_counter()
+            call()
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(a), a, statistics.median(b), b
+
+
+def profiled(gg, call):
+    gg.profile_reset()
+    gg.profile(True)
+    call()
+    gg.profile(False)
+    return {k: {"launches": v[0], "ms": v[1]} for k, v in gg.profile_get().items()}
 
 
 def reference_yardstick(pkg, workloads, limit_s):
@@ -80,6 +105,20 @@ def main():
         csr = gg.build_csr()
         out = {"metric": "triangle rows (closed 3-edge walks)", "workload": workload, "V": csr.V, "E": csr.E,
                "runs": args.runs, "orders": {}, "reference_three_join_count": ref}
+        def edges_call(order):
+            _, res = gg.triangles_edges(csr, ordered=bool(order))
+            res.close()
+
+        # the one-time cost of csr->rpos_by_src: the first edges call against the ones after it (the ordered form, the
+        # cheaper of the two; rnbr_by_src is there already, so the difference is the position sort alone)
+        gg.triangles(csr, ordered=True)
+        t0 = time.perf_counter()
+        first_kernels = profiled(gg, lambda: edges_call(1))
+        first_ms = (time.perf_counter() - t0) * 1e3
+        steady, steady_all = median_ms(lambda: edges_call(1), args.runs)
+        out["rpos_by_src_build"] = {"bytes": 4 * csr.E, "first_call_ms_profiled": first_ms, "steady_call_ms_median": steady,
+                                    "steady_call_ms_all": steady_all, "difference_ms": first_ms - steady,
+                                    "kernels_first_call": first_kernels}
         for order in (0, 1):
             st = gg.triangles(csr, ordered=bool(order))
             med, ms = median_ms(lambda: gg.triangles(csr, ordered=bool(order)), args.runs)
@@ -101,6 +140,13 @@ def main():
                 gg.profile(False)
                 entry.update({"rows_ms_median": rmed, "rows_ms_all": rms, "materialised_rows_per_s": st["rows"] / (rmed * 1e-3),
                               "kernels_rows": {k: {"launches": v[0], "ms": v[1]} for k, v in gg.profile_get().items()}})
+                emed, ems, imed, ims = alternated_ms(lambda: edges_call(order), rows_call, args.runs)
+                kernels = profiled(gg, lambda: edges_call(order))
+                entry.update({"edges_ms_median": emed, "edges_ms_all": ems, "ids_only_ms_median_same_run": imed,
+                              "ids_only_ms_all_same_run": ims, "edges_over_ids_only": emed / imed,
+                              "edge_rows_per_s": st["rows"] / (emed * 1e-3),
+                              "k_tri_write_edges_ms": kernels.get("k_tri_write_edges", {}).get("ms"),
+                              "kernels_edges": kernels})
             else:
                 entry["rows_ms_median"] = None  # too many rows to materialise in one call
             out["orders"]["order%d" % order] = entry
