@@ -24,7 +24,7 @@ SYMBOLS = [
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
-    "gg_result_filter_common_neighbour", "gg_staging_clear_edges", "gg_vertices_from_edges",
+    "gg_result_filter_common_neighbour", "gg_result_filter_edge", "gg_staging_clear_edges", "gg_vertices_from_edges",
     "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_bfs64_paths", "gg_bfs64_paths_rows", "gg_bfs64_paths_fetch",
     "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
@@ -62,6 +62,12 @@ class BfsStats(C.Structure):
 class TriStats(C.Structure):
     _fields_ = [("rows", C.c_uint64), ("digest", C.c_uint64), ("wedges", C.c_uint64)]
 
+
+class EdgeFilterStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("matches", C.c_uint64)]
+
+
+EDGE_MODES = {"inner": 0, "semi": 1, "anti": 2}  # GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
 
 _lib = None
 
@@ -120,6 +126,8 @@ def load_library(path: str | None = None):
     lib.gg_result_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
     lib.gg_expand_khop_result.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.POINTER(KhopStats), C.POINTER(P)]
     lib.gg_result_filter_common_neighbour.argtypes = [P, P, C.c_int, P, C.POINTER(P)]
+    lib.gg_result_filter_edge.argtypes = [P, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(EdgeFilterStats), C.POINTER(P)]
     lib.gg_staging_clear_edges.argtypes = [P]
     lib.gg_vertices_from_edges.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_result_destroy.argtypes = [P]
@@ -599,6 +607,32 @@ class GG:
         finally:
             self.lib.gg_result_destroy(res)
         return self._collect(out, hops + 1, hops + 1)[hops + 1]
+
+    def filter_edge(self, res: KhopResult, hops: int, csr: Csr, from_col: int, to_col: int, mode: str = "inner",
+                    materialise: bool = True):
+        """gg_result_filter_edge: the rows of res's `hops`-hop table by the number m of edge rows v_from_col -> v_to_col
+        in csr — "inner": m copies, "semi": the row if m > 0, "anti": the row if m == 0; input order is kept.  Returns
+        {"rows_in", "rows_out", "matches"}; with materialise, (that dict, KhopResult whose table `hops` holds the rows —
+        the caller closes it)."""
+        if mode not in EDGE_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(EDGE_MODES)}")
+        st, out = EdgeFilterStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_filter_edge(self.ctx, res.handle, hops, csr.handle, from_col, to_col,
+                                                 EDGE_MODES[mode], int(materialise), C.byref(st), C.byref(out)))
+        d = {"rows_in": int(st.rows_in), "rows_out": int(st.rows_out), "matches": int(st.matches)}
+        return (d, KhopResult(self, out, d)) if materialise else d
+
+    def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
+        """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows
+        (v0..v_{k-1}): the (k - 1)-hop walks whose last vertex has an edge row back to the first, one row per such edge
+        row.  2 <= k <= GG_MAX_HOPS + 1.  Returns what filter_edge returns."""
+        if not 2 <= k <= GG_MAX_HOPS + 1:
+            raise ValueError(f"closed walks of {k} edges: need 2 <= k <= {GG_MAX_HOPS + 1}")
+        walks = self.expand_khop_result(csr, k - 1, sources)
+        try:
+            return self.filter_edge(walks, k - 1, csr, k - 1, 0, "inner", materialise)
+        finally:
+            walks.close()
 
     def expand_khop_range(self, csr: Csr, lo: int, hi: int, k_min: int, k_max: int, materialise=False):
         st = KhopStats()

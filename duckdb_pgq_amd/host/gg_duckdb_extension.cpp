@@ -18,6 +18,11 @@
 //        -> (rows BIGINT, digest BIGINT, wedges BIGINT)          closed 3-edge walks (gg_triangles.cpp)
 //   gg_triangles(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered)
 //        -> (v0 BIGINT, v1 BIGINT, v2 BIGINT)
+//   gg_khop_edge_filter(vertex_table, vertex_key, edge_table, src_col, dst_col, sources_sql, hops, from_col, to_col, mode)
+//        -> (v0 BIGINT, ..., v{hops} BIGINT)   walks from the sources kept by an edge v{from_col} -> v{to_col}: mode 'inner'
+//                                              (one row per such edge row), 'semi' (EXISTS), 'anti' (NOT EXISTS)
+//   gg_khop_edge_filter_count(same arguments)
+//        -> (rows BIGINT, walks BIGINT, matches BIGINT)          (gg_edge_filter.cpp)
 //   gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //                           filter_table, filter_src, filter_dst, hops)
 //        -> (w BIGINT, v0 BIGINT, ..., v{hops} BIGINT)      Train Benchmark ConnectedSegments
@@ -694,6 +699,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &unpin_info);
 	catalog.CreateTableFunction(*con.context, &pins_info);
 	GGRegisterTriangleFunctions(*con.context);
+	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();
 }

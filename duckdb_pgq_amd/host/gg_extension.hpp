@@ -95,6 +95,9 @@ string GGQuote(const string &ident);
 //! gg_triangles.cpp: registers gg_triangles / gg_triangle_count (inside the caller's transaction)
 void GGRegisterTriangleFunctions(ClientContext &context);
 
+//! gg_edge_filter.cpp: registers gg_khop_edge_filter / gg_khop_edge_filter_count (inside the caller's transaction)
+void GGRegisterEdgeFilterFunctions(ClientContext &context);
+
 //! gg_plan_rule.cpp: hand the planner rules to the interposition shim if it is loaded; registers
 //! `PRAGMA enable_gpu_graph` / `PRAGMA disable_gpu_graph`.
 void GGRegisterPlanRules(ClientContext &context);

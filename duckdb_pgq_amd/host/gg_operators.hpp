@@ -12,11 +12,13 @@
 //        (physical_hash_join.cpp:217-254) of a k-hop pattern; a source that emits the walks.
 //   PhysicalGGTriangles                          <->  three PhysicalHashJoin probes, the last on two conditions
 //        (physical_hash_join.cpp:217-254) of the cyclic pattern a -> b -> c -> a (benchmark/ldbc/queries/bi-11.sql:22-33).
+//   PhysicalGGEdgeFilter                         <->  the last PhysicalHashJoin probe of a chain on two conditions, or the
+//        semi / anti join of an EXISTS / NOT EXISTS over the edge table (src/execution/join_hashtable.cpp:304-540).
 //   PhysicalGGShortestPath                       <->  PhysicalRecursiveCTE + min(hop) aggregate
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
-// The four sources whose rows stay on the device (path expansion, triangles, the two shortest-path ones) hand them to
+// The five sources whose rows stay on the device (path expansion, triangles, the edge filter, the two shortest-path ones) hand them to
 // the pipeline's threads through one helper, GGResultDrain + GGResultSlab below: claim under a lock, fetch without one.
 //
 // Compiled against the reference's headers; duckdb symbols are resolved by the hosting libduckdb at
@@ -412,6 +414,43 @@ public:
 	}
 	string GetName() const override {
 		return "GG_FILTERED_PATHS";
+	}
+};
+
+//! Source: the `hops`-hop walks from the sources, kept by the number m of edge rows that lead from column from_col to
+//! column to_col of the walk (gg_result_filter_edge, include/gg.h): mode GG_EDGE_INNER m copies — the last hash join of a
+//! chain carrying two conditions, e.g. the edge that closes a walk (src/execution/join_hashtable.cpp:304-476) —
+//! GG_EDGE_SEMI the row if m > 0 (EXISTS, NextSemiJoin, join_hashtable.cpp:522), GG_EDGE_ANTI the row if m == 0 (NOT
+//! EXISTS, benchmark/ldbc/queries/interactive-complex-10.sql:19-24, NextAntiJoin, join_hashtable.cpp:478-540).
+//! Output: (v0 BIGINT, ..., v{hops} BIGINT); count_only: the one row (rows BIGINT, walks BIGINT, matches BIGINT).
+class PhysicalGGEdgeFilter : public PhysicalOperator {
+public:
+	PhysicalGGEdgeFilter(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int from_col,
+	                     int to_col, int mode, bool count_only, idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes(int hops, bool count_only);
+
+	shared_ptr<GGGraph> graph;
+	int hops;
+	vector<int64_t> sources;
+	bool all_sources; // walks may start at any vertex
+	int from_col, to_col;
+	int mode; // GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
+	bool count_only;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_EDGE_FILTER";
 	}
 };
 

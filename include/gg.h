@@ -41,6 +41,13 @@
  *        <- the implicit vertex set of a join chain over an edge table alone (interactive-complex-3.sql:9-11)
  *   gg_result_filter_common_neighbour
  *        <- the six monitoredBy hash joins of benchmark/trainbenchmark/queries/connectedsegments.sql:1-25
+ *   gg_result_filter_edge
+ *        <- an edge condition between two columns of rows that are already joined: the last hash join of a chain carrying
+ *           two conditions (k4.dst = k1.src), Probe + ScanStructure::NextInnerJoin        join_hashtable.cpp:304-476;
+ *           NOT EXISTS (... knows WHERE k_person1id = C AND k_person2id = k2.k_person2id),
+ *           ScanStructure::ScanKeyMatches + NextAntiJoin                                  join_hashtable.cpp:478-540
+ *           (benchmark/ldbc/queries/interactive-complex-10.sql:19-24); EXISTS, NextSemiJoin   join_hashtable.cpp:522
+ *           (interactive-complex-7.sql:5, interactive-short-7.sql:3)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -268,6 +275,46 @@ int gg_expand_khop_result(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids
  * common to ALL of v0..vh, with the multiplicity the chained joins would give. */
 int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *filter,
                                       gg_result **out);
+/* Edge condition between two columns of a materialised walk table, as an inner, semi or anti join.
+ * What it replaces in the reference: the last hash join of a chain when it carries two conditions — `k4.dst = k1.src`
+ * closes a 4-walk, and likewise any longer one (PhysicalHashJoin::Execute -> JoinHashTable::Probe +
+ * ScanStructure::NextInnerJoin, src/execution/join_hashtable.cpp:304-476); `NOT EXISTS (SELECT * FROM knows WHERE
+ * k_person1id = C AND k_person2id = k2.k_person2id)`, "friends of friends who are not friends"
+ * (benchmark/ldbc/queries/interactive-complex-10.sql:19-24: ScanStructure::ScanKeyMatches + NextAntiJoin,
+ * join_hashtable.cpp:478-540); and `EXISTS (SELECT 1 FROM knows WHERE k_person1id = C AND k_person2id = p_personid)`
+ * (interactive-complex-7.sql:5, interactive-short-7.sql:3: NextSemiJoin, join_hashtable.cpp:522).
+ * Input: the `hops`-hop table of `res` with its id columns v0..v_hops — from gg_expand_khop_result,
+ * gg_expand_khop(materialise), gg_expand_khop_mid_result, gg_triangles(materialise) or an earlier call of this function.
+ * `csr` is the graph the condition is asked of: usually the one the walks came from, but any whole CSR of the same context
+ * is accepted (walks over one edge table, condition over another).  The cells are looked up in csr's id dictionary exactly
+ * as gg_csr_lookup does.  For a row, m = the number of kept edge rows of csr with source v_from_col and destination
+ * v_to_col; m = 0 if either id is no vertex of csr.  from_col == to_col is allowed: a self-loop test.
+ *   GG_EDGE_INNER: m copies of the row (the join's multiplicity); GG_EDGE_SEMI: the row once if m > 0; GG_EDGE_ANTI: the
+ *   row once if m == 0 — so a row with an id unknown to csr survives anti and nothing else, as NOT EXISTS demands.
+ * Output: table `hops` of *out_result (k_min = k_max = hops) with the same hops + 1 int64 id columns and no edge columns,
+ * for gg_result_rows / gg_result_fetch / gg_result_digest, this function again and gg_result_filter_common_neighbour.
+ * Row order is the input's: surviving rows keep their relative order and the m copies of a row are consecutive.  The rows
+ * are placed by count, scan, write — no atomics-ordered append — so placement is identical on every run.
+ * materialise == 0: only `stats` is filled (out_result may be NULL); 64-bit counters, no size limit.  stats may be NULL when
+ * materialising.  Chords are two calls in a row; closed walks of k edges from a source list are the (k - 1)-hop table
+ * filtered with from_col = k - 1, to_col = 0, inner; for hops = 2, from 2, to 0, inner over all sources the rows are
+ * gg_triangles(order = 0)'s.  Whole-graph triangles stay gg_triangles' business: it never materialises the wedges.
+ * Errors: NULL ctx / res / csr, objects of another context, hops outside the result's k_min..k_max, a column outside
+ * 0..hops, a mode outside {0, 1, 2}, materialise != 0 with NULL out_result: GG_ERR_INVALID_ARG.  A shard CSR, or a result
+ * without fixed-length tables (closures, level sets, paths): GG_ERR_STATE.  2^32 output rows or more when materialising:
+ * GG_ERR_TOO_LARGE (count them, or filter a smaller table).  After every error the context stays usable.
+ * The first call on a CSR sorts a copy of its reverse rows by source (gg_bfs64_paths' and gg_triangles' copy: 4 bytes per
+ * edge, kept with the CSR) and, if the build did not need the 16-byte id table, fills it. */
+#define GG_EDGE_INNER 0   /* one output row per matching edge row (join multiplicity) */
+#define GG_EDGE_SEMI  1   /* the row once if at least one edge row matches (EXISTS) */
+#define GG_EDGE_ANTI  2   /* the row once if no edge row matches (NOT EXISTS) */
+typedef struct gg_edge_filter_stats {
+  uint64_t rows_in;   /* rows of the input table */
+  uint64_t rows_out;  /* rows that pass, with multiplicity in inner mode */
+  uint64_t matches;   /* sum over input rows of the number of edge rows v_from -> v_to (= rows_out in inner mode) */
+} gg_edge_filter_stats;
+int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *csr, int from_col, int to_col,
+                          int mode, int materialise, gg_edge_filter_stats *stats, gg_result **out_result);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
