@@ -144,6 +144,7 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
 }
 
 extern "C" int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
+  GG_TRY(refuse_aggregate(res, "gg_walk_closure_levels"));
   if (!res || res->reach || res->level_sets || !n_levels || (capacity > 0 && !rows_per_level) || res->k_min <= res->k_max)
     return GG_ERR_INVALID_ARG;
   *n_levels = (int)res->level_rows.size();
@@ -153,6 +154,7 @@ extern "C" int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_l
 
 extern "C" int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_index,
                                      int64_t *edge_rowid, int32_t *level, uint32_t *n_out) {
+  GG_TRY(refuse_aggregate(res, "gg_walk_closure_fetch"));
   if (!res || res->reach || res->level_sets || !n_out || !seed_index || !edge_rowid || res->k_min <= res->k_max) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = res->ctx;
   uint64_t total = 0;

@@ -192,6 +192,7 @@ struct gg_ctx {
   int levels_set_mode = 0;      // gg_debug_level_sets: 0 the budget decides, 1 bitmap, 2 hash set (gg_levels.hip)
   int levels_order_mode = 0;    // gg_debug_level_sets: 0 the byte model decides per level, 1 sort, 2 compact
   uint32_t tri_lds_entries = 0; // gg_debug_triangle_tile: entries of an in-row gg_triangles may stage in LDS (0: the default)
+  uint32_t agg_long_row = 0;    // gg_debug_aggregate_long_row: rows of more entries go to a workgroup each (0: the default)
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;
@@ -307,6 +308,10 @@ struct gg_result {
   bool paths = false;
   // gg_triangles_edges: ecols[2][0..2] = rowids of e1: a -> b, e2: b -> c, e3: c -> a (gg_triangles_fetch_edges)
   bool tri_edges = false;
+  // gg_khop_aggregate (aggregate: k_min > k_max too): for h in [agg_k_min, agg_k_max] rows[h] groups, cols[h][0..3] =
+  // vertex id, walks, low and high half of the total (gg_khop_aggregate_rows / gg_khop_aggregate_fetch)
+  bool aggregate = false;
+  int agg_k_min = 0, agg_k_max = 0;
 };
 
 namespace gg {
@@ -341,6 +346,13 @@ struct DestroyWith {
 template <typename T, void (*Destroy)(T *)>
 using Owner = std::unique_ptr<T, DestroyWith<T, Destroy>>;
 using ResultOwner = Owner<gg_result, gg_result_destroy>;
+
+// GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only
+inline int refuse_aggregate(const gg_result *res, const char *fn) {
+  if (!res || !res->aggregate) return GG_OK;
+  set_error("%s: the result holds grouped aggregates (gg_khop_aggregate_rows / gg_khop_aggregate_fetch read it)", fn);
+  return GG_ERR_STATE;
+}
 
 inline ResultOwner make_result(gg_ctx *ctx, int k_min, int k_max) {
   ResultOwner res(new gg_result());

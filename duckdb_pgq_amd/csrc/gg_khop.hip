@@ -2354,6 +2354,7 @@ extern "C" int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_
 
 extern "C" int gg_result_fetch_edges(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows,
                                      int64_t *const *ecols, uint32_t *n_out) {
+  GG_TRY(refuse_aggregate(res, "gg_result_fetch_edges"));
   if (!res || !ecols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = res->ctx;
   GG_HIP(hipSetDevice(ctx->device));
@@ -2509,6 +2510,7 @@ extern "C" int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint
 }
 
 extern "C" int gg_result_rows(const gg_result *res, int hops, uint64_t *n_rows) {
+  GG_TRY(refuse_aggregate(res, "gg_result_rows"));
   if (!res || !n_rows || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[hops];
   return GG_OK;
@@ -2516,6 +2518,7 @@ extern "C" int gg_result_rows(const gg_result *res, int hops, uint64_t *n_rows) 
 
 extern "C" int gg_result_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows,
                                int64_t *const *cols, uint32_t *n_out) {
+  GG_TRY(refuse_aggregate(res, "gg_result_fetch"));
   if (!res || !cols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = res->ctx;
   GG_HIP(hipSetDevice(ctx->device));

@@ -31,6 +31,7 @@ SYMBOLS = [
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
     "gg_triangles", "gg_triangles_edges", "gg_triangles_fetch_edges", "gg_debug_triangle_tile",
+    "gg_khop_aggregate", "gg_khop_aggregate_rows", "gg_khop_aggregate_fetch", "gg_debug_aggregate_long_row",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -67,6 +68,15 @@ class EdgeFilterStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("matches", C.c_uint64)]
 
 
+class AggStats(C.Structure):
+    _fields_ = [
+        ("groups", C.c_uint64 * (GG_MAX_HOPS + 1)),
+        ("walks", C.c_uint64 * (GG_MAX_HOPS + 1)),
+        ("entries_pulled", C.c_uint64),
+    ]
+
+
+GROUP_BY = {"start": 0, "end": 1}  # GG_GROUP_START / GG_GROUP_END
 EDGE_MODES = {"inner": 0, "semi": 1, "anti": 2}  # GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
 
 _lib = None
@@ -170,6 +180,11 @@ def load_library(path: str | None = None):
     lib.gg_triangles_edges.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(TriStats), C.POINTER(P)]
     lib.gg_triangles_fetch_edges.argtypes = [P, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
     lib.gg_debug_triangle_tile.argtypes = [P, C.c_uint32]
+    lib.gg_khop_aggregate.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.c_int, i64p, C.POINTER(AggStats), C.POINTER(P)]
+    lib.gg_khop_aggregate_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
+    lib.gg_khop_aggregate_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, i64p, C.POINTER(u64), C.POINTER(u64), i64p,
+                                            C.POINTER(C.c_uint32)]
+    lib.gg_debug_aggregate_long_row.argtypes = [P, C.c_uint32]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
     lib.gg_profile_reset.argtypes = [P]
@@ -297,6 +312,42 @@ class KhopResult:
         got = C.c_uint32()
         self.gg._chk(self.gg.lib.gg_result_fetch(self.handle, h, offset, min(max_rows, GG_CHUNK_ROWS), ptrs, C.byref(got)))
         return np.stack([b[: got.value] for b in bufs], axis=1)
+
+    def close(self):
+        if self.handle:
+            self.gg.lib.gg_result_destroy(self.handle)
+            self.handle = None
+
+
+class KhopAggregate:
+    """Grouped aggregates over walks (gg_khop_aggregate), left in HBM: per level one row (vertex id, walks, total) per
+    group.  stats: {"groups", "walks", "entries_pulled"}; handle None: the call asked for the stats only."""
+
+    def __init__(self, gg: "GG", handle, stats):
+        self.gg, self.handle, self.stats = gg, handle, stats
+
+    def rows(self, h: int) -> int:
+        n = C.c_uint64()
+        self.gg._chk(self.gg.lib.gg_khop_aggregate_rows(self.handle, h, C.byref(n)))
+        return int(n.value)
+
+    def fetch(self, h: int):
+        """(ids int64, walks uint64, totals: an object array of Python ints put together from the two halves)"""
+        n = self.rows(h)
+        ids, walks = np.empty(n, np.int64), np.empty(n, np.uint64)
+        lo, hi = np.empty(n, np.uint64), np.empty(n, np.int64)
+        i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+        got, o = C.c_uint32(), 0
+        while o < n:
+            self.gg._chk(self.gg.lib.gg_khop_aggregate_fetch(
+                self.handle, h, o, min(n - o, 1 << 20), ids[o:].ctypes.data_as(i64p), walks[o:].ctypes.data_as(u64p),
+                lo[o:].ctypes.data_as(u64p), hi[o:].ctypes.data_as(i64p), C.byref(got)))
+            if not got.value:
+                raise GGError(-6, f"gg_khop_aggregate_fetch: no row at offset {o} of {n}")
+            o += got.value
+        totals = np.empty(n, object)
+        totals[:] = [(int(h_) << 64) + int(l_) for l_, h_ in zip(lo.tolist(), hi.tolist())]
+        return ids, walks, totals
 
     def close(self):
         if self.handle:
@@ -927,6 +978,36 @@ class GG:
         if a.size == 0:  # an empty list, not "every vertex": a non-NULL pointer with n_src = 0
             sp = C.cast((C.c_int64 * 1)(), C.POINTER(C.c_int64))
         return a, sp, a.size
+
+    # ---- grouped aggregates over walks
+    def khop_aggregate(self, csr: Csr, k_min: int, k_max: int, group_by: str = "start", sources=None, weights=None,
+                       fetch: bool = True) -> "KhopAggregate":
+        """gg_khop_aggregate: count(*) and sum(weight) over the h-hop walks from `sources` (None: every vertex once;
+        a list counts with multiplicity), h in k_min..k_max, grouped by their "start" vertex (the sum is over the end
+        vertices' weights) or their "end" vertex (over the start vertices').  weights: V integers in vertex-table order
+        (None: all 1, total == walks).  fetch=False: the stats only, nothing is kept on the device."""
+        if group_by not in GROUP_BY:
+            raise ValueError(f"group_by {group_by!r}: one of {sorted(GROUP_BY)}")
+        wp = None
+        if weights is not None:
+            w, wp = _i64(weights)
+            if w.ndim != 1 or w.size != csr.V:
+                raise ValueError(f"weights: {w.size} entries for {csr.V} vertices")
+        if sources is None:
+            sp, ns = None, 0
+        else:
+            a = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+            keep = a if a.size else np.zeros(1, np.int64)  # (an empty list is a list: the pointer must not be NULL)
+            sp, ns = keep.ctypes.data_as(C.POINTER(C.c_int64)), a.size
+        st, res = AggStats(), C.c_void_p()
+        self._chk(self.lib.gg_khop_aggregate(self.ctx, csr.handle, sp, ns, k_min, k_max, GROUP_BY[group_by], wp,
+                                             C.byref(st), C.byref(res) if fetch else None))
+        d = {"groups": list(st.groups), "walks": list(st.walks), "entries_pulled": int(st.entries_pulled)}
+        return KhopAggregate(self, res if fetch else None, d)
+
+    def debug_aggregate_long_row(self, n: int = 0):
+        """gg_khop_aggregate gives rows of more than n entries to a whole workgroup each (0: the default)."""
+        self._chk(self.lib.gg_debug_aggregate_long_row(self.ctx, int(n)))
 
     def debug_triangle_tile(self, n: int = 0):
         """gg_triangles stages at most n entries of an in-row in LDS (0: the default); longer rows are searched in

@@ -1,0 +1,271 @@
+// gg_aggregate.cpp — count(*) and sum(weight) over walks, grouped by one end of the walk, as a table function:
+//
+//   gg_khop_aggregate(vertex_table, vertex_key, edge_table, src_col, dst_col,
+//                     sources_sql VARCHAR, hops BIGINT, group_by VARCHAR, weight_column VARCHAR)
+//        -> (vertex BIGINT, walks BIGINT, total HUGEINT)
+//
+// One row per vertex that starts (group_by 'start') or ends ('end') a `hops`-hop walk from the ids `sources_sql` yields
+// (one integer column; NULL or '': from every vertex): how many such walks, and the sum of weight_column — an integer
+// column of vertex_table — over their other end.  weight_column NULL: counts only, total = walks.  What that stands for in
+// the reference is a grouped aggregate above a join chain,
+//     SELECT p0.id, count(*), sum(p2.score) FROM person p0, knows k1, person p1, knows k2, person p2 WHERE ... GROUP BY p0.id
+// (the shape of benchmark/ldbc/queries/bi-8.sql:41-53): PhysicalHashAggregate
+// (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266) fed by the hash joins' probes
+// (ScanStructure::NextInnerJoin, src/execution/join_hashtable.cpp:442-476), every walk row formed to be folded away.  Here
+// it is `hops` passes over the CSR on the device (gg_khop_aggregate, include/gg.h) and at most one row per vertex comes
+// back; total is the reference's own sum(BIGINT) type, HUGEINT (src/function/aggregate/distributive/sum.cpp:115-143).
+// One difference from SQL: a NULL weight weighs 0, so a group whose weights are all NULL sums to 0, not NULL.
+// No planner rule recognises the shape.
+//
+// The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
+// The weights are read in the statement's own transaction and brought into the order of the graph's vertex table.  The
+// groups stay on the device and the pipeline's threads drain them together (GGResultDrain, gg_operators.hpp).
+#include "duckdb.hpp"
+#include "duckdb/catalog/catalog.hpp"
+#include "duckdb/common/exception.hpp"
+#include "duckdb/main/client_context.hpp"
+#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
+
+#include <unordered_map>
+
+#include "gg_extension.hpp"
+#include "gg_operators.hpp"
+
+namespace duckdb {
+
+namespace {
+
+class AggregateState : public GlobalSourceState {
+public:
+	idx_t MaxThreads() override {
+		return max_threads;
+	}
+	gg_agg_stats stats {};
+	GGResultDrain drain;
+	idx_t max_threads = 1;
+};
+
+//! a sink that collects (key, weight) pairs on the host: rows with a NULL key are skipped, a NULL weight weighs 0
+class PairsGlobalState : public GlobalSinkState {
+public:
+	mutex lock;
+	vector<int64_t> keys, weights;
+};
+
+//! row `idx` of an integer vector as int64
+static int64_t IntegerAt(const VectorData &v, PhysicalType type, idx_t idx, const char *what) {
+	switch (type) {
+	case PhysicalType::INT64:
+		return ((const int64_t *)v.data)[idx];
+	case PhysicalType::INT32:
+		return ((const int32_t *)v.data)[idx];
+	case PhysicalType::INT16:
+		return ((const int16_t *)v.data)[idx];
+	case PhysicalType::INT8:
+		return ((const int8_t *)v.data)[idx];
+	default:
+		throw BinderException(string("gg_khop_aggregate: ") + what + " must be an integer column (TINYINT .. BIGINT)");
+	}
+}
+
+class PhysicalGGCollectPairs : public PhysicalOperator {
+public:
+	PhysicalGGCollectPairs()
+	    : PhysicalOperator(PhysicalOperatorType::INVALID, {LogicalType::BIGINT, LogicalType::BIGINT}, 0) {
+	}
+	unique_ptr<GlobalSinkState> GetGlobalSinkState(ClientContext &context) const override {
+		return make_unique<PairsGlobalState>();
+	}
+	unique_ptr<LocalSinkState> GetLocalSinkState(ExecutionContext &context) const override {
+		return make_unique<LocalSinkState>();
+	}
+	SinkResultType Sink(ExecutionContext &context, GlobalSinkState &gstate_p, LocalSinkState &lstate,
+	                    DataChunk &input) const override {
+		auto &gstate = (PairsGlobalState &)gstate_p;
+		const idx_t count = input.size();
+		const auto key_type = input.data[0].GetType().InternalType(), weight_type = input.data[1].GetType().InternalType();
+		VectorData key, weight;
+		input.data[0].Orrify(count, key);
+		input.data[1].Orrify(count, weight);
+		vector<int64_t> keys, weights;
+		keys.reserve(count);
+		weights.reserve(count);
+		for (idx_t i = 0; i < count; i++) {
+			const idx_t k = key.sel->get_index(i), w = weight.sel->get_index(i);
+			if (!key.validity.RowIsValid(k)) {
+				continue;
+			}
+			keys.push_back(IntegerAt(key, key_type, k, "the vertex key"));
+			weights.push_back(weight.validity.RowIsValid(w) ? IntegerAt(weight, weight_type, w, "weight_column") : 0);
+		}
+		lock_guard<mutex> guard(gstate.lock);
+		gstate.keys.insert(gstate.keys.end(), keys.begin(), keys.end());
+		gstate.weights.insert(gstate.weights.end(), weights.begin(), weights.end());
+		return SinkResultType::NEED_MORE_INPUT;
+	}
+	bool IsSink() const override {
+		return true;
+	}
+	bool ParallelSink() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_COLLECT_PAIRS";
+	}
+};
+
+//! weight_column of vertex_table in the order of the graph's vertex table (a vertex the scan did not see weighs 0)
+static vector<int64_t> WeightsInVertexOrder(ClientContext &context, GGGraph &graph, const string &vertex_table,
+                                            const string &vertex_key, const string &weight_column) {
+	PhysicalGGCollectPairs collect;
+	GGRunSinkPipeline(context, GGTableSource(context, vertex_table, {vertex_key, weight_column}, false), collect);
+	auto &pairs = (PairsGlobalState &)*collect.sink_state;
+	std::unordered_map<int64_t, int64_t> weight_of;
+	weight_of.reserve(pairs.keys.size());
+	for (idx_t i = 0; i < pairs.keys.size(); i++) {
+		weight_of[pairs.keys[i]] = pairs.weights[i];
+	}
+	shared_ptr<const vector<int64_t>> ids;
+	{
+		lock_guard<mutex> guard(graph.lock);
+		ids = graph.VertexIds();
+	}
+	vector<int64_t> weights(ids->size(), 0);
+	for (idx_t v = 0; v < ids->size(); v++) {
+		auto it = weight_of.find((*ids)[v]);
+		if (it != weight_of.end()) {
+			weights[v] = it->second;
+		}
+	}
+	return weights;
+}
+
+} // namespace
+
+PhysicalGGKhopAggregate::PhysicalGGKhopAggregate(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p,
+                                                 bool all_sources_p, int group_by_p, vector<int64_t> weights_p,
+                                                 bool weighted_p, idx_t estimated_cardinality)
+    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), estimated_cardinality), graph(move(graph_p)),
+      hops(hops_p), sources(move(sources_p)), all_sources(all_sources_p), group_by(group_by_p), weights(move(weights_p)),
+      weighted(weighted_p) {
+}
+
+vector<LogicalType> PhysicalGGKhopAggregate::OutputTypes() {
+	return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::HUGEINT};
+}
+
+unique_ptr<GlobalSourceState> PhysicalGGKhopAggregate::GetGlobalSourceState(ClientContext &context) const {
+	auto state = make_unique<AggregateState>();
+	lock_guard<mutex> guard(graph->lock);
+	if (!graph->csr) {
+		throw InternalException("GG_KHOP_AGGREGATE scheduled before the CSR was built");
+	}
+	static const int64_t none = 0; // an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex)
+	const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
+	state->drain.Replace(context, hops, [&](idx_t &rows) {
+		GGResultPtr owner;
+		GGGraph::Check(gg_khop_aggregate(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops, hops,
+		                                 group_by, weighted ? weights.data() : nullptr, &state->stats, GGResultOut(owner)),
+		               "gg_khop_aggregate");
+		rows = state->stats.groups[hops];
+		return owner;
+	});
+	state->max_threads = GGResultSlab::ThreadsFor(state->stats.groups[hops]);
+	return move(state);
+}
+
+unique_ptr<LocalSourceState> PhysicalGGKhopAggregate::GetLocalSourceState(ExecutionContext &context,
+                                                                          GlobalSourceState &gstate) const {
+	return make_unique<GGResultSlab>(graph);
+}
+
+void PhysicalGGKhopAggregate::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+                                      LocalSourceState &lstate) const {
+	auto &gstate = (AggregateState &)gstate_p;
+	if (context.client.interrupted) {
+		throw InterruptException();
+	}
+	auto &slab = (GGResultSlab &)lstate;
+	if (slab.pos >= slab.rows) {
+		auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
+			uint32_t got = 0;
+			auto columns = slab.Columns(4); // vertex id, walks, low and high half of the total
+			GGGraph::Check(gg_khop_aggregate_fetch(result, table, offset, want, columns[0], (uint64_t *)columns[1],
+			                                       (uint64_t *)columns[2], columns[3], &got),
+			               "gg_khop_aggregate_fetch");
+			return got;
+		};
+		if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
+			return;
+		}
+	}
+	// the two BIGINT columns as they are; the total's halves side by side
+	const idx_t first = slab.pos;
+	const idx_t n = slab.Emit(chunk, 0, 2);
+	auto total = FlatVector::GetData<hugeint_t>(chunk.data[2]);
+	for (idx_t i = 0; i < n; i++) {
+		total[i].lower = (uint64_t)slab.column[2][first + i];
+		total[i].upper = slab.column[3][first + i];
+	}
+}
+
+static unique_ptr<FunctionData> KhopAggregateBind(ClientContext &context, vector<Value> &inputs,
+                                                  unordered_map<string, Value> &named_parameters,
+                                                  vector<LogicalType> &input_table_types,
+                                                  vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                  vector<string> &names) {
+	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
+	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
+	if (inputs[6].is_null || inputs[7].is_null) {
+		throw BinderException("gg_khop_aggregate: hops and group_by must not be NULL");
+	}
+	const auto hops = inputs[6].GetValue<int64_t>();
+	const string group_name = inputs[7].ToString();
+	const bool weighted = !inputs[8].is_null;
+	const string weight_column = weighted ? inputs[8].ToString() : string();
+	if (hops < 1 || hops > GG_MAX_HOPS) {
+		throw BinderException("gg_khop_aggregate: need 1 <= hops <= " + to_string(GG_MAX_HOPS));
+	}
+	int group_by;
+	if (group_name == "start") {
+		group_by = GG_GROUP_START;
+	} else if (group_name == "end") {
+		group_by = GG_GROUP_END;
+	} else {
+		throw BinderException("gg_khop_aggregate: group_by '" + group_name + "' (one of 'start', 'end')");
+	}
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
+		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
+		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
+		opened.graph = GGBuildGraph(ctx, spec);
+		vector<int64_t> sources, weights;
+		if (!sources_sql.empty()) {
+			sources = GGQueryInt64Column(ctx, sources_sql, "gg_khop_aggregate: sources");
+		}
+		if (weighted) {
+			weights = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, weight_column);
+		}
+		opened.source = make_unique<PhysicalGGKhopAggregate>(opened.graph, (int)hops, move(sources), sources_sql.empty(),
+		                                                     group_by, move(weights), weighted, 0);
+	};
+	data->parallel_result = true;
+	data->description = (weighted ? "count, sum(" + weight_column + ")" : string("count")) + " by " + group_name + " over " +
+	                    to_string(hops) + "-hop walks of " + edge_table;
+	return_types = PhysicalGGKhopAggregate::OutputTypes();
+	names = {"vertex", "walks", "total"};
+	return move(data);
+}
+
+void GGRegisterAggregateFunctions(ClientContext &context) {
+	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
+	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
+	                                  LogicalType::BIGINT,  LogicalType::VARCHAR, LogicalType::VARCHAR};
+	auto fn = GGScanFunction("gg_khop_aggregate", args, KhopAggregateBind);
+	CreateTableFunctionInfo info(fn);
+	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
+}
+
+} // namespace duckdb

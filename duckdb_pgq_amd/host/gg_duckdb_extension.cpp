@@ -700,6 +700,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &pins_info);
 	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterEdgeFilterFunctions(*con.context);
+	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();
 }

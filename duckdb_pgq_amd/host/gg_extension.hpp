@@ -98,6 +98,9 @@ void GGRegisterTriangleFunctions(ClientContext &context);
 //! gg_edge_filter.cpp: registers gg_khop_edge_filter / gg_khop_edge_filter_count (inside the caller's transaction)
 void GGRegisterEdgeFilterFunctions(ClientContext &context);
 
+//! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
+void GGRegisterAggregateFunctions(ClientContext &context);
+
 //! gg_plan_rule.cpp: hand the planner rules to the interposition shim if it is loaded; registers
 //! `PRAGMA enable_gpu_graph` / `PRAGMA disable_gpu_graph`.
 void GGRegisterPlanRules(ClientContext &context);

@@ -18,7 +18,7 @@
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
-// The five sources whose rows stay on the device (path expansion, triangles, the edge filter, the two shortest-path ones) hand them to
+// The six sources whose rows stay on the device (path expansion, triangles, the edge filter, the grouped aggregate, the two shortest-path ones) hand them to
 // the pipeline's threads through one helper, GGResultDrain + GGResultSlab below: claim under a lock, fetch without one.
 //
 // Compiled against the reference's headers; duckdb symbols are resolved by the hosting libduckdb at
@@ -451,6 +451,43 @@ public:
 	}
 	string GetName() const override {
 		return "GG_EDGE_FILTER";
+	}
+};
+
+//! Source: one row (vertex BIGINT, walks BIGINT, total HUGEINT) per vertex that starts (group_by GG_GROUP_START) or ends
+//! (GG_GROUP_END) a `hops`-hop walk from the sources: the number of such walks and the sum of the weights at their other
+//! end (gg_khop_aggregate, include/gg.h) — PhysicalHashAggregate above a chain of hash joins
+//! (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266), the shape of
+//! benchmark/ldbc/queries/bi-8.sql:41-53.  weights: one per vertex in the graph's vertex-table order (weighted false:
+//! counts only, total = walks).
+class PhysicalGGKhopAggregate : public PhysicalOperator {
+public:
+	PhysicalGGKhopAggregate(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int group_by,
+	                        vector<int64_t> weights, bool weighted, idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes();
+
+	shared_ptr<GGGraph> graph;
+	int hops;
+	vector<int64_t> sources;
+	bool all_sources; // walks may start at any vertex
+	int group_by;     // GG_GROUP_START / GG_GROUP_END
+	vector<int64_t> weights;
+	bool weighted;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_KHOP_AGGREGATE";
 	}
 };
 

@@ -386,6 +386,47 @@ int gg_triangles_edges(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, u
 int gg_triangles_fetch_edges(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *const *ecols /* 3 */,
                              uint32_t *n_out);
 
+/* ---- grouped aggregates over walks (count and sum per start or end vertex) --------------------- */
+/* count(*) and sum(weight) over the h-hop walks, grouped by one end of the walk — what the reference computes with
+ * PhysicalHashAggregate (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266) above a chain of hash joins
+ * (ScanStructure::NextInnerJoin, src/execution/join_hashtable.cpp:442-476) for statements like
+ * benchmark/ldbc/queries/bi-8.sql:41-53 (sum(f.score) ... GROUP BY p.personid), forming every walk row only to fold it
+ * away.  The result is GROUP BY over the table gg_expand_khop(csr, src_ids, n_src, h, h, materialise) would produce, for
+ * every h in [k_min, k_max]: one row (vertex id, walks, total) per group,
+ *   GG_GROUP_START  the group is v0; walks = the h-hop rows with that v0, total = the sum of weight[v_h] over them
+ *   GG_GROUP_END    the group is v_h; total = the sum of weight[v0]
+ * Sources count with multiplicity, ids that are no vertices contribute nothing, src_ids NULL means every vertex once.
+ * weights: V int64 in vertex-table order (host memory); NULL: every weight is 1, total = walks, and no sum is formed.
+ * Parallel edge rows and self-loops multiply as in the walk table.  walks is a u64 and wraps mod 2^64 like gg_khop_count's
+ * counters; a group exists iff its wrapped count is not 0.  total is a 128-bit two's-complement integer (sum_lo, sum_hi)
+ * wrapping mod 2^128: the reference's own type, sum(BIGINT) -> HUGEINT (src/function/aggregate/distributive/sum.cpp:
+ * 115-118, 140-143).  The rows of a level come in ascending dense index (vertex-table order), placed by count, scan,
+ * write: the same on every run and on every route.
+ * Cost: k_max passes over all E entries of the CSR (the forward rows for START, the reverse rows for END) whatever the
+ * source count — a caller with a handful of sources and a small k may do better expanding and grouping the rows.  Rows of
+ * more entries than a threshold (gg_debug_aggregate_long_row) are reduced by a whole workgroup each.
+ * stats (nullable): per level the groups and the sum of their walks; out_result (NULL: stats only) answers
+ * gg_khop_aggregate_rows / gg_khop_aggregate_fetch only — gg_result_rows, gg_result_fetch and the other fetchers refuse it
+ * with GG_ERR_STATE, and the two calls refuse every other result with GG_ERR_STATE.  Edge rowids are not needed.
+ * GG_ERR_INVALID_ARG: NULL ctx or csr, objects of another context, hops outside 1..GG_MAX_HOPS, k_min > k_max, a group_by
+ * other than the two, stats and out_result both NULL; GG_ERR_STATE: a shard CSR.  The context stays usable. */
+#define GG_GROUP_START 0
+#define GG_GROUP_END   1
+typedef struct gg_agg_stats {
+  uint64_t groups[GG_MAX_HOPS + 1];  /* rows of level h */
+  uint64_t walks[GG_MAX_HOPS + 1];   /* sum of the groups' walks, mod 2^64 (= gg_khop_count's rows[h]) */
+  uint64_t entries_pulled;           /* CSR entries read over all passes */
+} gg_agg_stats;
+int gg_khop_aggregate(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, uint64_t n_src, int k_min, int k_max,
+                      int group_by, const int64_t *weights /* V entries or NULL */, gg_agg_stats *stats /* nullable */,
+                      gg_result **out_result /* NULL: stats only */);
+/* groups of level `hops` (inside the call's [k_min, k_max], else GG_ERR_INVALID_ARG) */
+int gg_khop_aggregate_rows(const gg_result *res, int hops, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows) of level `hops`, in row order, into host arrays of >= max_rows entries (sum_lo and
+ * sum_hi may be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
+int gg_khop_aggregate_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *vertex_id,
+                            uint64_t *walks, uint64_t *sum_lo, int64_t *sum_hi /* nullable */, uint32_t *n_out);
+
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {
   uint32_t levels;               /* levels expanded */
@@ -615,6 +656,10 @@ int gg_debug_level_sets(gg_ctx *ctx, int set_mode /* 0 auto, 1 bitmap, 2 hash */
  * longer in-rows in global memory (the route of hub vertices), so that route runs on small graphs; 0 restores the
  * default, the kernel's own budget is the upper bound.  Results must not depend on it. */
 int gg_debug_triangle_tile(gg_ctx *ctx, uint32_t lds_entries /* 0: default */);
+/* Testing knob: gg_khop_aggregate gives rows of more than `entries` entries to a whole workgroup each and shorter ones to
+ * 16 lanes, so both routes run on small graphs (1: every row of two entries or more is long; UINT32_MAX: none is); 0
+ * restores the default.  Results must not depend on it. */
+int gg_debug_aggregate_long_row(gg_ctx *ctx, uint32_t entries /* 0: default */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
