@@ -193,6 +193,9 @@ struct gg_ctx {
   int levels_order_mode = 0;    // gg_debug_level_sets: 0 the byte model decides per level, 1 sort, 2 compact
   uint32_t tri_lds_entries = 0; // gg_debug_triangle_tile: entries of an in-row gg_triangles may stage in LDS (0: the default)
   uint32_t agg_long_row = 0;    // gg_debug_aggregate_long_row: rows of more entries go to a workgroup each (0: the default)
+  int agg_top_route = 0;        // gg_debug_aggregate_top: 0 the survivor count decides, 1 the LDS sort, 2 the global passes
+  uint32_t agg_top_floor = 0;   // gg_debug_aggregate_top: candidates at which the selection compacts them (0: the default)
+  uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;
@@ -309,7 +312,8 @@ struct gg_result {
   // gg_triangles_edges: ecols[2][0..2] = rowids of e1: a -> b, e2: b -> c, e3: c -> a (gg_triangles_fetch_edges)
   bool tri_edges = false;
   // gg_khop_aggregate (aggregate: k_min > k_max too): for h in [agg_k_min, agg_k_max] rows[h] groups, cols[h][0..3] =
-  // vertex id, walks, low and high half of the total (gg_khop_aggregate_rows / gg_khop_aggregate_fetch)
+  // vertex id, walks, low and high half of the total (gg_khop_aggregate_rows / gg_khop_aggregate_fetch);
+  // gg_khop_aggregate_top: the same with one level, its rows in rank order
   bool aggregate = false;
   int agg_k_min = 0, agg_k_max = 0;
 };

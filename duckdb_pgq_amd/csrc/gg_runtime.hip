@@ -443,6 +443,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->levels_order_mode = 0;
   ctx->tri_lds_entries = 0;
   ctx->agg_long_row = 0;
+  ctx->agg_top_route = 0;
+  ctx->agg_top_floor = 0;
   ctx->keep_edge_rowid = true;
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));

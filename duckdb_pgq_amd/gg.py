@@ -32,6 +32,7 @@ SYMBOLS = [
     "gg_bfs_sharded_pairs", "gg_bfs_sharded_end", "gg_bfs_sharded_levels",
     "gg_triangles", "gg_triangles_edges", "gg_triangles_fetch_edges", "gg_debug_triangle_tile",
     "gg_khop_aggregate", "gg_khop_aggregate_rows", "gg_khop_aggregate_fetch", "gg_debug_aggregate_long_row",
+    "gg_khop_aggregate_top", "gg_debug_aggregate_top", "gg_debug_aggregate_top_listed",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -76,7 +77,13 @@ class AggStats(C.Structure):
     ]
 
 
+class TopStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("select_passes", C.c_uint32),
+                ("sort_route", C.c_uint32)]
+
+
 GROUP_BY = {"start": 0, "end": 1}  # GG_GROUP_START / GG_GROUP_END
+TOP_BY = {"total": 0, "walks": 1}  # GG_TOP_BY_TOTAL / GG_TOP_BY_WALKS
 EDGE_MODES = {"inner": 0, "semi": 1, "anti": 2}  # GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
 
 _lib = None
@@ -185,6 +192,9 @@ def load_library(path: str | None = None):
     lib.gg_khop_aggregate_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, i64p, C.POINTER(u64), C.POINTER(u64), i64p,
                                             C.POINTER(C.c_uint32)]
     lib.gg_debug_aggregate_long_row.argtypes = [P, C.c_uint32]
+    lib.gg_khop_aggregate_top.argtypes = [P, P, C.c_int, C.c_int, C.c_int, u64, P, i64p, C.POINTER(TopStats), C.POINTER(P)]
+    lib.gg_debug_aggregate_top.argtypes = [P, C.c_int, C.c_uint32]
+    lib.gg_debug_aggregate_top_listed.argtypes = [P, C.POINTER(u64)]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
     lib.gg_profile_reset.argtypes = [P]
@@ -1004,6 +1014,39 @@ class GG:
                                              C.byref(st), C.byref(res) if fetch else None))
         d = {"groups": list(st.groups), "walks": list(st.walks), "entries_pulled": int(st.entries_pulled)}
         return KhopAggregate(self, res if fetch else None, d)
+
+    def khop_aggregate_top(self, agg: "KhopAggregate", hops: int, order_by: str = "total", descending: bool = True,
+                           n: int = 100, csr=None, bias=None) -> "KhopAggregate":
+        """gg_khop_aggregate_top: the best n groups of level `hops` of `agg` in rank order — ORDER BY key [DESC], id
+        LIMIT n with key = "total" (+ bias[vertex]: V integers in vertex-table order, which needs `csr`) or "walks".
+        The answer is a KhopAggregate of that one level; stats: {"rows_in", "rows_out", "select_passes", "sort_route"}."""
+        if order_by not in TOP_BY:
+            raise ValueError(f"order_by {order_by!r}: one of {sorted(TOP_BY)}")
+        bp = None
+        if bias is not None:
+            if csr is None:
+                raise ValueError("a bias needs the csr of its vertices")
+            b, bp = _i64(bias)
+            if b.ndim != 1 or b.size != csr.V:
+                raise ValueError(f"bias: {b.size} entries for {csr.V} vertices")
+        st, res = TopStats(), C.c_void_p()
+        self._chk(self.lib.gg_khop_aggregate_top(self.ctx, agg.handle, hops, TOP_BY[order_by], 1 if descending else 0,
+                                                 int(n), csr.handle if csr is not None else None, bp, C.byref(st),
+                                                 C.byref(res)))
+        d = {"rows_in": int(st.rows_in), "rows_out": int(st.rows_out), "select_passes": int(st.select_passes),
+             "sort_route": int(st.sort_route)}
+        return KhopAggregate(self, res, d)
+
+    def debug_aggregate_top(self, sort_route: int = 0, candidate_floor: int = 0):
+        """gg_khop_aggregate_top orders its survivors in LDS (1) or by the global passes (2) and compacts the selection's
+        candidates at candidate_floor or fewer (0: the defaults)."""
+        self._chk(self.lib.gg_debug_aggregate_top(self.ctx, int(sort_route), int(candidate_floor)))
+
+    def debug_aggregate_top_listed(self) -> int:
+        """entries of the candidate list the last khop_aggregate_top's selection wrote (0: it did not compact)"""
+        n = C.c_uint64()
+        self._chk(self.lib.gg_debug_aggregate_top_listed(self.ctx, C.byref(n)))
+        return int(n.value)
 
     def debug_aggregate_long_row(self, n: int = 0):
         """gg_khop_aggregate gives rows of more than n entries to a whole workgroup each (0: the default)."""

@@ -17,6 +17,20 @@
 // One difference from SQL: a NULL weight weighs 0, so a group whose weights are all NULL sums to 0, not NULL.
 // No planner rule recognises the shape.
 //
+//   gg_khop_aggregate_top(vertex_table, vertex_key, edge_table, src_col, dst_col, sources_sql VARCHAR, hops BIGINT,
+//                         group_by VARCHAR, weight_column VARCHAR, order_by VARCHAR, descending BOOLEAN,
+//                         bias_column VARCHAR, n BIGINT)
+//        -> (rank BIGINT, vertex BIGINT, walks BIGINT, total HUGEINT)
+//
+// The same groups, but only the first n of them under ORDER BY key [DESC], vertex — the tail of bi-8.sql:41-53,
+//     ... GROUP BY p.personid, p.score ORDER BY p.score + sum(f.score) DESC, p.personid LIMIT 100
+// which the reference runs as PhysicalTopN (src/execution/operator/order/physical_top_n.cpp:238-293, 421-454) above
+// PhysicalHashAggregate (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266).  order_by 'total': key =
+// total + bias_column of the group's vertex (an integer column of vertex_table, read like weight_column; NULL: no bias);
+// 'walks': key = walks.  The operator runs gg_khop_aggregate, then gg_khop_aggregate_top on the device, and drains the n
+// rows of the answer only; rank is their 0-based place, and they leave in that order (one thread drains).  total is the
+// unbiased sum.  As with the weights, a NULL bias adds 0 (in SQL the key would be NULL and sort last or first).
+//
 // The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
 // The weights are read in the statement's own transaction and brought into the order of the graph's vertex table.  The
 // groups stay on the device and the pipeline's threads drain them together (GGResultDrain, gg_operators.hpp).
@@ -43,6 +57,7 @@ public:
 	gg_agg_stats stats {};
 	GGResultDrain drain;
 	idx_t max_threads = 1;
+	idx_t next_rank = 0; // gg_khop_aggregate_top: the rank of the next row to leave
 };
 
 //! a sink that collects (key, weight) pairs on the host: rows with a NULL key are skipped, a NULL weight weighs 0
@@ -259,6 +274,168 @@ static unique_ptr<FunctionData> KhopAggregateBind(ClientContext &context, vector
 	return move(data);
 }
 
+namespace {
+
+//! The first n groups of PhysicalGGKhopAggregate's answer in rank order: gg_khop_aggregate_top behind gg_khop_aggregate
+class PhysicalGGKhopAggregateTop : public PhysicalGGKhopAggregate {
+public:
+	PhysicalGGKhopAggregateTop(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p, bool all_sources_p,
+	                           int group_by_p, vector<int64_t> weights_p, bool weighted_p, int order_by_p, bool descending_p,
+	                           vector<int64_t> bias_p, bool biased_p, uint64_t n_p)
+	    : PhysicalGGKhopAggregate(move(graph_p), hops_p, move(sources_p), all_sources_p, group_by_p, move(weights_p),
+	                              weighted_p, 0),
+	      order_by(order_by_p), descending(descending_p), bias(move(bias_p)), biased(biased_p), n(n_p) {
+		types = OutputTypes();
+	}
+	static vector<LogicalType> OutputTypes() {
+		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::HUGEINT};
+	}
+
+	int order_by; // GG_TOP_BY_TOTAL / GG_TOP_BY_WALKS
+	bool descending;
+	vector<int64_t> bias; // one per vertex in the graph's vertex-table order
+	bool biased;
+	uint64_t n;
+
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
+		auto state = make_unique<AggregateState>();
+		lock_guard<mutex> guard(graph->lock);
+		if (!graph->csr) {
+			throw InternalException("GG_KHOP_AGGREGATE_TOP scheduled before the CSR was built");
+		}
+		static const int64_t none = 0; // (an EMPTY list must not arrive as a null pointer)
+		const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
+		state->drain.Replace(context, hops, [&](idx_t &rows) {
+			GGResultPtr groups, owner;
+			GGGraph::Check(gg_khop_aggregate(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops, hops,
+			                                 group_by, weighted ? weights.data() : nullptr, &state->stats,
+			                                 GGResultOut(groups)),
+			               "gg_khop_aggregate");
+			gg_top_stats top {};
+			GGGraph::Check(gg_khop_aggregate_top(graph->ctx, groups.get(), hops, order_by, descending ? 1 : 0, n,
+			                                     biased ? graph->csr : nullptr, biased ? bias.data() : nullptr, &top,
+			                                     GGResultOut(owner)),
+			               "gg_khop_aggregate_top");
+			rows = top.rows_out;
+			return owner; // (the groups go back to the pool here: only the top rows stay in HBM)
+		});
+		state->max_threads = 1; // the rows leave in rank order
+		return move(state);
+	}
+
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+	             LocalSourceState &lstate) const override {
+		auto &gstate = (AggregateState &)gstate_p;
+		if (context.client.interrupted) {
+			throw InterruptException();
+		}
+		auto &slab = (GGResultSlab &)lstate;
+		if (slab.pos >= slab.rows) {
+			auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
+				uint32_t got = 0;
+				auto columns = slab.Columns(4);
+				GGGraph::Check(gg_khop_aggregate_fetch(result, table, offset, want, columns[0], (uint64_t *)columns[1],
+				                                       (uint64_t *)columns[2], columns[3], &got),
+				               "gg_khop_aggregate_fetch");
+				return got;
+			};
+			if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) {
+				return;
+			}
+		}
+		const idx_t first = slab.pos;
+		const idx_t count = slab.Emit(chunk, 1, 2);
+		auto rank = FlatVector::GetData<int64_t>(chunk.data[0]);
+		auto total = FlatVector::GetData<hugeint_t>(chunk.data[3]);
+		for (idx_t i = 0; i < count; i++) {
+			rank[i] = (int64_t)(gstate.next_rank + i); // (one thread: the slabs are claimed and emitted in order)
+			total[i].lower = (uint64_t)slab.column[2][first + i];
+			total[i].upper = slab.column[3][first + i];
+		}
+		gstate.next_rank += count;
+	}
+
+	string GetName() const override {
+		return "GG_KHOP_AGGREGATE_TOP";
+	}
+};
+
+} // namespace
+
+static unique_ptr<FunctionData> KhopAggregateTopBind(ClientContext &context, vector<Value> &inputs,
+                                                     unordered_map<string, Value> &named_parameters,
+                                                     vector<LogicalType> &input_table_types,
+                                                     vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                     vector<string> &names) {
+	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
+	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
+	if (inputs[6].is_null || inputs[7].is_null || inputs[9].is_null || inputs[10].is_null || inputs[12].is_null) {
+		throw BinderException("gg_khop_aggregate_top: hops, group_by, order_by, descending and n must not be NULL");
+	}
+	const auto hops = inputs[6].GetValue<int64_t>();
+	const string group_name = inputs[7].ToString();
+	const bool weighted = !inputs[8].is_null;
+	const string weight_column = weighted ? inputs[8].ToString() : string();
+	const string order_name = inputs[9].ToString();
+	const bool descending = inputs[10].GetValue<bool>();
+	const bool biased = !inputs[11].is_null;
+	const string bias_column = biased ? inputs[11].ToString() : string();
+	const auto n = inputs[12].GetValue<int64_t>();
+	if (hops < 1 || hops > GG_MAX_HOPS) {
+		throw BinderException("gg_khop_aggregate_top: need 1 <= hops <= " + to_string(GG_MAX_HOPS));
+	}
+	if (n < 0) {
+		throw BinderException("gg_khop_aggregate_top: n must not be negative");
+	}
+	int group_by, order_by;
+	if (group_name == "start") {
+		group_by = GG_GROUP_START;
+	} else if (group_name == "end") {
+		group_by = GG_GROUP_END;
+	} else {
+		throw BinderException("gg_khop_aggregate_top: group_by '" + group_name + "' (one of 'start', 'end')");
+	}
+	if (order_name == "total") {
+		order_by = GG_TOP_BY_TOTAL;
+	} else if (order_name == "walks") {
+		order_by = GG_TOP_BY_WALKS;
+	} else {
+		throw BinderException("gg_khop_aggregate_top: order_by '" + order_name + "' (one of 'total', 'walks')");
+	}
+	if (biased && order_by == GG_TOP_BY_WALKS) {
+		throw BinderException("gg_khop_aggregate_top: a bias_column is added to the total only");
+	}
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
+		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
+		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
+		opened.graph = GGBuildGraph(ctx, spec);
+		vector<int64_t> sources, weights, bias;
+		if (!sources_sql.empty()) {
+			sources = GGQueryInt64Column(ctx, sources_sql, "gg_khop_aggregate_top: sources");
+		}
+		if (weighted) {
+			weights = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, weight_column);
+		}
+		if (biased) {
+			bias = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, bias_column);
+		}
+		opened.source = make_unique<PhysicalGGKhopAggregateTop>(opened.graph, (int)hops, move(sources), sources_sql.empty(),
+		                                                        group_by, move(weights), weighted, order_by, descending,
+		                                                        move(bias), biased, (uint64_t)n);
+	};
+	data->parallel_result = false; // the rows leave in rank order
+	data->description = "top " + to_string(n) + " by " + (biased ? bias_column + " + " : string()) + order_name +
+	                    (descending ? " desc" : "") + " of " +
+	                    (weighted ? "count, sum(" + weight_column + ")" : string("count")) + " by " + group_name + " over " +
+	                    to_string(hops) + "-hop walks of " + edge_table;
+	return_types = PhysicalGGKhopAggregateTop::OutputTypes();
+	names = {"rank", "vertex", "walks", "total"};
+	return move(data);
+}
+
 void GGRegisterAggregateFunctions(ClientContext &context) {
 	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
 	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
@@ -266,6 +443,11 @@ void GGRegisterAggregateFunctions(ClientContext &context) {
 	auto fn = GGScanFunction("gg_khop_aggregate", args, KhopAggregateBind);
 	CreateTableFunctionInfo info(fn);
 	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
+	vector<LogicalType> top_args = args;
+	top_args.insert(top_args.end(), {LogicalType::VARCHAR, LogicalType::BOOLEAN, LogicalType::VARCHAR, LogicalType::BIGINT});
+	auto top_fn = GGScanFunction("gg_khop_aggregate_top", top_args, KhopAggregateTopBind);
+	CreateTableFunctionInfo top_info(top_fn);
+	Catalog::GetCatalog(context).CreateTableFunction(context, &top_info);
 }
 
 } // namespace duckdb

@@ -427,6 +427,39 @@ int gg_khop_aggregate_rows(const gg_result *res, int hops, uint64_t *n_rows);
 int gg_khop_aggregate_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *vertex_id,
                             uint64_t *walks, uint64_t *sum_lo, int64_t *sum_hi /* nullable */, uint32_t *n_out);
 
+/* The best n groups of level `hops` of an aggregate result, in rank order — the `ORDER BY <aggregate> [DESC], <id> LIMIT n`
+ * that ends bi-8.sql:41-53 and the other aggregating LDBC statements, which the reference runs as PhysicalTopN
+ * (src/execution/operator/order/physical_top_n.cpp:238-293, 421-454) directly above PhysicalHashAggregate.  Row a comes
+ * before row b iff key(a) is better than key(b) — greater if descending != 0, else smaller — or the keys are equal and a's
+ * vertex id is the smaller one as a signed int64 (in both directions: ORDER BY key [DESC], id).  Ids are unique within a
+ * level, so the output is fully determined.
+ *   GG_TOP_BY_WALKS  key = walks, an unsigned 64-bit value (it wraps mod 2^64 and may exceed 2^63)
+ *   GG_TOP_BY_TOTAL  key = total + bias[dense index of the row's vertex], the bias sign-extended to 128 bits, the sum
+ *                    wrapping mod 2^128 and compared signed.  bias: V int64 in vertex-table order like `weights` (host
+ *                    memory), bi-8's `p.score +`; NULL: no bias, and csr may be NULL too.  The rows' ids are mapped
+ *                    through csr's id dictionary; an id that is no vertex of csr is GG_ERR_STATE (checked when n > 0).
+ * `agg` comes from gg_khop_aggregate or from this function; it is not modified.  *out_result is an aggregate result of
+ * the one level `hops` with min(n, rows) rows (vertex id, walks, total) — the unbiased total as the input held it — in
+ * columns of exactly that many rows; it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch and this function again.
+ * n == 0: an empty result; n >= rows: every group, ordered.  LIMIT n OFFSET o is n + o here and a fetch from offset o.
+ * The selection is a most-significant-byte-first radix select driven from the device, the order a one-workgroup LDS
+ * sort up to GG_CHUNK_ROWS rows and stable radix passes on a permutation above; one host
+ * synchronisation per call.
+ * GG_ERR_INVALID_ARG: NULL ctx / agg / out_result, objects of another context, hops outside the input's levels, an
+ * order_by other than the two, a bias without csr or with GG_TOP_BY_WALKS; GG_ERR_STATE: a result that is no aggregate, a
+ * shard CSR, a group id unknown to csr.  The context stays usable. */
+#define GG_TOP_BY_TOTAL 0 /* key = total (+ bias): 128-bit two's complement, compared SIGNED */
+#define GG_TOP_BY_WALKS 1 /* key = walks: u64, compared UNSIGNED */
+typedef struct gg_top_stats {
+  uint64_t rows_in;       /* groups of the level */
+  uint64_t rows_out;      /* min(n, rows_in) */
+  uint32_t select_passes; /* digit passes the selection ran (0: nothing to select, n >= rows_in or n == 0) */
+  uint32_t sort_route;    /* 0: none needed (fewer than two rows), 1: one workgroup in LDS, 2: global passes */
+} gg_top_stats;
+int gg_khop_aggregate_top(gg_ctx *ctx, const gg_result *agg, int hops, int order_by, int descending, uint64_t n,
+                          const gg_csr *csr /* needed iff bias */, const int64_t *bias /* V entries or NULL */,
+                          gg_top_stats *stats /* nullable */, gg_result **out_result);
+
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {
   uint32_t levels;               /* levels expanded */
@@ -660,6 +693,15 @@ int gg_debug_triangle_tile(gg_ctx *ctx, uint32_t lds_entries /* 0: default */);
  * 16 lanes, so both routes run on small graphs (1: every row of two entries or more is long; UINT32_MAX: none is); 0
  * restores the default.  Results must not depend on it. */
 int gg_debug_aggregate_long_row(gg_ctx *ctx, uint32_t entries /* 0: default */);
+/* Testing knob: gg_khop_aggregate_top orders its survivors by one workgroup in LDS (1; taken up to GG_CHUNK_ROWS rows,
+ * more go through the global passes all the same) or by the global passes (2) whatever their number, and compacts the
+ * selection's candidates once they are `candidate_floor` or fewer (1: never, there is nothing left to select by then;
+ * UINT32_MAX: after the first pass that at least halves them).  0 restores either default.  Results must not depend on
+ * it.  A sort_route outside 0..2 is GG_ERR_INVALID_ARG. */
+int gg_debug_aggregate_top(gg_ctx *ctx, int sort_route /* 0 auto, 1 LDS, 2 global */, uint32_t candidate_floor /* 0: default */);
+/* Diagnostics: the entries of the candidate list the selection of the LAST successful gg_khop_aggregate_top with
+ * 0 < n < rows wrote (0: it never compacted; its passes read every row).  Read-only. */
+int gg_debug_aggregate_top_listed(gg_ctx *ctx, uint64_t *list_entries);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
