@@ -195,6 +195,8 @@ struct gg_ctx {
   uint32_t agg_long_row = 0;    // gg_debug_aggregate_long_row: rows of more entries go to a workgroup each (0: the default)
   int agg_top_route = 0;        // gg_debug_aggregate_top: 0 the survivor count decides, 1 the LDS sort, 2 the global passes
   uint32_t agg_top_floor = 0;   // gg_debug_aggregate_top: candidates at which the selection compacts them (0: the default)
+  uint32_t pc_long_row = 0;     // gg_debug_pair_counts: in-rows of more entries go to a workgroup each (0: the default)
+  int pc_gather_mode = 0;       // gg_debug_pair_counts: 0 entries whose mask is 0 are skipped, 1 every state row is read
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
   bool profiling = false;
   std::vector<std::string> prof_names;
@@ -316,6 +318,9 @@ struct gg_result {
   // gg_khop_aggregate_top: the same with one level, its rows in rank order
   bool aggregate = false;
   int agg_k_min = 0, agg_k_max = 0;
+  // gg_khop_pair_counts (pair_counts: k_min > k_max too, the levels in agg_k_min / agg_k_max): rows[h] pairs, cols[h][0..2] =
+  // source index, vertex id, walks (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch)
+  bool pair_counts = false;
 };
 
 namespace gg {
@@ -351,8 +356,13 @@ template <typename T, void (*Destroy)(T *)>
 using Owner = std::unique_ptr<T, DestroyWith<T, Destroy>>;
 using ResultOwner = Owner<gg_result, gg_result_destroy>;
 
-// GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only
+// GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only; and
+// for one of gg_khop_pair_counts, which answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only
 inline int refuse_aggregate(const gg_result *res, const char *fn) {
+  if (res && res->pair_counts) {
+    set_error("%s: the result holds pair counts (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch read it)", fn);
+    return GG_ERR_STATE;
+  }
   if (!res || !res->aggregate) return GG_OK;
   set_error("%s: the result holds grouped aggregates (gg_khop_aggregate_rows / gg_khop_aggregate_fetch read it)", fn);
   return GG_ERR_STATE;

@@ -33,6 +33,7 @@ SYMBOLS = [
     "gg_triangles", "gg_triangles_edges", "gg_triangles_fetch_edges", "gg_debug_triangle_tile",
     "gg_khop_aggregate", "gg_khop_aggregate_rows", "gg_khop_aggregate_fetch", "gg_debug_aggregate_long_row",
     "gg_khop_aggregate_top", "gg_debug_aggregate_top", "gg_debug_aggregate_top_listed",
+    "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -74,6 +75,15 @@ class AggStats(C.Structure):
         ("groups", C.c_uint64 * (GG_MAX_HOPS + 1)),
         ("walks", C.c_uint64 * (GG_MAX_HOPS + 1)),
         ("entries_pulled", C.c_uint64),
+    ]
+
+
+class PairStats(C.Structure):
+    _fields_ = [
+        ("pairs", C.c_uint64 * (GG_MAX_HOPS + 1)),
+        ("walks", C.c_uint64 * (GG_MAX_HOPS + 1)),
+        ("entries_pulled", C.c_uint64),
+        ("rows_gathered", C.c_uint64),
     ]
 
 
@@ -195,6 +205,11 @@ def load_library(path: str | None = None):
     lib.gg_khop_aggregate_top.argtypes = [P, P, C.c_int, C.c_int, C.c_int, u64, P, i64p, C.POINTER(TopStats), C.POINTER(P)]
     lib.gg_debug_aggregate_top.argtypes = [P, C.c_int, C.c_uint32]
     lib.gg_debug_aggregate_top_listed.argtypes = [P, C.POINTER(u64)]
+    lib.gg_khop_pair_counts.argtypes = [P, P, i64p, C.c_int, C.c_int, C.c_int, i64p, u64, C.POINTER(PairStats),
+                                        C.POINTER(P)]
+    lib.gg_khop_pair_counts_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
+    lib.gg_khop_pair_counts_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    lib.gg_debug_pair_counts.argtypes = [P, C.c_uint32, C.c_int]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
     lib.gg_profile_reset.argtypes = [P]
@@ -363,6 +378,51 @@ class KhopAggregate:
         if self.handle:
             self.gg.lib.gg_result_destroy(self.handle)
             self.handle = None
+
+
+class KhopPairCounts:
+    """Walks counted per (source, end vertex) pair (gg_khop_pair_counts), left in HBM: per level one row (source index,
+    vertex id, walks) per pair, ascending by (source index, dense index of the vertex).  A source list longer than 64 is
+    several batches: `parts` holds (result handle, first source index) per batch.  stats: {"pairs", "walks",
+    "entries_pulled", "rows_gathered"} summed over the batches; no parts: the call asked for the stats only."""
+
+    def __init__(self, gg: "GG", parts, stats):
+        self.gg, self.parts, self.stats = gg, parts, stats
+
+    def rows(self, h: int) -> int:
+        total = 0
+        for handle, _ in self.parts:
+            n = C.c_uint64()
+            self.gg._chk(self.gg.lib.gg_khop_pair_counts_rows(handle, h, C.byref(n)))
+            total += int(n.value)
+        return total
+
+    def fetch(self, h: int):
+        """(src_index int64, vertex_id int64, walks uint64) of level h, the batches one after the other"""
+        i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+        out = []
+        for handle, base in self.parts:
+            cnt = C.c_uint64()
+            self.gg._chk(self.gg.lib.gg_khop_pair_counts_rows(handle, h, C.byref(cnt)))
+            n = int(cnt.value)
+            idx, ids, walks = np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.uint64)
+            got, o = C.c_uint32(), 0
+            while o < n:
+                self.gg._chk(self.gg.lib.gg_khop_pair_counts_fetch(
+                    handle, h, o, min(n - o, 1 << 20), idx[o:].ctypes.data_as(i64p), ids[o:].ctypes.data_as(i64p),
+                    walks[o:].ctypes.data_as(u64p), C.byref(got)))
+                if not got.value:
+                    raise GGError(-6, f"gg_khop_pair_counts_fetch: no row at offset {o} of {n}")
+                o += got.value
+            out.append((idx + base, ids, walks))
+        if not out:
+            return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.uint64)
+        return tuple(np.concatenate([part[c] for part in out]) for c in range(3))
+
+    def close(self):
+        for handle, _ in self.parts:
+            self.gg.lib.gg_result_destroy(handle)
+        self.parts = []
 
 
 class WalkClosure:
@@ -1051,6 +1111,49 @@ class GG:
     def debug_aggregate_long_row(self, n: int = 0):
         """gg_khop_aggregate gives rows of more than n entries to a whole workgroup each (0: the default)."""
         self._chk(self.lib.gg_debug_aggregate_long_row(self.ctx, int(n)))
+
+    # ---- walks counted per (source, end vertex) pair
+    def khop_pair_counts(self, csr: Csr, k_min: int, k_max: int, sources=None, targets=None,
+                         fetch: bool = True) -> "KhopPairCounts":
+        """gg_khop_pair_counts: per level h in k_min..k_max one row (index into `sources`, end vertex id, walks) per pair
+        with walks != 0.  sources None: every vertex in vertex-table order; a list longer than 64 runs in batches of 64, one
+        C call each, the rows concatenated with the batch's offset added to the source index and the stats added (walks
+        mod 2^64).  targets: only these ids may end a row (None: every vertex; an empty list: no rows).  fetch=False: the
+        stats only, nothing is kept on the device."""
+        if sources is None:
+            a = np.ascontiguousarray(csr.export()[3], dtype=np.int64)
+        else:
+            a = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        tp, nt = None, 0
+        if targets is not None:
+            t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+            keep = t if t.size else np.zeros(1, np.int64)  # (an empty list is a list: the pointer must not be NULL)
+            tp, nt = keep.ctypes.data_as(C.POINTER(C.c_int64)), t.size
+        d = {"pairs": [0] * (GG_MAX_HOPS + 1), "walks": [0] * (GG_MAX_HOPS + 1), "entries_pulled": 0, "rows_gathered": 0}
+        out = KhopPairCounts(self, [], d)
+        try:
+            for base in range(0, a.size, GG_BFS_LANES):  # (an empty list: no batch, no rows)
+                part = np.ascontiguousarray(a[base:base + GG_BFS_LANES])
+                st, res = PairStats(), C.c_void_p()
+                self._chk(self.lib.gg_khop_pair_counts(
+                    self.ctx, csr.handle, part.ctypes.data_as(C.POINTER(C.c_int64)), part.size,
+                    k_min, k_max, tp, nt, C.byref(st), C.byref(res) if fetch else None))
+                if fetch:
+                    out.parts.append((res, base))
+                for h in range(GG_MAX_HOPS + 1):
+                    d["pairs"][h] += int(st.pairs[h])
+                    d["walks"][h] = (d["walks"][h] + int(st.walks[h])) % (1 << 64)
+                d["entries_pulled"] += int(st.entries_pulled)
+                d["rows_gathered"] += int(st.rows_gathered)
+        except Exception:
+            out.close()
+            raise
+        return out
+
+    def debug_pair_counts(self, long_row_entries: int = 0, gather_mode: int = 0):
+        """gg_khop_pair_counts gives in-rows of more than long_row_entries entries to a whole workgroup each (0: the
+        default) and with gather_mode 1 reads every entry's state row whatever its mask."""
+        self._chk(self.lib.gg_debug_pair_counts(self.ctx, int(long_row_entries), int(gather_mode)))
 
     def debug_triangle_tile(self, n: int = 0):
         """gg_triangles stages at most n entries of an in-row in LDS (0: the default); longer rows are searched in

@@ -701,6 +701,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
+	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();
 }

@@ -101,6 +101,9 @@ void GGRegisterEdgeFilterFunctions(ClientContext &context);
 //! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
 void GGRegisterAggregateFunctions(ClientContext &context);
 
+//! gg_pair_counts.cpp: registers gg_khop_pair_counts (inside the caller's transaction)
+void GGRegisterPairCountFunctions(ClientContext &context);
+
 //! gg_plan_rule.cpp: hand the planner rules to the interposition shim if it is loaded; registers
 //! `PRAGMA enable_gpu_graph` / `PRAGMA disable_gpu_graph`.
 void GGRegisterPlanRules(ClientContext &context);

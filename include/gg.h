@@ -460,6 +460,49 @@ int gg_khop_aggregate_top(gg_ctx *ctx, const gg_result *agg, int hops, int order
                           const gg_csr *csr /* needed iff bias */, const int64_t *bias /* V entries or NULL */,
                           gg_top_stats *stats /* nullable */, gg_result **out_result);
 
+/* ---- walks counted per (source, end vertex) pair, 64 sources a pass -------------------------------- */
+/* count(*) over the h-hop walks grouped by BOTH ends — the pair form of benchmark/ldbc/queries/bi-14.sql:103-112
+ * (GROUP BY person1id, person2id); with h = 2 over a mirrored knows the mutual-friend count behind
+ * interactive-complex-10.sql:19-24; and, as the rows with walks != 0, the SELECT DISTINCT p1, p2 of bi-14.sql:30-102.  The
+ * reference computes it with PhysicalHashAggregate on two keys
+ * (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266) above a chain of hash joins
+ * (ScanStructure::NextInnerJoin, src/execution/join_hashtable.cpp:442-476), forming every walk row only to fold it away.
+ * Lane i is src_ids[i] (1 <= n_src <= GG_BFS_LANES): each listed position is its own lane, so a duplicate id gives two
+ * lanes with equal rows, and a source that is not a vertex has no rows.  Level h in [k_min, k_max] has one row
+ * (i, id(v), walks) per lane i and vertex v whose walks != 0, walks being the number of h-walks src_ids[i] -> v.  Parallel
+ * edge rows and self-loops multiply as in the walk table.  walks is a u64 and wraps mod 2^64 like gg_khop_count's counters;
+ * a pair exists iff its wrapped count is not 0.
+ * Targets: dst_ids NULL: every vertex may end a row; else only the vertices whose id is listed may (ids that are no
+ * vertices are ignored, duplicates collapse, n_dst == 0 gives no rows — gg_bfs64's convention).  The filter applies to the
+ * rows reported, never to the recurrence.
+ * The rows of a level ascend by (source index, dense index of the end vertex) — gg_reach_closure's (class, vertex) order —
+ * placed by count, scan, write: the same on every run, on every route and under every knob.
+ * Cost: k_max passes over all E reverse entries whatever the source count; an entry none of whose 64 lanes is alive costs
+ * its 4-byte index and an 8-byte mask, a live one a 512-byte row of the state.  State: 2 x 512 V bytes on the device.
+ * stats (nullable): per level the rows and the sum of their walks (without targets walks[h] equals
+ * gg_khop_count(csr, src_ids, n_src, h, h)'s rows[h]), the reverse entries looked at and how many of them were gathered.
+ * out_result (NULL: stats only) answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only — every other fetcher
+ * refuses it with GG_ERR_STATE, and the two calls refuse every other result with GG_ERR_STATE.  Edge rowids are not needed.
+ * GG_ERR_INVALID_ARG: NULL ctx, csr or src_ids, objects of another context, n_src outside 1..GG_BFS_LANES, hops outside
+ * 1..GG_MAX_HOPS, k_min > k_max, dst_ids NULL with n_dst != 0, stats and out_result both NULL; GG_ERR_STATE: a shard CSR;
+ * GG_ERR_TOO_LARGE: a level of 2^32 rows or more (decided from a 64-bit count); GG_ERR_OOM: the state does not fit.  The
+ * context stays usable. */
+typedef struct gg_pair_stats {
+  uint64_t pairs[GG_MAX_HOPS + 1];   /* rows of level h */
+  uint64_t walks[GG_MAX_HOPS + 1];   /* sum of those rows' walks, mod 2^64 */
+  uint64_t entries_pulled;           /* reverse entries looked at over all passes */
+  uint64_t rows_gathered;            /* of those, the ones whose 512-byte state row was read (mask != 0) */
+} gg_pair_stats;
+int gg_khop_pair_counts(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src /* 1..GG_BFS_LANES */,
+                        int k_min, int k_max, const int64_t *dst_ids /* nullable */, uint64_t n_dst,
+                        gg_pair_stats *stats /* nullable */, gg_result **out_result /* NULL: stats only */);
+/* rows of level `hops` (inside the call's [k_min, k_max], else GG_ERR_INVALID_ARG) */
+int gg_khop_pair_counts_rows(const gg_result *res, int hops, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows) of level `hops`, in row order, into host arrays of >= max_rows entries (any of the
+ * three may be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
+int gg_khop_pair_counts_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *src_index,
+                              int64_t *vertex_id, uint64_t *walks, uint32_t *n_out);
+
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {
   uint32_t levels;               /* levels expanded */
@@ -702,6 +745,12 @@ int gg_debug_aggregate_top(gg_ctx *ctx, int sort_route /* 0 auto, 1 LDS, 2 globa
 /* Diagnostics: the entries of the candidate list the selection of the LAST successful gg_khop_aggregate_top with
  * 0 < n < rows wrote (0: it never compacted; its passes read every row).  Read-only. */
 int gg_debug_aggregate_top_listed(gg_ctx *ctx, uint64_t *list_entries);
+/* Testing knob: gg_khop_pair_counts gives in-rows of more than `long_row_entries` entries to a whole workgroup each and
+ * shorter ones to one wavefront (1: every row of two entries or more is long; UINT32_MAX: none is; 0: the default, 512), and
+ * with gather_mode 1 reads the state row of every entry whatever its mask (0: entries whose mask is 0 are skipped).  Rows
+ * and entries_pulled must not depend on either; rows_gathered equals entries_pulled with gather_mode 1.  A gather_mode
+ * outside 0..1 is GG_ERR_INVALID_ARG. */
+int gg_debug_pair_counts(gg_ctx *ctx, uint32_t long_row_entries /* 0: default */, int gather_mode /* 0 auto, 1 never skip */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
