@@ -197,6 +197,10 @@ struct gg_ctx {
   uint32_t agg_top_floor = 0;   // gg_debug_aggregate_top: candidates at which the selection compacts them (0: the default)
   uint32_t pc_long_row = 0;     // gg_debug_pair_counts: in-rows of more entries go to a workgroup each (0: the default)
   int pc_gather_mode = 0;       // gg_debug_pair_counts: 0 entries whose mask is 0 are skipped, 1 every state row is read
+  int cc_init_mode = 0;         // gg_debug_components: 0 the default start of the forest, 1 every vertex its own root (the same)
+  uint32_t cc_jumps_per_check = 0;  // gg_debug_components: pointer-doubling launches per look at the changed word (0: the default)
+  bool cc_size_fold = true;     // GG_CC_SIZE_FOLD=0 at context creation: gg_components adds sizes per lane, never per wave
+                                // (a measurement switch, scripts/bench_components.py; sizes are the same either way)
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
   bool profiling = false;
   std::vector<std::string> prof_names;
@@ -321,6 +325,9 @@ struct gg_result {
   // gg_khop_pair_counts (pair_counts: k_min > k_max too, the levels in agg_k_min / agg_k_max): rows[h] pairs, cols[h][0..2] =
   // source index, vertex id, walks (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch)
   bool pair_counts = false;
+  // gg_components (components: k_min > k_max too): rows[0] = V, cols[0][0..2] = vertex id, component id, size; rows[1]
+  // components, cols[1][0..1] = component id, size (gg_components_rows / gg_components_fetch / gg_components_fetch_sizes)
+  bool components = false;
 };
 
 namespace gg {
@@ -357,8 +364,13 @@ using Owner = std::unique_ptr<T, DestroyWith<T, Destroy>>;
 using ResultOwner = Owner<gg_result, gg_result_destroy>;
 
 // GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only; and
-// for one of gg_khop_pair_counts, which answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only
+// for one of gg_khop_pair_counts, which answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only; and for one of
+// gg_components, which answers gg_components_rows / gg_components_fetch / gg_components_fetch_sizes only
 inline int refuse_aggregate(const gg_result *res, const char *fn) {
+  if (res && res->components) {
+    set_error("%s: the result holds components (gg_components_rows / gg_components_fetch[_sizes] read it)", fn);
+    return GG_ERR_STATE;
+  }
   if (res && res->pair_counts) {
     set_error("%s: the result holds pair counts (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch read it)", fn);
     return GG_ERR_STATE;

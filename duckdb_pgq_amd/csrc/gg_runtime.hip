@@ -447,6 +447,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->agg_top_floor = 0;
   ctx->pc_long_row = 0;
   ctx->pc_gather_mode = 0;
+  ctx->cc_init_mode = 0;
+  ctx->cc_jumps_per_check = 0;
   ctx->keep_edge_rowid = true;
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));
@@ -511,6 +513,7 @@ extern "C" int gg_ctx_create(int device, gg_ctx **out) {
   if (const char *e = getenv("GG_PLACE_PROBES")) ctx->place_probes = atoi(e) > 0 ? (atoi(e) < 16 ? atoi(e) : 16) : 1;
   if (const char *e = getenv("GG_MIRROR_PAIRS")) ctx->mirror_pairs = atoi(e) != 0;
   if (const char *e = getenv("GG_MIRROR_REVERSE")) ctx->mirror_reverse = atoi(e) != 0;
+  if (const char *e = getenv("GG_CC_SIZE_FOLD")) ctx->cc_size_fold = atoi(e) != 0;
   for (int i = 0; i < 2; i++) {
     GG_HIP(hipHostMalloc((void **)&ctx->pin_v[i], gg_ctx::STAGE_ROWS * sizeof(int64_t), hipHostMallocDefault));
     GG_HIP(hipEventCreateWithFlags(&ctx->pin_v_free[i], hipEventDisableTiming));

@@ -34,6 +34,7 @@ SYMBOLS = [
     "gg_khop_aggregate", "gg_khop_aggregate_rows", "gg_khop_aggregate_fetch", "gg_debug_aggregate_long_row",
     "gg_khop_aggregate_top", "gg_debug_aggregate_top", "gg_debug_aggregate_top_listed",
     "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
+    "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -84,6 +85,18 @@ class PairStats(C.Structure):
         ("walks", C.c_uint64 * (GG_MAX_HOPS + 1)),
         ("entries_pulled", C.c_uint64),
         ("rows_gathered", C.c_uint64),
+    ]
+
+
+class CcStats(C.Structure):
+    _fields_ = [
+        ("vertices", C.c_uint64),
+        ("components", C.c_uint64),
+        ("largest", C.c_uint64),
+        ("singletons", C.c_uint64),
+        ("entries_read", C.c_uint64),
+        ("hooks", C.c_uint64),
+        ("jump_launches", C.c_uint32),
     ]
 
 
@@ -210,6 +223,11 @@ def load_library(path: str | None = None):
     lib.gg_khop_pair_counts_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_khop_pair_counts_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.gg_debug_pair_counts.argtypes = [P, C.c_uint32, C.c_int]
+    lib.gg_components.argtypes = [P, P, C.POINTER(CcStats), C.POINTER(P)]
+    lib.gg_components_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
+    lib.gg_components_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    lib.gg_components_fetch_sizes.argtypes = [P, u64, C.c_uint32, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    lib.gg_debug_components.argtypes = [P, C.c_int, C.c_uint32]
     lib.gg_profile_enable.argtypes = [P, C.c_int]
     lib.gg_profile_select.argtypes = [P, C.c_char_p]
     lib.gg_profile_reset.argtypes = [P]
@@ -1154,6 +1172,44 @@ class GG:
         """gg_khop_pair_counts gives in-rows of more than long_row_entries entries to a whole workgroup each (0: the
         default) and with gather_mode 1 reads every entry's state row whatever its mask."""
         self._chk(self.lib.gg_debug_pair_counts(self.ctx, int(long_row_entries), int(gather_mode)))
+
+    # ---- weakly connected components
+    def components(self, csr: Csr, fetch: bool = True) -> dict:
+        """gg_components: {"stats": {...}} and, with fetch, table 0 as "vertex", "component" (int64) and "size" (uint64), one
+        row per vertex in vertex-table order, and table 1 as "components" (int64) and "sizes" (uint64), one row per component
+        ascending by its representative's position.  A component's id is the id of its first vertex in the vertex table."""
+        st, res = CcStats(), C.c_void_p()
+        self._chk(self.lib.gg_components(self.ctx, csr.handle, C.byref(st), C.byref(res) if fetch else None))
+        out = {"stats": {name: int(getattr(st, name)) for name, _ in CcStats._fields_}}
+        if not fetch:
+            return out
+        i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+        try:
+            tables = []
+            for table in (0, 1):
+                cnt = C.c_uint64()
+                self._chk(self.lib.gg_components_rows(res, table, C.byref(cnt)))
+                n = int(cnt.value)
+                cols = [np.empty(n, np.int64) for _ in range(2 - table)] + [np.empty(n, np.uint64)]
+                got, o = C.c_uint32(), 0
+                while o < n:
+                    ptrs = [c[o:].ctypes.data_as(i64p) for c in cols[:-1]] + [cols[-1][o:].ctypes.data_as(u64p)]
+                    fn = self.lib.gg_components_fetch_sizes if table else self.lib.gg_components_fetch
+                    self._chk(fn(res, o, min(n - o, 1 << 20), *ptrs, C.byref(got)))
+                    if not got.value:
+                        raise GGError(-6, f"gg_components_fetch: no row at offset {o} of {n}")
+                    o += got.value
+                tables.append(cols)
+        finally:
+            self.lib.gg_result_destroy(res)
+        out["vertex"], out["component"], out["size"] = tables[0]
+        out["components"], out["sizes"] = tables[1]
+        return out
+
+    def debug_components(self, init_mode: int = 0, jumps_per_check: int = 0):
+        """gg_components looks at the flatten's changed word once per jumps_per_check launches (0: the default); init_mode 1
+        starts every vertex as its own root, which is also the default start (0)."""
+        self._chk(self.lib.gg_debug_components(self.ctx, int(init_mode), int(jumps_per_check)))
 
     def debug_triangle_tile(self, n: int = 0):
         """gg_triangles stages at most n entries of an in-row in LDS (0: the default); longer rows are searched in

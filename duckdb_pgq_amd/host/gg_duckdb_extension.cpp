@@ -702,6 +702,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
+	GGRegisterComponentFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();
 }

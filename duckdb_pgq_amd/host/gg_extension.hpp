@@ -104,6 +104,9 @@ void GGRegisterAggregateFunctions(ClientContext &context);
 //! gg_pair_counts.cpp: registers gg_khop_pair_counts (inside the caller's transaction)
 void GGRegisterPairCountFunctions(ClientContext &context);
 
+//! gg_components.cpp: registers gg_components and gg_component_sizes (inside the caller's transaction)
+void GGRegisterComponentFunctions(ClientContext &context);
+
 //! gg_plan_rule.cpp: hand the planner rules to the interposition shim if it is loaded; registers
 //! `PRAGMA enable_gpu_graph` / `PRAGMA disable_gpu_graph`.
 void GGRegisterPlanRules(ClientContext &context);

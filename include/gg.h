@@ -503,6 +503,51 @@ int gg_khop_pair_counts_rows(const gg_result *res, int hops, uint64_t *n_rows);
 int gg_khop_pair_counts_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *src_index,
                               int64_t *vertex_id, uint64_t *walks, uint32_t *n_out);
 
+/* ---- weakly connected components: a label and a size per vertex ------------------------------------ */
+/* "Which vertices hang together, and how big is each piece."  In the reference that is a UNION recursive CTE under an
+ * aggregate,
+ *     WITH RECURSIVE cc(v, root) AS (SELECT id, id FROM vertices
+ *                                    UNION SELECT u.b, cc.root FROM cc, und u WHERE cc.v = u.a)   -- und: both directions
+ *     SELECT v, min(root), count(*) FROM cc GROUP BY v
+ * PhysicalRecursiveCTE (src/execution/operator/set/physical_recursive_cte.cpp:47-139) re-runs the arm's hash join once per
+ * level and probes sum |component|^2 rows against one GroupedAggregateHashTable
+ * (src/execution/aggregate_hashtable.cpp:367-504) before PhysicalHashAggregate
+ * (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266) folds them: quadratic in the size of the giant
+ * component.  gg_reach_closure with one class per vertex would need V x V visited bits, gg_bfs64 V / 64 passes.  Here it is
+ * one pass over the edge entries with a lock-free union-find, a pointer-doubling flatten and a count.
+ * Two vertices are in one component iff a path of kept edge rows joins them, direction ignored: u -> v alone joins u and v.
+ * Self-loops and parallel rows change nothing; rows dropped as dangling at build time do not exist; a vertex without kept
+ * edges is a component of one.  The representative of a component is its member with the smallest dense index
+ * (vertex-table position) and component_id is that vertex's id: the answer is a function of the tables alone, the same on
+ * every run, on every build form and under every knob.
+ * Table 0: V rows (vertex id, component_id, size of its component) in dense-index order.  Table 1: one row (component_id,
+ * size) per component, ascending by the representative's dense index, placed by count, scan, write.
+ * Cost: the E edge entries once (8 B each), 12 V bytes per pointer-doubling launch, 28 V bytes for sizes and table 0.
+ * Edge rowids are not needed.  V == 0: GG_OK with two empty tables.
+ * out_result (NULL: stats only) answers gg_components_rows / gg_components_fetch / gg_components_fetch_sizes only — every
+ * other fetcher refuses it with GG_ERR_STATE, and the three calls refuse every other result with GG_ERR_STATE.
+ * GG_ERR_INVALID_ARG: NULL ctx or csr, objects of another context, stats and out_result both NULL; GG_ERR_STATE: a shard
+ * CSR.  The context stays usable. */
+typedef struct gg_cc_stats {
+  uint64_t vertices;      /* V */
+  uint64_t components;    /* number of components (a vertex without kept edges is one) */
+  uint64_t largest;       /* members of the largest component (0 if V == 0) */
+  uint64_t singletons;    /* components of exactly one vertex */
+  uint64_t entries_read;  /* edge entries looked at (= kept edges of the CSR) */
+  uint64_t hooks;         /* successful links; equals vertices - components */
+  uint32_t jump_launches; /* pointer-doubling launches of the flatten: <= ceil(log2(max(V, 2))) + jumps_per_check */
+} gg_cc_stats;
+int gg_components(gg_ctx *ctx, const gg_csr *csr, gg_cc_stats *stats /* nullable */,
+                  gg_result **out_result /* NULL: stats only */);
+/* rows of table 0 (one per vertex) or 1 (one per component); another table is GG_ERR_INVALID_ARG */
+int gg_components_rows(const gg_result *res, int table, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows) of table 0 / of table 1, in row order, into host arrays of >= max_rows entries (any
+ * of them may be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
+int gg_components_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *vertex_id,
+                        int64_t *component_id, uint64_t *size /* each nullable */, uint32_t *n_out);
+int gg_components_fetch_sizes(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *component_id,
+                              uint64_t *size /* each nullable */, uint32_t *n_out);
+
 /* ---- 64-lane bitset BFS (shortest path length) --------------------------------------------- */
 typedef struct gg_bfs_stats {
   uint32_t levels;               /* levels expanded */
@@ -751,6 +796,13 @@ int gg_debug_aggregate_top_listed(gg_ctx *ctx, uint64_t *list_entries);
  * and entries_pulled must not depend on either; rows_gathered equals entries_pulled with gather_mode 1.  A gather_mode
  * outside 0..1 is GG_ERR_INVALID_ARG. */
 int gg_debug_pair_counts(gg_ctx *ctx, uint32_t long_row_entries /* 0: default */, int gather_mode /* 0 auto, 1 never skip */);
+/* Testing knob: gg_components looks at the flatten's changed word once per `jumps_per_check` pointer-doubling launches
+ * (0: the default, 4).  init_mode 0 is the default start of the forest and 1 starts every vertex as its own root; the two
+ * are the same start since the other candidate (under the first smaller out-neighbour) measured slower and was removed.
+ * Rows and every stats field but jump_launches must not depend on either.  An init_mode outside 0..1 is
+ * GG_ERR_INVALID_ARG. */
+int gg_debug_components(gg_ctx *ctx, int init_mode /* 0 default, 1 every vertex starts as its own root */,
+                        uint32_t jumps_per_check /* 0: default */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
