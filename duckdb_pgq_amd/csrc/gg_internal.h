@@ -199,6 +199,7 @@ struct gg_ctx {
   int pc_gather_mode = 0;       // gg_debug_pair_counts: 0 entries whose mask is 0 are skipped, 1 every state row is read
   int cc_init_mode = 0;         // gg_debug_components: 0 the default start of the forest, 1 every vertex its own root (the same)
   uint32_t cc_jumps_per_check = 0;  // gg_debug_components: pointer-doubling launches per look at the changed word (0: the default)
+  uint32_t extend_tile_rows = 0;    // gg_debug_extend: output rows per workgroup of gg_result_extend_edge's write pass (0: the default)
   bool cc_size_fold = true;     // GG_CC_SIZE_FOLD=0 at context creation: gg_components adds sizes per lane, never per wave
                                 // (a measurement switch, scripts/bench_components.py; sizes are the same either way)
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to

@@ -449,6 +449,7 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->pc_gather_mode = 0;
   ctx->cc_init_mode = 0;
   ctx->cc_jumps_per_check = 0;
+  ctx->extend_tile_rows = 0;
   ctx->keep_edge_rowid = true;
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));

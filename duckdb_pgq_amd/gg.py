@@ -35,6 +35,7 @@ SYMBOLS = [
     "gg_khop_aggregate_top", "gg_debug_aggregate_top", "gg_debug_aggregate_top_listed",
     "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
     "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
+    "gg_result_extend_edge", "gg_debug_extend",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -69,6 +70,10 @@ class TriStats(C.Structure):
 
 class EdgeFilterStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("matches", C.c_uint64)]
+
+
+class ExtendStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("rows_matched", C.c_uint64)]
 
 
 class AggStats(C.Structure):
@@ -195,6 +200,9 @@ def load_library(path: str | None = None):
     lib.gg_level_sets.argtypes = [P, P, i64p, C.POINTER(C.c_uint32), u64, C.c_uint32, C.c_int, C.POINTER(P)]
     lib.gg_level_sets_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_level_sets_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    lib.gg_result_extend_edge.argtypes = [P, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.POINTER(ExtendStats),
+                                          C.POINTER(P)]
+    lib.gg_debug_extend.argtypes = [P, C.c_uint32]
     lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
@@ -760,6 +768,23 @@ class GG:
                                                  EDGE_MODES[mode], int(materialise), C.byref(st), C.byref(out)))
         d = {"rows_in": int(st.rows_in), "rows_out": int(st.rows_out), "matches": int(st.matches)}
         return (d, KhopResult(self, out, d)) if materialise else d
+
+    def extend_edge(self, res: KhopResult, hops: int, csr: Csr, from_col: int, edges: bool = False,
+                    materialise: bool = True):
+        """gg_result_extend_edge: every row of res's `hops`-hop table joined with the edge rows of csr whose source is the
+        row's cell in from_col — one output row (v0..v_hops, w) per such edge row, input order kept, the copies of a row in
+        CSR order.  edges: the output carries e1..e_{hops+1} (fetch_edges), the last being the joined row's rowid.  Returns
+        {"rows_in", "rows_out", "rows_matched"}; with materialise, (that dict, KhopResult whose table hops + 1 holds the
+        rows — the caller closes it)."""
+        st, out = ExtendStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_extend_edge(self.ctx, res.handle, hops, csr.handle, from_col, int(edges),
+                                                 int(materialise), C.byref(st), C.byref(out)))
+        d = {"rows_in": int(st.rows_in), "rows_out": int(st.rows_out), "rows_matched": int(st.rows_matched)}
+        return (d, KhopResult(self, out, d)) if materialise else d
+
+    def debug_extend(self, tile_rows: int = 0):
+        """Output rows per workgroup of extend_edge's write pass (0: the default).  Results must not depend on it."""
+        self._chk(self.lib.gg_debug_extend(self.ctx, int(tile_rows)))
 
     def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
         """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows

@@ -23,6 +23,12 @@
 //                                              (one row per such edge row), 'semi' (EXISTS), 'anti' (NOT EXISTS)
 //   gg_khop_edge_filter_count(same arguments)
 //        -> (rows BIGINT, walks BIGINT, matches BIGINT)          (gg_edge_filter.cpp)
+//   gg_khop_extend(vertex_table, vertex_key, edge_table, src_col, dst_col, sources_sql, hops,
+//                  ext_table, ext_key_col, ext_next_col, from_col)
+//        -> (v0 BIGINT, ..., v{hops} BIGINT, w BIGINT, ext_rowid BIGINT)   walks from the sources joined with the rows of
+//                                              a second keyed table on v{from_col} = ext_key_col, with the row's rowid
+//   gg_khop_extend_count(same arguments)
+//        -> (rows BIGINT, walks BIGINT, matched BIGINT)          (gg_extend.cpp)
 //   gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //                           filter_table, filter_src, filter_dst, hops)
 //        -> (w BIGINT, v0 BIGINT, ..., v{hops} BIGINT)      Train Benchmark ConnectedSegments
@@ -700,6 +706,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &pins_info);
 	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterEdgeFilterFunctions(*con.context);
+	GGRegisterExtendFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterComponentFunctions(*con.context);

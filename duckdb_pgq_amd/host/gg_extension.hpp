@@ -98,6 +98,9 @@ void GGRegisterTriangleFunctions(ClientContext &context);
 //! gg_edge_filter.cpp: registers gg_khop_edge_filter / gg_khop_edge_filter_count (inside the caller's transaction)
 void GGRegisterEdgeFilterFunctions(ClientContext &context);
 
+//! gg_extend.cpp: registers gg_khop_extend / gg_khop_extend_count (inside the caller's transaction)
+void GGRegisterExtendFunctions(ClientContext &context);
+
 //! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
 void GGRegisterAggregateFunctions(ClientContext &context);
 

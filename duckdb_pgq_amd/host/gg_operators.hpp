@@ -136,7 +136,7 @@ public:
 	shared_ptr<GGGraph> graph;
 	int64_t *memory = nullptr;
 	idx_t capacity_columns = 0;
-	int64_t *column[GG_MAX_HOPS + 1];
+	int64_t *column[2 * GG_MAX_HOPS + 1]; // (GG_EXTEND: hops + 2 id columns and hops + 1 edge columns, hops < GG_MAX_HOPS)
 	idx_t rows = 0, pos = 0; // filled rows, next row to serve
 	int table = 0;           // which table of the result the slab holds (hop length / batch)
 };
@@ -451,6 +451,42 @@ public:
 	}
 	string GetName() const override {
 		return "GG_EDGE_FILTER";
+	}
+};
+
+//! Source: the `hops`-hop walks from the sources joined with the rows of a second edge table (GGGraph::filter_csr, built
+//! with rowids) whose key is column from_col of the walk (gg_result_extend_edge, include/gg.h) — the next hash join of a
+//! chain over a different build table with its payload gathered by rowid (src/execution/join_hashtable.cpp:304-476;
+//! benchmark/ldbc/queries/interactive-complex-2.sql:2-7).
+//! Output: (v0 BIGINT, ..., v{hops} BIGINT, w BIGINT, ext_rowid BIGINT); count_only: the one row (rows BIGINT, walks
+//! BIGINT, matched BIGINT).
+class PhysicalGGExtend : public PhysicalOperator {
+public:
+	PhysicalGGExtend(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int from_col,
+	                 bool count_only, idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes(int hops, bool count_only);
+
+	shared_ptr<GGGraph> graph;
+	int hops;
+	vector<int64_t> sources;
+	bool all_sources; // walks may start at any vertex
+	int from_col;
+	bool count_only;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return "GG_EXTEND";
 	}
 };
 

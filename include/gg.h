@@ -48,6 +48,12 @@
  *           ScanStructure::ScanKeyMatches + NextAntiJoin                                  join_hashtable.cpp:478-540
  *           (benchmark/ldbc/queries/interactive-complex-10.sql:19-24); EXISTS, NextSemiJoin   join_hashtable.cpp:522
  *           (interactive-complex-7.sql:5, interactive-short-7.sql:3)
+ *   gg_result_extend_edge
+ *        <- the next hash join of a chain over a DIFFERENT build table, its payload gathered by rowid: Probe +
+ *           ScanStructure::NextInnerJoin + GatherResult                                   join_hashtable.cpp:304-476
+ *           (knows -> message on k_person2id = m_creatorid, benchmark/ldbc/queries/interactive-complex-2.sql:2-7;
+ *           knows -> message -> message_tag, interactive-complex-4.sql:2-8; interactive-complex-9.sql:13-15,
+ *           interactive-complex-6.sql:14-17; a branch off a middle column, interactive-complex-5.sql:15)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -315,6 +321,42 @@ typedef struct gg_edge_filter_stats {
 } gg_edge_filter_stats;
 int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *csr, int from_col, int to_col,
                           int mode, int materialise, gg_edge_filter_stats *stats, gg_result **out_result);
+/* One more hop over a second edge table: every row of a materialised walk table joined with the edge rows of `csr` whose
+ * source is the row's cell in from_col.
+ * What it replaces in the reference: the next hash join of a chain when its build table is a different one — `knows k,
+ * message m WHERE m.m_creatorid = k.k_person2id` (benchmark/ldbc/queries/interactive-complex-2.sql:2-7), knows -> message ->
+ * message_tag (interactive-complex-4.sql:2-8), friends and friends of friends, their messages, their tags
+ * (interactive-complex-9.sql:13-15, interactive-complex-6.sql:14-17), forum_person joined on a middle column
+ * (interactive-complex-5.sql:15) — PhysicalHashJoin::Execute -> JoinHashTable::Probe + ScanStructure::NextInnerJoin, with
+ * the payload columns (m_creationdate, m_content) gathered by row in ScanStructure::GatherResult
+ * (src/execution/join_hashtable.cpp:304-476).  Without it such a plan leaves the device after the last knows hop.
+ * Input: the `hops`-hop table of `res` with its id columns v0..v_hops — whatever gg_result_filter_edge accepts, or an earlier
+ * result of this function, so patterns chain and branch; from_col is any column 0..hops.  `csr` is any whole CSR of the same
+ * context, usually over another edge table; the cell is looked up in its id dictionary exactly as gg_csr_lookup does, and an
+ * id that is no vertex of csr matches nothing.
+ * Output: table hops + 1 of *out_result (k_min = k_max = hops + 1): the input's hops + 1 columns and a new last column w, one
+ * row per kept edge row v_from_col -> w of csr.  Input rows keep their order; the copies of one input row are consecutive
+ * and in CSR order (the append order of the edge rows, the order gg_csr_export shows).  Rows are placed by count, scan,
+ * write — no atomics-ordered append — so they are identical on every run and for every gg_debug_extend tile.
+ * want_edges != 0: the output carries edge columns e1..e_{hops+1} for gg_result_fetch_edges; e_{hops+1} is the rowid of the
+ * joined edge row (the rowid the Sink passed, or the append position), e1..e_hops are the input's edge columns if it has
+ * them and -1 otherwise.  It needs a csr built with rowids (GG_ERR_STATE otherwise, as gg_expand_khop_edges).
+ * materialise == 0: only `stats` is filled, from degrees: 64-bit counters, no size limit, nothing kept per row; out_result
+ * may be NULL.  stats may be NULL when materialising.
+ * The result answers gg_result_rows, gg_result_fetch, gg_result_fetch_edges, gg_result_digest, gg_result_filter_edge,
+ * gg_result_filter_common_neighbour and this function again.
+ * Errors: NULL ctx / res / csr, objects of another context, hops outside the result's k_min..k_max, hops + 1 > GG_MAX_HOPS,
+ * from_col outside 0..hops, materialise != 0 with NULL out_result: GG_ERR_INVALID_ARG.  A shard CSR, or a result without
+ * fixed-length tables: GG_ERR_STATE.  2^32 output rows or more when materialising: GG_ERR_TOO_LARGE.  After every error the
+ * context stays usable.  An empty input table, a csr without edge rows and an input of which no row matches give GG_OK and an
+ * empty table.  If the build did not need the 16-byte id table, the first call on a CSR fills it. */
+typedef struct gg_extend_stats {
+  uint64_t rows_in;      /* rows of the input table */
+  uint64_t rows_out;     /* sum over input rows of the kept edge rows of csr whose source is v_from_col */
+  uint64_t rows_matched; /* input rows with at least one such edge row */
+} gg_extend_stats;
+int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *csr, int from_col, int want_edges,
+                          int materialise, gg_extend_stats *stats, gg_result **out_result);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
@@ -803,6 +845,10 @@ int gg_debug_pair_counts(gg_ctx *ctx, uint32_t long_row_entries /* 0: default */
  * GG_ERR_INVALID_ARG. */
 int gg_debug_components(gg_ctx *ctx, int init_mode /* 0 default, 1 every vertex starts as its own root */,
                         uint32_t jumps_per_check /* 0: default */);
+/* Testing knob: a workgroup of gg_result_extend_edge's write pass owns `tile_rows` consecutive output rows (0: the default,
+ * 1024), so parents that span many tiles and runs of input rows without an edge row that are longer than a tile occur on
+ * small graphs.  Results must not depend on it. */
+int gg_debug_extend(gg_ctx *ctx, uint32_t tile_rows /* 0: default */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
