@@ -9,8 +9,8 @@
 //   D  k_densify_pairs    one read of the (src, dst) id columns; two dictionary probes per edge row, or per PAIR of
 //                         rows where row i + E/2 mirrors row i (an undirected table loaded twice: "mirrored halves")
 //                         (gg_dict.h: direct array / packed 8-byte slots / 16-byte slots); writes the dense
-//                         pair (u, v) in rowid order; counts, per tile, the bucket of u (forward) and the
-//                         bucket of v (reverse) in LDS
+//                         pair (u, v) in rowid order (a mirrored pair once: FB_PARTNER); counts, per tile, the
+//                         bucket of u (forward) and the bucket of v (reverse) in LDS
 //      k_col_*            three small kernels: the (tile x bucket) counters of both directions -> global positions
 //   A  k_partition_dual   one read of the pairs, TWO stable bucket partitions written from one LDS staging
 //                         area: forward (low(u), v[, edge position]) by bucket(u), reverse (low(v), u) by
@@ -121,6 +121,19 @@ __device__ __forceinline__ void tile_rows(const FastGeom &g, uint64_t E, uint64_
 // Shard builds mark, in the dense pair, the direction a row does not take part in: bit 31 of u = "source not
 // owned: no forward entry", bit 31 of v = "destination not owned: no reverse entry" (dense indices stay below 2^22).
 constexpr uint32_t FB_SKIP = 0x80000000u;
+// The paired densification stores a mirrored pair once: bit 30 of the SECOND word of first-half row i's pair = "row
+// i + h is this pair swapped, and was not stored".  The second word, so that a dropped row, (INVALID_U32, ...), still
+// tests as dropped by its first word: (INVALID_U32, INVALID_U32) drops its mirrored partner with it, (INVALID_U32,
+// INVALID_U32 & ~FB_PARTNER) leaves the partner to its own stored pair.  Only first-half rows carry the mark and only
+// k_partition_dual reads it (partner_pair); shards never take the paired form, and the bit is not FB_SKIP's anyway.
+constexpr uint32_t FB_PARTNER = 0x40000000u;
+// The pair of second-half row i + h from first-half row i's marked pair p
+__device__ __forceinline__ u32x2 partner_pair(u32x2 p) {
+  u32x2 q;
+  q.x = p.x == INVALID_U32 ? INVALID_U32 : p.y & ~FB_PARTNER;
+  q.y = p.x;
+  return q;
+}
 
 // Stable ranking inside a wave.  Every ranking kernel below gives a wave its own row of LDS cursors, so the only
 // lanes that meet on a cursor belong to one instruction of one wave.  gfx950 serves the lanes of one ds_add_rtn_u32
@@ -321,8 +334,9 @@ __device__ __forceinline__ void densify_tile(const int64_t *__restrict__ src, co
 // Mirrored halves (whole builds): rows [a0, a1) of a first-half tile and their partners [b0, b1) = [a0 + h, ...)
 // of the second half, where row i + h usually is row i with source and destination swapped (an undirected edge table
 // loaded twice, the second time with the id columns exchanged).  A lane loads both rows of a pair and looks up only
-// the first one's ids; where the partner is (dst, src) of it, the partner's dense pair is (v, u) without a probe.
-// Partners that differ are looked up in a second round, which a wave skips when every one of its pairs matched.
+// the first one's ids; where the partner is (dst, src) of it, the partner's dense pair is (v, u) without a probe — and
+// without a store: row i's pair is marked FB_PARTNER instead, and the readers make the partner's pair from it.
+// Partners that differ are looked up and stored in a second round, which a wave skips when every one of its pairs matched.
 // Row b0 + k past a1 - a0 (row 2h of an odd E) has no partner and takes the first round itself.
 // hist: [4][nb], forward and reverse counts of the first tile, then of the second.  (Whole builds own everything.)
 template <int MODE>
@@ -379,18 +393,16 @@ __device__ __forceinline__ void densify_tile_pairs(const int64_t *__restrict__ s
         atomicAdd(&hf[u >> low], 1u);
         atomicAdd(&hf[nb + (v >> low)], 1u);
       }
+      // The mirrored partner, (v, u), is stored nowhere: row a's pair says so in its second word (FB_PARTNER).  A
+      // dropped row's second word has the bit set as it is; it is cleared where the partner is a row of its own.
+      const bool mir = pa && !two[j];
       u32x2 pr;
       pr.x = u;
-      pr.y = v;
+      pr.y = mir ? v | FB_PARTNER : pa ? v & (keep ? ~0u : ~FB_PARTNER) : v;
       st_stream(pairs + (pa ? a : b), pr);
-      if (pa && !two[j]) {  // the mirrored partner: (v, u), forward bucket of v, reverse bucket of u
-        if (keep) {
-          atomicAdd(&hist[2 * nb + (v >> low)], 1u);
-          atomicAdd(&hist[3 * nb + (u >> low)], 1u);
-        }
-        pr.x = v;
-        pr.y = u;
-        st_stream(pairs + b, pr);
+      if (mir && keep) {  // its counts: forward bucket of v, reverse bucket of u
+        atomicAdd(&hist[2 * nb + (v >> low)], 1u);
+        atomicAdd(&hist[3 * nb + (u >> low)], 1u);
       }
     }
     if (__ballot(any2) == 0) continue;  // (uniform) every pair of the wave mirrored
@@ -468,15 +480,19 @@ __global__ __launch_bounds__(FB_THREADS) GG_FB_DATTR void k_densify_pairs(
 // ---- A: two stable bucket partitions from one read of the pairs ---------------------------------------------
 // Element order inside a tile: wave w owns rows [w * FB_WTILE, (w + 1) * FB_WTILE), 64 consecutive rows per
 // step.  PACK: output word = low(key) << key_bits | payload; otherwise the pair (low(key), payload).
-// MIRROR: the derived-reverse form (an instantiation of its own: the kernel sits at two workgroups per CU), ONE stable
-// partition by bucket(u) of (low(u), v): first-half tiles into out_f, second-half tiles into out_r, whose positions are
-// the second set of nb columns of the tile's row of bases.  With g.derive both forms are launched, one returns at once.
+// MIRROR: the derived-reverse form (an instantiation of its own: the kernel sits at two workgroups per CU), over the
+// first-half tiles only (nblocks = g.nt1): second-half tile nt1 + t holds, row for row, tile t's pairs swapped, so its
+// partition by source is tile t's partition by destination.  Direction 0 writes (low(u), v) by bucket(u) into out_f at
+// tile t's bases, direction 1 (low(v), u) by bucket(v) into out_r at the second set of nb columns of tile nt1 + t's
+// bases; the second half of the pairs is never read.  With g.derive both forms are launched, one returns at once.
 template <bool PACK, bool ROWID, int STOP = 0, bool MIRROR = false>  // STOP > 0: timing probes that write nothing (GG_FB_A_PROBE builds)
 __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
     const u32x2 *__restrict__ pairs, uint64_t E, FastGeom g, uint64_t nblocks, const uint32_t *__restrict__ bases,
     const BuildStatus *__restrict__ st, uint32_t *__restrict__ out_f, uint32_t *__restrict__ out_r,
-    uint32_t *__restrict__ epos_f) {
+    uint32_t *__restrict__ epos_f, const uint32_t *__restrict__ mirror_tally) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  // (read next to the status word: the two scalar loads then wait together, ahead of the tile's first loads)
+  const bool paired = g.h && mirror_pays(mirror_tally);      // (uniform over the grid) the paired densification ran
   if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
   const uint32_t nb = 1u << g.hb;
   uint32_t *xw = lds;                                   // staged words (PACK) or low keys
@@ -498,17 +514,43 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const uint32_t low_mask = (1u << g.low) - 1u;
 
+  // The tile's pairs.  After the paired densification (mirror_tally says so) a second-half row's pair is stored only
+  // where it is not its partner's mirror image: a second-half tile loads the partners' pairs (row - h: the same rows of
+  // first-half tile - nt1), swaps the marked ones and loads the own pair of the others (none on a fully mirrored
+  // table); row 2h of an odd E has no partner.  First-half tiles, and every tile after the unpaired densification,
+  // load their own rows; the mark is masked off (no bit of a kept row's v otherwise, see FB_PARTNER).
   uint32_t u[FB_ITEMS], v[FB_ITEMS];
   const uint64_t wbase = tile_base + (uint64_t)wave * FB_WTILE;
+  const bool via_partner = !MIRROR && paired && tile >= g.nt1;  // (uniform over the workgroup)
+  const u32x2 *first = pairs - (via_partner ? g.h : 0);    // the rows of the first load: the tile's own, or their partners
+  const uint64_t first_end = via_partner && 2 * (uint64_t)g.h < tile_end ? 2 * (uint64_t)g.h : tile_end;
 #pragma unroll
   for (int it = 0; it < FB_ITEMS; it++) {
     const uint64_t idx = wbase + (uint64_t)it * 64 + lane;
     u32x2 p;
     p.x = INVALID_U32;
     p.y = INVALID_U32;
-    if (idx < tile_end) p = ld_stream(pairs + idx);
+    if (idx < first_end) p = ld_stream(first + idx);
     u[it] = p.x;
     v[it] = p.y;
+  }
+  if (via_partner) {
+#pragma unroll
+    for (int it = 0; it < FB_ITEMS; it++) {
+      const uint64_t idx = wbase + (uint64_t)it * 64 + lane;
+      u32x2 p;
+      p.x = u[it];
+      p.y = v[it];
+      if (idx < first_end && (p.y & FB_PARTNER))
+        p = partner_pair(p);
+      else if (idx < tile_end)  // a partner that differs, or the unpartnered last row: the row's own pair
+        p = ld_stream(pairs + idx);
+      u[it] = p.x;
+      v[it] = p.y;
+    }
+  } else if (paired) {
+#pragma unroll
+    for (int it = 0; it < FB_ITEMS; it++) v[it] &= ~FB_PARTNER;
   }
   const uint64_t lane_lt = (1ULL << lane) - 1ULL;
   uint32_t *myh = hw + wave * nb;
@@ -521,8 +563,9 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
   }
 
 #pragma unroll 1
-  for (int dir = 0; dir < (MIRROR ? 1 : 2); dir++) {
-    const uint32_t col = MIRROR ? (tile >= g.nt1 ? 1u : 0u) : (uint32_t)dir;  // the set of nb columns, and the output
+  for (int dir = 0; dir < 2; dir++) {
+    const uint32_t col = (uint32_t)dir;  // the set of nb columns, and the output
+    const uint64_t brow = MIRROR && dir ? g.nt1 + tile : tile;  // the tile whose row of bases this partition fills
     for (uint32_t i = threadIdx.x; i < FB_WAVES * nb; i += FB_THREADS) hw[i] = 0;
     __syncthreads();
     // (decided once per wave and direction, on its first 64 rows: the table's order does not change in between)
@@ -575,7 +618,7 @@ __global__ __launch_bounds__(FB_THREADS) void k_partition_dual(
       for (uint32_t q = 0; q < dpt; q++) {
         const uint32_t d = threadIdx.x * dpt + q;
         if (d < nb) {
-          gb[d] = bases[tile * 2 * nb + (uint64_t)col * nb + d] - ex;
+          gb[d] = bases[brow * 2 * nb + (uint64_t)col * nb + d] - ex;
 #pragma unroll
           for (int w = 0; w < FB_WAVES; w++) hw[w * nb + d] += ex;  // ... + the bucket's first staged slot
           ex += tot[q];
@@ -2058,13 +2101,14 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   const size_t lds_a = ((size_t)FB_TILE * (words + (rowid ? 1 : 0)) + (size_t)(FB_WAVES + 2) * nb + FB_WAVES + 2) *
                            sizeof(uint32_t) +
                        (size_t)FB_TILE * sizeof(uint16_t) + 16 + (0 ? (size_t)FB_WAVES * nb * 8 : 0);
-  const unsigned grid_a = (unsigned)(((nblocks64 + 7) / 8) * 8);
+  // (the derived-reverse form runs over the first-half tiles only)
 #define GG_FB_LAUNCH_A(NAME, P, R, M)                                                                               \
   GG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_partition_dual<P, R, 0, M>),                           \
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_a));                                \
-  GG_LAUNCH(ctx, NAME, (k_partition_dual<P, R, 0, M>), dim3(grid_a), dim3(FB_THREADS), lds_a,                        \
-            (const u32x2 *)pairs, E, g, nblocks64, (const uint32_t *)counts, (const BuildStatus *)st, part_f, part_r, \
-            epos_f)
+  GG_LAUNCH(ctx, NAME, (k_partition_dual<P, R, 0, M>),                                                               \
+            dim3((unsigned)((((M) ? (uint64_t)g.nt1 : nblocks64) + 7) / 8 * 8)), dim3(FB_THREADS), lds_a,            \
+            (const u32x2 *)pairs, E, g, (M) ? (uint64_t)g.nt1 : nblocks64, (const uint32_t *)counts,                 \
+            (const BuildStatus *)st, part_f, part_r, epos_f, (const uint32_t *)mirror_tally)
   // g.derive: the derived-reverse form and the plain one, one of which returns at once.  The plain launches are timed
   // under "<name>_plain" then, so that each name's time per launch is one form's (as with "densify_unpaired")
   if (g.derive) {
