@@ -496,7 +496,8 @@ template <typename DistT>
 static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops, const int64_t *dst_ids,
                    uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats, bool *overflow,
                    gg_result *pairs = nullptr /* filled with (source, vertex, distance) rows if non-null */,
-                   const PathsRequest *paths = nullptr /* the paths of these pairs into paths->res if non-null */) {
+                   const PathsRequest *paths = nullptr /* the paths of these pairs into paths->res if non-null */,
+                   const AllPathsRequest *all_paths = nullptr /* all shortest paths / their number (gg_all_paths.hip) */) {
   constexpr int MAX_LEVEL = sizeof(DistT) == 1 ? 254 : 65534;
   ApiScope scope(ctx);  // (per run: an 8-bit run's blocks are back in the pool before the 16-bit rerun)
   *overflow = false;
@@ -621,6 +622,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
     pairs->rows[table] = reached;
   }
   if (paths && !*overflow) GG_TRY(paths_emit(ctx, csr, dist8, sizeof(DistT), *paths));
+  if (all_paths && !*overflow) GG_TRY(all_paths_emit(ctx, csr, dist8, sizeof(DistT), st.levels, *all_paths));
   if (out_dist && !*overflow) {
     uint32_t *dst_dense = nullptr;
     int32_t *out_dev = nullptr;
@@ -637,7 +639,7 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
 
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
-                        gg_result *pairs, const PathsRequest *paths = nullptr);
+                        gg_result *pairs, const PathsRequest *paths = nullptr, const AllPathsRequest *all_paths = nullptr);
 
 extern "C" int gg_bfs64(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats) {
@@ -701,7 +703,7 @@ extern "C" int gg_bfs64_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src
 
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
-                        gg_result *pairs, const PathsRequest *paths) {
+                        gg_result *pairs, const PathsRequest *paths, const AllPathsRequest *all_paths) {
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
   if (!ctx || !csr || csr->ctx != ctx || n_src < 0 || n_src > GG_BFS_LANES || (n_src && !src_ids) ||
       (n_dst && !dst_ids)) {
@@ -714,14 +716,21 @@ static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids
   }
   // one byte per (vertex, lane) covers 254 levels; deeper searches (max_hops < 0 or > 254 only) rerun with two-byte cells
   bool overflow = false;
-  GG_TRY(bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths));
+  GG_TRY(bfs_run<uint8_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths,
+                          all_paths));
   if (!overflow) return GG_OK;
-  GG_TRY(bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths));
+  GG_TRY(bfs_run<uint16_t>(ctx, csr, src_ids, n_src, max_hops, dst_ids, n_dst, out_dist, stats, &overflow, pairs, paths,
+                           all_paths));
   if (overflow) {
     set_error("gg_bfs64: search deeper than 65534 levels is not supported");
     return GG_ERR_TOO_LARGE;
   }
   return GG_OK;
+}
+
+int gg::bfs64_all_paths_run(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
+                            gg_bfs_stats *stats, const AllPathsRequest &rq) {
+  return bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, nullptr, nullptr, &rq);
 }
 
 // ------------------------------------------------------------------------------------------------------

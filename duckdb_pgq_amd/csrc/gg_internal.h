@@ -329,6 +329,10 @@ struct gg_result {
   // gg_components (components: k_min > k_max too): rows[0] = V, cols[0][0..2] = vertex id, component id, size; rows[1]
   // components, cols[1][0..1] = component id, size (gg_components_rows / gg_components_fetch / gg_components_fetch_sizes)
   bool components = false;
+  // gg_bfs64_all_paths (all_paths: k_min > k_max too): rows[gg::AP_PAIRS_TABLE] reached pairs, cols[..][0..3] = pair index,
+  // hops (int32 cells), paths, kept; rows[gg::AP_ROWS_TABLE] path rows, cols[..][0..4] = pair index, path index, step (int32
+  // cells), vertex id, and the edge rowid if edges were asked for (gg_bfs64_all_paths_rows / _fetch_pairs / _fetch)
+  bool all_paths = false;
 };
 
 namespace gg {
@@ -366,8 +370,15 @@ using ResultOwner = Owner<gg_result, gg_result_destroy>;
 
 // GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only; and
 // for one of gg_khop_pair_counts, which answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only; and for one of
-// gg_components, which answers gg_components_rows / gg_components_fetch / gg_components_fetch_sizes only
+// gg_components, which answers gg_components_rows / gg_components_fetch / gg_components_fetch_sizes only; and for one of
+// gg_bfs64_all_paths, which answers gg_bfs64_all_paths_rows / gg_bfs64_all_paths_fetch_pairs / gg_bfs64_all_paths_fetch only
+inline int refuse_all_paths(const gg_result *res, const char *fn) {
+  if (!res || !res->all_paths) return GG_OK;
+  set_error("%s: the result holds all shortest paths (gg_bfs64_all_paths_rows / _fetch_pairs / _fetch read it)", fn);
+  return GG_ERR_STATE;
+}
 inline int refuse_aggregate(const gg_result *res, const char *fn) {
+  GG_TRY(refuse_all_paths(res, fn));
   if (res && res->components) {
     set_error("%s: the result holds components (gg_components_rows / gg_components_fetch[_sizes] read it)", fn);
     return GG_ERR_STATE;
@@ -716,5 +727,26 @@ struct PathsRequest {
 };
 // dist: the batch's [V][64] distance cells of cell_bytes (1 or 2) each, on the device.  Fills rq.res; synchronises.
 int paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, const PathsRequest &rq);
+
+// ---- all shortest paths and their number off a finished BFS batch (gg_all_paths.hip; called by bfs_run in gg_bfs.hip)
+constexpr int AP_PAIRS_TABLE = 0, AP_ROWS_TABLE = 1;  // the gg_result tables of the reached pairs and of the path rows
+struct AllPathsRequest {
+  const int64_t *src_ids;       // host, n_src: the batch's sources (the seeds of the count)
+  int n_src;
+  const uint32_t *pair_lane;    // host, n_pairs: the pair's source as an index into the batch's source list
+  const int64_t *pair_dst_ids;  // host, n_pairs
+  uint64_t n_pairs;
+  uint64_t path_limit;          // 0: none
+  bool want_edges;
+  bool materialise;
+  gg_all_paths_stats *stats;    // nullable; its bfs member is left alone
+  gg_result *res;               // nullable: totals only
+};
+// dist: as paths_emit; levels: the BFS levels that ran.  Fills rq.stats and rq.res; synchronises.
+int all_paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, uint32_t levels,
+                   const AllPathsRequest &rq);
+// gg_bfs64's dispatch (8-bit cells, 16-bit rerun) with the request handed to bfs_run (gg_bfs.hip)
+int bfs64_all_paths_run(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
+                        gg_bfs_stats *stats, const AllPathsRequest &rq);
 
 }  // namespace gg

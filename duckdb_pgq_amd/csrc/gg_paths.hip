@@ -278,6 +278,7 @@ int paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, co
 }  // namespace gg
 
 extern "C" int gg_bfs64_paths_rows(const gg_result *res, uint64_t *n_rows) {
+  GG_TRY(refuse_all_paths(res, "gg_bfs64_paths_rows"));
   if (!res || !res->paths || !n_rows) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[PATHS_TABLE];
   return GG_OK;
@@ -285,6 +286,7 @@ extern "C" int gg_bfs64_paths_rows(const gg_result *res, uint64_t *n_rows) {
 
 extern "C" int gg_bfs64_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
                                     int32_t *step, int64_t *vertex_id, int64_t *edge_rowid, uint32_t *n_out) {
+  GG_TRY(refuse_all_paths(res, "gg_bfs64_paths_fetch"));
   if (!res || !res->paths || !n_out || !pair_index || !step || !vertex_id) return GG_ERR_INVALID_ARG;
   gg_ctx *ctx = res->ctx;
   const uint64_t total = res->rows[PATHS_TABLE];

@@ -323,12 +323,14 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
 }
 
 extern "C" int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
+  GG_TRY(refuse_all_paths(res, "gg_reach_closure_levels"));
   if (!res || !res->reach) return GG_ERR_INVALID_ARG;
   return pair_rows_levels(res, rows_per_level, capacity, n_levels);
 }
 
 extern "C" int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
                                       int64_t *vertex_id, int32_t *level, uint32_t *n_out) {
+  GG_TRY(refuse_all_paths(res, "gg_reach_closure_fetch"));
   if (!res || !res->reach) return GG_ERR_INVALID_ARG;
   return pair_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
 }

@@ -26,6 +26,7 @@ SYMBOLS = [
     "gg_expand_khop_edges", "gg_result_fetch_edges",
     "gg_result_filter_common_neighbour", "gg_result_filter_edge", "gg_staging_clear_edges", "gg_vertices_from_edges",
     "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_bfs64_paths", "gg_bfs64_paths_rows", "gg_bfs64_paths_fetch",
+    "gg_bfs64_all_paths", "gg_bfs64_all_paths_rows", "gg_bfs64_all_paths_fetch_pairs", "gg_bfs64_all_paths_fetch",
     "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
@@ -61,6 +62,18 @@ class BfsStats(C.Structure):
         ("traversed_edges", C.c_uint64),
         ("active_vertices", C.c_uint64),
         ("reached_pairs", C.c_uint64),
+    ]
+
+
+class AllPathsStats(C.Structure):
+    _fields_ = [
+        ("bfs", BfsStats),
+        ("pairs_reached", C.c_uint64),
+        ("paths", C.c_uint64),
+        ("paths_kept", C.c_uint64),
+        ("rows", C.c_uint64),
+        ("sigma_entries", C.c_uint64),
+        ("sigma_gathered", C.c_uint64),
     ]
 
 
@@ -191,6 +204,12 @@ def load_library(path: str | None = None):
                                    C.POINTER(BfsStats), C.POINTER(P)]
     lib.gg_bfs64_paths_rows.argtypes = [P, C.POINTER(u64)]
     lib.gg_bfs64_paths_fetch.argtypes = [P, u64, C.c_uint32, i64p, C.POINTER(C.c_int32), i64p, i64p, C.POINTER(C.c_uint32)]
+    u32p, i32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(u64)
+    lib.gg_bfs64_all_paths.argtypes = [P, P, i64p, C.c_int, C.c_int, u32p, i64p, u64, u64, C.c_int, C.c_int,
+                                       C.POINTER(AllPathsStats), C.POINTER(P)]
+    lib.gg_bfs64_all_paths_rows.argtypes = [P, C.c_int, u64p]
+    lib.gg_bfs64_all_paths_fetch_pairs.argtypes = [P, u64, C.c_uint32, i64p, i32p, u64p, u64p, u32p]
+    lib.gg_bfs64_all_paths_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, i32p, i64p, i64p, u32p]
     lib.gg_walk_endpoints.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
     lib.gg_walk_closure.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
     lib.gg_walk_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
@@ -984,6 +1003,90 @@ class GG:
         pair, step, vtx, edge = (np.concatenate([p[c] for p in parts]) for c in range(4))
         order = np.argsort(pair, kind="stable")  # batches interleave; inside a pair the steps already ascend
         return pair[order], step[order], vtx[order], edge[order]
+
+    def bfs64_all_paths(self, csr: Csr, sources, pair_lane, pair_dst, max_hops: int = -1, path_limit: int = 0,
+                        edges: bool = True, materialise: bool = True, fetch: bool = True):
+        """gg_bfs64_all_paths: one <=64-source batch.  Returns (table 0, table 1, stats): table 0 = (pair int64, hops int32,
+        paths uint64, kept uint64) per reached pair; table 1 = (pair int64, path int64, step int32, vertex int64, edge int64)
+        per step of every kept path, ascending by (pair, path, step) — None with materialise=False; stats = the call's
+        gg_all_paths_stats as a dict, the BFS's under "bfs".  fetch=False: the stats alone, the tables are made and left on the
+        device (benchmarks)."""
+        i64p, i32p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+        s, ps = _i64(sources)
+        d, pd = _i64(pair_dst)
+        lane = np.ascontiguousarray(pair_lane, dtype=np.uint32)
+        if lane.size != d.size:
+            raise ValueError("one source lane per target")
+        st, res = AllPathsStats(), C.c_void_p()
+        self._chk(self.lib.gg_bfs64_all_paths(self.ctx, csr.handle, ps, s.size, int(max_hops),
+                                              lane.ctypes.data_as(C.POINTER(C.c_uint32)), pd, d.size, int(path_limit),
+                                              1 if edges else 0, 1 if materialise else 0, C.byref(st), C.byref(res)))
+        try:
+            def fetch_table(table, cols, call):
+                n = C.c_uint64()
+                self._chk(self.lib.gg_bfs64_all_paths_rows(res, table, C.byref(n)))
+                n = int(n.value)
+                out = [np.empty(n, t) for t in cols]
+                done = 0
+                while done < n:
+                    got = C.c_uint32()
+                    ptrs = [a[done:].ctypes.data_as({np.int64: i64p, np.int32: i32p, np.uint64: u64p}[t])
+                            for a, t in zip(out, cols)]
+                    self._chk(call(res, done, min(n - done, 1 << 30), *ptrs, C.byref(got)))
+                    assert got.value
+                    done += got.value
+                return tuple(out)
+            t0 = t1 = None
+            if fetch:
+                t0 = fetch_table(0, (np.int64, np.int32, np.uint64, np.uint64), self.lib.gg_bfs64_all_paths_fetch_pairs)
+            if fetch and materialise:
+                t1 = fetch_table(1, (np.int64, np.int64, np.int32, np.int64, np.int64), self.lib.gg_bfs64_all_paths_fetch)
+        finally:
+            self.lib.gg_result_destroy(res)
+        stats = {k: int(getattr(st, k)) for k in ("pairs_reached", "paths", "paths_kept", "rows", "sigma_entries",
+                                                  "sigma_gathered")}
+        stats["bfs"] = {"levels": st.bfs.levels, "traversed_edges": st.bfs.traversed_edges,
+                        "active_vertices": st.bfs.active_vertices, "reached_pairs": st.bfs.reached_pairs}
+        return (t0, t1, stats) if fetch else stats
+
+    def _all_paths_batches(self, src, dst):
+        """(sources of the batch, lanes of its pairs, their targets, their pair indices) per batch of 64 distinct sources,
+        grouped as shortest_paths groups them"""
+        s, _ = _i64(src)
+        d, _ = _i64(dst)
+        if s.size != d.size:
+            raise ValueError("one target per source")
+        uniq, inv = np.unique(s, return_inverse=True)
+        for b0 in range(0, uniq.size, GG_BFS_LANES):
+            members = np.flatnonzero((inv >= b0) & (inv < b0 + GG_BFS_LANES))  # ascending pair index
+            yield uniq[b0:b0 + GG_BFS_LANES], inv[members] - b0, d[members], members
+
+    def all_shortest_paths(self, csr: Csr, src, dst, max_hops: int = -1, path_limit: int = 0, edges: bool = True):
+        """Every shortest path (include/gg.h, gg_bfs64_all_paths) of every pair (src[i], dst[i]), at most path_limit of a
+        pair (0: all), unnested: arrays (pair_index int64, path int64, step int32, vertex int64, edge int64) ascending by
+        (pair, path, step).  Any number of pairs, grouped by source into device batches of at most 64 distinct sources."""
+        parts = []
+        for sources, lanes, targets, members in self._all_paths_batches(src, dst):
+            _, t1, _ = self.bfs64_all_paths(csr, sources, lanes, targets, max_hops, path_limit, edges)
+            parts.append((members[t1[0]],) + t1[1:])
+        if not parts:
+            return tuple(np.empty(0, np.int32 if k == 2 else np.int64) for k in range(5))
+        cols = [np.concatenate([p[c] for p in parts]) for c in range(5)]
+        order = np.argsort(cols[0], kind="stable")  # batches interleave; inside a pair (path, step) already ascend
+        return tuple(c[order] for c in cols)
+
+    def shortest_path_counts(self, csr: Csr, src, dst, max_hops: int = -1):
+        """(pair_index int64, hops int32, paths uint64) of the pairs that have a path, ascending by pair index; paths is the
+        number of shortest paths, 2^64 - 1 standing for that many or more."""
+        parts = []
+        for sources, lanes, targets, members in self._all_paths_batches(src, dst):
+            t0, _, _ = self.bfs64_all_paths(csr, sources, lanes, targets, max_hops, 0, False, materialise=False)
+            parts.append((members[t0[0]], t0[1], t0[2]))
+        if not parts:
+            return np.empty(0, np.int64), np.empty(0, np.int32), np.empty(0, np.uint64)
+        cols = [np.concatenate([p[c] for p in parts]) for c in range(3)]
+        order = np.argsort(cols[0], kind="stable")
+        return tuple(c[order] for c in cols)
 
     def walk_endpoints(self, csr: Csr, sources, k_max: int):
         """gg_walk_endpoints: (vertex ids, masks) — bit h of a mask: the vertex ends a walk of exactly h edges

@@ -14,6 +14,10 @@
 //        -> (startPerson BIGINT, friend BIGINT, hopCount INTEGER)
 //   gg_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
 //        -> (src BIGINT, dst BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT)   the paths, unnested
+//   gg_all_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops, path_limit)
+//        -> (src BIGINT, dst BIGINT, path BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT)   ALL SHORTEST, unnested
+//   gg_shortest_path_counts(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
+//        -> (src BIGINT, dst BIGINT, hops INTEGER, paths HUGEINT)   how many shortest paths (2^64 - 1: or more)
 //   gg_triangle_count(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered)
 //        -> (rows BIGINT, digest BIGINT, wedges BIGINT)          closed 3-edge walks (gg_triangles.cpp)
 //   gg_triangles(vertex_table, vertex_key, edge_table, src_col, dst_col, ordered)
@@ -562,6 +566,45 @@ static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<
 	return move(data);
 }
 
+//! gg_all_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops, path_limit) and
+//! gg_shortest_path_counts(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
+template <bool COUNT_ONLY>
+static unique_ptr<FunctionData> AllShortestBind(ClientContext &context, vector<Value> &inputs,
+                                                unordered_map<string, Value> &named_parameters,
+                                                vector<LogicalType> &input_table_types,
+                                                vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                vector<string> &names) {
+	const GraphArguments graph(inputs);
+	const string pairs_sql = inputs[5].ToString();
+	const auto max_hops = inputs[6].GetValue<int64_t>();
+	const auto path_limit = COUNT_ONLY ? (int64_t)0 : inputs[7].GetValue<int64_t>();
+	if (path_limit < 0) {
+		throw InvalidInputException("gg_all_shortest_path_rows: path_limit must be >= 0 (0: every path)");
+	}
+	const char *what = COUNT_ONLY ? "gg_shortest_path_counts: pairs" : "gg_all_shortest_path_rows: pairs";
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec;
+		spec.vertices = GGTableSource(ctx, graph.vertex_table, {graph.vertex_key}, false);
+		spec.edges = GGTableSource(ctx, graph.edge_table, {graph.edge_src, graph.edge_dst}, true);
+		spec.edges_with_rowid = true;
+		opened.graph = GGBuildGraphWithRowids(ctx, spec);
+		vector<int64_t> src, dst;
+		QueryInt64Pairs(ctx, pairs_sql, what, src, dst);
+		opened.source = make_unique<PhysicalGGAllShortestPaths>(opened.graph, move(src), move(dst),
+		                                                        max_hops < 0 ? -1 : (int)max_hops, (uint64_t)path_limit,
+		                                                        COUNT_ONLY, 0);
+	};
+	data->parallel_result = true;
+	return_types = PhysicalGGAllShortestPaths::OutputTypes(COUNT_ONLY);
+	if (COUNT_ONLY) {
+		names = {"src", "dst", "hops", "paths"};
+	} else {
+		names = {"src", "dst", "path", "step", "vertex", "edge_rowid"};
+	}
+	return move(data);
+}
+
 //! gg_graph_pin(vertex_table, vertex_key, edge_table, src_col, dst_col) -> (vertices, edges, build_ms);
 //! vertex_table = '' pins the edge-only form (vertex set = endpoint ids).  gg_graph_unpin() drops all.
 struct PinResultData : public TableFunctionData {
@@ -682,6 +725,10 @@ static void LoadInternal(DatabaseInstance &db) {
 	auto khop_count = GGScanFunction("gg_khop_count", khop_args, KhopCountBind);
 	auto shortest = GGScanFunction("gg_shortest_path", sp_args, ShortestBind);
 	auto shortest_rows = GGScanFunction("gg_shortest_path_rows", sp_args, ShortestRowsBind);
+	auto all_args = sp_args;
+	all_args.push_back(LogicalType::BIGINT);
+	auto all_shortest_rows = GGScanFunction("gg_all_shortest_path_rows", all_args, AllShortestBind<false>);
+	auto shortest_counts = GGScanFunction("gg_shortest_path_counts", sp_args, AllShortestBind<true>);
 	auto filtered = GGScanFunction("gg_same_neighbour_paths",
 	                               {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
 	                                LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
@@ -691,7 +738,8 @@ static void LoadInternal(DatabaseInstance &db) {
 	TableFunction unpin("gg_graph_unpin", {}, GraphUnpinFunction, GraphUnpinBind);
 	TableFunction pins("gg_graph_pins", {}, GraphUnpinFunction, GraphPinsBind);
 	CreateTableFunctionInfo khop_info(khop), khop_count_info(khop_count), shortest_info(shortest), shortest_rows_info(shortest_rows),
-	    filtered_info(filtered), pin_info(pin), unpin_info(unpin), pins_info(pins);
+	    filtered_info(filtered), pin_info(pin), unpin_info(unpin), pins_info(pins),
+	    all_shortest_rows_info(all_shortest_rows), shortest_counts_info(shortest_counts);
 
 	Connection con(db);
 	con.BeginTransaction();
@@ -700,6 +748,8 @@ static void LoadInternal(DatabaseInstance &db) {
 	catalog.CreateTableFunction(*con.context, &khop_count_info);
 	catalog.CreateTableFunction(*con.context, &shortest_info);
 	catalog.CreateTableFunction(*con.context, &shortest_rows_info);
+	catalog.CreateTableFunction(*con.context, &all_shortest_rows_info);
+	catalog.CreateTableFunction(*con.context, &shortest_counts_info);
 	catalog.CreateTableFunction(*con.context, &filtered_info);
 	catalog.CreateTableFunction(*con.context, &pin_info);
 	catalog.CreateTableFunction(*con.context, &unpin_info);

@@ -16,6 +16,7 @@
 //        semi / anti join of an EXISTS / NOT EXISTS over the edge table (src/execution/join_hashtable.cpp:304-540).
 //   PhysicalGGShortestPath                       <->  PhysicalRecursiveCTE + min(hop) aggregate
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
+//   PhysicalGGAllShortestPaths                   <->  PhysicalRecursiveCTE (UNION ALL) over friends_shortest x knows [+ count]
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
 // The six sources whose rows stay on the device (path expansion, triangles, the edge filter, the grouped aggregate, the two shortest-path ones) hand them to
@@ -620,6 +621,43 @@ public:
 	}
 	string GetName() const override {
 		return "GG_SHORTEST_PATH_ROWS";
+	}
+};
+
+//! Source: every shortest path of every (src[i], dst[i]), unnested — (src BIGINT, dst BIGINT, path BIGINT, step INTEGER,
+//! vertex BIGINT, edge_rowid BIGINT), at most path_limit paths of a pair (0: all), path numbers in the pinned rank order of
+//! include/gg.h (gg_bfs64_all_paths), edge_rowid NULL at step 0 — or, count_only, their number: (src BIGINT, dst BIGINT,
+//! hops INTEGER, paths HUGEINT), 2^64 - 1 standing for that many or more.  The graph must have been built with the edge
+//! table's rowids.  Batching and draining as PhysicalGGShortestPathRows.
+class PhysicalGGAllShortestPaths : public PhysicalOperator {
+public:
+	PhysicalGGAllShortestPaths(shared_ptr<GGGraph> graph, vector<int64_t> src, vector<int64_t> dst, int max_hops,
+	                           uint64_t path_limit, bool count_only, idx_t estimated_cardinality);
+	static vector<LogicalType> OutputTypes(bool count_only);
+
+	//! BFS, count and (unless count_only) unranking of batch `batch`; caller holds graph->lock
+	GGResultPtr RunBatch(GlobalSourceState &gstate, idx_t batch, idx_t &rows) const;
+
+	shared_ptr<GGGraph> graph;
+	vector<int64_t> src, dst;
+	int max_hops;
+	uint64_t path_limit;
+	bool count_only;
+
+public:
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
+	                                                 GlobalSourceState &gstate) const override;
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override;
+	bool IsSource() const override {
+		return true;
+	}
+	bool ParallelSource() const override {
+		return true;
+	}
+	string GetName() const override {
+		return count_only ? "GG_SHORTEST_PATH_COUNTS" : "GG_ALL_SHORTEST_PATH_ROWS";
 	}
 };
 

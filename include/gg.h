@@ -33,6 +33,11 @@
  *           is one more hash join of friends_shortest with knows per step under a min(rowid) aggregate
  *                                                               physical_hash_join.cpp:217-254, join_hashtable.cpp:304-476,
  *                                                               physical_hash_aggregate.cpp:152-266
+ *   gg_bfs64_all_paths / gg_bfs64_all_paths_rows / gg_bfs64_all_paths_fetch_pairs / gg_bfs64_all_paths_fetch
+ *        <- ALL SHORTEST and its count: PhysicalRecursiveCTE (UNION ALL) over friends_shortest joined with knows once per
+ *           level, a hash aggregate above it for the count
+ *                                                               physical_recursive_cte.cpp:60-139, join_hashtable.cpp:304-476,
+ *                                                               physical_hash_aggregate.cpp:152-266
  *   gg_walk_endpoints
  *        <- PhysicalUnion + the hash-aggregate dedupe above it (friends UNION friends of friends)
  *                                                               src/execution/physical_plan/plan_distinct.cpp:12-78,
@@ -652,6 +657,63 @@ int gg_bfs64_paths_rows(const gg_result *res, uint64_t *n_rows);
  * *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
 int gg_bfs64_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index, int32_t *step,
                          int64_t *vertex_id, int64_t *edge_rowid, uint32_t *n_out);
+
+/* How many shortest paths a pair has, and all of them (ALL SHORTEST), off the distances of one gg_bfs64 batch while they
+ * are still on the device.  With the reference's operators this is a recursive UNION ALL CTE over friends_shortest joined
+ * with knows once per level (src/execution/operator/set/physical_recursive_cte.cpp:60-139 over
+ * src/execution/join_hashtable.cpp:304-476) and, for the number, a hash aggregate above it
+ * (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266): every path row is formed to be folded away.
+ * The batch is gg_bfs64(src_ids, n_src <= 64, max_hops); pair i asks about src_ids[pair_lane[i]] -> pair_dst_ids[i].  For
+ * lane s and a vertex x at distance d:
+ *     sigma(s, s) = 1
+ *     sigma(s, x) = SUM over the ENTRIES u -> x of x's reverse row with dist(s, u) == d - 1 of sigma(s, u)     (d >= 1)
+ * An entry is a kept edge row, so parallel rows multiply: a path is a sequence of edge rows, with the join's multiplicity
+ * as everywhere in this library.  A self-loop is never on a shortest path.  All sums SATURATE at 2^64 - 1 — they do not
+ * wrap, unlike walk counts — so that "2^32 rows or more" can be decided from the count; saturating addition of
+ * non-negative numbers is associative and commutative, so every route gives the same bits.
+ * Rank order of the paths of a pair (s, t) at distance d: path number r (0-based) is found by unranking from the target
+ * backwards.  At x = t with rank r go through x's reverse row in ascending order of (source dense index, forward CSR
+ * position) — among parallel rows that is append order; an entry u with dist(s, u) == d - 1 is taken if r < sigma(s, u),
+ * otherwise r -= sigma(s, u); continue from u with distance d - 1.  So path 0 of every pair is exactly the path
+ * gg_bfs64_paths reports, vertices and edge rowids; the order is a function of the tables alone; and the edge of a step is
+ * the rowid of the entry taken (the rowid the Sink passed with the row, or its append position).
+ * Table 0: one row (pair index, d, sigma, kept = min(sigma, path_limit); path_limit == 0: kept = sigma) per reached pair,
+ * ascending by pair index; in both modes.  materialise == 0 stops here (out_result may be NULL if only stats are wanted).
+ * Table 1 (materialise != 0): one row (pair, path, step i, vertex id p_i, rowid of the edge into p_i; -1 at step 0) per
+ * step of every kept path, ascending by (pair, path, step).
+ * As gg_bfs64_paths: s == t and s a vertex is one path of one row; no path of at most max_hops edges, or s or t not a
+ * vertex: no rows; duplicate pairs each get their rows; two lanes may carry the same source.  A shard CSR: GG_ERR_STATE;
+ * materialising with want_edges on a CSR without rowids: GG_ERR_STATE; a pair_lane >= n_src: GG_ERR_INVALID_ARG; n_pairs >=
+ * 2^32: GG_ERR_TOO_LARGE; the unranking running off a row (distances and CSR disagree): GG_ERR_STATE, never a loop.  When
+ * materialising, paths_kept >= 2^32 or rows >= 2^32 is GG_ERR_TOO_LARGE, decided from the saturating totals before
+ * anything is written (set a path_limit or ask for fewer pairs).  The context stays usable after every error.
+ * State: 512 bytes per vertex for the call (GG_ERR_OOM if that does not fit).  The first materialising call on a CSR
+ * sorts copies of its reverse rows by source (gg_bfs64_paths' copy, and with want_edges gg_triangles_edges').
+ * The result answers gg_bfs64_all_paths_rows / gg_bfs64_all_paths_fetch_pairs / gg_bfs64_all_paths_fetch only, and those
+ * three refuse every other result with GG_ERR_STATE. */
+typedef struct gg_all_paths_stats {
+  gg_bfs_stats bfs;          /* the batch's BFS, as gg_bfs64 reports it */
+  uint64_t pairs_reached;    /* pairs with at least one path */
+  uint64_t paths;            /* sum over the pairs of sigma, saturating, before path_limit */
+  uint64_t paths_kept;       /* sum over the pairs of min(sigma, path_limit), saturating */
+  uint64_t rows;             /* sum over the pairs of kept * (d + 1), saturating */
+  uint64_t sigma_entries;    /* reverse entries looked at by the count passes: per level L the in-rows of the vertices
+                                that some lane reaches at distance L */
+  uint64_t sigma_gathered;   /* of those, the ones whose 512-byte sigma row was read: some lane that has the vertex at L
+                                has the entry's source at L - 1 */
+} gg_all_paths_stats;
+int gg_bfs64_all_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
+                       const uint32_t *pair_lane, const int64_t *pair_dst_ids, uint64_t n_pairs,
+                       uint64_t path_limit /* 0: none */, int want_edges, int materialise,
+                       gg_all_paths_stats *stats /* nullable when materialising */, gg_result **out_result);
+int gg_bfs64_all_paths_rows(const gg_result *res, int table /* 0 pairs, 1 path rows */, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows) of table 0 / of table 1, in row order, into host arrays of >= max_rows entries.
+ * *n_out = rows copied, 0 past the end (gg_result_fetch's convention). */
+int gg_bfs64_all_paths_fetch_pairs(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
+                                   int32_t *hops, uint64_t *paths, uint64_t *kept /* each nullable */, uint32_t *n_out);
+int gg_bfs64_all_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
+                             int64_t *path_index, int32_t *step, int64_t *vertex_id,
+                             int64_t *edge_rowid /* nullable */, uint32_t *n_out);
 
 /* Distinct endpoints of the walks of 1..k_max edges that start at any of the given sources — the device form of
  *   SELECT dst FROM e WHERE src = C  UNION  SELECT e2.dst FROM e e1, e e2 WHERE e1.src = C AND e1.dst = e2.src
