@@ -290,11 +290,7 @@ extern "C" int gg_khop_aggregate(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
   const uint64_t V = csr->V, E = csr->E;
   const bool all = src_ids == nullptr, weighted = weights != nullptr, end = group_by == GG_GROUP_END;
   ResultOwner res;
-  if (out_result) {
-    res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-    res->aggregate = true;
-    res->agg_k_min = k_min, res->agg_k_max = k_max;
-  }
+  if (out_result) res = make_result(ctx, ResultKind::AGGREGATE, k_min, k_max);
   if (V && E && (all || n_src)) {
     hipStream_t st = ctx->stream;
     if (end) GG_TRY(ensure_reverse(ctx, csr));
@@ -403,11 +399,8 @@ extern "C" int gg_khop_aggregate(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
 
 extern "C" int gg_khop_aggregate_rows(const gg_result *res, int hops, uint64_t *n_rows) {
   if (!res || !n_rows) return GG_ERR_INVALID_ARG;
-  if (!res->aggregate) {
-    set_error("gg_khop_aggregate_rows: the result is not one of gg_khop_aggregate");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->agg_k_min || hops > res->agg_k_max) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::AGGREGATE, "gg_khop_aggregate_rows"));
+  if (hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[hops];
   return GG_OK;
 }
@@ -416,27 +409,11 @@ extern "C" int gg_khop_aggregate_fetch(const gg_result *res, int hops, uint64_t 
                                        int64_t *vertex_id, uint64_t *walks, uint64_t *sum_lo, int64_t *sum_hi,
                                        uint32_t *n_out) {
   if (!res || !n_out || !vertex_id || !walks) return GG_ERR_INVALID_ARG;
-  if (!res->aggregate) {
-    set_error("gg_khop_aggregate_fetch: the result is not one of gg_khop_aggregate");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->agg_k_min || hops > res->agg_k_max) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[hops];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  const uint64_t take = total - offset < max_rows ? total - offset : max_rows;
-  void *dst[4] = {vertex_id, walks, nullptr, nullptr};
-  const void *src[4] = {res->cols[hops][0] + offset, res->cols[hops][1] + offset, nullptr, nullptr};
-  int n = 2;
-  if (sum_lo) dst[n] = sum_lo, src[n] = res->cols[hops][2] + offset, n++;
-  if (sum_hi) dst[n] = sum_hi, src[n] = res->cols[hops][3] + offset, n++;
-  GG_TRY(ctx->fetch_columns(dst, src, n, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  GG_TRY(expect_kind(res, ResultKind::AGGREGATE, "gg_khop_aggregate_fetch"));
+  if (hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
+  int64_t *const *col = res->cols[hops];
+  return fetch_slice(res->ctx, res->rows[hops], offset, max_rows,
+                     {{vertex_id, col[0]}, {walks, col[1]}, {sum_lo, col[2]}, {sum_hi, col[3]}}, n_out);
 }
 
 extern "C" int gg_debug_aggregate_long_row(gg_ctx *ctx, uint32_t entries) {

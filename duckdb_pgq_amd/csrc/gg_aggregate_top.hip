@@ -374,12 +374,9 @@ extern "C" int gg_khop_aggregate_top(gg_ctx *ctx, const gg_result *agg, int hops
     set_error("gg_khop_aggregate_top: bad context / result / csr / out_result argument");
     return GG_ERR_INVALID_ARG;
   }
-  if (!agg->aggregate) {
-    set_error("gg_khop_aggregate_top: the result is not one of gg_khop_aggregate");
-    return GG_ERR_STATE;
-  }
-  if (hops < agg->agg_k_min || hops > agg->agg_k_max) {
-    set_error("gg_khop_aggregate_top: level %d outside the result's %d..%d", hops, agg->agg_k_min, agg->agg_k_max);
+  GG_TRY(expect_kind(agg, ResultKind::AGGREGATE, "gg_khop_aggregate_top"));
+  if (hops < agg->k_min || hops > agg->k_max) {
+    set_error("gg_khop_aggregate_top: level %d outside the result's %d..%d", hops, agg->k_min, agg->k_max);
     return GG_ERR_INVALID_ARG;
   }
   if (order_by != GG_TOP_BY_TOTAL && order_by != GG_TOP_BY_WALKS) {
@@ -397,9 +394,7 @@ extern "C" int gg_khop_aggregate_top(gg_ctx *ctx, const gg_result *agg, int hops
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t N = agg->rows[hops], m = n < N ? n : N;
-  ResultOwner res = make_result(ctx, 1, 0);
-  res->aggregate = true;
-  res->agg_k_min = res->agg_k_max = hops;
+  ResultOwner res = make_result(ctx, ResultKind::AGGREGATE, hops, hops);
   res->rows[hops] = m;
   if (stats) stats->rows_in = N, stats->rows_out = m;
   if (m == 0) {

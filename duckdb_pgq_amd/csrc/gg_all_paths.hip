@@ -465,36 +465,6 @@ int all_paths_emit_t(gg_ctx *ctx, gg_csr *csr, const DistT *dist, uint32_t level
   return GG_OK;
 }
 
-int all_paths_fetch(const gg_result *res, const char *fn, int table, int n_cols, int cell32, void *const *want,
-                    uint64_t offset, uint32_t max_rows, uint32_t *n_out) {
-  if (!res || !n_out) return GG_ERR_INVALID_ARG;
-  if (!res->all_paths) {
-    set_error("%s: the result is not one of gg_bfs64_all_paths", fn);
-    return GG_ERR_STATE;
-  }
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[table];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  const uint64_t take = total - offset < max_rows ? total - offset : max_rows;
-  void *dst[5];
-  const void *src[5];
-  int k = 0;
-  for (int c = 0; c < n_cols; c++)
-    if (c != cell32 && want[c] && res->cols[table][c]) dst[k] = want[c], src[k] = res->cols[table][c] + offset, k++;
-  if (k) GG_TRY(ctx->fetch_columns(dst, src, k, take * sizeof(int64_t)));
-  if (want[cell32]) {
-    void *dst_s[1] = {want[cell32]};
-    const void *src_s[1] = {reinterpret_cast<const int32_t *>(res->cols[table][cell32]) + offset};
-    GG_TRY(ctx->fetch_columns(dst_s, src_s, 1, take * sizeof(int32_t)));
-  }
-  *n_out = (uint32_t)take;
-  return GG_OK;
-}
-
 }  // namespace
 
 int all_paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, uint32_t levels,
@@ -534,10 +504,7 @@ extern "C" int gg_bfs64_all_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t 
       return GG_ERR_INVALID_ARG;
     }
   ResultOwner res;
-  if (out_result) {
-    res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-    res->all_paths = true;
-  }
+  if (out_result) res = make_result(ctx, ResultKind::ALL_PATHS);
   const AllPathsRequest rq{src_ids, n_src, pair_lane, pair_dst_ids, n_pairs, path_limit, materialise && want_edges,
                            materialise != 0, stats, res.get()};
   GG_TRY(bfs64_all_paths_run(ctx, csr, src_ids, n_src, max_hops, stats ? &stats->bfs : nullptr, rq));
@@ -547,10 +514,7 @@ extern "C" int gg_bfs64_all_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t 
 
 extern "C" int gg_bfs64_all_paths_rows(const gg_result *res, int table, uint64_t *n_rows) {
   if (!res || !n_rows) return GG_ERR_INVALID_ARG;
-  if (!res->all_paths) {
-    set_error("gg_bfs64_all_paths_rows: the result is not one of gg_bfs64_all_paths");
-    return GG_ERR_STATE;
-  }
+  GG_TRY(expect_kind(res, ResultKind::ALL_PATHS, "gg_bfs64_all_paths_rows"));
   if (table < 0 || table > 1) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[table];
   return GG_OK;
@@ -559,17 +523,24 @@ extern "C" int gg_bfs64_all_paths_rows(const gg_result *res, int table, uint64_t
 extern "C" int gg_bfs64_all_paths_fetch_pairs(const gg_result *res, uint64_t offset, uint32_t max_rows,
                                               int64_t *pair_index, int32_t *hops, uint64_t *paths, uint64_t *kept,
                                               uint32_t *n_out) {
-  void *want[4] = {pair_index, hops, paths, kept};
-  return all_paths_fetch(res, "gg_bfs64_all_paths_fetch_pairs", AP_PAIRS_TABLE, 4, 1, want, offset, max_rows, n_out);
+  if (!res || !n_out) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::ALL_PATHS, "gg_bfs64_all_paths_fetch_pairs"));
+  int64_t *const *col = res->cols[AP_PAIRS_TABLE];
+  return fetch_slice(res->ctx, res->rows[AP_PAIRS_TABLE], offset, max_rows,
+                     {{pair_index, col[0]}, {paths, col[2]}, {kept, col[3]}, {hops, col[1], sizeof(int32_t)}}, n_out);
 }
 
 extern "C" int gg_bfs64_all_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
                                         int64_t *path_index, int32_t *step, int64_t *vertex_id, int64_t *edge_rowid,
                                         uint32_t *n_out) {
-  if (res && res->all_paths && (!pair_index || !path_index || !step || !vertex_id)) return GG_ERR_INVALID_ARG;
-  void *want[5] = {pair_index, path_index, step, vertex_id, edge_rowid};
-  GG_TRY(all_paths_fetch(res, "gg_bfs64_all_paths_fetch", AP_ROWS_TABLE, 5, 2, want, offset, max_rows, n_out));
-  if (edge_rowid && !res->cols[AP_ROWS_TABLE][4])
+  if (!res || !n_out) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::ALL_PATHS, "gg_bfs64_all_paths_fetch"));
+  if (!pair_index || !path_index || !step || !vertex_id) return GG_ERR_INVALID_ARG;
+  int64_t *const *col = res->cols[AP_ROWS_TABLE];
+  GG_TRY(fetch_slice(res->ctx, res->rows[AP_ROWS_TABLE], offset, max_rows,
+                     {{pair_index, col[0]}, {path_index, col[1]}, {vertex_id, col[3]}, {edge_rowid, col[4]},
+                      {step, col[2], sizeof(int32_t)}}, n_out));
+  if (edge_rowid && !col[4])
     for (uint32_t r = 0; r < *n_out; r++) edge_rowid[r] = -1;  // searched without edges
   return GG_OK;
 }

@@ -664,7 +664,8 @@ static int bfs_pairs(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int
   if (!out_result) return GG_ERR_INVALID_ARG;
   *out_result = nullptr;
   if (!ctx) return GG_ERR_INVALID_ARG;
-  ResultOwner res = make_result(ctx, table, table);  // table 2: three id columns; table 0: one packed column
+  // table 2: three id columns; table 0: one packed column
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, table, table);
   GG_TRY(bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, res.get()));
   *out_result = res.release();
   return GG_OK;
@@ -693,8 +694,7 @@ extern "C" int gg_bfs64_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src
       set_error("gg_bfs64_paths: pair %llu names source %u of %d", (unsigned long long)i, pair_lane[i], n_src);
       return GG_ERR_INVALID_ARG;
     }
-  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-  res->paths = true;
+  ResultOwner res = make_result(ctx, ResultKind::PATHS);
   const PathsRequest rq{pair_lane, pair_dst_ids, n_pairs, want_edges != 0, res.get()};
   GG_TRY(bfs_dispatch(ctx, csr, src_ids, n_src, max_hops, nullptr, 0, nullptr, stats, nullptr, &rq));
   *out_result = res.release();
@@ -1011,7 +1011,7 @@ extern "C" int gg_bfs_sharded_pairs(gg_bfs_run *run, gg_result **out_result) {
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t V = csr->V;
-  ResultOwner res = make_result(ctx, 2, 2);
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, 2, 2);
   if (V) {
     uint32_t *counts = nullptr;
     uint64_t rows = 0;
@@ -1051,7 +1051,7 @@ extern "C" int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const uint64_t V = csr->V;
-  ResultOwner res = make_result(ctx, 1, 1);  // table 1: (vertex id, mask of walk lengths)
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, 1, 1);  // table 1: (vertex id, mask of walk lengths)
   if (V && n_src) {
     const uint64_t words = (V + 31) / 32;
     uint32_t *dense = nullptr, *bits = nullptr, *counts = nullptr;

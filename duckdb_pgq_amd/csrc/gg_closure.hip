@@ -85,7 +85,7 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
     return GG_ERR_TOO_LARGE;
   }
   GG_HIP(hipSetDevice(ctx->device));
-  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
+  ResultOwner res = make_result(ctx, ResultKind::WALK_CLOSURE);
   uint32_t *seed_dense = nullptr;
   GG_TRY(upload_ids(ctx, csr, seed_ids, n_seeds, &seed_dense));
 
@@ -125,17 +125,12 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
     n_parent = M;
   }
 
-  uint64_t n_rows = 0;
-  for (uint64_t m : res->level_rows) n_rows += m;
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_seed, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_seed);
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_rowid, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_rowid);
+  GG_TRY(alloc_level_columns(ctx, res.get()));
   uint64_t at = 0;
   for (size_t l = 0; l < levels.size(); l++) {
     const uint64_t m = res->level_rows[l];
     GG_LAUNCH(ctx, "closure_emit", k_closure_emit, stride_grid(ctx, m), dim3(256), 0, levels[l], m, csr->eid, csr->epos,
-              res->walk_seed + at, res->walk_rowid + at, (const unsigned long long *)ctx->dev_err);
+              res->cols[0][0] + at, res->cols[0][1] + at, (const unsigned long long *)ctx->dev_err);
     at += m;
   }
   GG_TRY(sync_checked(ctx));
@@ -144,39 +139,12 @@ extern "C" int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *se
 }
 
 extern "C" int gg_walk_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
-  GG_TRY(refuse_aggregate(res, "gg_walk_closure_levels"));
-  if (!res || res->reach || res->level_sets || !n_levels || (capacity > 0 && !rows_per_level) || res->k_min <= res->k_max)
-    return GG_ERR_INVALID_ARG;
-  *n_levels = (int)res->level_rows.size();
-  for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
-  return GG_OK;
+  GG_TRY(expect_kind(res, ResultKind::WALK_CLOSURE, "gg_walk_closure_levels"));
+  return level_rows_levels(res, rows_per_level, capacity, n_levels);
 }
 
 extern "C" int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_index,
                                      int64_t *edge_rowid, int32_t *level, uint32_t *n_out) {
-  GG_TRY(refuse_aggregate(res, "gg_walk_closure_fetch"));
-  if (!res || res->reach || res->level_sets || !n_out || !seed_index || !edge_rowid || res->k_min <= res->k_max) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  uint64_t total = 0;
-  for (uint64_t m : res->level_rows) total += m;
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  GG_HIP(hipSetDevice(ctx->device));
-  void *dst[2] = {seed_index, edge_rowid};
-  const void *src[2] = {res->walk_seed + offset, res->walk_rowid + offset};
-  GG_TRY(ctx->fetch_columns(dst, src, 2, take * sizeof(int64_t)));
-  if (level) {  // the level of a row follows from the per-level row counts
-    uint64_t start = 0;
-    for (size_t l = 0; l < res->level_rows.size(); l++) {
-      const uint64_t end = start + res->level_rows[l];
-      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + take; r++) level[r - offset] = (int32_t)(l + 1);
-      start = end;
-    }
-  }
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  GG_TRY(expect_kind(res, ResultKind::WALK_CLOSURE, "gg_walk_closure_fetch"));
+  return level_rows_fetch(res, offset, max_rows, seed_index, edge_rowid, level, n_out);
 }

@@ -203,31 +203,6 @@ __global__ __launch_bounds__(256) void k_cc_reps(const uint32_t *__restrict__ ro
     }
 }
 
-int components_fetch(const gg_result *res, const char *fn, int table, int n_cols, void *const *want, uint64_t offset,
-                     uint32_t max_rows, uint32_t *n_out) {
-  if (!res || !n_out) return GG_ERR_INVALID_ARG;
-  if (!res->components) {
-    set_error("%s: the result is not one of gg_components", fn);
-    return GG_ERR_STATE;
-  }
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[table];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  const uint64_t take = total - offset < max_rows ? total - offset : max_rows;
-  void *dst[3];
-  const void *src[3];
-  int n = 0;
-  for (int c = 0; c < n_cols; c++)
-    if (want[c]) dst[n] = want[c], src[n] = res->cols[table][c] + offset, n++;
-  if (n && take) GG_TRY(ctx->fetch_columns(dst, src, n, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
-}
-
 }  // namespace
 }  // namespace gg
 
@@ -243,10 +218,7 @@ extern "C" int gg_components(gg_ctx *ctx, const gg_csr *csr, gg_cc_stats *stats,
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t V = csr->V, E = csr->E;
   ResultOwner res;
-  if (out_result) {
-    res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-    res->components = true;
-  }
+  if (out_result) res = make_result(ctx, ResultKind::COMPONENTS);
   if (V) {
     hipStream_t st = ctx->stream;
     unsigned long long *words = nullptr;
@@ -328,10 +300,7 @@ extern "C" int gg_components(gg_ctx *ctx, const gg_csr *csr, gg_cc_stats *stats,
 
 extern "C" int gg_components_rows(const gg_result *res, int table, uint64_t *n_rows) {
   if (!res || !n_rows) return GG_ERR_INVALID_ARG;
-  if (!res->components) {
-    set_error("gg_components_rows: the result is not one of gg_components");
-    return GG_ERR_STATE;
-  }
+  GG_TRY(expect_kind(res, ResultKind::COMPONENTS, "gg_components_rows"));
   if (table < 0 || table > 1) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[table];
   return GG_OK;
@@ -339,14 +308,19 @@ extern "C" int gg_components_rows(const gg_result *res, int table, uint64_t *n_r
 
 extern "C" int gg_components_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *vertex_id,
                                    int64_t *component_id, uint64_t *size, uint32_t *n_out) {
-  void *want[3] = {vertex_id, component_id, size};
-  return components_fetch(res, "gg_components_fetch", 0, 3, want, offset, max_rows, n_out);
+  if (!res || !n_out) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::COMPONENTS, "gg_components_fetch"));
+  int64_t *const *col = res->cols[0];
+  return fetch_slice(res->ctx, res->rows[0], offset, max_rows, {{vertex_id, col[0]}, {component_id, col[1]}, {size, col[2]}},
+                     n_out);
 }
 
 extern "C" int gg_components_fetch_sizes(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *component_id,
                                          uint64_t *size, uint32_t *n_out) {
-  void *want[2] = {component_id, size};
-  return components_fetch(res, "gg_components_fetch_sizes", 1, 2, want, offset, max_rows, n_out);
+  if (!res || !n_out) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::COMPONENTS, "gg_components_fetch_sizes"));
+  return fetch_slice(res->ctx, res->rows[1], offset, max_rows, {{component_id, res->cols[1][0]}, {size, res->cols[1][1]}},
+                     n_out);
 }
 
 extern "C" int gg_debug_components(gg_ctx *ctx, int init_mode, uint32_t jumps_per_check) {

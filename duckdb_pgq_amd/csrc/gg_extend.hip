@@ -207,7 +207,7 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
     set_error("gg_result_extend_edge: a CSR shard (gg_csr_build_shard) cannot be the joined table");
     return GG_ERR_STATE;
   }
-  if (res->k_min > res->k_max) {
+  if (res->kind != ResultKind::TABLES) {
     set_error("gg_result_extend_edge: the result has no fixed-length table (a closure, level sets or paths)");
     return GG_ERR_STATE;
   }
@@ -230,7 +230,8 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
   const uint64_t n_rows = res->rows[hops];
   const int out_hops = hops + 1;
   ResultOwner o;
-  if (materialise) o = make_result(ctx, out_hops, out_hops);  // table hops + 1: v0..v_hops, w (and e1..e_{hops+1})
+  // table hops + 1: v0..v_hops, w (and e1..e_{hops+1})
+  if (materialise) o = make_result(ctx, ResultKind::TABLES, out_hops, out_hops);
   uint64_t total = 0, matched = 0;
   if (n_rows && csr->V && csr->E) {  // (without an edge row nothing matches: nothing to look up)
     GG_TRY(ensure_ht(ctx, csr));

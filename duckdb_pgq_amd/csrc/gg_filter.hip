@@ -86,8 +86,8 @@ __global__ __launch_bounds__(256) void k_filter(RowCols in, int ncols, uint64_t 
 
 extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *filter,
                                                  gg_result **out) {
-  if (!ctx || !res || !filter || !out || res->ctx != ctx || filter->ctx != ctx || hops < res->k_min ||
-      hops > res->k_max || hops + 1 > GG_MAX_HOPS || filter->n_parts > 1) {
+  if (!ctx || !res || !filter || !out || res->ctx != ctx || filter->ctx != ctx || res->kind != ResultKind::TABLES ||
+      hops < res->k_min || hops > res->k_max || hops + 1 > GG_MAX_HOPS || filter->n_parts > 1) {
     set_error("gg_result_filter_common_neighbour: bad argument");
     return GG_ERR_INVALID_ARG;
   }
@@ -96,7 +96,7 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
   GG_HIP(hipSetDevice(ctx->device));
   const uint64_t n_rows = res->rows[hops];
   const int ncols = hops + 1;
-  ResultOwner o = make_result(ctx, hops + 1, hops + 1);  // the table with hops+2 columns: (w, v0..vh)
+  ResultOwner o = make_result(ctx, ResultKind::TABLES, hops + 1, hops + 1);  // the table with hops+2 columns: (w, v0..vh)
   RowCols in;
   for (int c = 0; c < ncols; c++) in.c[c] = res->cols[hops][c];
   OutCols oc;
@@ -270,7 +270,7 @@ extern "C" int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops
     set_error("gg_result_filter_edge: a CSR shard (gg_csr_build_shard) cannot be the condition graph");
     return GG_ERR_STATE;
   }
-  if (res->k_min > res->k_max) {
+  if (res->kind != ResultKind::TABLES) {
     set_error("gg_result_filter_edge: the result has no fixed-length table (a closure, level sets or paths)");
     return GG_ERR_STATE;
   }
@@ -291,7 +291,8 @@ extern "C" int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
   const uint64_t n_rows = res->rows[hops];
   ResultOwner o;
-  if (materialise) o = make_result(ctx, hops, hops);  // table hops: the id columns v0..v_hops, no edge columns
+  // table hops: the id columns v0..v_hops, no edge columns
+  if (materialise) o = make_result(ctx, ResultKind::TABLES, hops, hops);
   uint64_t total = 0, matches = 0;
   if (n_rows) {
     EdgeArgs a{};

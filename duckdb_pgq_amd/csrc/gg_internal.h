@@ -298,41 +298,38 @@ struct gg_csr {
   uint32_t *pin_nbr = nullptr; // E_rev
 };
 
+// What a device result holds and which calls read it.  The kinds from AGGREGATE on were born with a refusal contract:
+// every call but their own answers them with GG_ERR_STATE, and theirs answer every other kind so (gg::expect_kind).
+enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS };
+
+// kind          tables and columns (h: a level in k_min..k_max)                     read by
+// TABLES        rows[h], cols[h][0..h] = ids v0..vh; ecols[h][j] = rowid of the     gg_result_rows / _fetch / _fetch_edges /
+//               (j + 1)-th edge if asked for; tri_edges: ecols[2][0..2] = e1, e2,   _digest / _filter_* / _extend_edge,
+//               e3 of a triangle row                                                gg_triangles_fetch_edges
+// WALK_CLOSURE  rows[0] walks level by level, level_rows[L - 1] those of L edges;   gg_walk_closure_levels / _fetch
+//               cols[0][0..1] = index of the seed, rowid of the last edge
+// REACH         the same; cols[0][0..1] = class, vertex id of level L's new pairs   gg_reach_closure_levels / _fetch
+// LEVEL_SETS    the same; cols[0][0..1] = class, vertex id of level L's members     gg_level_sets_levels / _fetch
+// PATHS         rows[PATHS_TABLE], cols[..][0..3] = pair index, vertex id, step     gg_bfs64_paths_rows / _fetch
+//               (int32 cells), edge rowid if asked for
+// AGGREGATE     rows[h] groups, cols[h][0..3] = vertex id, walks, total low, high   gg_khop_aggregate_rows / _fetch / _top
+//               (gg_khop_aggregate_top: one level, in rank order)
+// PAIR_COUNTS   rows[h] pairs, cols[h][0..2] = source index, vertex id, walks       gg_khop_pair_counts_rows / _fetch
+// COMPONENTS    rows[0] = V, cols[0][0..2] = vertex id, component id, size;         gg_components_rows / _fetch / _fetch_sizes
+//               rows[1] components, cols[1][0..1] = component id, size
+// ALL_PATHS     rows[AP_PAIRS_TABLE], cols[..][0..3] = pair index, hops (int32      gg_bfs64_all_paths_rows / _fetch_pairs /
+//               cells), paths, kept; rows[AP_ROWS_TABLE], cols[..][0..4] = pair     _fetch
+//               index, path index, step (int32 cells), vertex id, edge rowid if
+//               asked for
 struct gg_result {
   gg_ctx *ctx = nullptr;
-  int k_min = 0, k_max = 0;
+  ResultKind kind = ResultKind::TABLES;
+  int k_min = 0, k_max = -1;  // the levels that have a table (TABLES, AGGREGATE, PAIR_COUNTS; none otherwise)
   uint64_t rows[GG_MAX_HOPS + 1] = {0};
-  int64_t *cols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};  // cols[h][c], device
-  int64_t *ecols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};  // ecols[h][j]: rowid of the walk's (j + 1)-th edge (gg_expand_khop_edges)
-  // gg_walk_closure (k_min > k_max: no fixed-length table): one row per walk of >= 1 edges, level by level
-  std::vector<uint64_t> level_rows;  // level_rows[L - 1]: walks of L edges
-  int64_t *walk_seed = nullptr;      // device: index into the seed list of the walk's seed
-  int64_t *walk_rowid = nullptr;     // device: rowid of the walk's last edge (as staged)
-  // gg_reach_closure (reach: the same fields): level_rows[L - 1] new (class, vertex) rows of level L, walk_seed their
-  // classes, walk_rowid their vertex ids
-  bool reach = false;
-  // gg_level_sets (level_sets, reach false: the same fields): level_rows[L - 1] the members of level L
-  bool level_sets = false;
-  // gg_bfs64_paths (paths: k_min > k_max too): cols[gg::PATHS_TABLE] = pair index, vertex id, step (int32 cells), and
-  // the edge rowid if edges were asked for; rows[gg::PATHS_TABLE] their number
-  bool paths = false;
-  // gg_triangles_edges: ecols[2][0..2] = rowids of e1: a -> b, e2: b -> c, e3: c -> a (gg_triangles_fetch_edges)
-  bool tri_edges = false;
-  // gg_khop_aggregate (aggregate: k_min > k_max too): for h in [agg_k_min, agg_k_max] rows[h] groups, cols[h][0..3] =
-  // vertex id, walks, low and high half of the total (gg_khop_aggregate_rows / gg_khop_aggregate_fetch);
-  // gg_khop_aggregate_top: the same with one level, its rows in rank order
-  bool aggregate = false;
-  int agg_k_min = 0, agg_k_max = 0;
-  // gg_khop_pair_counts (pair_counts: k_min > k_max too, the levels in agg_k_min / agg_k_max): rows[h] pairs, cols[h][0..2] =
-  // source index, vertex id, walks (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch)
-  bool pair_counts = false;
-  // gg_components (components: k_min > k_max too): rows[0] = V, cols[0][0..2] = vertex id, component id, size; rows[1]
-  // components, cols[1][0..1] = component id, size (gg_components_rows / gg_components_fetch / gg_components_fetch_sizes)
-  bool components = false;
-  // gg_bfs64_all_paths (all_paths: k_min > k_max too): rows[gg::AP_PAIRS_TABLE] reached pairs, cols[..][0..3] = pair index,
-  // hops (int32 cells), paths, kept; rows[gg::AP_ROWS_TABLE] path rows, cols[..][0..4] = pair index, path index, step (int32
-  // cells), vertex id, and the edge rowid if edges were asked for (gg_bfs64_all_paths_rows / _fetch_pairs / _fetch)
-  bool all_paths = false;
+  int64_t *cols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};   // cols[h][c], device
+  int64_t *ecols[GG_MAX_HOPS + 1][GG_MAX_HOPS + 1] = {{nullptr}};  // ecols[h][j], device
+  std::vector<uint64_t> level_rows;  // the closures and the level sets: rows of level L at [L - 1]
+  bool tri_edges = false;            // TABLES of gg_triangles_edges
 };
 
 namespace gg {
@@ -343,6 +340,8 @@ namespace gg {
 //
 // The rules of an entry point: every launch goes through GG_LAUNCH; caller ids reach the device through upload_ids;
 // a result (or any other C-ABI object) under construction is held by an Owner and release()d only on success;
+// a result is made by make_result with its ResultKind, every call that reads one starts with expect_kind, and rows leave
+// through fetch_slice;
 // failures return at once through GG_TRY / GG_HIP, and the ApiScope frees the pool blocks; every host synchronisation
 // of a compute call is read_back / sync_checked, which test the chained scans' error word whenever a scan ran.  An
 // explicit dev_free is only worth writing where it lowers the pool's peak, i.e. before a later allocation in the same
@@ -368,36 +367,53 @@ template <typename T, void (*Destroy)(T *)>
 using Owner = std::unique_ptr<T, DestroyWith<T, Destroy>>;
 using ResultOwner = Owner<gg_result, gg_result_destroy>;
 
-// GG_ERR_STATE for a result of gg_khop_aggregate: it answers gg_khop_aggregate_rows / gg_khop_aggregate_fetch only; and
-// for one of gg_khop_pair_counts, which answers gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch only; and for one of
-// gg_components, which answers gg_components_rows / gg_components_fetch / gg_components_fetch_sizes only; and for one of
-// gg_bfs64_all_paths, which answers gg_bfs64_all_paths_rows / gg_bfs64_all_paths_fetch_pairs / gg_bfs64_all_paths_fetch only
-inline int refuse_all_paths(const gg_result *res, const char *fn) {
-  if (!res || !res->all_paths) return GG_OK;
-  set_error("%s: the result holds all shortest paths (gg_bfs64_all_paths_rows / _fetch_pairs / _fetch read it)", fn);
-  return GG_ERR_STATE;
-}
-inline int refuse_aggregate(const gg_result *res, const char *fn) {
-  GG_TRY(refuse_all_paths(res, fn));
-  if (res && res->components) {
-    set_error("%s: the result holds components (gg_components_rows / gg_components_fetch[_sizes] read it)", fn);
-    return GG_ERR_STATE;
-  }
-  if (res && res->pair_counts) {
-    set_error("%s: the result holds pair counts (gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch read it)", fn);
-    return GG_ERR_STATE;
-  }
-  if (!res || !res->aggregate) return GG_OK;
-  set_error("%s: the result holds grouped aggregates (gg_khop_aggregate_rows / gg_khop_aggregate_fetch read it)", fn);
+// The one rule for a result handed to a call that reads another kind (include/gg.h): GG_ERR_STATE if either kind was born
+// with a refusal contract, GG_ERR_INVALID_ARG among the five older kinds, and for a NULL result.
+struct KindName {
+  const char *holds, *readers;
+};
+constexpr KindName KIND_NAMES[] = {
+    {"fixed-length walk tables", "gg_result_rows / gg_result_fetch / gg_result_fetch_edges"},
+    {"a walk closure", "gg_walk_closure_levels / gg_walk_closure_fetch"},
+    {"a reach closure", "gg_reach_closure_levels / gg_reach_closure_fetch"},
+    {"level sets", "gg_level_sets_levels / gg_level_sets_fetch"},
+    {"shortest paths", "gg_bfs64_paths_rows / gg_bfs64_paths_fetch"},
+    {"grouped aggregates", "gg_khop_aggregate_rows / gg_khop_aggregate_fetch"},
+    {"pair counts", "gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch"},
+    {"components", "gg_components_rows / gg_components_fetch[_sizes]"},
+    {"all shortest paths", "gg_bfs64_all_paths_rows / _fetch_pairs / _fetch"},
+};
+inline int expect_kind(const gg_result *res, ResultKind want, const char *fn) {
+  if (!res) return GG_ERR_INVALID_ARG;
+  if (res->kind == want) return GG_OK;
+  if (res->kind < ResultKind::AGGREGATE && want < ResultKind::AGGREGATE) return GG_ERR_INVALID_ARG;
+  const KindName &has = KIND_NAMES[(int)res->kind];
+  set_error("%s reads %s, but the result holds %s (%s read it)", fn, KIND_NAMES[(int)want].holds, has.holds, has.readers);
   return GG_ERR_STATE;
 }
 
-inline ResultOwner make_result(gg_ctx *ctx, int k_min, int k_max) {
+inline ResultOwner make_result(gg_ctx *ctx, ResultKind kind, int k_min = 0, int k_max = -1) {
   ResultOwner res(new gg_result());
   res->ctx = ctx;
+  res->kind = kind;
   res->k_min = k_min;
   res->k_max = k_max;
   return res;
+}
+
+// Rows [offset, offset + max_rows) of a table of `total` rows to the host: the range is clamped to the table, *n_out is
+// its length, and every column that has both a destination and a device array is copied — one fetch_columns call per cell
+// width, as many as the readers ever made (gg_runtime.hip).  A reader keeps its own required-argument checks.
+struct SliceCol {
+  void *dst;         // host, NULL: not asked for
+  const void *base;  // device, row 0 of the column; NULL: the result has none
+  size_t cell = sizeof(int64_t);  // bytes per cell: 8 or 4
+};
+int fetch_slice(gg_ctx *ctx, uint64_t total, uint64_t offset, uint32_t max_rows, const SliceCol *cols, int n_cols,
+                uint32_t *n_out);
+inline int fetch_slice(gg_ctx *ctx, uint64_t total, uint64_t offset, uint32_t max_rows, std::initializer_list<SliceCol> cols,
+                       uint32_t *n_out) {
+  return fetch_slice(ctx, total, offset, max_rows, cols.begin(), (int)cols.size(), n_out);
 }
 
 // RAII-free helper: launch wrapper that records events when profiling is on.
@@ -709,12 +725,15 @@ int frontier_offsets(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fvtx, uint6
 int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, const uint32_t *fvtx, const uint64_t *foff,
                         uint64_t n_parent, uint64_t M, const Visited &vs, uint32_t n_classes, uint32_t *count,
                         PairLevel *out);
-// the levels' rows as the result's kept int64 columns (walk_seed: class, walk_rowid: vertex id); synchronises
+// the levels' rows as the result's kept int64 columns (cols[0][0]: class, cols[0][1]: vertex id); synchronises
 int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel> &levels, gg_result *res);
-// the bodies of gg_reach_closure_levels / _fetch and gg_level_sets_levels / _fetch (res is not NULL)
-int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
-int pair_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class, int64_t *vertex_id,
-                    int32_t *level, uint32_t *n_out);
+// the two kept columns of rows[0] = the sum of level_rows rows each, allocated (gg_closure.hip, emit_pair_levels)
+int alloc_level_columns(gg_ctx *ctx, gg_result *res);
+// the bodies of the _levels / _fetch readers of the walk closure, the reach closure and the level sets, after their kind
+// check: both columns of cols[0] and, if asked for, every row's level from level_rows
+int level_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels);
+int level_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *col0, int64_t *col1, int32_t *level,
+                     uint32_t *n_out);
 
 // ---- shortest paths off a finished BFS batch (gg_paths.hip; called by bfs_run in gg_bfs.hip)
 constexpr int PATHS_TABLE = 3;  // the gg_result table that holds the path rows

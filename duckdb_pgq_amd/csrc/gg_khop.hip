@@ -2229,7 +2229,7 @@ extern "C" int gg_expand_khop_range(gg_ctx *ctx, const gg_csr *csr, uint64_t src
     GG_TRY(khop_count(ctx, csr, true, (uint32_t)src_lo, n0, M1, DevFrontier(), k_min, k_max, stats));
   }
   if (materialise) {
-    ResultOwner res = make_result(ctx, k_min, k_max);
+    ResultOwner res = make_result(ctx, ResultKind::TABLES, k_min, k_max);
     if (k_max == 2 && all && ctx->force_frontier == 0) {
       // every vertex is a source: the rows are the per-vertex products in(x) x out(x), grouped by x (k_mat_mid2)
       GG_TRY(khop_materialise_mid2(ctx, const_cast<gg_csr *>(csr), 0, csr->V, k_min, res.get()));
@@ -2260,7 +2260,7 @@ extern "C" int gg_expand_khop(gg_ctx *ctx, const gg_csr *csr, const int64_t *src
     GG_HIP(hipMemsetAsync(f0.foff, 0, sizeof(uint64_t), ctx->stream));
   GG_TRY(khop_count(ctx, csr, false, 0, f0.n, f0.M, f0, k_min, k_max, stats));
   if (materialise) {
-    ResultOwner res = make_result(ctx, k_min, k_max);
+    ResultOwner res = make_result(ctx, ResultKind::TABLES, k_min, k_max);
     GG_TRY(khop_materialise(ctx, csr, f0.fv, f0.n, k_min, k_max, res.get()));
     *out_result = res.release();
   }
@@ -2278,7 +2278,7 @@ extern "C" int gg_join_probe(gg_ctx *ctx, const gg_csr *csr, const int64_t *keys
     return GG_ERR_STATE;
   }
   GG_HIP(hipSetDevice(ctx->device));
-  ResultOwner res = make_result(ctx, 1, 1);
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, 1, 1);
   uint64_t M = 0;
   uint32_t *dense = nullptr;
   uint64_t *poff = nullptr;
@@ -2344,7 +2344,7 @@ extern "C" int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_
   } else {
     GG_TRY(frontier_from_range(ctx, csr, 0, n0, &fv));
   }
-  ResultOwner res = make_result(ctx, k, k);
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, k, k);
   GG_TRY(khop_materialise(ctx, csr, fv, n0, k, k, res.get(), true));
   memset(stats, 0, sizeof(*stats));
   stats->rows[k] = res->rows[k];
@@ -2354,30 +2354,17 @@ extern "C" int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_
 
 extern "C" int gg_result_fetch_edges(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows,
                                      int64_t *const *ecols, uint32_t *n_out) {
-  GG_TRY(refuse_aggregate(res, "gg_result_fetch_edges"));
-  if (!res || !ecols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[hops];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  void *dst[GG_MAX_HOPS + 1];
-  const void *src[GG_MAX_HOPS + 1];
+  GG_TRY(expect_kind(res, ResultKind::TABLES, "gg_result_fetch_edges"));
+  if (!ecols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
+  SliceCol want[GG_MAX_HOPS + 1];
   for (int c = 0; c < hops; c++) {
-    if (!ecols[c] || !res->ecols[hops][c]) {
+    if (offset < res->rows[hops] && (!ecols[c] || !res->ecols[hops][c])) {  // (past the end nothing is asked of them)
       set_error("gg_result_fetch_edges: the result carries no edge columns (gg_expand_khop_edges makes them)");
       return GG_ERR_INVALID_ARG;
     }
-    dst[c] = ecols[c];
-    src[c] = res->ecols[hops][c] + offset;
+    want[c] = {ecols[c], res->ecols[hops][c]};
   }
-  GG_TRY(ctx->fetch_columns(dst, src, hops, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  return fetch_slice(res->ctx, res->rows[hops], offset, max_rows, want, hops, n_out);
 }
 
 extern "C" int gg_khop_partition(gg_ctx *ctx, const gg_csr *csr, int n_parts, uint64_t *bounds) {
@@ -2441,7 +2428,7 @@ extern "C" int gg_expand_khop_mid_result(gg_ctx *ctx, gg_csr *csr, uint64_t mid_
   GG_HIP(hipSetDevice(ctx->device));
   // (stats == NULL: the rows only — no counting expansion in front of the materialisation; gg_result_rows has the counts)
   if (stats) GG_TRY(khop_count_mid(ctx, csr, mid_lo, mid_hi, k_min, stats));
-  ResultOwner res = make_result(ctx, k_min, 2);
+  ResultOwner res = make_result(ctx, ResultKind::TABLES, k_min, 2);
   GG_TRY(khop_materialise_mid2(ctx, csr, mid_lo, mid_hi, k_min, res.get()));
   *out_result = res.release();
   return GG_OK;
@@ -2510,35 +2497,22 @@ extern "C" int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint
 }
 
 extern "C" int gg_result_rows(const gg_result *res, int hops, uint64_t *n_rows) {
-  GG_TRY(refuse_aggregate(res, "gg_result_rows"));
-  if (!res || !n_rows || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::TABLES, "gg_result_rows"));
+  if (!n_rows || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[hops];
   return GG_OK;
 }
 
 extern "C" int gg_result_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows,
                                int64_t *const *cols, uint32_t *n_out) {
-  GG_TRY(refuse_aggregate(res, "gg_result_fetch"));
-  if (!res || !cols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  uint64_t total = res->rows[hops];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  void *dst[GG_MAX_HOPS + 1];
-  const void *src[GG_MAX_HOPS + 1];
+  GG_TRY(expect_kind(res, ResultKind::TABLES, "gg_result_fetch"));
+  if (!cols || !n_out || hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
+  SliceCol want[GG_MAX_HOPS + 1];
   for (int c = 0; c <= hops; c++) {
-    if (!cols[c]) return GG_ERR_INVALID_ARG;
-    dst[c] = cols[c];
-    src[c] = res->cols[hops][c] + offset;
+    if (offset < res->rows[hops] && !cols[c]) return GG_ERR_INVALID_ARG;  // (past the end nothing is asked of them)
+    want[c] = {cols[c], res->cols[hops][c]};
   }
-  GG_TRY(ctx->fetch_columns(dst, src, hops + 1, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  return fetch_slice(res->ctx, res->rows[hops], offset, max_rows, want, hops + 1, n_out);
 }
 
 // ---- digest of materialised rows ------------------------------------------------------------------------------------
@@ -2580,7 +2554,7 @@ __global__ __launch_bounds__(256) void k_result_digest(IdColsIn cols, int hops, 
 extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result *res, int hops, uint64_t *n_rows,
                                 uint64_t *digest) {
   if (!ctx || !csr || !res || !digest || res->ctx != ctx || csr->ctx != ctx) return GG_ERR_INVALID_ARG;
-  if (hops < res->k_min || hops > res->k_max || hops < 1 || hops > GG_MAX_HOPS) {
+  if (res->kind != ResultKind::TABLES || hops < res->k_min || hops > res->k_max || hops < 1 || hops > GG_MAX_HOPS) {
     set_error("gg_result_digest: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
     return GG_ERR_INVALID_ARG;
   }
@@ -2621,8 +2595,6 @@ extern "C" void gg_result_destroy(gg_result *res) {
         ctx->dev_free(res->cols[h][c]);
         ctx->dev_free(res->ecols[h][c]);
       }
-    ctx->dev_free(res->walk_seed);
-    ctx->dev_free(res->walk_rowid);
   }
   delete res;
 }

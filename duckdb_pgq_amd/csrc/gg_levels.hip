@@ -144,8 +144,7 @@ extern "C" int gg_level_sets(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed
     }
   }
   GG_HIP(hipSetDevice(ctx->device));
-  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-  res->level_sets = true;
+  ResultOwner res = make_result(ctx, ResultKind::LEVEL_SETS);
   uint32_t *seed_dense = nullptr, *seed_cls = nullptr;
   GG_TRY(upload_ids(ctx, csr, seed_ids, n_seeds, &seed_dense));
   GG_TRY(ctx->dev_alloc((void **)&seed_cls, (n_seeds ? n_seeds : 1) * sizeof(uint32_t)));
@@ -255,14 +254,12 @@ extern "C" int gg_level_sets(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed
 }
 
 extern "C" int gg_level_sets_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
-  GG_TRY(refuse_all_paths(res, "gg_level_sets_levels"));
-  if (!res || !res->level_sets) return GG_ERR_INVALID_ARG;
-  return pair_rows_levels(res, rows_per_level, capacity, n_levels);
+  GG_TRY(expect_kind(res, ResultKind::LEVEL_SETS, "gg_level_sets_levels"));
+  return level_rows_levels(res, rows_per_level, capacity, n_levels);
 }
 
 extern "C" int gg_level_sets_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
                                    int64_t *vertex_id, int32_t *level, uint32_t *n_out) {
-  GG_TRY(refuse_all_paths(res, "gg_level_sets_fetch"));
-  if (!res || !res->level_sets) return GG_ERR_INVALID_ARG;
-  return pair_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
+  GG_TRY(expect_kind(res, ResultKind::LEVEL_SETS, "gg_level_sets_fetch"));
+  return level_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
 }

@@ -261,11 +261,7 @@ extern "C" int gg_khop_pair_counts(gg_ctx *ctx, const gg_csr *csr_c, const int64
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
   const uint64_t V = csr->V, E = csr->E;
   ResultOwner res;
-  if (out_result) {
-    res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-    res->pair_counts = true;
-    res->agg_k_min = k_min, res->agg_k_max = k_max;
-  }
+  if (out_result) res = make_result(ctx, ResultKind::PAIR_COUNTS, k_min, k_max);
   if (V && E) {
     hipStream_t st = ctx->stream;
     GG_TRY(ensure_reverse(ctx, csr));
@@ -378,11 +374,8 @@ extern "C" int gg_khop_pair_counts(gg_ctx *ctx, const gg_csr *csr_c, const int64
 
 extern "C" int gg_khop_pair_counts_rows(const gg_result *res, int hops, uint64_t *n_rows) {
   if (!res || !n_rows) return GG_ERR_INVALID_ARG;
-  if (!res->pair_counts) {
-    set_error("gg_khop_pair_counts_rows: the result is not one of gg_khop_pair_counts");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->agg_k_min || hops > res->agg_k_max) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::PAIR_COUNTS, "gg_khop_pair_counts_rows"));
+  if (hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[hops];
   return GG_OK;
 }
@@ -390,28 +383,11 @@ extern "C" int gg_khop_pair_counts_rows(const gg_result *res, int hops, uint64_t
 extern "C" int gg_khop_pair_counts_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows,
                                          int64_t *src_index, int64_t *vertex_id, uint64_t *walks, uint32_t *n_out) {
   if (!res || !n_out) return GG_ERR_INVALID_ARG;
-  if (!res->pair_counts) {
-    set_error("gg_khop_pair_counts_fetch: the result is not one of gg_khop_pair_counts");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->agg_k_min || hops > res->agg_k_max) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[hops];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  const uint64_t take = total - offset < max_rows ? total - offset : max_rows;
-  void *want[3] = {src_index, vertex_id, walks};
-  void *dst[3];
-  const void *src[3];
-  int n = 0;
-  for (int c = 0; c < 3; c++)
-    if (want[c]) dst[n] = want[c], src[n] = res->cols[hops][c] + offset, n++;
-  if (n && take) GG_TRY(ctx->fetch_columns(dst, src, n, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  GG_TRY(expect_kind(res, ResultKind::PAIR_COUNTS, "gg_khop_pair_counts_fetch"));
+  if (hops < res->k_min || hops > res->k_max) return GG_ERR_INVALID_ARG;
+  int64_t *const *col = res->cols[hops];
+  return fetch_slice(res->ctx, res->rows[hops], offset, max_rows,
+                     {{src_index, col[0]}, {vertex_id, col[1]}, {walks, col[2]}}, n_out);
 }
 
 extern "C" int gg_debug_pair_counts(gg_ctx *ctx, uint32_t long_row_entries, int gather_mode) {

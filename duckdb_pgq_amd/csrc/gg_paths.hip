@@ -278,35 +278,21 @@ int paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes, co
 }  // namespace gg
 
 extern "C" int gg_bfs64_paths_rows(const gg_result *res, uint64_t *n_rows) {
-  GG_TRY(refuse_all_paths(res, "gg_bfs64_paths_rows"));
-  if (!res || !res->paths || !n_rows) return GG_ERR_INVALID_ARG;
+  GG_TRY(expect_kind(res, ResultKind::PATHS, "gg_bfs64_paths_rows"));
+  if (!n_rows) return GG_ERR_INVALID_ARG;
   *n_rows = res->rows[PATHS_TABLE];
   return GG_OK;
 }
 
 extern "C" int gg_bfs64_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
                                     int32_t *step, int64_t *vertex_id, int64_t *edge_rowid, uint32_t *n_out) {
-  GG_TRY(refuse_all_paths(res, "gg_bfs64_paths_fetch"));
-  if (!res || !res->paths || !n_out || !pair_index || !step || !vertex_id) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  const uint64_t total = res->rows[PATHS_TABLE];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  GG_HIP(hipSetDevice(ctx->device));
-  const bool edges = res->cols[PATHS_TABLE][3] != nullptr;
-  void *dst[3] = {pair_index, vertex_id, edge_rowid};
-  const void *src[3] = {res->cols[PATHS_TABLE][0] + offset, res->cols[PATHS_TABLE][1] + offset,
-                        edges ? res->cols[PATHS_TABLE][3] + offset : nullptr};
-  GG_TRY(ctx->fetch_columns(dst, src, edges && edge_rowid ? 3 : 2, take * sizeof(int64_t)));
-  void *dst_s[1] = {step};
-  const void *src_s[1] = {reinterpret_cast<const int32_t *>(res->cols[PATHS_TABLE][2]) + offset};
-  GG_TRY(ctx->fetch_columns(dst_s, src_s, 1, take * sizeof(int32_t)));
-  if (!edges && edge_rowid)
-    for (uint64_t r = 0; r < take; r++) edge_rowid[r] = -1;  // searched without edges
-  *n_out = (uint32_t)take;
+  GG_TRY(expect_kind(res, ResultKind::PATHS, "gg_bfs64_paths_fetch"));
+  if (!n_out || !pair_index || !step || !vertex_id) return GG_ERR_INVALID_ARG;
+  int64_t *const *col = res->cols[PATHS_TABLE];
+  GG_TRY(fetch_slice(res->ctx, res->rows[PATHS_TABLE], offset, max_rows,
+                     {{pair_index, col[0]}, {vertex_id, col[1]}, {edge_rowid, col[3]}, {step, col[2], sizeof(int32_t)}},
+                     n_out));
+  if (!col[3] && edge_rowid)
+    for (uint32_t r = 0; r < *n_out; r++) edge_rowid[r] = -1;  // searched without edges
   return GG_OK;
 }

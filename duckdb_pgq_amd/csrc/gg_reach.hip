@@ -171,54 +171,46 @@ int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, co
   return GG_OK;
 }
 
+int alloc_level_columns(gg_ctx *ctx, gg_result *res) {
+  for (uint64_t m : res->level_rows) res->rows[0] += m;
+  for (int c = 0; c < 2; c++) {
+    GG_TRY(ctx->dev_alloc((void **)&res->cols[0][c], (res->rows[0] ? res->rows[0] : 1) * sizeof(int64_t)));
+    ctx->keep(res->cols[0][c]);
+  }
+  return GG_OK;
+}
+
 int emit_pair_levels(gg_ctx *ctx, const gg_csr *csr, const std::vector<PairLevel> &levels, gg_result *res) {
-  uint64_t n_rows = 0;
-  for (uint64_t m : res->level_rows) n_rows += m;
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_seed, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_seed);
-  GG_TRY(ctx->dev_alloc((void **)&res->walk_rowid, (n_rows ? n_rows : 1) * sizeof(int64_t)));
-  ctx->keep(res->walk_rowid);
+  GG_TRY(alloc_level_columns(ctx, res));
   uint64_t at = 0;
   for (const PairLevel &l : levels) {
     GG_LAUNCH(ctx, "reach_emit", k_reach_emit, stride_grid(ctx, l.n), dim3(256), 0, l.cls, l.vtx, l.n, csr->vid,
-              res->walk_seed + at, res->walk_rowid + at, (const unsigned long long *)ctx->dev_err);
+              res->cols[0][0] + at, res->cols[0][1] + at, (const unsigned long long *)ctx->dev_err);
     at += l.n;
   }
   return sync_checked(ctx);
 }
 
-int pair_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
+int level_rows_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
   if (!n_levels || (capacity > 0 && !rows_per_level)) return GG_ERR_INVALID_ARG;
   *n_levels = (int)res->level_rows.size();
   for (int l = 0; l < capacity && l < *n_levels; l++) rows_per_level[l] = res->level_rows[l];
   return GG_OK;
 }
 
-int pair_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class, int64_t *vertex_id,
-                    int32_t *level, uint32_t *n_out) {
-  if (!n_out || !seed_class || !vertex_id) return GG_ERR_INVALID_ARG;
-  gg_ctx *ctx = res->ctx;
-  uint64_t total = 0;
-  for (uint64_t m : res->level_rows) total += m;
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  uint64_t take = total - offset;
-  if (take > max_rows) take = max_rows;
-  GG_HIP(hipSetDevice(ctx->device));
-  void *dst[2] = {seed_class, vertex_id};
-  const void *src[2] = {res->walk_seed + offset, res->walk_rowid + offset};
-  GG_TRY(ctx->fetch_columns(dst, src, 2, take * sizeof(int64_t)));
+int level_rows_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *col0, int64_t *col1, int32_t *level,
+                     uint32_t *n_out) {
+  if (!n_out || !col0 || !col1) return GG_ERR_INVALID_ARG;
+  GG_TRY(fetch_slice(res->ctx, res->rows[0], offset, max_rows, {{col0, res->cols[0][0]}, {col1, res->cols[0][1]}}, n_out));
   if (level) {  // the level of a row follows from the per-level row counts
     uint64_t start = 0;
     for (size_t l = 0; l < res->level_rows.size(); l++) {
       const uint64_t end = start + res->level_rows[l];
-      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + take; r++) level[r - offset] = (int32_t)(l + 1);
+      for (uint64_t r = offset > start ? offset : start; r < end && r < offset + *n_out; r++)
+        level[r - offset] = (int32_t)(l + 1);
       start = end;
     }
   }
-  *n_out = (uint32_t)take;
   return GG_OK;
 }
 
@@ -250,8 +242,7 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
     n_seen += seed_seen && seed_seen[i];
   }
   GG_HIP(hipSetDevice(ctx->device));
-  ResultOwner res = make_result(ctx, 1, 0);  // (no fixed-length table: gg_result_rows / gg_result_fetch refuse it)
-  res->reach = true;
+  ResultOwner res = make_result(ctx, ResultKind::REACH);
   uint32_t *seed_dense = nullptr, *seed_cls = nullptr;
   uint8_t *seen = nullptr;
   GG_TRY(upload_ids(ctx, csr, seed_ids, n_seeds, &seed_dense));
@@ -323,14 +314,12 @@ extern "C" int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *s
 }
 
 extern "C" int gg_reach_closure_levels(const gg_result *res, uint64_t *rows_per_level, int capacity, int *n_levels) {
-  GG_TRY(refuse_all_paths(res, "gg_reach_closure_levels"));
-  if (!res || !res->reach) return GG_ERR_INVALID_ARG;
-  return pair_rows_levels(res, rows_per_level, capacity, n_levels);
+  GG_TRY(expect_kind(res, ResultKind::REACH, "gg_reach_closure_levels"));
+  return level_rows_levels(res, rows_per_level, capacity, n_levels);
 }
 
 extern "C" int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *seed_class,
                                       int64_t *vertex_id, int32_t *level, uint32_t *n_out) {
-  GG_TRY(refuse_all_paths(res, "gg_reach_closure_fetch"));
-  if (!res || !res->reach) return GG_ERR_INVALID_ARG;
-  return pair_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
+  GG_TRY(expect_kind(res, ResultKind::REACH, "gg_reach_closure_fetch"));
+  return level_rows_fetch(res, offset, max_rows, seed_class, vertex_id, level, n_out);
 }

@@ -619,6 +619,24 @@ int gg_ctx::fetch_columns(void *const *dst, const void *const *src, int n_cols, 
   return GG_OK;
 }
 
+int gg::fetch_slice(gg_ctx *ctx, uint64_t total, uint64_t offset, uint32_t max_rows, const SliceCol *cols, int n_cols,
+                    uint32_t *n_out) {
+  GG_HIP(hipSetDevice(ctx->device));
+  const uint64_t left = offset < total ? total - offset : 0, take = left < max_rows ? left : max_rows;
+  if (n_cols > GG_MAX_HOPS + 1) return GG_ERR_INVALID_ARG;  // (no table has more columns)
+  for (const size_t cell : {sizeof(int64_t), sizeof(int32_t)}) {
+    void *dst[GG_MAX_HOPS + 1];
+    const void *src[GG_MAX_HOPS + 1];
+    int n = 0;
+    for (int c = 0; c < n_cols; c++)
+      if (cols[c].cell == cell && cols[c].dst && cols[c].base)
+        dst[n] = cols[c].dst, src[n] = (const char *)cols[c].base + offset * cell, n++;
+    if (n && take) GG_TRY(ctx->fetch_columns(dst, src, n, take * cell));
+  }
+  *n_out = (uint32_t)take;
+  return GG_OK;
+}
+
 extern "C" int gg_host_alloc(gg_ctx *ctx, uint64_t bytes, void **out) {
   if (!ctx || !out) return GG_ERR_INVALID_ARG;
   *out = nullptr;

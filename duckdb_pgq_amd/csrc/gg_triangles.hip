@@ -383,7 +383,8 @@ int tri_call(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, uint64_t 
   hipStream_t st = ctx->stream;
   const uint64_t V = csr->V, E = csr->E;
   ResultOwner res;
-  if (materialise) res = make_result(ctx, 2, 2);  // table 2: (a, b, c), with edges also ecols (e1, e2, e3)
+  // table 2: (a, b, c), with edges also ecols (e1, e2, e3)
+  if (materialise) res = make_result(ctx, ResultKind::TABLES, 2, 2);
   if (edges) res->tri_edges = true;
   const bool all = src_ids == nullptr;
   if (all) n_src = V;
@@ -504,23 +505,9 @@ extern "C" int gg_triangles_fetch_edges(const gg_result *res, uint64_t offset, u
     set_error("gg_triangles_fetch_edges: the result carries no triangle edge columns (gg_triangles_edges makes them)");
     return GG_ERR_STATE;
   }
-  gg_ctx *ctx = res->ctx;
-  GG_HIP(hipSetDevice(ctx->device));
-  const uint64_t total = res->rows[2];
-  if (offset >= total) {
-    *n_out = 0;
-    return GG_OK;
-  }
-  const uint64_t take = total - offset < max_rows ? total - offset : max_rows;
-  void *dst[3];
-  const void *src[3];
-  for (int c = 0; c < 3; c++) {
-    dst[c] = ecols[c];
-    src[c] = res->ecols[2][c] + offset;
-  }
-  GG_TRY(ctx->fetch_columns(dst, src, 3, take * sizeof(int64_t)));
-  *n_out = (uint32_t)take;
-  return GG_OK;
+  int64_t *const *col = res->ecols[2];
+  return fetch_slice(res->ctx, res->rows[2], offset, max_rows, {{ecols[0], col[0]}, {ecols[1], col[1]}, {ecols[2], col[2]}},
+                     n_out);
 }
 
 extern "C" int gg_debug_triangle_tile(gg_ctx *ctx, uint32_t lds_entries) {

@@ -251,6 +251,13 @@ int gg_stream_wait(gg_ctx *ctx, void *other_stream, int direction);
 /* Split [0,V) into n_parts contiguous middle-vertex ranges of near-equal product work. */
 int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint64_t *bounds);
 
+/* A result answers the calls of its own kind only.  The five older kinds — fixed-length walk tables, walk closure, reach
+ * closure, level sets, paths — refuse one another with GG_ERR_INVALID_ARG; the kinds that state a refusal contract of their
+ * own (grouped aggregates, pair counts, components, all shortest paths) are refused by every other call, and their calls
+ * refuse every other result, with GG_ERR_STATE.  A fixed-length walk table (a result of gg_expand_khop*, gg_bfs64_pairs*,
+ * gg_walk_endpoints, gg_join_probe, gg_triangles*, the filters or gg_result_extend_edge) answers gg_result_rows,
+ * gg_result_fetch, gg_result_fetch_edges and gg_result_digest for the levels it holds; a closure, level-set or paths result
+ * is GG_ERR_INVALID_ARG to them for every `hops`. */
 int gg_result_rows(const gg_result *res, int hops, uint64_t *n_rows);
 /* Copy rows [offset, offset+max_rows) of the h-hop table into cols[0..h] (host arrays of >= max_rows).  Destinations
  * in page-locked memory (gg_host_alloc) are filled over the context's fetch lanes (concurrent callers
@@ -648,7 +655,9 @@ int gg_bfs64_pairs_packed(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids
  * distance cell per entry looked at and a piece of a forward row: a path of 10^5 steps (a chain) is 10^5 dependent
  * steps of one lane group, slow and correct.  stats: those of the BFS.
  * The first call on a CSR sorts a copy of its reverse rows by source (4 bytes per edge, kept with the CSR).
- * The result answers gg_bfs64_paths_rows / gg_bfs64_paths_fetch only. */
+ * The result answers gg_bfs64_paths_rows / gg_bfs64_paths_fetch only: those two refuse a walk table, a closure or level sets
+ * with GG_ERR_INVALID_ARG, as the calls of those kinds refuse this result (the walk closure's included), and an aggregate,
+ * pair-count, component or all-paths result with GG_ERR_STATE. */
 int gg_bfs64_paths(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
                    const uint32_t *pair_lane, const int64_t *pair_dst_ids, uint64_t n_pairs, int want_edges,
                    gg_bfs_stats *stats, gg_result **out_result);
@@ -743,7 +752,9 @@ int gg_walk_endpoints(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, ui
  * first) — a caller that may meet cycles bounds max_levels.  A level of 2^32 walks or more fails with GG_ERR_TOO_LARGE;
  * a shard CSR with GG_ERR_STATE; a CSR built without edge rowids with GG_ERR_STATE too, whichever build made it (no
  * rows without their rowid column), and the context stays usable.
- * The result answers gg_walk_closure_levels / gg_walk_closure_fetch (not gg_result_rows / gg_result_fetch). */
+ * The result answers gg_walk_closure_levels / gg_walk_closure_fetch only (not gg_result_rows / gg_result_fetch): those two
+ * refuse a walk table, a reach closure, level sets or paths with GG_ERR_INVALID_ARG and the kinds with a refusal contract
+ * of their own with GG_ERR_STATE. */
 int gg_walk_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, uint64_t n_seeds, int max_levels,
                     gg_result **out_result);
 /* *n_levels = the deepest level L with walks; rows_per_level[L - 1] = walks of L edges, for the first `capacity`. */
@@ -772,7 +783,8 @@ int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_ro
  * class << 32 | vertex (gg_debug_reach_visited forces either).  A level of 2^32 children or more fails with
  * GG_ERR_TOO_LARGE, as do 2^32 seeds or more; a class >= n_classes with GG_ERR_INVALID_ARG; a shard CSR with
  * GG_ERR_STATE.  The result answers gg_reach_closure_levels / gg_reach_closure_fetch (not gg_result_rows /
- * gg_result_fetch, nor the walk closure's calls). */
+ * gg_result_fetch, nor the walk closure's calls): those two refuse another of the older kinds with GG_ERR_INVALID_ARG and an
+ * aggregate, pair-count, component or all-paths result with GG_ERR_STATE. */
 int gg_reach_closure(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, const uint32_t *seed_class,
                      const uint8_t *seed_seen, uint64_t n_seeds, uint32_t n_classes, gg_result **out_result);
 /* *n_levels = the deepest level L with rows; rows_per_level[L - 1] = rows of level L, for the first `capacity`. */
@@ -799,7 +811,9 @@ int gg_reach_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_r
  * more; a class >= n_classes with GG_ERR_INVALID_ARG; a shard CSR with GG_ERR_STATE.
  * The per-level set is a bitmap of n_classes x V bits within gg_reach_closure's budget, else a hash set sized from the
  * level's child count; a level's rows are read off the bitmap in order or claimed and sorted (DESIGN.md 4.9;
- * gg_debug_level_sets forces either).  The result answers gg_level_sets_levels / gg_level_sets_fetch only. */
+ * gg_debug_level_sets forces either).  The result answers gg_level_sets_levels / gg_level_sets_fetch only: those two
+ * refuse another of the older kinds with GG_ERR_INVALID_ARG and an aggregate, pair-count, component or all-paths result with
+ * GG_ERR_STATE. */
 int gg_level_sets(gg_ctx *ctx, const gg_csr *csr, const int64_t *seed_ids, const uint32_t *seed_class, uint64_t n_seeds,
                   uint32_t n_classes, int max_levels, gg_result **out_result);
 /* *n_levels = the deepest level L with rows; rows_per_level[L - 1] = members of level L, for the first `capacity`. */
