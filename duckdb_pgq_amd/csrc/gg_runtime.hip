@@ -450,6 +450,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->cc_init_mode = 0;
   ctx->cc_jumps_per_check = 0;
   ctx->extend_tile_rows = 0;
+  ctx->group_route = 0;
+  ctx->group_lds_keys = 0;
   ctx->keep_edge_rowid = true;
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));

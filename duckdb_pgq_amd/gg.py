@@ -37,6 +37,7 @@ SYMBOLS = [
     "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
     "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
     "gg_result_extend_edge", "gg_debug_extend",
+    "gg_result_group_by", "gg_debug_group",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -87,6 +88,10 @@ class EdgeFilterStats(C.Structure):
 
 class ExtendStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("rows_matched", C.c_uint64)]
+
+
+class GroupStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_grouped", C.c_uint64), ("groups", C.c_uint64), ("route", C.c_uint32)]
 
 
 class AggStats(C.Structure):
@@ -222,6 +227,8 @@ def load_library(path: str | None = None):
     lib.gg_result_extend_edge.argtypes = [P, P, C.c_int, P, C.c_int, C.c_int, C.c_int, C.POINTER(ExtendStats),
                                           C.POINTER(P)]
     lib.gg_debug_extend.argtypes = [P, C.c_uint32]
+    lib.gg_result_group_by.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, i64p, C.POINTER(GroupStats), C.POINTER(P)]
+    lib.gg_debug_group.argtypes = [P, C.c_int, C.c_uint32]
     lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
@@ -804,6 +811,34 @@ class GG:
     def debug_extend(self, tile_rows: int = 0):
         """Output rows per workgroup of extend_edge's write pass (0: the default).  Results must not depend on it."""
         self._chk(self.lib.gg_debug_extend(self.ctx, int(tile_rows)))
+
+    def group_by(self, res: KhopResult, hops: int, key_col: int, key_csr: Csr, weight_col=None, weight_csr=None,
+                 weights=None, fetch: bool = True) -> "KhopAggregate":
+        """gg_result_group_by: the rows of res's `hops`-hop table grouped by column key_col, whose cells are vertices of
+        key_csr (other rows form no group): per key one row (vertex id, walks = its rows, total = the sum of
+        weights[vertex of weight_csr (None: key_csr) in column weight_col]; without weights total == walks), ascending by
+        dense index in key_csr.  weights: V(weight_csr) integers in vertex-table order.  The answer is a KhopAggregate of
+        the one level `hops` (khop_aggregate_top orders it); stats: {"rows_in", "rows_grouped", "groups", "route"}.
+        fetch=False: the stats only, nothing is kept on the device."""
+        wcsr = weight_csr if weight_csr is not None else key_csr
+        wp = None
+        if weights is not None:
+            w, wp = _i64(weights)
+            if w.ndim != 1 or w.size != wcsr.V:
+                raise ValueError(f"weights: {w.size} entries for {wcsr.V} vertices")
+        st, out = GroupStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_group_by(self.ctx, res.handle, hops, key_col, key_csr.handle,
+                                              -1 if weight_col is None else int(weight_col),
+                                              weight_csr.handle if weight_csr is not None else None, wp, C.byref(st),
+                                              C.byref(out) if fetch else None))
+        d = {"rows_in": int(st.rows_in), "rows_grouped": int(st.rows_grouped), "groups": int(st.groups),
+             "route": int(st.route)}
+        return KhopAggregate(self, out if fetch else None, d)
+
+    def debug_group(self, route: int = 0, lds_keys: int = 0):
+        """group_by accumulates in the workgroup-private LDS table where it fits (1) or in the global cells (2); lds_keys
+        shrinks the keys that table may hold (0: the defaults).  Results must not depend on it."""
+        self._chk(self.lib.gg_debug_group(self.ctx, int(route), int(lds_keys)))
 
     def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
         """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows

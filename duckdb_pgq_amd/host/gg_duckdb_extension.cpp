@@ -33,6 +33,9 @@
 //                                              a second keyed table on v{from_col} = ext_key_col, with the row's rowid
 //   gg_khop_extend_count(same arguments)
 //        -> (rows BIGINT, walks BIGINT, matched BIGINT)          (gg_extend.cpp)
+//   gg_khop_extend_group(the same arguments, key_col, n)
+//        -> (rank BIGINT, key BIGINT, rows BIGINT)   those joined rows counted per value of column key_col (hops + 1: w),
+//                                              the first n groups under ORDER BY rows DESC, key (gg_group.cpp)
 //   gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //                           filter_table, filter_src, filter_dst, hops)
 //        -> (w BIGINT, v0 BIGINT, ..., v{hops} BIGINT)      Train Benchmark ConnectedSegments
@@ -757,6 +760,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterExtendFunctions(*con.context);
+	GGRegisterGroupFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterComponentFunctions(*con.context);

@@ -137,8 +137,8 @@ void PhysicalGGExtend::GetData(ExecutionContext &context, DataChunk &chunk, Glob
 
 //! The statement's own graph: the walk CSR over (vertices, edges), then the CSR of the joined table with its rowids over
 //! the union of the vertex ids and its endpoints, in GGGraph::filter_csr
-static shared_ptr<GGGraph> BuildExtendGraph(ClientContext &context, const GGScanSource &vertices, const GGScanSource &edges,
-                                            const GGScanSource &ext) {
+shared_ptr<GGGraph> GGBuildExtendGraph(ClientContext &context, const GGScanSource &vertices, const GGScanSource &edges,
+                                       const GGScanSource &ext) {
 	auto graph = make_shared<GGGraph>(0, false, 1); // (the walks carry no edge rowids)
 	PhysicalGGVertexSink vsink(graph, {LogicalType::BIGINT}, 0);
 	GGRunSinkPipeline(context, vertices, vsink);
@@ -172,9 +172,9 @@ static unique_ptr<FunctionData> ExtendBindInternal(vector<Value> &inputs, vector
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
 		// (tables and columns are resolved at execution time: a missing one raises here)
-		opened.graph = BuildExtendGraph(ctx, GGTableSource(ctx, vertex_table, {vertex_key}, false),
-		                                GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false),
-		                                GGTableSource(ctx, ext_table, {ext_key, ext_next}, true));
+		opened.graph = GGBuildExtendGraph(ctx, GGTableSource(ctx, vertex_table, {vertex_key}, false),
+		                                  GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false),
+		                                  GGTableSource(ctx, ext_table, {ext_key, ext_next}, true));
 		vector<int64_t> sources;
 		if (!sources_sql.empty()) {
 			sources = GGQueryInt64Column(ctx, sources_sql, count_only ? "gg_khop_extend_count: sources"

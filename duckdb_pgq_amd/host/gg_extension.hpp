@@ -100,6 +100,13 @@ void GGRegisterEdgeFilterFunctions(ClientContext &context);
 
 //! gg_extend.cpp: registers gg_khop_extend / gg_khop_extend_count (inside the caller's transaction)
 void GGRegisterExtendFunctions(ClientContext &context);
+//! gg_extend.cpp: the graph of such a statement — the walk CSR over (vertices, edges), then the CSR of the joined table with
+//! its rowids over the union of the vertex ids and its endpoints, in GGGraph::filter_csr.  Never a pinned graph.
+shared_ptr<GGGraph> GGBuildExtendGraph(ClientContext &context, const GGScanSource &vertices, const GGScanSource &edges,
+                                       const GGScanSource &ext);
+
+//! gg_group.cpp: registers gg_khop_extend_group (inside the caller's transaction)
+void GGRegisterGroupFunctions(ClientContext &context);
 
 //! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
 void GGRegisterAggregateFunctions(ClientContext &context);

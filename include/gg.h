@@ -59,6 +59,13 @@
  *           (knows -> message on k_person2id = m_creatorid, benchmark/ldbc/queries/interactive-complex-2.sql:2-7;
  *           knows -> message -> message_tag, interactive-complex-4.sql:2-8; interactive-complex-9.sql:13-15,
  *           interactive-complex-6.sql:14-17; a branch off a middle column, interactive-complex-5.sql:15)
+ *   gg_result_group_by
+ *        <- PhysicalHashAggregate above the last hash join of such a chain: GROUP BY one column of the joined rows
+ *                                                               physical_hash_aggregate.cpp:152-266,
+ *                                                               src/execution/aggregate_hashtable.cpp:367-504,
+ *                                                               join_hashtable.cpp:442-476
+ *           (count(*) GROUP BY tag over knows [-> knows] -> message -> message_tag, interactive-complex-4.sql:1-22,
+ *           interactive-complex-6.sql:1-22; by forum, interactive-complex-5.sql; a score summed per person, bi-8.sql:41-53)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -369,6 +376,52 @@ typedef struct gg_extend_stats {
 } gg_extend_stats;
 int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *csr, int from_col, int want_edges,
                           int materialise, gg_extend_stats *stats, gg_result **out_result);
+/* GROUP BY one column of a materialised walk table: count(*) and sum(weight) per key, left on the device as an aggregate
+ * result.
+ * What it replaces in the reference: PhysicalHashAggregate (src/execution/operator/aggregate/physical_hash_aggregate.cpp:
+ * 152-266, GroupedAggregateHashTable::FindOrCreateGroups, src/execution/aggregate_hashtable.cpp:367-504) fed by the last
+ * hash join's ScanStructure::NextInnerJoin (src/execution/join_hashtable.cpp:442-476) — the end of
+ * benchmark/ldbc/queries/interactive-complex-4.sql:1-22 and interactive-complex-6.sql:1-22 (knows [-> knows] -> message ->
+ * message_tag under count(*) GROUP BY tag ORDER BY 2 DESC, name LIMIT 10), of interactive-complex-5.sql (by forum) and of
+ * bi-8.sql:41-53 (a score summed per person above a mixed chain).  gg_khop_aggregate groups the walks of ONE CSR by their
+ * first or last vertex and never sees a table; this groups whatever table the expansion, the filters and
+ * gg_result_extend_edge left in HBM, so expand -> filter -> extend -> group -> gg_khop_aggregate_top runs without a row
+ * leaving the device.
+ * Input: the `hops`-hop table of `res` with its id columns v0..v_hops — whatever gg_result_extend_edge accepts, its own
+ * output and the filters' included; edge columns are ignored.  Tables of 2^32 rows or more are accepted: every counter is
+ * 64-bit and the kernels stride.
+ * Key: the cell of key_col is looked up in key_csr's id dictionary exactly as gg_csr_lookup does; a row whose key is no
+ * vertex of key_csr forms no group (the inner join with the key's table) and shows as rows_in - rows_grouped.
+ * Aggregates per group: walks = the number of its rows, exact; total = the sum over its rows of weights[dense index in
+ * weight_csr (NULL: key_csr) of the cell of weight_col], a weight cell that is no vertex of weight_csr weighing 0 (the host
+ * operators' NULL convention), as a 128-bit two's-complement integer wrapping mod 2^128 like gg_khop_aggregate's.
+ * weight_col == -1 (then weights must be NULL): total = walks and no sum is formed.  weights: V(weight_csr) int64 in
+ * vertex-table order, host memory.
+ * Output: an aggregate result of the single level `hops` (k_min = k_max = hops), one row (vertex id, walks, total lo, total
+ * hi) per key that occurs, ascending by dense index in key_csr, placed by count, scan, write.  It answers
+ * gg_khop_aggregate_rows / gg_khop_aggregate_fetch / gg_khop_aggregate_top (with csr = key_csr the bias is per key) and is
+ * refused by every other reader, this function included, with GG_ERR_STATE.  The rows are identical on every run, on both
+ * routes and under every testing knob: the sums are integer additions mod 2^64 and mod 2^128.
+ * Two routes, chosen per call (stats->route): a workgroup-private table in LDS when key_csr's vertices fit it, flushed with
+ * one global atomic per non-zero cell and workgroup; global cells otherwise.  On both, lanes of a wavefront that hold the
+ * same key in adjacent rows are combined first, so a hub key costs one atomic per wavefront.
+ * stats (nullable) and out_result (NULL: stats only) as gg_khop_aggregate's; one host synchronisation per call.
+ * Errors: NULL ctx / res / key_csr, objects of another context, hops outside the result's k_min..k_max, key_col outside
+ * 0..hops, weight_col outside -1..hops, weights NULL with weight_col >= 0 or non-NULL with weight_col == -1, stats and
+ * out_result both NULL: GG_ERR_INVALID_ARG.  A shard CSR in either role, or a result without fixed-length tables:
+ * GG_ERR_STATE.  Per-key state that does not fit: GG_ERR_OOM.  After every error the context stays usable.  An empty input
+ * table, or a key_csr without vertices, gives GG_OK and an empty level.  If the build did not need the 16-byte id table, the
+ * first call on a CSR fills it. */
+typedef struct gg_group_stats {
+  uint64_t rows_in;       /* rows of the input table */
+  uint64_t rows_grouped;  /* of those, rows whose key cell is a vertex of key_csr (= the sum of the groups' walks) */
+  uint64_t groups;        /* rows of the output */
+  uint32_t route;         /* 0: nothing to do (no input rows / V == 0), 1: workgroup-private LDS table, 2: global cells */
+} gg_group_stats;
+int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, int key_col, const gg_csr *key_csr,
+                       int weight_col /* -1: none */, const gg_csr *weight_csr /* NULL: key_csr */,
+                       const int64_t *weights /* V(weight_csr) entries, host; NULL iff weight_col == -1 */,
+                       gg_group_stats *stats /* nullable */, gg_result **out_result /* NULL: stats only */);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
@@ -925,6 +978,12 @@ int gg_debug_components(gg_ctx *ctx, int init_mode /* 0 default, 1 every vertex 
  * 1024), so parents that span many tiles and runs of input rows without an edge row that are longer than a tile occur on
  * small graphs.  Results must not depend on it. */
 int gg_debug_extend(gg_ctx *ctx, uint32_t tile_rows /* 0: default */);
+/* Testing knob: gg_result_group_by accumulates in a workgroup-private LDS table wherever key_csr's vertices fit it (1; where
+ * they do not, the global cells run all the same) or in the global cells whatever their number (2); lds_keys shrinks the
+ * number of keys that table may hold (0: the default, 6144 for counts and 2048 with weights; larger values change nothing),
+ * so the automatic switch and the "does not fit" case occur on small graphs.  stats->route says which route ran.  Results
+ * must not depend on it.  A route outside 0..2 is GG_ERR_INVALID_ARG. */
+int gg_debug_group(gg_ctx *ctx, int route /* 0 auto, 1 LDS where the table fits, 2 global */, uint32_t lds_keys /* 0: default capacity */);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
