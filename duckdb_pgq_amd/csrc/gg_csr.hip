@@ -621,21 +621,66 @@ int radix_sort_stable(gg_ctx *ctx, const RadixIO &io, uint64_t n, bool has_b, bo
   return GG_OK;
 }
 
+// sort_pairs_by_key / sort_triples_by_key / gg_debug_sort_pairs: the contract of gg_internal.h, then the passes.
+// valid_dev (nullable): a device word that holds n on entry and the number of keys other than INVALID_U32 afterwards.
+int sort_by_key(gg_ctx *ctx, const RadixIO &io, uint64_t n, bool has_b, int key_bits, unsigned long long *valid_dev) {
+  if (key_bits >= 32) {
+    set_error("internal: a sort by %d key bits: key 0xFFFFFFFF is the radix sort's \"no element\", whole 32-bit keys "
+              "must be sorted in pieces",
+              key_bits);
+    return GG_ERR_INVALID_ARG;
+  }
+  return radix_sort_stable(ctx, io, n, has_b, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, valid_dev);
+}
+
 }  // namespace
 
 namespace gg {
 // (key, value) pairs sorted by key < 2^key_bits, stable (gg_internal.h): the LSD passes of the multi-pass build
 int sort_pairs_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *val, uint64_t n, int key_bits, uint32_t *key_out,
                       uint32_t *val_out) {
-  RadixIO io{key, val, nullptr, key_out, val_out, nullptr};
-  return radix_sort_stable(ctx, io, n, false, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, nullptr);
+  return sort_by_key(ctx, RadixIO{key, val, nullptr, key_out, val_out, nullptr}, n, false, key_bits, nullptr);
 }
 int sort_triples_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, const uint32_t *b, uint64_t n, int key_bits,
                         uint32_t *key_out, uint32_t *a_out, uint32_t *b_out) {
-  RadixIO io{key, a, b, key_out, a_out, b_out};
-  return radix_sort_stable(ctx, io, n, true, false, key_bits < 1 ? 1 : key_bits, nullptr, 0, nullptr);
+  return sort_by_key(ctx, RadixIO{key, a, b, key_out, a_out, b_out}, n, true, key_bits, nullptr);
 }
 }  // namespace gg
+
+extern "C" int gg_debug_sort_pairs(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, const uint32_t *b, uint64_t n,
+                                   int key_bits, uint32_t *key_out, uint32_t *a_out, uint32_t *b_out, uint64_t *n_valid) {
+  if (!ctx || !n_valid || (n && (!key || !a || !key_out || !a_out || (b && !b_out))) || n >= (1ull << 31)) {
+    set_error("gg_debug_sort_pairs: bad argument");
+    return GG_ERR_INVALID_ARG;
+  }
+  *n_valid = 0;
+  ApiScope scope(ctx);
+  GG_HIP(hipSetDevice(ctx->device));
+  const size_t bytes = (n ? n : 1) * sizeof(uint32_t);
+  const int n_cols = b ? 3 : 2;
+  const uint32_t *host_in[3] = {key, a, b};
+  uint32_t *host_out[3] = {key_out, a_out, b_out};
+  uint32_t *in[3] = {nullptr, nullptr, nullptr}, *out[3] = {nullptr, nullptr, nullptr};
+  for (int c = 0; c < n_cols; c++) {
+    GG_TRY(ctx->dev_alloc((void **)&in[c], bytes));
+    GG_TRY(ctx->dev_alloc((void **)&out[c], bytes));
+    if (n) GG_HIP(hipMemcpyAsync(in[c], host_in[c], n * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    GG_HIP(hipMemsetD32Async((hipDeviceptr_t)out[c], (int)GG_DEBUG_SORT_PREFILL, n ? n : 1, ctx->stream));
+  }
+  unsigned long long *valid = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&valid, sizeof(unsigned long long)));
+  GG_HIP(hipMemsetD32Async((hipDeviceptr_t)valid, (int)(uint32_t)n, 1, ctx->stream));
+  GG_HIP(hipMemsetD32Async((hipDeviceptr_t)((uint32_t *)valid + 1), 0, 1, ctx->stream));
+  int rc = sort_by_key(ctx, RadixIO{in[0], in[1], in[2], out[0], out[1], out[2]}, n, b != nullptr, key_bits, valid);
+  if (rc == GG_OK) {
+    for (int c = 0; c < n_cols && n; c++)
+      GG_HIP(hipMemcpyAsync(host_out[c], out[c], n * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    rc = read_back(ctx, {{valid, sizeof(uint64_t), n_valid}});
+  } else {
+    (void)hipStreamSynchronize(ctx->stream);  // the uploads read caller memory: they are over before this returns
+  }
+  return rc;
+}
 
 extern "C" void gg_csr_destroy(gg_csr *csr) {
   if (!csr) return;

@@ -449,7 +449,9 @@ int check_whole_csr(gg_ctx *ctx, const gg_csr *csr);
 
 // exclusive scan of n uint32 values (in place allowed: out may equal in); writes the grand
 // total (as uint64) to *total_dev if non-null.  One hand-written kernel, tiles chained by decoupled
-// look-back (gg_runtime.hip).
+// look-back (gg_runtime.hip).  Sums are kept in 64 bits: the u32 form writes each prefix mod 2^32 and the total exactly.
+// The grand total must stay below 2^62 — a tile's status word carries its flag in the top two bits and its sum or prefix
+// in the other 62, so a larger sum would be read as another flag; no caller sums anything but counts of rows.
 int scan_exclusive_u32(gg_ctx *ctx, const uint32_t *in, uint32_t *out, uint64_t n, uint64_t *total_dev);
 // exclusive scan of n uint64 values
 int scan_exclusive_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, uint64_t *total_dev);
@@ -487,7 +489,21 @@ int lookup_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids_dev, uint64_t 
 // it returns, so the copy has read it by then.
 int upload_ids(gg_ctx *ctx, const gg_csr *csr, const int64_t *ids, uint64_t n, uint32_t **dense,
                int64_t **ids_dev = nullptr);
-// n (key, value) pairs of u32 sorted by key < 2^key_bits, stably, into (key_out, val_out) — device arrays (gg_csr.hip)
+// n (key, value) pairs of u32 sorted by key < 2^key_bits, stably, into (key_out, val_out) — device arrays (gg_csr.hip).
+// The contract, for the triples as well:
+//   - key 0xFFFFFFFF (INVALID_U32) means "no element" to the radix kernels, whatever key_bits says: such an element is
+//     not counted and not written, the elements after it move up, the outputs' last slots keep what they held, and the
+//     passes after the first see only the others.  A caller either has no such key or means exactly that (the builds'
+//     dropped edges) and then knows the number of valid keys from elsewhere: these two entry points do not report it.
+//   - so a whole 32-bit word can NOT be a key.  key_bits >= 32 is refused (GG_ERR_INVALID_ARG, "internal: ..."); wider
+//     keys are sorted in pieces of fewer bits, lowest piece first (gg_triangles.hip's ranks, gg_aggregate_top.hip, the id
+//     sort of gg_csr.hip), which is what stability is for.  key_bits < 1 counts as 1.  The callers that sort by dense
+//     vertex index (gg_khop.hip, gg_reach.hip, gg_paths.hip) take their bits from V, so a graph of more than 2^31
+//     vertices meets this refusal there; its indices would never be 0xFFFFFFFF (V <= 2^32 - 2), but no such graph has
+//     been built, and two pieces are the way to serve it.
+//   - bits of a valid key at or above key_bits are ignored, not refused: elements that differ only there keep their
+//     input order.
+//   - n < 2^32 (positions are 32-bit counters); no output may alias an input; n == 0 launches nothing.
 int sort_pairs_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *val, uint64_t n, int key_bits, uint32_t *key_out,
                       uint32_t *val_out);
 int sort_triples_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, const uint32_t *b, uint64_t n, int key_bits,

@@ -1138,6 +1138,38 @@ int scan_total_u64(gg_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, u
   return scan_total<uint64_t>(ctx, in, out, n, total_host, append_total ? out + n : nullptr, extra);
 }
 
+template <typename T>
+static int debug_scan(gg_ctx *ctx, const T *in, uint64_t n, T *out, uint64_t *total) {
+  T *din = nullptr, *dout = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&din, (n ? n : 1) * sizeof(T)));
+  dout = din;
+  if ((const void *)in != (const void *)out) GG_TRY(ctx->dev_alloc((void **)&dout, (n ? n : 1) * sizeof(T)));
+  if (n) GG_HIP(hipMemcpyAsync(din, in, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  if (n && dout != din) GG_HIP(hipMemsetAsync(dout, 0xA5, n * sizeof(T), ctx->stream));
+  GG_TRY(scan_total<T>(ctx, din, dout, n, total, nullptr, {}));
+  if (n) {
+    GG_HIP(hipMemcpyAsync(out, dout, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    GG_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  return GG_OK;
+}
+
+}  // namespace gg
+
+extern "C" int gg_debug_scan(gg_ctx *ctx, const void *in, uint64_t n, int width, void *out, uint64_t *total) {
+  if (!ctx || !total || (width != 4 && width != 8) || (n && (!in || !out))) {
+    set_error("gg_debug_scan: bad argument");
+    return GG_ERR_INVALID_ARG;
+  }
+  *total = 0;
+  ApiScope scope(ctx);
+  GG_HIP(hipSetDevice(ctx->device));
+  return width == 4 ? debug_scan<uint32_t>(ctx, (const uint32_t *)in, n, (uint32_t *)out, total)
+                    : debug_scan<uint64_t>(ctx, (const uint64_t *)in, n, (uint64_t *)out, total);
+}
+
+namespace gg {
+
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lookup_ids(const int64_t *__restrict__ ids, uint64_t n,
                                                     const HtSlot *__restrict__ ht, uint64_t cap,

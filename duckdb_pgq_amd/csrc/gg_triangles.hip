@@ -51,13 +51,18 @@ constexpr int TRI_LDS_IN = 1535;    // in-row entries a wavefront may stage: (TR
 constexpr uint64_t TRI_MAX_GROUPS = 0xFFFFFFFFull / 256;
 
 // ---- order = 1: rank of every vertex id, filtered rows ------------------------------------------------------------
+// One LSD piece of the rank sort: TRI_RANK_PIECE_BITS bits at `shift` of the id with its sign bit flipped (so that the
+// unsigned pieces order the ids signed), of the vertices in the order the earlier pieces left (perm; null: 0..V-1).
+// (Pieces, not 32-bit halves: the shared radix sort keeps key 0xFFFFFFFF for "no element" — gg_internal.h — and a half
+// of an id such as -1, 4294967295 or INT64_MAX is exactly that.)
+constexpr int TRI_RANK_PIECE_BITS = 16;
 __global__ __launch_bounds__(256) void k_tri_rank_key(const int64_t *__restrict__ vid, const uint32_t *__restrict__ perm,
-                                                      uint64_t V, uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
+                                                      uint64_t V, uint32_t shift, uint32_t *__restrict__ key,
+                                                      uint32_t *__restrict__ val) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (uint64_t)gridDim.x * blockDim.x) {
     const uint32_t v = perm ? perm[i] : (uint32_t)i;
-    const uint64_t id = (uint64_t)vid[v];
-    // first pass: the low half; second pass (perm given): the high half, sign bit flipped so that it sorts signed
-    key[i] = perm ? (uint32_t)(id >> 32) ^ 0x80000000u : (uint32_t)id;
+    const uint64_t id = (uint64_t)vid[v] ^ (1ull << 63);
+    key[i] = (uint32_t)(id >> shift) & ((1u << TRI_RANK_PIECE_BITS) - 1);
     val[i] = v;
   }
 }
@@ -323,17 +328,16 @@ int tri_launch(gg_ctx *ctx, const TriArgs &args, uint64_t n_tiles, const TriEdge
   return GG_OK;
 }
 
-// rank[v] = position of vid[v] among the ids ascending (signed)
+// rank[v] = position of vid[v] among the ids ascending (signed): four stable sorts by 16-bit pieces, lowest first
 int tri_ranks(gg_ctx *ctx, const gg_csr *csr, uint32_t **rank_out) {
   const uint64_t V = csr->V;
   uint32_t *key = nullptr, *val = nullptr, *key2 = nullptr, *perm = nullptr, *rank = nullptr;
   for (uint32_t **p : {&key, &val, &key2, &perm, &rank}) GG_TRY(ctx->dev_alloc((void **)p, V * sizeof(uint32_t)));
-  GG_LAUNCH(ctx, "k_tri_rank_key", k_tri_rank_key, stride_grid(ctx, V), dim3(256), 0, (const int64_t *)csr->vid,
-            (const uint32_t *)nullptr, V, key, val);
-  GG_TRY(sort_pairs_by_key(ctx, key, val, V, 32, key2, perm));
-  GG_LAUNCH(ctx, "k_tri_rank_key", k_tri_rank_key, stride_grid(ctx, V), dim3(256), 0, (const int64_t *)csr->vid,
-            (const uint32_t *)perm, V, key, val);
-  GG_TRY(sort_pairs_by_key(ctx, key, val, V, 32, key2, perm));
+  for (uint32_t shift = 0; shift < 64; shift += TRI_RANK_PIECE_BITS) {
+    GG_LAUNCH(ctx, "k_tri_rank_key", k_tri_rank_key, stride_grid(ctx, V), dim3(256), 0, (const int64_t *)csr->vid,
+              shift ? (const uint32_t *)perm : (const uint32_t *)nullptr, V, shift, key, val);
+    GG_TRY(sort_pairs_by_key(ctx, key, val, V, TRI_RANK_PIECE_BITS, key2, perm));
+  }
   GG_LAUNCH(ctx, "k_tri_rank_scatter", k_tri_rank_scatter, stride_grid(ctx, V), dim3(256), 0, (const uint32_t *)perm, V,
             rank);
   *rank_out = rank;

@@ -11,6 +11,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libgg.so")
 GG_MAX_HOPS = 8
 GG_BFS_LANES = 64
 GG_CHUNK_ROWS = 1024
+SORT_PREFILL = 0xA5A5A5A5  # GG_DEBUG_SORT_PREFILL
 
 # every symbol include/gg.h declares (tests/test_abi.py checks the library exports exactly these)
 SYMBOLS = [
@@ -19,7 +20,7 @@ SYMBOLS = [
     "gg_ctx_set_edge_rowid", "gg_csr_build", "gg_csr_build_shard", "gg_csr_destroy", "gg_csr_info", "gg_csr_export",
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
-    "gg_debug_csr_reverse",
+    "gg_debug_csr_reverse", "gg_debug_scan", "gg_debug_sort_pairs",
     "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_reach_visited",
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
@@ -181,6 +182,8 @@ def load_library(path: str | None = None):
     lib.gg_debug_rank_mode.argtypes = [P, C.c_int]
     lib.gg_debug_csr_reverse.argtypes = [P, i64p, i64p, i64p, C.POINTER(C.c_int)]
     lib.gg_debug_scan_fault.argtypes = [P, C.c_uint32, u64]
+    lib.gg_debug_scan.argtypes = [P, C.c_void_p, u64, C.c_int, C.c_void_p, C.POINTER(u64)]
+    lib.gg_debug_sort_pairs.argtypes = [P] + [C.c_void_p] * 3 + [u64, C.c_int] + [C.c_void_p] * 3 + [C.POINTER(u64)]
     lib.gg_debug_max_grid_tiles.argtypes = [P, u64]
     lib.gg_debug_reset.argtypes = [P]
     lib.gg_debug_placement.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
@@ -887,6 +890,31 @@ class GG:
 
     def scan_fault(self, spin_limit: int = 0, mute_tile: int = (1 << 64) - 1):
         self._chk(self.lib.gg_debug_scan_fault(self.ctx, spin_limit, mute_tile))
+
+    def debug_scan(self, values: np.ndarray, in_place: bool = False):
+        """(exclusive prefix, total) of a uint32 / uint64 array by the library's shared scan (gg_debug_scan); the prefix
+        has the input's type (uint32: mod 2^32), the total is exact.  in_place: the device scans over its input."""
+        a = np.ascontiguousarray(values)
+        assert a.dtype in (np.uint32, np.uint64) and a.ndim == 1
+        out = a.copy() if in_place else np.empty_like(a)
+        src = out if in_place else a
+        total = C.c_uint64()
+        self._chk(self.lib.gg_debug_scan(self.ctx, src.ctypes.data, a.size, a.dtype.itemsize, out.ctypes.data,
+                                         C.byref(total)))
+        return out, int(total.value)
+
+    def debug_sort_pairs(self, key, a, b=None, key_bits: int = 31):
+        """(key_out, a_out, b_out or None, n_valid) of the library's shared stable radix sort (gg_debug_sort_pairs): the
+        first n_valid outputs are the elements whose key is not 0xFFFFFFFF, sorted stably by key; the rest hold
+        SORT_PREFILL."""
+        cols = [np.ascontiguousarray(c, dtype=np.uint32) for c in (key, a) + (() if b is None else (b,))]
+        n = cols[0].size
+        assert all(c.ndim == 1 and c.size == n for c in cols)
+        outs = [np.zeros(n, np.uint32) for _ in cols]
+        ptr = lambda arrs: [x.ctypes.data for x in arrs] + [None] * (3 - len(arrs))
+        n_valid = C.c_uint64()
+        self._chk(self.lib.gg_debug_sort_pairs(self.ctx, *ptr(cols), n, int(key_bits), *ptr(outs), C.byref(n_valid)))
+        return outs[0], outs[1], (outs[2] if b is not None else None), int(n_valid.value)
 
     def rank_mode(self, mode: int):
         """0: probe the LDS atomic order once (default), 1: ranks from ds_add_rtn, 2: ranks from match masks."""

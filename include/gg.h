@@ -984,6 +984,21 @@ int gg_debug_extend(gg_ctx *ctx, uint32_t tile_rows /* 0: default */);
  * so the automatic switch and the "does not fit" case occur on small graphs.  stats->route says which route ran.  Results
  * must not depend on it.  A route outside 0..2 is GG_ERR_INVALID_ARG. */
 int gg_debug_group(gg_ctx *ctx, int route /* 0 auto, 1 LDS where the table fits, 2 global */, uint32_t lds_keys /* 0: default capacity */);
+/* Testing hook, stateless: the library's shared exclusive prefix scan over a host array.  `in` and `out` are n values of
+ * `width` bytes (4: uint32, 8: uint64); out[i] = in[0] + ... + in[i-1] — the width-4 form mod 2^32 — and *total is the
+ * exact sum in 64 bits, which must stay below 2^62 (the scan's status words keep two flag bits; a larger sum is not
+ * defined).  out == in scans in place on the device, otherwise out of place.  A width other than 4 or 8 is
+ * GG_ERR_INVALID_ARG. */
+int gg_debug_scan(gg_ctx *ctx, const void *in, uint64_t n, int width /* 4 or 8 */, void *out, uint64_t *total);
+/* Testing hook, stateless: the library's shared stable radix sort over host arrays.  n < 2^31 (key, a) pairs — triples with b, which
+ * may be NULL together with b_out — are sorted by key < 2^key_bits into (key_out, a_out, b_out).  Key 0xFFFFFFFF means "no
+ * element": *n_valid is the number of other keys, the first *n_valid outputs are their stable sort, and the rest hold
+ * GG_DEBUG_SORT_PREFILL, which every device output is filled with beforehand.  key_bits >= 32 is GG_ERR_INVALID_ARG (the
+ * library's internal refusal of whole-word keys), and nothing is written. */
+#define GG_DEBUG_SORT_PREFILL 0xA5A5A5A5u
+int gg_debug_sort_pairs(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, const uint32_t *b /* nullable */, uint64_t n,
+                        int key_bits, uint32_t *key_out, uint32_t *a_out, uint32_t *b_out /* nullable */,
+                        uint64_t *n_valid);
 /* Every testing knob above and gg_ctx_set_edge_rowid back to its default (a test suite that shares one context
  * calls this between tests). */
 int gg_debug_reset(gg_ctx *ctx);
