@@ -39,6 +39,7 @@ SYMBOLS = [
     "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
     "gg_result_extend_edge", "gg_debug_extend",
     "gg_result_group_by", "gg_debug_group",
+    "gg_result_filter_value", "gg_result_top_rows", "gg_debug_value_top",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -95,6 +96,15 @@ class GroupStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_grouped", C.c_uint64), ("groups", C.c_uint64), ("route", C.c_uint32)]
 
 
+class ValueFilterStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_valued", C.c_uint64), ("rows_out", C.c_uint64)]
+
+
+class ValueTopStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_valued", C.c_uint64), ("candidates", C.c_uint64), ("rows_out", C.c_uint64),
+                ("select_passes", C.c_uint32), ("sort_route", C.c_uint32)]
+
+
 class AggStats(C.Structure):
     _fields_ = [
         ("groups", C.c_uint64 * (GG_MAX_HOPS + 1)),
@@ -132,6 +142,8 @@ class TopStats(C.Structure):
 GROUP_BY = {"start": 0, "end": 1}  # GG_GROUP_START / GG_GROUP_END
 TOP_BY = {"total": 0, "walks": 1}  # GG_TOP_BY_TOTAL / GG_TOP_BY_WALKS
 EDGE_MODES = {"inner": 0, "semi": 1, "anti": 2}  # GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
+VALUE_MODES = {"in": 0, "not_in": 1}  # GG_VALUE_IN / GG_VALUE_NOT_IN
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 
 _lib = None
 
@@ -232,6 +244,11 @@ def load_library(path: str | None = None):
     lib.gg_debug_extend.argtypes = [P, C.c_uint32]
     lib.gg_result_group_by.argtypes = [P, P, C.c_int, C.c_int, P, C.c_int, P, i64p, C.POINTER(GroupStats), C.POINTER(P)]
     lib.gg_debug_group.argtypes = [P, C.c_int, C.c_uint32]
+    lib.gg_result_filter_value.argtypes = [P, P, C.c_int, C.c_int, P, i64p, C.POINTER(u64), C.c_int64, C.c_int64, C.c_int,
+                                           C.c_int, C.POINTER(ValueFilterStats), C.POINTER(P)]
+    lib.gg_result_top_rows.argtypes = [P, P, C.c_int, C.c_int, P, i64p, C.POINTER(u64), C.c_int64, C.c_int64, C.c_int,
+                                       C.c_int, C.c_int, u64, C.POINTER(ValueTopStats), C.POINTER(P)]
+    lib.gg_debug_value_top.argtypes = [P, C.c_int, C.c_uint32]
     lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
@@ -842,6 +859,58 @@ class GG:
         """group_by accumulates in the workgroup-private LDS table where it fits (1) or in the global cells (2); lds_keys
         shrinks the keys that table may hold (0: the defaults).  Results must not depend on it."""
         self._chk(self.lib.gg_debug_group(self.ctx, int(route), int(lds_keys)))
+
+    @staticmethod
+    def _value_args(value_csr: Csr, values, valid):
+        """(values array, its pointer, valid array, its pointer or None) for the value calls; the arrays must outlive the
+        call"""
+        v, vp = _i64(values)
+        if v.ndim != 1 or v.size != value_csr.V:
+            raise ValueError(f"values: {v.size} entries for {value_csr.V} vertices")
+        b, bp = None, None
+        if valid is not None:
+            b = np.ascontiguousarray(valid, dtype=np.uint64)
+            if b.ndim != 1 or b.size != (value_csr.V + 63) // 64:
+                raise ValueError(f"valid: {b.size} words for {value_csr.V} vertices")
+            bp = b.ctypes.data_as(C.POINTER(C.c_uint64))
+        return v, vp, b, bp
+
+    def filter_value(self, res: KhopResult, hops: int, value_col: int, value_csr: Csr, values, valid=None,
+                     lo: int = INT64_MIN, hi: int = INT64_MAX, mode: str = "in", materialise: bool = True):
+        """gg_result_filter_value: the rows of res's `hops`-hop table whose value passes — the cell of value_col is a vertex
+        d of value_csr, bit d of `valid` (uint64 words; None: every vertex) is set and values[d] lies in [lo, hi] ("in") or
+        outside it ("not_in"); rows without a value pass nothing.  Input order and the input's edge columns are kept.
+        Returns {"rows_in", "rows_valued", "rows_out"}; with materialise, (that dict, KhopResult whose table `hops` holds
+        the rows — the caller closes it)."""
+        if mode not in VALUE_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(VALUE_MODES)}")
+        v, vp, b, bp = self._value_args(value_csr, values, valid)
+        st, out = ValueFilterStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_filter_value(self.ctx, res.handle, hops, value_col, value_csr.handle, vp, bp, int(lo),
+                                                  int(hi), VALUE_MODES[mode], int(materialise), C.byref(st), C.byref(out)))
+        d = {"rows_in": int(st.rows_in), "rows_valued": int(st.rows_valued), "rows_out": int(st.rows_out)}
+        return (d, KhopResult(self, out, d)) if materialise else d
+
+    def top_rows(self, res: KhopResult, hops: int, value_col: int, value_csr: Csr, values, n: int, valid=None,
+                 lo: int = INT64_MIN, hi: int = INT64_MAX, mode: str = "in", descending: bool = True, tie_col=None):
+        """gg_result_top_rows: the best n of the rows filter_value would keep, in rank order — by value (descending or
+        ascending, signed), then by the cell of tie_col ascending (None: no tie column), then by input row.  Returns
+        ({"rows_in", "rows_valued", "candidates", "rows_out", "select_passes", "sort_route"}, KhopResult whose table `hops`
+        holds the min(n, candidates) rows and the input's edge columns — the caller closes it)."""
+        if mode not in VALUE_MODES:
+            raise ValueError(f"mode {mode!r}: one of {sorted(VALUE_MODES)}")
+        v, vp, b, bp = self._value_args(value_csr, values, valid)
+        st, out = ValueTopStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_top_rows(self.ctx, res.handle, hops, value_col, value_csr.handle, vp, bp, int(lo),
+                                              int(hi), VALUE_MODES[mode], 1 if descending else 0,
+                                              -1 if tie_col is None else int(tie_col), int(n), C.byref(st), C.byref(out)))
+        d = {f: int(getattr(st, f)) for f, _ in ValueTopStats._fields_}
+        return d, KhopResult(self, out, d)
+
+    def debug_value_top(self, sort_route: int = 0, candidate_floor: int = 0):
+        """top_rows orders its survivors in LDS (1) or by the global passes (2) and compacts the selection's candidates at
+        candidate_floor or fewer (0: the defaults).  Results must not depend on it."""
+        self._chk(self.lib.gg_debug_value_top(self.ctx, int(sort_route), int(candidate_floor)))
 
     def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
         """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows

@@ -60,15 +60,16 @@ public:
 	idx_t next_rank = 0; // gg_khop_aggregate_top: the rank of the next row to leave
 };
 
-//! a sink that collects (key, weight) pairs on the host: rows with a NULL key are skipped, a NULL weight weighs 0
+//! a sink that collects (key, value) pairs on the host (GGKeyedValues, gg_extension.hpp): rows with a NULL key are skipped,
+//! a NULL value is kept as 0 with has = 0
 class PairsGlobalState : public GlobalSinkState {
 public:
 	mutex lock;
-	vector<int64_t> keys, weights;
+	GGKeyedValues pairs;
 };
 
 //! row `idx` of an integer vector as int64
-static int64_t IntegerAt(const VectorData &v, PhysicalType type, idx_t idx, const char *what) {
+static int64_t IntegerAt(const VectorData &v, PhysicalType type, idx_t idx, const string &fn, const char *what) {
 	switch (type) {
 	case PhysicalType::INT64:
 		return ((const int64_t *)v.data)[idx];
@@ -79,15 +80,17 @@ static int64_t IntegerAt(const VectorData &v, PhysicalType type, idx_t idx, cons
 	case PhysicalType::INT8:
 		return ((const int8_t *)v.data)[idx];
 	default:
-		throw BinderException(string("gg_khop_aggregate: ") + what + " must be an integer column (TINYINT .. BIGINT)");
+		throw BinderException(fn + ": " + what + " must be an integer column (TINYINT .. BIGINT)");
 	}
 }
 
 class PhysicalGGCollectPairs : public PhysicalOperator {
 public:
-	PhysicalGGCollectPairs()
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, {LogicalType::BIGINT, LogicalType::BIGINT}, 0) {
+	PhysicalGGCollectPairs(string fn_p, string value_name_p)
+	    : PhysicalOperator(PhysicalOperatorType::INVALID, {LogicalType::BIGINT, LogicalType::BIGINT}, 0), fn(move(fn_p)),
+	      value_name(move(value_name_p)) {
 	}
+	string fn, value_name; // for the error that names a column of another type
 	unique_ptr<GlobalSinkState> GetGlobalSinkState(ClientContext &context) const override {
 		return make_unique<PairsGlobalState>();
 	}
@@ -98,24 +101,29 @@ public:
 	                    DataChunk &input) const override {
 		auto &gstate = (PairsGlobalState &)gstate_p;
 		const idx_t count = input.size();
-		const auto key_type = input.data[0].GetType().InternalType(), weight_type = input.data[1].GetType().InternalType();
-		VectorData key, weight;
+		const auto key_type = input.data[0].GetType().InternalType(), value_type = input.data[1].GetType().InternalType();
+		VectorData key, value;
 		input.data[0].Orrify(count, key);
-		input.data[1].Orrify(count, weight);
-		vector<int64_t> keys, weights;
-		keys.reserve(count);
-		weights.reserve(count);
+		input.data[1].Orrify(count, value);
+		GGKeyedValues got;
+		got.keys.reserve(count);
+		got.values.reserve(count);
+		got.has.reserve(count);
 		for (idx_t i = 0; i < count; i++) {
-			const idx_t k = key.sel->get_index(i), w = weight.sel->get_index(i);
+			const idx_t k = key.sel->get_index(i), v = value.sel->get_index(i);
 			if (!key.validity.RowIsValid(k)) {
 				continue;
 			}
-			keys.push_back(IntegerAt(key, key_type, k, "the vertex key"));
-			weights.push_back(weight.validity.RowIsValid(w) ? IntegerAt(weight, weight_type, w, "weight_column") : 0);
+			const bool valid = value.validity.RowIsValid(v);
+			got.keys.push_back(IntegerAt(key, key_type, k, fn, "the key"));
+			got.values.push_back(valid ? IntegerAt(value, value_type, v, fn, value_name.c_str()) : 0);
+			got.has.push_back(valid);
 		}
 		lock_guard<mutex> guard(gstate.lock);
-		gstate.keys.insert(gstate.keys.end(), keys.begin(), keys.end());
-		gstate.weights.insert(gstate.weights.end(), weights.begin(), weights.end());
+		auto &all = gstate.pairs;
+		all.keys.insert(all.keys.end(), got.keys.begin(), got.keys.end());
+		all.values.insert(all.values.end(), got.values.begin(), got.values.end());
+		all.has.insert(all.has.end(), got.has.begin(), got.has.end());
 		return SinkResultType::NEED_MORE_INPUT;
 	}
 	bool IsSink() const override {
@@ -129,16 +137,27 @@ public:
 	}
 };
 
+} // namespace
+
+GGKeyedValues GGCollectKeyedValues(ClientContext &context, const GGScanSource &source, const string &fn,
+                                   const string &value_name) {
+	PhysicalGGCollectPairs collect(fn, value_name);
+	GGRunSinkPipeline(context, source, collect);
+	return move(((PairsGlobalState &)*collect.sink_state).pairs);
+}
+
+namespace {
+
 //! weight_column of vertex_table in the order of the graph's vertex table (a vertex the scan did not see weighs 0)
 static vector<int64_t> WeightsInVertexOrder(ClientContext &context, GGGraph &graph, const string &vertex_table,
                                             const string &vertex_key, const string &weight_column) {
-	PhysicalGGCollectPairs collect;
-	GGRunSinkPipeline(context, GGTableSource(context, vertex_table, {vertex_key, weight_column}, false), collect);
-	auto &pairs = (PairsGlobalState &)*collect.sink_state;
+	// (a NULL weight arrives as 0: it weighs nothing)
+	const auto pairs = GGCollectKeyedValues(context, GGTableSource(context, vertex_table, {vertex_key, weight_column}, false),
+	                                        "gg_khop_aggregate", "weight_column");
 	std::unordered_map<int64_t, int64_t> weight_of;
 	weight_of.reserve(pairs.keys.size());
 	for (idx_t i = 0; i < pairs.keys.size(); i++) {
-		weight_of[pairs.keys[i]] = pairs.weights[i];
+		weight_of[pairs.keys[i]] = pairs.values[i];
 	}
 	shared_ptr<const vector<int64_t>> ids;
 	{

@@ -761,6 +761,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterExtendFunctions(*con.context);
 	GGRegisterGroupFunctions(*con.context);
+	GGRegisterValueRowsFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterComponentFunctions(*con.context);

@@ -89,6 +89,16 @@ void GGDropPinsOfTable(idx_t table_oid);
 //! first column of `sql` (run on a side connection) as int64, NULLs skipped
 vector<int64_t> GGQueryInt64Column(ClientContext &context, const string &sql, const char *what);
 
+//! The (key, value) rows of a two-column integer source (TINYINT .. BIGINT; anything else raises, naming `fn` and
+//! `value_name`), read through the ingest path in the statement's own transaction, order unspecified.  Rows with a NULL key
+//! are skipped; a NULL value is kept as values[i] = 0 with has[i] = 0.  (gg_aggregate.cpp)
+struct GGKeyedValues {
+	vector<int64_t> keys, values;
+	vector<uint8_t> has;
+};
+GGKeyedValues GGCollectKeyedValues(ClientContext &context, const GGScanSource &source, const string &fn,
+                                   const string &value_name);
+
 //! "identifier" with embedded quotes doubled
 string GGQuote(const string &ident);
 
@@ -107,6 +117,10 @@ shared_ptr<GGGraph> GGBuildExtendGraph(ClientContext &context, const GGScanSourc
 
 //! gg_group.cpp: registers gg_khop_extend_group (inside the caller's transaction)
 void GGRegisterGroupFunctions(ClientContext &context);
+
+//! gg_value_rows.cpp: registers gg_khop_extend_filter / gg_khop_extend_filter_count / gg_khop_extend_top (inside the caller's
+//! transaction)
+void GGRegisterValueRowsFunctions(ClientContext &context);
 
 //! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
 void GGRegisterAggregateFunctions(ClientContext &context);

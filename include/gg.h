@@ -66,6 +66,13 @@
  *                                                               join_hashtable.cpp:442-476
  *           (count(*) GROUP BY tag over knows [-> knows] -> message -> message_tag, interactive-complex-4.sql:1-22,
  *           interactive-complex-6.sql:1-22; by forum, interactive-complex-5.sql; a score summed per person, bi-8.sql:41-53)
+ *   gg_result_filter_value / gg_result_top_rows
+ *        <- a comparison on a payload column of the joined rows, run inside the scan, and PhysicalTopN above the last hash
+ *           join                                     src/execution/operator/order/physical_top_n.cpp:238-293, 421-454
+ *           (m_creationdate < :date ... ORDER BY m_creationdate DESC, m_messageid ASC LIMIT 20,
+ *           benchmark/ldbc/queries/interactive-complex-2.sql:5,8-9, interactive-complex-9.sql:16-18; a date range before the
+ *           GROUP BY, interactive-complex-4.sql:9,18, interactive-complex-3.sql:20,27; k2.k_person2id <> :person,
+ *           interactive-complex-9.sql:12)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -422,6 +429,89 @@ int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, int key_col,
                        int weight_col /* -1: none */, const gg_csr *weight_csr /* NULL: key_csr */,
                        const int64_t *weights /* V(weight_csr) entries, host; NULL iff weight_col == -1 */,
                        gg_group_stats *stats /* nullable */, gg_result **out_result /* NULL: stats only */);
+/* A value predicate on one column of a materialised walk table, and (gg_result_top_rows below) the best n rows by that
+ * value.
+ * What it replaces in the reference: a comparison on a payload column of the joined rows, evaluated inside the scan of the
+ * payload's table below the last hash join — `m_creationdate < :date` (benchmark/ldbc/queries/interactive-complex-2.sql:5,
+ * interactive-complex-9.sql:16), the half-open date range before the GROUP BY (interactive-complex-4.sql:9,18,
+ * interactive-complex-3.sql:20,27) and `k2.k_person2id <> :person` (interactive-complex-9.sql:12).  Without it the only way
+ * to apply one to the rows gg_result_extend_edge left in HBM is to drain them.
+ * The value of a row (shared with gg_result_top_rows): `values` is V(value_csr) int64 in vertex-table order, host memory, as
+ * gg_result_group_by's weights; `valid` (nullable) holds ceil(V / 64) uint64 words, bit i of word i / 64 saying that vertex i
+ * has a value, NULL: every vertex has one.  The cell of value_col (0..hops) is looked up in value_csr's id dictionary exactly
+ * as gg_csr_lookup does; the row has the value x = values[d] iff the cell is a vertex d of value_csr and d's valid bit is
+ * set.  A row without a value behaves as SQL's NULL under a comparison: it passes no predicate in either mode and is never a
+ * candidate of the top.  The message of an extended row is its last column and a vertex of the extension's CSR, so
+ * m_creationdate per message is such a column; a person's property is one over the walk CSR.  Values keyed by edge rowid
+ * (k_creationdate) are out of scope, and so is a device-resident value column shared between calls: each call uploads its
+ * 8 V bytes (and V / 8 of valid), as gg_result_group_by does.
+ * Predicate: GG_VALUE_IN keeps a row iff it has a value x and lo <= x <= hi (signed); GG_VALUE_NOT_IN iff it has a value x
+ * and (x < lo or x > hi).  lo > hi: IN keeps nothing, NOT_IN every valued row.  `<` and `>=` are bounds +- 1 on the caller's
+ * side, `<>` is NOT_IN with lo == hi.
+ * Input: the `hops`-hop table of `res` — whatever gg_result_extend_edge accepts, its own output, the filters' and
+ * gg_result_top_rows' included.  Tables of 2^32 rows or more are accepted when counting.
+ * Output: table `hops` of *out_result (k_min = k_max = hops) with the same hops + 1 id columns and, unlike
+ * gg_result_filter_edge, the input's edge columns e1..e_hops when it has them (the rowid of an extension survives the
+ * filter); a gg_triangles_edges table loses its triangle edge columns, as under every filter.  Surviving rows keep the
+ * input's order.  Placement is count, scan, write — no atomics-ordered append — so the rows are identical on every run and
+ * under gg_debug_max_grid_tiles.  The result answers every reader of a walk table: gg_result_rows, gg_result_fetch,
+ * gg_result_fetch_edges, gg_result_digest, both filters, gg_result_extend_edge, gg_result_group_by, this call and
+ * gg_result_top_rows.
+ * materialise == 0: only `stats` is filled (out_result may be NULL); 64-bit counters, no size limit, one host
+ * synchronisation.  stats may be NULL when materialising, which synchronises twice (the total, the rows).
+ * Errors: NULL ctx / res / value_csr / values, objects of another context, hops outside the result's k_min..k_max, value_col
+ * outside 0..hops, a mode outside {0, 1}, materialise != 0 with NULL out_result: GG_ERR_INVALID_ARG.  A shard CSR, or a
+ * result without fixed-length tables (gg_result's kinds, above): GG_ERR_STATE.  2^32 output rows or more when materialising:
+ * GG_ERR_TOO_LARGE.  After every error the context stays usable.  An empty input table, a value_csr without vertices and a
+ * predicate no row passes give GG_OK and an empty table.  If the build did not need the 16-byte id table, the first call on
+ * a CSR fills it. */
+#define GG_VALUE_IN     0  /* keep a row iff it has a value x and lo <= x <= hi (signed) */
+#define GG_VALUE_NOT_IN 1  /* keep a row iff it has a value x and (x < lo or x > hi) */
+typedef struct gg_value_filter_stats {
+  uint64_t rows_in;     /* rows of the input table */
+  uint64_t rows_valued; /* of those, rows that have a value */
+  uint64_t rows_out;    /* rows that pass the predicate */
+} gg_value_filter_stats;
+int gg_result_filter_value(gg_ctx *ctx, const gg_result *res, int hops, int value_col, const gg_csr *value_csr,
+                           const int64_t *values, const uint64_t *valid /* nullable */, int64_t lo, int64_t hi,
+                           int mode, int materialise, gg_value_filter_stats *stats, gg_result **out_result);
+/* The best n rows of a materialised walk table by the value of a row, among the rows gg_result_filter_value would keep:
+ * `WHERE value BETWEEN lo AND hi ORDER BY value [DESC], id LIMIT n` in one upload and one pass over the cells.
+ * What it replaces in the reference: PhysicalTopN (src/execution/operator/order/physical_top_n.cpp:238-293 heap sink /
+ * reduce, :421-454 Sink / Combine) above the last hash join, with the scan's filter below it — the tail `ORDER BY
+ * m_creationdate DESC, m_messageid ASC LIMIT 20` of benchmark/ldbc/queries/interactive-complex-2.sql:8-9 and
+ * interactive-complex-9.sql:17-18.
+ * Input, the value of a row, lo / hi / mode: as gg_result_filter_value; lo = INT64_MIN, hi = INT64_MAX, GG_VALUE_IN means
+ * every valued row.  The candidates are the rows that filter would keep.
+ * Order: row a comes before row b iff x(a) is better than x(b) — greater if descending != 0, else smaller, signed; or the
+ * values are equal and a's cell in tie_col is the smaller signed int64 (in both directions: ORDER BY value [DESC], id); or
+ * those are equal too, or tie_col == -1, and a is the earlier input row.  Walk tables hold duplicate rows and one message is
+ * reached over many walks, so (value, tie id) is not unique; the row number as the last key word makes the key unique, the
+ * n-th key exist and the output fully determined.
+ * Output: table `hops` of *out_result (k_min = k_max = hops) with exactly min(n, candidates) rows in rank order: the id
+ * columns gathered, and the edge columns if the input has them (a gg_triangles_edges table loses its own).  It is an
+ * ordinary walk table, answered by every reader gg_result_filter_value's is, so it can be extended again (to fetch the
+ * person).  n == 0 gives an empty table, n >= candidates every candidate, ordered.  LIMIT n OFFSET o is n + o here and a
+ * fetch from offset o.
+ * One host synchronisation per call: the number of candidates stays on the device, the rank selected there is min(n,
+ * candidates), and the buffers and the sort route (stats->sort_route) follow min(n, rows_in), which the host knows.
+ * stats->select_passes: the digit passes that ran — bytes that are zero in every key (the row number's above
+ * bits_for(rows), the tie word without a tie column) get none.
+ * Errors: as gg_result_filter_value, and NULL out_result or tie_col outside -1..hops: GG_ERR_INVALID_ARG.  An input table
+ * of 2^32 rows or more (which min(n, candidates) >= 2^32 needs): GG_ERR_TOO_LARGE — row numbers are 32-bit here; filter
+ * first.  An empty input table, a value_csr without vertices, n == 0 and no candidate give GG_OK and an empty table. */
+typedef struct gg_value_top_stats {
+  uint64_t rows_in;       /* rows of the input table */
+  uint64_t rows_valued;   /* of those, rows that have a value */
+  uint64_t candidates;    /* rows that pass the predicate */
+  uint64_t rows_out;      /* min(n, candidates) */
+  uint32_t select_passes; /* digit passes the selection ran (as gg_top_stats) */
+  uint32_t sort_route;    /* 0: none needed (fewer than two rows), 1: one workgroup in LDS, 2: global passes */
+} gg_value_top_stats;
+int gg_result_top_rows(gg_ctx *ctx, const gg_result *res, int hops, int value_col, const gg_csr *value_csr,
+                       const int64_t *values, const uint64_t *valid /* nullable */, int64_t lo, int64_t hi, int mode,
+                       int descending, int tie_col /* -1: none */, uint64_t n, gg_value_top_stats *stats /* nullable */,
+                       gg_result **out_result);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
@@ -984,6 +1074,10 @@ int gg_debug_extend(gg_ctx *ctx, uint32_t tile_rows /* 0: default */);
  * so the automatic switch and the "does not fit" case occur on small graphs.  stats->route says which route ran.  Results
  * must not depend on it.  A route outside 0..2 is GG_ERR_INVALID_ARG. */
 int gg_debug_group(gg_ctx *ctx, int route /* 0 auto, 1 LDS where the table fits, 2 global */, uint32_t lds_keys /* 0: default capacity */);
+/* Testing knob: what gg_debug_aggregate_top is to gg_khop_aggregate_top, for gg_result_top_rows — the two calls share their
+ * passes (csrc/gg_top.h) but not this setting, so a test of one never moves the other.  sort_route 1 is taken while min(n,
+ * rows_in) <= GG_CHUNK_ROWS.  Results must not depend on it.  A sort_route outside 0..2 is GG_ERR_INVALID_ARG. */
+int gg_debug_value_top(gg_ctx *ctx, int sort_route /* 0 auto, 1 LDS, 2 global */, uint32_t candidate_floor /* 0: default */);
 /* Testing hook, stateless: the library's shared exclusive prefix scan over a host array.  `in` and `out` are n values of
  * `width` bytes (4: uint32, 8: uint64); out[i] = in[0] + ... + in[i-1] — the width-4 form mod 2^32 — and *total is the
  * exact sum in 64 bits, which must stay below 2^62 (the scan's status words keep two flag bits; a larger sum is not
