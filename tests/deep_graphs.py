@@ -124,3 +124,59 @@ def sources_of(name, vid):
         return vid[64:64 + FUNNEL_SOURCES]
     pick = datagen.pick_sources(vid, max(1, vid.size // 3), 77)
     return np.concatenate([pick, pick[:5], np.array([-1, vid.max() + 17], np.int64)])
+
+
+EXT_HUB_ROWS = 300  # the rows of the long key: more than a workgroup has threads
+
+
+@functools.lru_cache(maxsize=None)
+def ext_table(name, seed: int = 0xE18):
+    """A second edge table (key -> next) over the vertices of a small shape, modelled on extend_ref.ext_table and sized for
+    walk tables of 4 to 8 hops: (src, dst, rowid, info).  info: hub (the key of EXT_HUB_ROWS rows: of the sources that
+    start a 7-hop walk, the one that stands in the fewest cells of columns 0, 3 and 7 of that table, so that its rows
+    are joined but the output stays small; on a shape without such walks, the first vertex), stranger (a key that is no
+    vertex), base (the next ids that are no vertex ids start there)."""
+    from tests import edge_filter_ref, triangles_ref
+
+    vid, s, d = shape(name)
+    rng = np.random.RandomState(seed)
+    V = vid.size
+    g = triangles_ref.TriangleGraph(vid, s, d)
+    deep = edge_filter_ref.walks(g, sources_of(name, vid), 7)
+    starts = np.unique(deep[:, 0])
+    cells = np.bincount(deep[:, [0, 3, 7]].reshape(-1), minlength=V)
+    hub = int(vid[starts[np.argmin(cells[starts])]]) if starts.size else int(vid[0])
+    others = vid[vid != hub]
+    light = rng.choice(others, V // 4, replace=False)
+    n_light = rng.randint(1, 4, light.size)
+    src = np.concatenate([np.repeat(light, n_light), np.full(EXT_HUB_ROWS, hub, np.int64)])
+    src = src[rng.permutation(src.size)]  # the rows of a key are not adjacent in append order
+    base = int(vid.max()) + 1_000_000
+    stranger = int(vid.max()) + 500_000
+    dst = base + rng.permutation(src.size).astype(np.int64)
+    dst[::7] = vid[rng.randint(0, V, dst[::7].size)]  # next ids that are vertex ids
+    # a negative next id, on a row that is neither doubled below nor one of every seventh
+    dst[[i for i in range(src.size) if i % 7 and src[i] != hub][0]] = -4242
+    # parallel rows (same key, same next), and a key that is no vertex
+    twice = np.nonzero(src == hub)[0][:5]
+    src = np.concatenate([src, src[twice], np.full(3, stranger, np.int64)])
+    dst = np.concatenate([dst, dst[twice], base + np.array([1, 2, 2], np.int64)])
+    rowid = (src.size - np.arange(src.size, dtype=np.int64)) * 3 + 5
+    info = {"hub": hub, "stranger": stranger, "base": base}
+    # what the tests rely on
+    keys, per = np.unique(src, return_counts=True)
+    per_key = dict(zip(keys.tolist(), per.tolist()))
+    vertices = set(vid.tolist())
+    assert per_key[hub] == EXT_HUB_ROWS + 5 > 256
+    at_hub = np.nonzero(src == hub)[0]
+    assert (np.diff(at_hub) > 1).any()  # not adjacent in append order
+    with_rows = [k for k in per_key if k in vertices and k != hub]
+    assert len(with_rows) == V // 4 and all(1 <= per_key[k] <= 3 for k in with_rows)
+    pairs = np.stack([src, dst], axis=1)
+    assert pairs.shape[0] - np.unique(pairs, axis=0).shape[0] >= 5
+    assert stranger not in vertices and per_key[stranger] == 3
+    assert np.isin(dst[:-8:7], vid).all() and (dst < 0).sum() == 1
+    assert not np.array_equal(rowid, np.arange(src.size)) and np.unique(rowid).size == rowid.size
+    for a in (src, dst, rowid):
+        a.setflags(write=False)
+    return src, dst, rowid, info

@@ -12,7 +12,8 @@ answers GG_OK; otherwise GG_ERR_STATE if the result's kind or the reader's is on
 contract (aggregates, pair counts, components, all shortest paths), and GG_ERR_INVALID_ARG among the five older kinds
 (walk tables, walk closure, reach closure, level sets, paths).  gg_triangles_fetch_edges answers GG_ERR_STATE to every
 result without triangle edge columns, gg_result_fetch_edges GG_ERR_INVALID_ARG to a table without edge columns, and the
-consumers keep the codes their own comments promise."""
+consumers keep the codes their own comments promise: gg_result_group_by, gg_result_filter_value and gg_result_top_rows
+answer GG_OK on the four walk-table kinds and GG_ERR_STATE on every other kind, whose level they never get to look at."""
 import ctypes as C
 
 import numpy as np
@@ -72,6 +73,10 @@ CODE_TABLE = {
     "gg_result_extend_edge":             "....SSSSSSSSS",
     "gg_result_digest":                  "....IIIIIIIII",
     "gg_khop_aggregate_top":             "SSSSSSSS..SSS",
+    # the three younger consumers look at the kind before the level: GG_ERR_STATE to everything but a walk table
+    "gg_result_group_by":                "....SSSSSSSSS",
+    "gg_result_filter_value":            "....SSSSSSSSS",
+    "gg_result_top_rows":                "....SSSSSSSSS",
 }
 
 
@@ -206,6 +211,17 @@ def call_reader(gg, csr, name, res):
             return lib.gg_result_digest(ctx, csr.handle, res, HOPS, n, C.byref(C.c_uint64()))
         if name == "gg_khop_aggregate_top":
             return lib.gg_khop_aggregate_top(ctx, res, HOPS, 0, 1, 3, None, None, None, C.byref(made))
+        if name == "gg_result_group_by":
+            st = lib.gg_result_group_by.argtypes[8]._type_()
+            return lib.gg_result_group_by(ctx, res, HOPS, HOPS, csr.handle, -1, None, None, C.byref(st), C.byref(made))
+        if name == "gg_result_filter_value":
+            st = lib.gg_result_filter_value.argtypes[11]._type_()
+            return lib.gg_result_filter_value(ctx, res, HOPS, HOPS, csr.handle, _p(np.zeros(VID.size, np.int64)), None, -1, 1,
+                                              0, 1, C.byref(st), C.byref(made))
+        if name == "gg_result_top_rows":
+            st = lib.gg_result_top_rows.argtypes[13]._type_()
+            return lib.gg_result_top_rows(ctx, res, HOPS, HOPS, csr.handle, _p(np.zeros(VID.size, np.int64)), None, -1, 1, 0,
+                                          1, 0, 3, C.byref(st), C.byref(made))
         raise AssertionError(name)
     finally:
         if made.value is not None:
@@ -215,7 +231,7 @@ def call_reader(gg, csr, name, res):
 def test_every_reader_on_every_result_returns_the_code_of_the_rule(graph):
     gg, csr, results = graph
     make_results(gg, csr, results)
-    assert len(CODE_TABLE) == 27 and all(len(row) == len(KINDS) for row in CODE_TABLE.values())
+    assert len(CODE_TABLE) == 30 and all(len(row) == len(KINDS) for row in CODE_TABLE.values())
     wrong = []
     for name, row in CODE_TABLE.items():
         for kind, want in zip(KINDS, row):
