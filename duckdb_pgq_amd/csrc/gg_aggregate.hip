@@ -295,7 +295,7 @@ extern "C" int gg_khop_aggregate(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
     hipStream_t st = ctx->stream;
     if (end) GG_TRY(ensure_reverse(ctx, csr));
     PullArgs p{};
-    p.off = end ? csr->roff : csr->off, p.nbr = end ? csr->rnbr : csr->nbr;
+    p.off = end ? csr->roff : csr->off, p.nbr = end ? csr->rnbr_rows : csr->nbr;
     p.V = V;
     p.threshold = ctx->agg_long_row ? ctx->agg_long_row : AGG_LONG_ROW;
 

@@ -370,9 +370,10 @@ int all_paths_emit_t(gg_ctx *ctx, gg_csr *csr, const DistT *dist, uint32_t level
   {
     const uint64_t want = (V + 3) / 4, cap = (uint64_t)ctx->num_cus * 32;  // four vertices (wavefronts) per workgroup
     const dim3 grid((unsigned)(want < cap ? want : cap));
-    for (uint32_t level = 1; level <= levels; level++)  // (levels >= 1: the BFS built csr->roff / csr->rnbr)
+    if (levels) GG_TRY(ensure_reverse(ctx, csr));  // (returns at once: a BFS of one level or more wrote the rows)
+    for (uint32_t level = 1; level <= levels; level++)
       GG_LAUNCH(ctx, "ap_count", (k_ap_count<DistT>), grid, dim3(256), 0, dist, (const uint32_t *)csr->roff,
-                (const uint32_t *)csr->rnbr, V, level, sigma, words);
+                (const uint32_t *)csr->rnbr_rows, V, level, sigma, words);
   }
 
   uint32_t *lane_dev = nullptr, *dst_dense = nullptr, *reached = nullptr, *kept32 = nullptr, *rows32 = nullptr;

@@ -562,18 +562,18 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
   std::vector<BfsStep> host_steps((size_t)level_cap + 2);
   int launched = 0;  // levels 1..launched are enqueued
   uint64_t reached = 0;
-  bool pull_ready = csr->roff != nullptr;
+  bool pull_ready = csr->roff && csr->rnbr_rows;  // (a derived build has the offsets and no rows yet)
   while (true) {
     const int upto = launched + BFS_CHUNK < level_cap ? launched + BFS_CHUNK : level_cap;
     for (int level = launched + 1; level <= upto; level++) {
-      if (!pull_ready) {  // (whole builds make the reverse CSR eagerly; legacy builds on first use)
+      if (!pull_ready) {  // (whole builds make the reverse CSR eagerly; legacy and derived builds on first use)
         GG_TRY(ensure_reverse(ctx, csr));
         pull_ready = true;
       }
       GG_LAUNCH(ctx, "bfs_push", k_bfs_push_dev, dim3(push_grid), dim3(256), 0, (const BfsStep *)steps, (uint32_t)level,
                 csr->E, (const uint64_t *)fa, (const uint64_t *)fb, fnext, (const uint64_t *)seen, csr->off, csr->nbr, V);
       GG_LAUNCH(ctx, "bfs_finish", (k_bfs_finish_dev<DistT>), dim3(pull_grid > ugrid ? pull_grid : ugrid), dim3(256), 0, steps,
-                (uint32_t)level, csr->E, fa, fb, fnext, seen, V, csr->off, csr->roff, csr->rnbr, dist8, (uint32_t)ugrid);
+                (uint32_t)level, csr->E, fa, fb, fnext, seen, V, csr->off, csr->roff, csr->rnbr_rows, dist8, (uint32_t)ugrid);
     }
     launched = upto;
     GG_HIP(hipMemcpyAsync(host_steps.data(), steps, (size_t)(launched + 1) * sizeof(BfsStep), hipMemcpyDeviceToHost, s));
@@ -793,11 +793,11 @@ static int ensure_push_in(gg_ctx *ctx, gg_csr *csr) {
   GG_TRY(ctx->dev_alloc((void **)&cnt, (V + 1) * sizeof(uint32_t)));
   GG_HIP(hipMemsetAsync(cnt, 0, (V + 1) * sizeof(uint32_t), s));
   if (n)
-    GG_LAUNCH(ctx, "pin_count", k_pin_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr, n, cnt);
+    GG_LAUNCH(ctx, "pin_count", k_pin_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr_rows, n, cnt);
   GG_TRY(scan_exclusive_u32(ctx, cnt, pin_off, V + 1, nullptr));
   GG_LAUNCH(ctx, "pin_copy", k_copy_u32, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, pin_off, cnt, V + 1);
   if (n)
-    GG_LAUNCH(ctx, "pin_fill", k_pin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr, csr->rrow, n, cnt,
+    GG_LAUNCH(ctx, "pin_fill", k_pin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr_rows, csr->rrow, n, cnt,
               pin_nbr);
   GG_TRY(sync_checked(ctx));
   ctx->dev_free(cnt);
@@ -891,7 +891,7 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
   gg_csr *csr = const_cast<gg_csr *>(csr_c);
   if (!ctx || !csr || csr->ctx != ctx || n_src < 0 || n_src > GG_BFS_LANES || (n_src && !src_ids))
     return GG_ERR_INVALID_ARG;
-  if (!csr->roff || !csr->rnbr) GG_TRY(ensure_reverse(ctx, csr));  // a whole CSR works too (one shard)
+  if (!csr->roff || !csr->rnbr_rows) GG_TRY(ensure_reverse(ctx, csr));  // a whole CSR works too (one shard)
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
@@ -963,7 +963,7 @@ extern "C" int gg_bfs_sharded_expand(gg_bfs_run *run, void **next_words_dev, uin
     GG_LAUNCH(ctx, "bfs_shard_push", k_shard_push, dim3(push_grid), dim3(256), 0, run->lv + 1, E_rev, run->front, run->acc,
               run->seen, pin_off, pin_nbr, V);
     GG_LAUNCH(ctx, "bfs_shard_finish", (k_shard_finish<uint8_t>), dim3(pull_grid > ugrid ? pull_grid : ugrid), dim3(256), 0,
-              run->lv + 1, E_rev, run->front, run->next, run->acc, run->seen, V, run->level, csr->off, csr->roff, csr->rnbr,
+              run->lv + 1, E_rev, run->front, run->next, run->acc, run->seen, V, run->level, csr->off, csr->roff, csr->rnbr_rows,
               run->dist8, run->lv, ugrid);
   }
   BfsLevel lv[2];  // synchronises: the words are complete in memory, the caller's collective may read them

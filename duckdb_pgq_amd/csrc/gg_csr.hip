@@ -697,8 +697,9 @@ extern "C" void gg_csr_destroy(gg_csr *csr) {
     ctx->dev_free(csr->vid);
     ctx->dev_free(csr->ht);
     ctx->dev_free(csr->roff);
-    ctx->dev_free(csr->rnbr);
+    ctx->dev_free(csr->rnbr_rows);  // (null on a derived build that never rotated: dev_free takes a null)
     ctx->dev_free(csr->rrow);
+    ctx->dev_free(csr->rot);
     ctx->dev_free(csr->rnbr_by_src);
     ctx->dev_free(csr->rpos_by_src);
     ctx->dev_free(csr->pin_off);
@@ -770,7 +771,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
     GG_TRY(ctx->dev_alloc((void **)&kept_rev_dev, sizeof(unsigned long long)));
     GG_HIP(hipMemsetAsync(kept_rev_dev, 0, sizeof(unsigned long long), s));
     GG_TRY(ctx->dev_alloc((void **)&csr->roff, (V + 1) * sizeof(uint32_t)));
-    GG_TRY(ctx->dev_alloc((void **)&csr->rnbr, (E ? E : 1) * sizeof(uint32_t)));
+    GG_TRY(ctx->dev_alloc((void **)&csr->rnbr_rows, (E ? E : 1) * sizeof(uint32_t)));
     GG_TRY(ctx->dev_alloc((void **)&rkey_sorted, (E ? E : 1) * sizeof(uint32_t)));
   }
   if (E && !fast) {
@@ -800,7 +801,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
       RadixIO io{su, dv, nullptr, csr->row, csr->nbr, nullptr};
       GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, counts0, bits0, kept_dev, tvf));
       // reverse CSR of the edges whose DESTINATION this shard owns (rowid order inside a row)
-      RadixIO ior{rk, rv, nullptr, rkey_sorted, csr->rnbr, nullptr};
+      RadixIO ior{rk, rv, nullptr, rkey_sorted, csr->rnbr_rows, nullptr};
       GG_TRY(radix_sort_stable(ctx, ior, E, false, false, key_bits, counts0r, bits0, kept_rev_dev, tvr));
     } else {
       // direct-address dictionary for dense ids (decided on the device; see DirectMap)
@@ -897,9 +898,20 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   csr->rev_derived = fast && hs.rev_derived != 0;
   csr->owned_vertices = shard ? hs.owned : V;
   csr->dropped = shard ? 0 : E - hs.kept;  // a shard cannot tell dropped edges from other shards' edges
+  // A build that may derive allocates both the plain form's reverse rows and the derived form's rotation counts,
+  // since its kernels are queued before the status says which form runs.  The unused one goes back to the pool here,
+  // behind the build's one wait (whoever takes the block next is queued behind the kernels that hold its address).
+  if (csr->rev_derived) {
+    ctx->dev_free(csr->rnbr_rows);
+    csr->rnbr_rows = nullptr;  // ensure_reverse rotates the forward rows into a new block on first use
+  } else {
+    ctx->dev_free(csr->rot);
+    csr->rot = nullptr;
+  }
   for (void *p : {(void *)csr->off, (void *)csr->nbr, (void *)csr->row, (void *)csr->epos, (void *)csr->eid,
-                  (void *)csr->vid, (void *)csr->ht, (void *)csr->roff, (void *)csr->rnbr, (void *)csr->rrow})
-    ctx->keep(p);
+                  (void *)csr->vid, (void *)csr->ht, (void *)csr->roff, (void *)csr->rnbr_rows, (void *)csr->rrow,
+                  (void *)csr->rot})
+    ctx->keep(p);  // (a null is ignored)
   *out = owner.release();
   return GG_OK;
 }
@@ -936,27 +948,81 @@ int ensure_ht(gg_ctx *ctx, gg_csr *csr) {
 
 // Reverse CSR from the forward COO view (row, nbr), which is sorted by (source, rowid): a stable sort
 // by destination leaves every in-neighbour list in ascending (source, rowid) order.
-int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
+//
+// A derived build (gg_csr_fast.hip "Derived reverse") left roff = off, rrow and rot = |A| per vertex, and no reverse
+// rows: row x of the reverse CSR is the forward row of x rotated by |A| (B ++ A), written here by one thread per entry
+// on the context's stream, without a host synchronisation.  An entry is a chain of three dependent loads (rrow; off and
+// rot; nbr), so a thread takes ROT_EPT entries a block width apart and issues each stage for all of them together.
+constexpr int ROT_EPT = 4;
+__global__ __launch_bounds__(256) void k_rotate_rows(const uint32_t *__restrict__ off, const uint32_t *__restrict__ nbr,
+                                                     const uint32_t *__restrict__ rrow,
+                                                     const uint32_t *__restrict__ rot, uint64_t E,
+                                                     uint32_t *__restrict__ rnbr) {
+  const uint64_t p0 = (uint64_t)blockIdx.x * (256 * ROT_EPT) + threadIdx.x;
+  uint32_t x[ROT_EPT], o[ROT_EPT], e[ROT_EPT], a[ROT_EPT], v[ROT_EPT];
+#pragma unroll
+  for (int k = 0; k < ROT_EPT; k++) x[k] = p0 + k * 256 < E ? rrow[p0 + k * 256] : 0u;  // (vertex 0 exists: E > 0)
+#pragma unroll
+  for (int k = 0; k < ROT_EPT; k++) {
+    o[k] = off[x[k]];
+    e[k] = off[x[k] + 1];
+    a[k] = rot[x[k]];
+  }
+#pragma unroll
+  for (int k = 0; k < ROT_EPT; k++) {
+    const uint64_t p = p0 + k * 256;
+    const uint32_t deg = e[k] - o[k], i = (uint32_t)p - o[k];
+    const uint32_t ak = a[k] < deg ? a[k] : deg, b = deg - ak;  // (|A| <= the row's length: the index stays in the row)
+    v[k] = p < E ? nbr[o[k] + (i < b ? ak + i : i - b)] : 0u;
+  }
+#pragma unroll
+  for (int k = 0; k < ROT_EPT; k++)
+    if (p0 + k * 256 < E) rnbr[p0 + k * 256] = v[k];
+}
+
+int ensure_reverse_index(gg_ctx *ctx, gg_csr *csr) {
   if (csr->roff && csr->rrow) return GG_OK;
+  return ensure_reverse(ctx, csr);
+}
+
+int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
+  if (csr->roff && csr->rrow && csr->rnbr_rows) return GG_OK;
+  if (csr->roff && csr->rrow && csr->rev_derived) {
+    if (!csr->rot) {
+      set_error("internal: a derived reverse CSR without its rotation counts");
+      return GG_ERR_STATE;
+    }
+    const uint64_t E = csr->E;
+    GG_HIP(hipSetDevice(ctx->device));
+    uint32_t *rows = nullptr;
+    GG_TRY(ctx->dev_alloc((void **)&rows, (E ? E : 1) * sizeof(uint32_t)));
+    if (E)
+      GG_LAUNCH(ctx, "rotate_rows", k_rotate_rows, dim3((unsigned)((E + 256 * ROT_EPT - 1) / (256 * ROT_EPT))), dim3(256), 0,
+                (const uint32_t *)csr->off, (const uint32_t *)csr->nbr, (const uint32_t *)csr->rrow,
+                (const uint32_t *)csr->rot, E, rows);
+    ctx->keep(rows);
+    csr->rnbr_rows = rows;
+    return GG_OK;
+  }
   struct Reset {  // a failed attempt must not leave half-built members behind
     gg_csr *c;
     bool armed = true;
     ~Reset() {
       if (armed) {
         c->ctx->dev_free(c->roff);
-        c->ctx->dev_free(c->rnbr);
-        c->roff = c->rnbr = c->rrow = nullptr;
+        c->ctx->dev_free(c->rnbr_rows);
+        c->roff = c->rnbr_rows = c->rrow = nullptr;
       }
     }
   } reset{csr};
   const uint64_t V = csr->V, E = csr->E;
   uint32_t *rkey = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&csr->roff, (V + 1) * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&csr->rnbr, (E ? E : 1) * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&csr->rnbr_rows, (E ? E : 1) * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&rkey, (E ? E : 1) * sizeof(uint32_t)));
   if (E) {
     const int key_bits = ceil_log2_u64(V < 2 ? 2 : V);
-    RadixIO io{csr->nbr, csr->row, nullptr, rkey, csr->rnbr, nullptr};
+    RadixIO io{csr->nbr, csr->row, nullptr, rkey, csr->rnbr_rows, nullptr};
     GG_TRY(radix_sort_stable(ctx, io, E, false, false, key_bits, nullptr, 0, nullptr));
   }
   GG_LAUNCH(ctx, "row_offsets", k_row_offsets, dim3((unsigned)(((E ? E : 1) + 1023) / 1024)), dim3(256), 0, rkey, E,
@@ -964,7 +1030,7 @@ int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
   GG_TRY(sync_checked(ctx));
   csr->rrow = rkey;
   ctx->keep(csr->roff);
-  ctx->keep(csr->rnbr);
+  ctx->keep(csr->rnbr_rows);
   ctx->keep(csr->rrow);
   reset.armed = false;
   return GG_OK;
@@ -1719,7 +1785,13 @@ extern "C" int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, i
   };
   GG_TRY(fetch(roff, csr->roff, csr->V + 1));
   const uint64_t n_rev = csr->n_parts > 1 ? csr->E_rev : csr->E;
-  GG_TRY(fetch(rnbr, csr->rnbr, n_rev));
+  GG_TRY(fetch(rnbr, csr->rnbr_rows, n_rev));
   GG_TRY(fetch(rrow, csr->rrow, n_rev));
+  return GG_OK;
+}
+
+extern "C" int gg_debug_csr_reverse_ready(const gg_csr *csr, int *ready) {
+  if (!csr || !ready) return GG_ERR_INVALID_ARG;
+  *ready = csr->roff && csr->rrow && csr->rnbr_rows ? 1 : 0;  // (asks only: nothing is built or launched)
   return GG_OK;
 }

@@ -1564,13 +1564,15 @@ __global__ __launch_bounds__(FB_THREADS) void k_vsort_pipe(uint32_t *__restrict_
 }
 
 // where the rows of every group of VG vertices start: one wave per bucket, lane = group (at most 64 groups)
-// mirror (derived reverse, nb workgroups): bucket j's rows take the entries of BOTH half-buckets j and nb + j
+// mirror (derived reverse, read from the status block: one launch of 2 nb workgroups serves either form, and the
+// upper nb return): bucket j's rows take the entries of BOTH half-buckets j and nb + j
 __global__ __launch_bounds__(64) void k_vgroups(const uint16_t *__restrict__ offs, const uint32_t *__restrict__ bstart,
                                                 const uint32_t *__restrict__ cstart, FastGeom g,
-                                                uint32_t *__restrict__ gstart /* [2 nb][64] */, uint32_t mirror,
+                                                uint32_t *__restrict__ gstart /* [2 nb][64] */,
                                                 const BuildStatus *__restrict__ st) {
-  if (g.derive && (st->rev_derived != 0) != (mirror != 0)) return;  // (uniform over the grid) the other form's work
+  const uint32_t mirror = g.derive && st->rev_derived != 0;  // (uniform over the grid)
   const uint32_t nb = 1u << g.hb, nk = 1u << g.low, i = blockIdx.x, dir = i / nb, j = i % nb;
+  if (mirror && i >= nb) return;
   const uint32_t vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG, groups = nk / vg;
   const int lane = threadIdx.x;
   const uint32_t k0 = (uint32_t)lane * vg;
@@ -1752,18 +1754,19 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
 // chunks of half-bucket j (A: from first-half rows, in part_f) followed by those of half-bucket nb + j (B: from
 // second-half rows, in part_r); walking the chunks in that order, the running row positions put A then B into every
 // forward row exactly as above.  The offset rows of the two halves give |A| and |B| per vertex on the way, and the
-// reverse row is the forward row rotated by |A|: an A entry at forward position p lies at p + |B| in rnbr, a B entry
-// at p - |A|.  roff = off; rrow[p] is the vertex whose row holds p, in either CSR.  The staged path reads the rotated
-// entry back from the stage, so all three arrays go out as whole lines; large groups store each entry twice.
+// reverse row is the forward row rotated by |A|: an A entry at forward position p lies at p + |B| in the reverse row, a
+// B entry at p - |A|.  roff = off; rrow[p] is the vertex whose row holds p, in either CSR.  The rotated rows are NOT
+// written here: the build's own consumer, the counting 2-hop expansion, only sums over a row and reads the forward one
+// in its place, so this step leaves rot[v] = |A| and ensure_reverse (gg_csr.hip) rotates on first use.  The staged path
+// writes nbr and rrow as whole lines; large groups store each entry straight to both.
 __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                              const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
                                              const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
                                              FastGeom g, uint64_t V, uint32_t *__restrict__ off,
                                              uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
-                                             uint32_t *__restrict__ rnbr, uint32_t *__restrict__ rrow) {
+                                             uint32_t *__restrict__ rot, uint32_t *__restrict__ rrow) {
   __shared__ uint32_t s_delta[FB_VCG * FB_VG];
   __shared__ uint32_t s_run[2 * FB_VCG];  // [c]: first entry of the run inside chunk c, [FB_VCG + c]: its length
-  __shared__ uint32_t s_vt[3 * FB_VG];    // per vertex of the group: row start inside the group, |A|, |B|
   __shared__ uint32_t s_stage[GG_FB_VCAP];
   const uint32_t nb = 1u << g.hb, nk = 1u << g.low;
   const uint32_t vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG, groups = nk / vg;  // (powers of two)
@@ -1815,15 +1818,11 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
       off[vv] = base;
       roff[vv] = base;
     }
+    if ((uint32_t)lane < vg && vv < V) rot[vv] = degA;
   }
   const uint32_t t0 = gs;
   const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)dincl, 63);  // entries of the group
   const bool staged = n <= (uint32_t)GG_FB_VCAP;  // uniform
-  if ((uint32_t)lane < vg) {
-    s_vt[lane] = base - t0;
-    s_vt[vg + lane] = degA;
-    s_vt[2 * vg + lane] = degB;
-  }
   if (staged) base -= t0;  // positions inside the stage
 #pragma unroll 1
   for (uint32_t cg = 0; cg < nch; cg += FB_VCG) {
@@ -1904,7 +1903,6 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
             const uint32_t pay = kw[q] & pay_mask;
             nbr[pos] = pay;
             rrow[pos] = (uint32_t)v0 + d;
-            rnbr[(kx[q] >> 24) < nAr ? pos + s_vt[2 * vg + d] : pos - s_vt[vg + d]] = pay;
           }
         }
       }
@@ -1918,30 +1916,29 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
     for (uint32_t x0 = 0; x0 < n + hd; x0 += 64) {
       const uint32_t x = x0 + lane - hd;  // (wraps below zero for the lanes before the first entry)
       if (x < n) {
-        const uint32_t sw = s_stage[x], d = sw >> g.key_bits;
-        const uint32_t rs = s_vt[d], a = s_vt[vg + d], b = s_vt[2 * vg + d], i = x - rs;  // entry i of d's row
+        const uint32_t sw = s_stage[x];
         nbr[t0 + x] = sw & pay_mask;
-        rrow[t0 + x] = (uint32_t)v0 + d;
-        rnbr[t0 + x] = s_stage[rs + (i < b ? a + i : i - b)] & pay_mask;  // B ++ A
+        rrow[t0 + x] = (uint32_t)v0 + (sw >> g.key_bits);
       }
     }
   }
 }
 
 // MIRROR: the derived-reverse form.  With g.derive both forms are launched and one returns at once.
+// rows: the reverse rows (rnbr) of the plain form, the rotation counts (rot, one per vertex) of the derived one.
 template <bool MIRROR>
 __global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                               const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
                                               const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
                                               FastGeom g, uint64_t V, const BuildStatus *__restrict__ st,
                                               uint32_t *__restrict__ off, uint32_t *__restrict__ nbr,
-                                              uint32_t *__restrict__ roff, uint32_t *__restrict__ rnbr,
+                                              uint32_t *__restrict__ roff, uint32_t *__restrict__ rows,
                                               uint32_t *__restrict__ rrow) {
   if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
   if (MIRROR)
-    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rnbr, rrow);
+    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows, rrow);
   else
-    vrows_plain(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rnbr, rrow);
+    vrows_plain(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows, rrow);
 }
 
 static int bits_of(uint64_t v) {  // bits needed for values 0..v
@@ -2096,7 +2093,11 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&part_r, E * words * sizeof(uint32_t)));
   if (rowid) GG_TRY(ctx->dev_alloc((void **)&epos_f, E * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&csr->roff, (V + 1) * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&csr->rnbr, E * sizeof(uint32_t)));
+  // (the plain form's reverse rows and, where the device may derive, the derived form's rotation counts: both launches
+  // are queued before the host knows which one works, and csr_build_impl returns the other block to the pool behind the
+  // status wait it has anyway)
+  GG_TRY(ctx->dev_alloc((void **)&csr->rnbr_rows, E * sizeof(uint32_t)));
+  if (g.derive) GG_TRY(ctx->dev_alloc((void **)&csr->rot, V * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&csr->rrow, E * sizeof(uint32_t)));
   const size_t lds_a = ((size_t)FB_TILE * (words + (rowid ? 1 : 0)) + (size_t)(FB_WAVES + 2) * nb + FB_WAVES + 2) *
                            sizeof(uint32_t) +
@@ -2139,7 +2140,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_LAUNCH(ctx, "leaf_rows", (k_leaf_rows<P, R>), dim3(grid_l), dim3(LEAF_WAVES * 64), lds_l,                          \
             (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)epos_f, (const uint32_t *)bstart,     \
             (const uint32_t *)cstart, (const uint32_t *)offs, (const uint32_t *)substart, g, V, csr->off, csr->nbr,     \
-            csr->epos, csr->roff, csr->rnbr, csr->rrow)
+            csr->epos, csr->roff, csr->rnbr_rows, csr->rrow)
 #define GG_FB_LAUNCH_B2(P, R)      \
   do {                             \
     if (g.sub > 6) {               \
@@ -2159,21 +2160,18 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "sub_sort", k_vsort_pipe, dim3(grid_p), dim3(FB_THREADS), lds_v, part_f, part_r,
               (const uint32_t *)cstart, (const uint4 *)part_of, g, offs16);
     const uint32_t nk = 1u << low, vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG;
-    if (g.derive) {  // (the derived-reverse forms: nb buckets of both halves' entries)
-      GG_LAUNCH(ctx, "sub_totals", k_vgroups, dim3(nb), dim3(64), 0, (const uint16_t *)offs16,
-                (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, 1u, (const BuildStatus *)st);
+    // the group sums: one launch, which reads the form from the status block itself
+    GG_LAUNCH(ctx, "sub_totals", k_vgroups, dim3(2 * nb), dim3(64), 0, (const uint16_t *)offs16,
+              (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, (const BuildStatus *)st);
+    if (g.derive)  // (the derived-reverse form: nb buckets of both halves' entries; the rotation counts, not the rows)
       GG_LAUNCH(ctx, "leaf_rows", k_vrows<true>, dim3((unsigned)((uint64_t)nb * (nk / vg))), dim3(64), 0,
                 (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart, (const uint32_t *)cstart,
                 (const uint16_t *)offs16, (const uint32_t *)gstart, g, V, (const BuildStatus *)st, csr->off, csr->nbr,
-                csr->roff, csr->rnbr, csr->rrow);
-    }
-    GG_LAUNCH(ctx, g.derive ? "sub_totals_plain" : "sub_totals", k_vgroups, dim3(2 * nb), dim3(64), 0,
-              (const uint16_t *)offs16, (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, 0u,
-              (const BuildStatus *)st);
+                csr->roff, csr->rot, csr->rrow);
     GG_LAUNCH(ctx, g.derive ? "leaf_rows_plain" : "leaf_rows", k_vrows<false>, dim3((unsigned)(2ull * nb * (nk / vg))),
               dim3(64), 0, (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart,
               (const uint32_t *)cstart, (const uint16_t *)offs16, (const uint32_t *)gstart, g, V,
-              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr, csr->rrow);
+              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr_rows, csr->rrow);
   } else if (g.pack && rowid) {
     GG_FB_LAUNCH_B2(true, true);
   } else if (g.pack && g.rank_atomic && GG_FB_SUBPIPE) {
@@ -2197,7 +2195,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "leaf_rows", (k_leaf_rows<true, false>), dim3(grid_l), dim3(LEAF_WAVES * 64), lds_l,
               (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)epos_f, (const uint32_t *)bstart,
               (const uint32_t *)cstart, (const uint32_t *)offs, (const uint32_t *)substart, g, V, csr->off, csr->nbr,
-              csr->epos, csr->roff, csr->rnbr, csr->rrow);
+              csr->epos, csr->roff, csr->rnbr_rows, csr->rrow);
   } else if (g.pack) {
     GG_FB_LAUNCH_B2(true, false);
   } else if (rowid) {

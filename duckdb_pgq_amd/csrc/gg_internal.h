@@ -287,9 +287,14 @@ struct gg_csr {
   // reverse CSR (in-neighbours): row x lists the sources u of every edge u->x — in ascending (u, rowid) order when
   // ensure_reverse() built it lazily, in rowid order when the bucketed build made it (gg_csr_fast.hip)
   uint32_t *roff = nullptr;    // V+1
-  uint32_t *rnbr = nullptr;    // E   source u of the reverse entry
+  // E   source u of the reverse entry.  NULL on a derived build (rev_derived) until ensure_reverse() rotates the
+  // forward rows into it: every reader goes through ensure_reverse() first; ensure_reverse_index() does not write it
+  uint32_t *rnbr_rows = nullptr;
   uint32_t *rrow = nullptr;    // E   destination x of the reverse entry (COO view, sorted by x)
-  bool rev_derived = false;    // the bucketed build derived roff / rnbr / rrow from the forward rows (fully mirrored table)
+  bool rev_derived = false;    // the bucketed build derived roff / rrow from the forward rows (fully mirrored table)
+  // V   derived builds: |A| of every vertex, the first-half entries its forward row starts with.  The reverse row is
+  // the forward row rotated by it (B ++ A), which is what ensure_reverse() writes on first use
+  uint32_t *rot = nullptr;
   // the reverse rows again with their sources ascending (gg_paths.hip: ensure_reverse_by_source, whole CSRs, on first
   // use by gg_bfs64_paths or gg_triangles): the bucketed build leaves rnbr's rows in rowid order, which a pull does not mind and a path trace does
   uint32_t *rnbr_by_src = nullptr;  // E
@@ -515,8 +520,11 @@ int sort_triples_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, con
 int grow_column(gg_ctx *ctx, Column &c, size_t live_rows, size_t need_rows);
 // GG_STAGING_TRACE=1: print and reset the edge staging's waiting-time counters (gg_runtime.hip)
 void staging_trace_print();
-// build csr->roff / csr->rnbr if absent (gg_csr.hip)
+// build csr->roff / csr->rrow / csr->rnbr_rows if absent (gg_csr.hip).  A derived build left the first two and
+// csr->rot: the rows are then one rotation kernel on the context's stream, no host synchronisation
 int ensure_reverse(gg_ctx *ctx, gg_csr *csr);
+// csr->roff / csr->rrow only, for callers that never read the reverse rows themselves: a derived build has both
+int ensure_reverse_index(gg_ctx *ctx, gg_csr *csr);
 // build csr->rnbr_by_src if absent: the reverse rows with their sources ascending, under csr->roff (gg_paths.hip)
 int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr);
 // build csr->rpos_by_src if absent: the same sort carrying the forward CSR position (gg_paths.hip)

@@ -1124,7 +1124,7 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     GG_TRY(ctx->dev_alloc((void **)&foff2, (E + 1) * sizeof(uint64_t)));
     if (E)
       GG_LAUNCH(ctx, "front3_prepare", k_front3_prepare, dim3((unsigned)((E + 255) / 256)), dim3(256), 0,
-                (const uint32_t *)froff, (const uint32_t *)csr->rnbr, E, foff2);
+                (const uint32_t *)froff, (const uint32_t *)csr->rnbr_rows, E, foff2);
     uint64_t M2 = 0;
     GG_TRY(offsets_from_deg(ctx, foff2, E, &M2));
     if (M2 != M) {
@@ -1149,7 +1149,7 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     for (uint64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {
       const uint64_t nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
       GG_LAUNCH(ctx, "expand_front3", k_expand_mid3, dim3((unsigned)nt), dim3(XT), 0, csr->off, csr->nbr,
-                (const uint32_t *)froff, csr->rrow, csr->rnbr, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
+                (const uint32_t *)froff, csr->rrow, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
                 (int)(j + 1 >= k_min), partial + t0 * 4, t0, (const uint64_t *)fqs, j);
     }
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
@@ -1303,7 +1303,14 @@ __global__ void k_pack_stats(const unsigned long long *__restrict__ tmp3, unsign
 int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, int k_min, gg_khop_stats *st,
                    unsigned long long *dev_out6 = nullptr) {
   if (st) memset(st, 0, sizeof(*st));
-  GG_TRY(ensure_reverse(ctx, csr));
+  // The kernel only sums over the in-row of every middle vertex x (the 1-hop digest, one staged state per entry).  On a
+  // derived CSR that row is the forward row of x in another order under the same offsets (roff == off), so the forward
+  // rows stand in for it — the same counts and digests — and the reverse rows stay unwritten (gg_csr.hip: ensure_reverse).
+  if (csr->rev_derived)
+    GG_TRY(ensure_reverse_index(ctx, csr));
+  else
+    GG_TRY(ensure_reverse(ctx, csr));
+  const uint32_t *in_rows = csr->rev_derived ? csr->nbr : csr->rnbr_rows;
   const uint64_t n_mid = mid_hi - mid_lo;
   uint64_t M = csr->E_rev, fbase = 0;
   if (!(mid_lo == 0 && mid_hi == csr->V)) {
@@ -1322,7 +1329,7 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
       GG_TRY(ctx->dev_alloc((void **)&partial, n_tiles * 4 * sizeof(unsigned long long)));
       GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
       GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, csr->rrow,
-                csr->rnbr, fbase, M, (int)(k_min <= 1), partial, tmp);
+                in_rows, fbase, M, (int)(k_min <= 1), partial, tmp);
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
     }
     GG_LAUNCH(ctx, "pack_stats", k_pack_stats, dim3(1), dim3(64), 0, (const unsigned long long *)tmp, (unsigned long long)M,
@@ -1337,7 +1344,7 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
     GG_TRY(ctx->dev_alloc((void **)&partial, n_tiles * 4 * sizeof(unsigned long long)));
     GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
     GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, csr->rrow,
-              csr->rnbr, fbase, M, (int)(k_min <= 1), partial, tmp);
+              in_rows, fbase, M, (int)(k_min <= 1), partial, tmp);
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
     uint64_t h[3];
     GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
@@ -1371,7 +1378,7 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
     GG_TRY(ctx->dev_alloc((void **)&foff2, (E + 1) * sizeof(uint64_t)));
     GG_TRY(ctx->dev_alloc((void **)&partial, nb1 * 4 * sizeof(unsigned long long)));
     GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
-    GG_LAUNCH(ctx, "mid3_prepare", k_mid3_prepare, dim3((unsigned)nb1), dim3(256), 0, csr->roff, csr->rrow, csr->rnbr,
+    GG_LAUNCH(ctx, "mid3_prepare", k_mid3_prepare, dim3((unsigned)nb1), dim3(256), 0, csr->roff, csr->rrow, csr->rnbr_rows,
               E, foff2, partial);
     GG_TRY(reduce_partials(ctx, partial, nb1, tmp));
     GG_TRY(offsets_from_deg(ctx, foff2, E, &M2, {{tmp, sizeof(uint64_t), &dig1}}));  // (the 1-hop digest rides on its sync)
@@ -1393,7 +1400,7 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
       for (uint64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {  // (one launch up to 1.3e10 2-hop rows)
         const uint64_t nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
         GG_LAUNCH(ctx, "expand_mid3", k_expand_mid3, dim3((unsigned)nt), dim3(XT), 0, csr->off, csr->nbr, csr->roff,
-                  csr->rrow, csr->rnbr, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
+                  csr->rrow, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
                   (int)(k_min <= 2), partial + t0 * 4, t0, (const uint64_t *)nullptr, 0);
       }
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
@@ -1830,7 +1837,7 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
     GG_LAUNCH(ctx, "mat_tile_entries", k_mat_tile_entries, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0,
               (const uint64_t *)foff, n, n_tiles, M2, tile_entry);
     GG_LAUNCH(ctx, "mat_mid2", k_mat_mid2, dim3((unsigned)n_tiles), dim3(256), 0, csr->off, csr->nbr, csr->rrow,
-              csr->rnbr, csr->vid, (const uint64_t *)foff, (const uint32_t *)tile_entry, e0, n, M2, res->cols[2][0],
+              csr->rnbr_rows, csr->vid, (const uint64_t *)foff, (const uint32_t *)tile_entry, e0, n, M2, res->cols[2][0],
               res->cols[2][1], res->cols[2][2], (uint32_t)n_tiles);
     ctx->dev_free(tile_entry);
   }
@@ -1841,7 +1848,7 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
       ctx->keep(res->cols[1][c]);
       if (n)
         GG_LAUNCH(ctx, "gather_ids", k_gather_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                  (c ? csr->rrow : csr->rnbr) + e0, csr->vid, n, res->cols[1][c]);
+                  (c ? csr->rrow : csr->rnbr_rows) + e0, csr->vid, n, res->cols[1][c]);
     }
   }
   ctx->dev_free(foff);
@@ -2090,7 +2097,12 @@ int khop_count_rows(gg_ctx *ctx, gg_csr *csr, const uint32_t *dense_src, uint64_
   const uint64_t V = csr->V;
   if (V == 0) return GG_OK;
   const bool all = dense_src == nullptr;
-  if (k_max >= 2 || (all && csr->n_parts > 1)) GG_TRY(ensure_reverse(ctx, csr));
+  // k_wc_pull reads the reverse rows: from a source list at h >= 2, from every vertex at h >= 3 (h = 2 is a dot of the
+  // two offset arrays, which a derived build has without its rows)
+  if (all ? k_max >= 3 : k_max >= 2)
+    GG_TRY(ensure_reverse(ctx, csr));
+  else if (k_max >= 2 || (all && csr->n_parts > 1))
+    GG_TRY(ensure_reverse_index(ctx, csr));
   unsigned long long *out = nullptr, *wa = nullptr, *wb = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&out, (GG_MAX_HOPS + 1) * sizeof(unsigned long long)));
   GG_HIP(hipMemsetAsync(out, 0, (GG_MAX_HOPS + 1) * sizeof(unsigned long long), ctx->stream));
@@ -2119,7 +2131,7 @@ int khop_count_rows(gg_ctx *ctx, gg_csr *csr, const uint32_t *dense_src, uint64_
         if (!dst) GG_TRY(ctx->dev_alloc((void **)&dst, V * sizeof(unsigned long long)));
         // from every vertex the first explicit level is w_2 = pull(indeg)
         const bool from_indeg = all && level < 2;
-        GG_LAUNCH(ctx, "wc_pull", k_wc_pull, dim3(pull_grid), dim3(256), 0, csr->roff, csr->rnbr,
+        GG_LAUNCH(ctx, "wc_pull", k_wc_pull, dim3(pull_grid), dim3(256), 0, csr->roff, csr->rnbr_rows,
                   from_indeg ? (const unsigned long long *)nullptr : w, V, dst);
         level = from_indeg ? 2 : level + 1;
         w = dst;
@@ -2472,7 +2484,7 @@ extern "C" int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint
     for (int i = 1; i < n_parts; i++) bounds[i] = V;
     return GG_OK;
   }
-  GG_TRY(ensure_reverse(ctx, csr));
+  GG_TRY(ensure_reverse_index(ctx, csr));  // (k_mid_work reads the two offset arrays only)
   uint64_t *work = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&work, (V + 1) * sizeof(uint64_t)));
   GG_LAUNCH(ctx, "mid_work", k_mid_work, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, csr->off, csr->roff, V,

@@ -324,11 +324,11 @@ extern "C" int gg_khop_pair_counts(gg_ctx *ctx, const gg_csr *csr_c, const int64
     for (int h = 1; h <= k_max; h++) {
       const int nxt = cur ^ 1;
       GG_LAUNCH(ctx, "pc_pull", k_pc_pull, pull_grid, dim3(256), 0, (const uint32_t *)csr->roff,
-                (const uint32_t *)csr->rnbr, (const unsigned long long *)mask[cur], (const uint64_t *)W[cur], V, threshold,
+                (const uint32_t *)csr->rnbr_rows, (const unsigned long long *)mask[cur], (const uint64_t *)W[cur], V, threshold,
                 all, mask[nxt], W[nxt], (unsigned long long *)d_gathered);
       if (list)
         GG_LAUNCH(ctx, "pc_pull_long", k_pc_pull_long, dim3((unsigned)(V < long_cap ? V : long_cap)), dim3(256), 0,
-                  (const uint32_t *)csr->roff, (const uint32_t *)csr->rnbr, (const unsigned long long *)mask[cur],
+                  (const uint32_t *)csr->roff, (const uint32_t *)csr->rnbr_rows, (const unsigned long long *)mask[cur],
                   (const uint64_t *)W[cur], list, (const uint64_t *)d_nlong, all, mask[nxt], W[nxt],
                   (unsigned long long *)d_gathered);
       cur = nxt;

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(256) void k_entry_rows(const uint32_t *__restrict__
 // forward entries by destination, once per CSR (first gg_bfs64_paths call), 4 E bytes kept with it.
 int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr) {
   if (csr->rnbr_by_src) return GG_OK;
-  if (!csr->roff) GG_TRY(ensure_reverse(ctx, csr));  // (a search of zero levels never built it)
+  // (a search of zero levels never built it; a derived build has the offsets and not yet the rows its callers pull along)
+  if (!csr->roff || !csr->rnbr_rows) GG_TRY(ensure_reverse(ctx, csr));
   const uint64_t V = csr->V, E = csr->E;
   uint32_t *row = csr->row, *own_row = nullptr, *key_out = nullptr, *sorted = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&sorted, (E ? E : 1) * sizeof(uint32_t)));

@@ -428,6 +428,20 @@ extern "C" int gg_debug_placement(gg_ctx *ctx, uint64_t *sets_built, uint64_t *f
   return GG_OK;
 }
 
+extern "C" int gg_debug_pool(gg_ctx *ctx, uint64_t *blocks, uint64_t *in_use) {
+  if (!ctx) return GG_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(ctx->pool_mu);
+  uint64_t n = 0, used = 0;
+  for (auto &b : ctx->blocks)
+    if (b.ptr) {
+      n++;
+      used += b.in_use ? 1 : 0;
+    }
+  if (blocks) *blocks = n;
+  if (in_use) *in_use = used;
+  return GG_OK;
+}
+
 extern "C" int gg_debug_reset(gg_ctx *ctx) {
   if (!ctx) return GG_ERR_INVALID_ARG;
   ctx->force_frontier = 0;

@@ -20,8 +20,8 @@ SYMBOLS = [
     "gg_ctx_set_edge_rowid", "gg_csr_build", "gg_csr_build_shard", "gg_csr_destroy", "gg_csr_info", "gg_csr_export",
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
-    "gg_debug_csr_reverse", "gg_debug_scan", "gg_debug_sort_pairs",
-    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_reach_visited",
+    "gg_debug_csr_reverse", "gg_debug_csr_reverse_ready", "gg_debug_scan", "gg_debug_sort_pairs",
+    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_pool", "gg_debug_reach_visited",
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
@@ -193,12 +193,14 @@ def load_library(path: str | None = None):
     lib.gg_debug_force_legacy_build.argtypes = [P, C.c_int]
     lib.gg_debug_rank_mode.argtypes = [P, C.c_int]
     lib.gg_debug_csr_reverse.argtypes = [P, i64p, i64p, i64p, C.POINTER(C.c_int)]
+    lib.gg_debug_csr_reverse_ready.argtypes = [P, C.POINTER(C.c_int)]
     lib.gg_debug_scan_fault.argtypes = [P, C.c_uint32, u64]
     lib.gg_debug_scan.argtypes = [P, C.c_void_p, u64, C.c_int, C.c_void_p, C.POINTER(u64)]
     lib.gg_debug_sort_pairs.argtypes = [P] + [C.c_void_p] * 3 + [u64, C.c_int] + [C.c_void_p] * 3 + [C.POINTER(u64)]
     lib.gg_debug_max_grid_tiles.argtypes = [P, u64]
     lib.gg_debug_reset.argtypes = [P]
     lib.gg_debug_placement.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
+    lib.gg_debug_pool.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
     lib.gg_debug_reach_visited.argtypes = [P, C.c_int, u64]
     lib.gg_result_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_result_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
@@ -578,6 +580,13 @@ class Csr:
         d = C.c_int()
         self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, None, None, None, C.byref(d)))
         return d.value
+
+    @property
+    def reverse_rows_ready(self) -> bool:
+        """True if the reverse rows (rnbr) are written; asking does not write them (gg_debug_csr_reverse_ready)."""
+        r = C.c_int()
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse_ready(self.handle, C.byref(r)))
+        return bool(r.value)
 
     def export_reverse(self):
         """(roff, rnbr, rrow) of the reverse CSR as int64 arrays (gg_debug_csr_reverse)."""
@@ -1004,6 +1013,12 @@ class GG:
         """(column sets placed by probing, fast pairs of the last set: 3 = each result column in its own memory rank)."""
         a, b = C.c_uint64(), C.c_uint64()
         self._chk(self.lib.gg_debug_placement(self.ctx, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def pool(self):
+        """(blocks the device pool holds, blocks handed out right now) (gg_debug_pool)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.gg_debug_pool(self.ctx, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
     def khop_partition(self, csr: Csr, n_parts: int):

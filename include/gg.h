@@ -1016,6 +1016,12 @@ int gg_debug_rank_mode(gg_ctx *ctx, int mode);
  * (row i + E/2 = row i with source and destination swapped, for every i), which must give the same arrays as sorting;
  * GG_MIRROR_REVERSE=0 in the environment at gg_ctx_create (or GG_MIRROR_PAIRS=0) switches that off. */
 int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, int64_t *rrow, int *derived);
+/* *ready = 1 if the CSR holds its reverse rows (rnbr), 0 if they are still to be written.  A derived build keeps only
+ * the row offsets, the COO column and one rotation count per vertex, and writes the rows when the first call that reads
+ * them arrives (counting 1- and 2-hop walks never does); every other build has them from the start or, for the
+ * multi-pass build of a whole graph, from that first call.  This call asks only: it builds and launches nothing, where
+ * gg_debug_csr_reverse with an array to fill writes the rows first. */
+int gg_debug_csr_reverse_ready(const gg_csr *csr, int *ready);
 /* Testing knob (fault injection): tile `mute_tile` of every chained prefix scan never publishes its sum and the
  * tiles behind it give up after `spin_limit` polls instead of 2^24; the call that ran the scan must then
  * fail with GG_ERR_HIP instead of returning a wrong result.  spin_limit 0 and mute_tile UINT64_MAX restore
@@ -1100,6 +1106,10 @@ int gg_debug_reset(gg_ctx *ctx);
  * context has placed by probing, and how many of the three pairs of the LAST set lie in different memory ranks (3 = every
  * column in its own rank class, the 7.2 TB/s case; 2 = two classes, 7.0; 0 = one class or never probed).  Read-only. */
 int gg_debug_placement(gg_ctx *ctx, uint64_t *sets_built, uint64_t *fast_pairs_of_last_set);
+/* The context's device pool: how many blocks it holds, and how many of them are handed out right now (to a live CSR or
+ * result, or inside a running call).  A block that is never given back shows as in_use growing from call to call, one
+ * given back twice or lost as the counts of two identical rounds of calls differing.  Read-only; either may be NULL. */
+int gg_debug_pool(gg_ctx *ctx, uint64_t *blocks, uint64_t *in_use);
 
 int gg_profile_enable(gg_ctx *ctx, int on);
 /* Time only the kernels named in the comma-separated list (NULL: every kernel).  Two event records per
