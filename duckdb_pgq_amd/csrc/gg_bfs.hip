@@ -507,6 +507,8 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
   gg_bfs_stats st;
   memset(&st, 0, sizeof(st));
   const uint64_t n_out = dst_ids ? n_dst : V;
+  ctx->bfs_steps.clear();  // (a call that runs no level reports none)
+  ctx->bfs_cell_bytes = 0;
   if (n_src == 0 || n_out == 0) {
     if (stats) *stats = st;
     return GG_OK;
@@ -590,8 +592,21 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
         st.active_vertices += host_steps[l].n_active;
         st.traversed_edges += host_steps[l].te;
       }
-      // the deepest recordable level is reached with work left and the caller did not bound the search there
-      if (frontier_left && launched == MAX_LEVEL && (max_hops < 0 || max_hops > MAX_LEVEL)) *overflow = true;
+      // the deepest recordable level is reached with work left and the caller did not bound the search there.  A two-byte
+      // run whose last frontier has no out-edge (te == 0) has no work left: it is the answer, not a refusal (a chain of
+      // 65 535 vertices).  The one-byte run keeps its rerun in that case (open points).
+      const bool dead_end = sizeof(DistT) == 2 && host_steps[launched].te == 0;
+      if (frontier_left && !dead_end && launched == MAX_LEVEL && (max_hops < 0 || max_hops > MAX_LEVEL)) *overflow = true;
+      // gg_debug_bfs_steps: what the levels recorded about themselves (an overflowing run's copy is replaced by its rerun's)
+      ctx->bfs_cell_bytes = (int)sizeof(DistT);
+      ctx->bfs_steps.resize((size_t)(ran + 1) * 4);
+      for (int l = 0; l <= ran; l++) {
+        uint64_t *o = &ctx->bfs_steps[(size_t)l * 4];
+        o[0] = host_steps[l].n_active;
+        o[1] = host_steps[l].te;
+        o[2] = host_steps[l].reached;
+        o[3] = host_steps[l].cur;
+      }
       break;
     }
   }
@@ -640,6 +655,18 @@ static int bfs_run(gg_ctx *ctx, gg_csr *csr, const int64_t *src_ids, int n_src, 
 static int bfs_dispatch(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats,
                         gg_result *pairs, const PathsRequest *paths = nullptr, const AllPathsRequest *all_paths = nullptr);
+
+extern "C" int gg_debug_bfs_steps(gg_ctx *ctx, uint64_t *out, uint64_t cap_levels, uint64_t *n_levels, int *cell_bytes,
+                                  int *pull_factor) {
+  if (!ctx || (cap_levels && !out)) return GG_ERR_INVALID_ARG;
+  const uint64_t n = ctx->bfs_steps.size() / 4;
+  const uint64_t take = n < cap_levels ? n : cap_levels;
+  if (take) memcpy(out, ctx->bfs_steps.data(), take * 4 * sizeof(uint64_t));
+  if (n_levels) *n_levels = n;
+  if (cell_bytes) *cell_bytes = ctx->bfs_cell_bytes;
+  if (pull_factor) *pull_factor = GG_BFS_PULL_FACTOR;
+  return GG_OK;
+}
 
 extern "C" int gg_bfs64(gg_ctx *ctx, const gg_csr *csr_c, const int64_t *src_ids, int n_src, int max_hops,
                         const int64_t *dst_ids, uint64_t n_dst, int32_t *out_dist, gg_bfs_stats *stats) {

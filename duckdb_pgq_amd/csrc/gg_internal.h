@@ -207,6 +207,8 @@ struct gg_ctx {
   bool cc_size_fold = true;     // GG_CC_SIZE_FOLD=0 at context creation: gg_components adds sizes per lane, never per wave
                                 // (a measurement switch, scripts/bench_components.py; sizes are the same either way)
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
+  std::vector<uint64_t> bfs_steps;  // gg_debug_bfs_steps: (n_active, te, reached, cur) of levels 0..ran of the last bfs_run
+  int bfs_cell_bytes = 0;           // gg_debug_bfs_steps: sizeof(DistT) of that run (0: no run since the last reset)
   bool profiling = false;
   std::vector<std::string> prof_names;
   std::vector<uint64_t> prof_launches;

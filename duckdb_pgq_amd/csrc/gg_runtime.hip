@@ -469,6 +469,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->group_route = 0;
   ctx->group_lds_keys = 0;
   ctx->keep_edge_rowid = true;
+  ctx->bfs_steps.clear();
+  ctx->bfs_cell_bytes = 0;
   if (ctx->dev_err) {  // a fault-injection test may have left the chained scans' error word set
     GG_HIP(hipSetDevice(ctx->device));
     GG_HIP(hipMemsetAsync(ctx->dev_err, 0, sizeof(unsigned long long), ctx->stream));

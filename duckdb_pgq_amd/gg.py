@@ -28,6 +28,7 @@ SYMBOLS = [
     "gg_result_filter_common_neighbour", "gg_result_filter_edge", "gg_staging_clear_edges", "gg_vertices_from_edges",
     "gg_bfs64", "gg_bfs64_pairs", "gg_bfs64_pairs_packed", "gg_bfs64_paths", "gg_bfs64_paths_rows", "gg_bfs64_paths_fetch",
     "gg_bfs64_all_paths", "gg_bfs64_all_paths_rows", "gg_bfs64_all_paths_fetch_pairs", "gg_bfs64_all_paths_fetch",
+    "gg_debug_bfs_steps",
     "gg_walk_endpoints", "gg_walk_closure", "gg_walk_closure_levels",
     "gg_walk_closure_fetch", "gg_reach_closure", "gg_reach_closure_levels", "gg_reach_closure_fetch", "gg_host_alloc", "gg_host_free", "gg_csr_lookup",
     "gg_bfs_sharded_begin", "gg_bfs_sharded_expand", "gg_bfs_sharded_words", "gg_bfs_sharded_commit",
@@ -202,6 +203,7 @@ def load_library(path: str | None = None):
     lib.gg_debug_placement.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
     lib.gg_debug_pool.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
     lib.gg_debug_reach_visited.argtypes = [P, C.c_int, u64]
+    lib.gg_debug_bfs_steps.argtypes = [P, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.gg_result_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_result_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(C.c_uint32)]
     lib.gg_expand_khop_result.argtypes = [P, P, i64p, u64, C.c_int, C.c_int, C.POINTER(KhopStats), C.POINTER(P)]
@@ -1043,6 +1045,19 @@ class GG:
             rc = self.lib.gg_bfs64(self.ctx, csr.handle, ps, s.size, max_hops, pt, t.size, out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(st))
         self._chk(rc)
         return out, {"levels": st.levels, "traversed_edges": st.traversed_edges, "active_vertices": st.active_vertices, "reached_pairs": st.reached_pairs}
+
+    def debug_bfs_steps(self):
+        """The last 64-lane BFS of this context as its levels recorded it (gg_debug_bfs_steps): a dict of `steps`, a
+        uint64 array [entries, 4] of (n_active, te, reached, cur) for the seed and every level that ran (no entries: no
+        BFS since the last reset), `levels` = entries - 1, `cell_bytes` and `pull_factor`."""
+        n, cell, factor = C.c_uint64(), C.c_int(), C.c_int()
+        self._chk(self.lib.gg_debug_bfs_steps(self.ctx, None, 0, C.byref(n), None, None))
+        steps = np.zeros((int(n.value), 4), np.uint64)
+        self._chk(self.lib.gg_debug_bfs_steps(self.ctx, steps.ctypes.data_as(C.POINTER(C.c_uint64)), steps.shape[0],
+                                              C.byref(n), C.byref(cell), C.byref(factor)))
+        assert int(n.value) == steps.shape[0]
+        return {"steps": steps, "levels": steps.shape[0] - 1, "cell_bytes": int(cell.value),
+                "pull_factor": int(factor.value)}
 
     def lookup(self, csr: Csr, ids) -> np.ndarray:
         """Dense index of each id (uint32, 0xFFFFFFFF = not a vertex)."""

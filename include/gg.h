@@ -758,6 +758,8 @@ typedef struct gg_bfs_stats {
  * Targets: dst_ids == NULL -> every vertex in vertex-table order (n = V); else the n_dst given ids
  * (ids absent from the vertex table get -1).  A source absent from the vertex table reaches nothing.
  * out_dist == NULL: run the BFS and fill *stats only (no device-to-host copy of the distances).
+ * Distances up to 65 534 are recorded: a search that still has edges to follow at that level and is not bounded there by
+ * max_hops fails with GG_ERR_TOO_LARGE ("deeper than 65534 levels"); the context stays usable.
  * Equals, for the reached pairs, the reference relation
  *   SELECT startPerson, friend, min(hopCount) FROM friends GROUP BY startPerson, friend
  * with the recursion bound `f.hopCount < max_hops` (bi-10-shortestpath.sql:8-31). */
@@ -1110,6 +1112,17 @@ int gg_debug_placement(gg_ctx *ctx, uint64_t *sets_built, uint64_t *fast_pairs_o
  * result, or inside a running call).  A block that is never given back shows as in_use growing from call to call, one
  * given back twice or lost as the counts of two identical rounds of calls differing.  Read-only; either may be NULL. */
 int gg_debug_pool(gg_ctx *ctx, uint64_t *blocks, uint64_t *in_use);
+/* Diagnostics of the LAST 64-lane BFS of this context (gg_bfs64 and every call that runs one: pairs, paths, all paths):
+ * what its levels recorded about themselves on the device, as the host read it back when the search ended.  *n_levels =
+ * stats.levels + 1 entries (entry 0: the seed; entry l: level l), 0 if no BFS ran since gg_ctx_create / gg_debug_reset or
+ * the last call ran no level (no sources, no targets, no vertices).  out receives min(*n_levels, cap_levels) entries of
+ * four words: n_active (vertices of the frontier the level produced), te (their out-degrees), reached (its new (lane,
+ * vertex) cells) and cur, the word buffer (0 / 1) that holds that frontier — a level that pulled flipped it, one that
+ * pushed kept it, so cur's flips are the direction each level took.  *cell_bytes = bytes of a distance cell in the run
+ * that answered (1, or 2 after the rerun of a search deeper than 254 levels); *pull_factor = the compiled threshold: level l
+ * pulls iff te[l - 1] * pull_factor > E.  Read-only; every pointer but ctx may be NULL (out only with cap_levels 0). */
+int gg_debug_bfs_steps(gg_ctx *ctx, uint64_t *out, uint64_t cap_levels, uint64_t *n_levels, int *cell_bytes,
+                       int *pull_factor);
 
 int gg_profile_enable(gg_ctx *ctx, int on);
 /* Time only the kernels named in the comma-separated list (NULL: every kernel).  Two event records per
