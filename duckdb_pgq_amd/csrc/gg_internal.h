@@ -197,6 +197,8 @@ struct gg_ctx {
   uint32_t agg_top_floor = 0;   // gg_debug_aggregate_top: candidates at which the selection compacts them (0: the default)
   uint32_t pc_long_row = 0;     // gg_debug_pair_counts: in-rows of more entries go to a workgroup each (0: the default)
   int pc_gather_mode = 0;       // gg_debug_pair_counts: 0 entries whose mask is 0 are skipped, 1 every state row is read
+  uint32_t cp_long_row = 0;     // gg_debug_cheapest: in-rows of more entries go to a workgroup each (0: the default)
+  int cp_gather_mode = 0;       // gg_debug_cheapest: 0 entries whose mask is 0 are skipped, 1 every entry counts as live
   int cc_init_mode = 0;         // gg_debug_components: 0 the default start of the forest, 1 every vertex its own root (the same)
   uint32_t cc_jumps_per_check = 0;  // gg_debug_components: pointer-doubling launches per look at the changed word (0: the default)
   uint32_t extend_tile_rows = 0;    // gg_debug_extend: output rows per workgroup of gg_result_extend_edge's write pass (0: the default)
@@ -311,7 +313,7 @@ struct gg_csr {
 
 // What a device result holds and which calls read it.  The kinds from AGGREGATE on were born with a refusal contract:
 // every call but their own answers them with GG_ERR_STATE, and theirs answer every other kind so (gg::expect_kind).
-enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS };
+enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS, CHEAPEST };
 
 // kind          tables and columns (h: a level in k_min..k_max)                     read by
 // TABLES        rows[h], cols[h][0..h] = ids v0..vh; ecols[h][j] = rowid of the     gg_result_rows / _fetch / _fetch_edges /
@@ -333,6 +335,8 @@ enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGAT
 //               cells), paths, kept; rows[AP_ROWS_TABLE], cols[..][0..4] = pair     _fetch
 //               index, path index, step (int32 cells), vertex id, edge rowid if
 //               asked for
+// CHEAPEST      rows[0], cols[0][0..3] = source index, vertex id, cost, hops (int32     gg_cheapest64_rows / _fetch
+//               cells)
 struct gg_result {
   gg_ctx *ctx = nullptr;
   ResultKind kind = ResultKind::TABLES;
@@ -394,6 +398,7 @@ constexpr KindName KIND_NAMES[] = {
     {"pair counts", "gg_khop_pair_counts_rows / gg_khop_pair_counts_fetch"},
     {"components", "gg_components_rows / gg_components_fetch[_sizes]"},
     {"all shortest paths", "gg_bfs64_all_paths_rows / _fetch_pairs / _fetch"},
+    {"cheapest path costs", "gg_cheapest64_rows / gg_cheapest64_fetch"},
 };
 inline int expect_kind(const gg_result *res, ResultKind want, const char *fn) {
   if (!res) return GG_ERR_INVALID_ARG;

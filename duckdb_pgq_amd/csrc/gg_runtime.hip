@@ -463,6 +463,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->val_top_floor = 0;
   ctx->pc_long_row = 0;
   ctx->pc_gather_mode = 0;
+  ctx->cp_long_row = 0;
+  ctx->cp_gather_mode = 0;
   ctx->cc_init_mode = 0;
   ctx->cc_jumps_per_check = 0;
   ctx->extend_tile_rows = 0;

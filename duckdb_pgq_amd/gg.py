@@ -37,6 +37,8 @@ SYMBOLS = [
     "gg_khop_aggregate", "gg_khop_aggregate_rows", "gg_khop_aggregate_fetch", "gg_debug_aggregate_long_row",
     "gg_khop_aggregate_top", "gg_debug_aggregate_top", "gg_debug_aggregate_top_listed",
     "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
+    "gg_edge_weights_create", "gg_edge_weights_destroy", "gg_cheapest64", "gg_cheapest64_rows", "gg_cheapest64_fetch",
+    "gg_debug_cheapest",
     "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
     "gg_result_extend_edge", "gg_debug_extend",
     "gg_result_group_by", "gg_debug_group",
@@ -123,6 +125,16 @@ class PairStats(C.Structure):
     ]
 
 
+class CheapestStats(C.Structure):
+    _fields_ = [
+        ("rounds", C.c_uint64),
+        ("reached_pairs", C.c_uint64),
+        ("cells_lowered", C.c_uint64),
+        ("entries_pulled", C.c_uint64),
+        ("rows_gathered", C.c_uint64),
+    ]
+
+
 class CcStats(C.Structure):
     _fields_ = [
         ("vertices", C.c_uint64),
@@ -143,6 +155,7 @@ class TopStats(C.Structure):
 GROUP_BY = {"start": 0, "end": 1}  # GG_GROUP_START / GG_GROUP_END
 TOP_BY = {"total": 0, "walks": 1}  # GG_TOP_BY_TOTAL / GG_TOP_BY_WALKS
 EDGE_MODES = {"inner": 0, "semi": 1, "anti": 2}  # GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
+WEIGHTS_BY = {"rowid": 0, "entry": 1}  # GG_WEIGHTS_BY_ROWID / GG_WEIGHTS_BY_ENTRY
 VALUE_MODES = {"in": 0, "not_in": 1}  # GG_VALUE_IN / GG_VALUE_NOT_IN
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 
@@ -281,6 +294,13 @@ def load_library(path: str | None = None):
     lib.gg_khop_pair_counts_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_khop_pair_counts_fetch.argtypes = [P, C.c_int, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
     lib.gg_debug_pair_counts.argtypes = [P, C.c_uint32, C.c_int]
+    lib.gg_edge_weights_create.argtypes = [P, P, i64p, u64, C.c_int, C.POINTER(P)]
+    lib.gg_edge_weights_destroy.argtypes = [P]
+    lib.gg_edge_weights_destroy.restype = None
+    lib.gg_cheapest64.argtypes = [P, P, P, i64p, C.c_int, C.c_int64, i64p, u64, C.POINTER(CheapestStats), C.POINTER(P)]
+    lib.gg_cheapest64_rows.argtypes = [P, C.POINTER(u64)]
+    lib.gg_cheapest64_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    lib.gg_debug_cheapest.argtypes = [P, C.c_uint32, C.c_int]
     lib.gg_components.argtypes = [P, P, C.POINTER(CcStats), C.POINTER(P)]
     lib.gg_components_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_components_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -494,6 +514,64 @@ class KhopPairCounts:
         if not out:
             return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.uint64)
         return tuple(np.concatenate([part[c] for part in out]) for c in range(3))
+
+    def close(self):
+        for handle, _ in self.parts:
+            self.gg.lib.gg_result_destroy(handle)
+        self.parts = []
+
+
+class EdgeWeights:
+    """A device-resident weight column of one CSR (gg_edge_weights); close() before the CSR."""
+
+    def __init__(self, gg: "GG", handle):
+        self.gg, self.handle = gg, handle
+
+    def close(self):
+        if self.handle:
+            self.gg.lib.gg_edge_weights_destroy(self.handle)
+            self.handle = None
+
+
+class CheapestPaths:
+    """Cheapest path costs (gg_cheapest64), left in HBM: one row (source index, vertex id, cost, hops) per reached pair,
+    ascending by (source index, dense index of the vertex).  A source list longer than 64 is several batches: `parts` holds
+    (result handle, first source index) per batch.  stats: {"rounds", "reached_pairs", "cells_lowered", "entries_pulled",
+    "rows_gathered"} summed over the batches; no parts: the call asked for the stats only."""
+
+    def __init__(self, gg: "GG", parts, stats):
+        self.gg, self.parts, self.stats = gg, parts, stats
+
+    def rows(self) -> int:
+        total = 0
+        for handle, _ in self.parts:
+            n = C.c_uint64()
+            self.gg._chk(self.gg.lib.gg_cheapest64_rows(handle, C.byref(n)))
+            total += int(n.value)
+        return total
+
+    def fetch(self):
+        """(src_index int64, vertex_id int64, cost int64, hops int32), the batches one after the other"""
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        out = []
+        for handle, base in self.parts:
+            cnt = C.c_uint64()
+            self.gg._chk(self.gg.lib.gg_cheapest64_rows(handle, C.byref(cnt)))
+            n = int(cnt.value)
+            idx, ids, cost, hops = (np.empty(n, np.int64), np.empty(n, np.int64), np.empty(n, np.int64),
+                                    np.empty(n, np.int32))
+            got, o = C.c_uint32(), 0
+            while o < n:
+                self.gg._chk(self.gg.lib.gg_cheapest64_fetch(
+                    handle, o, min(n - o, 1 << 20), idx[o:].ctypes.data_as(i64p), ids[o:].ctypes.data_as(i64p),
+                    cost[o:].ctypes.data_as(i64p), hops[o:].ctypes.data_as(i32p), C.byref(got)))
+                if not got.value:
+                    raise GGError(-6, f"gg_cheapest64_fetch: no row at offset {o} of {n}")
+                o += got.value
+            out.append((idx + base, ids, cost, hops))
+        if not out:
+            return np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.int64), np.empty(0, np.int32)
+        return tuple(np.concatenate([part[c] for part in out]) for c in range(4))
 
     def close(self):
         for handle, _ in self.parts:
@@ -1462,6 +1540,66 @@ class GG:
         """gg_khop_pair_counts gives in-rows of more than long_row_entries entries to a whole workgroup each (0: the
         default) and with gather_mode 1 reads every entry's state row whatever its mask."""
         self._chk(self.lib.gg_debug_pair_counts(self.ctx, int(long_row_entries), int(gather_mode)))
+
+    # ---- cheapest paths over weighted edge rows
+    def edge_weights(self, csr: Csr, weights, by: str = "rowid") -> "EdgeWeights":
+        """gg_edge_weights_create: one int64 weight >= 0 per edge row, by="rowid": indexed by the edge row's rowid (without
+        explicit rowids: in the order of append_edges), by="entry": one per kept entry in the order of csr.export()."""
+        w = np.ascontiguousarray(weights, dtype=np.int64).reshape(-1)
+        keep = w if w.size else np.zeros(1, np.int64)
+        h = C.c_void_p()
+        self._chk(self.lib.gg_edge_weights_create(self.ctx, csr.handle, keep.ctypes.data_as(C.POINTER(C.c_int64)), w.size,
+                                                  WEIGHTS_BY[by], C.byref(h)))
+        return EdgeWeights(self, h)
+
+    def _cheapest(self, csr: Csr, weights: "EdgeWeights", a, max_hops: int, targets, fetch: bool) -> "CheapestPaths":
+        tp, nt = None, 0
+        if targets is not None:
+            t = np.ascontiguousarray(targets, dtype=np.int64).reshape(-1)
+            keep = t if t.size else np.zeros(1, np.int64)  # (an empty list is a list: the pointer must not be NULL)
+            tp, nt = keep.ctypes.data_as(C.POINTER(C.c_int64)), t.size
+        d = {"rounds": 0, "reached_pairs": 0, "cells_lowered": 0, "entries_pulled": 0, "rows_gathered": 0}
+        out = CheapestPaths(self, [], d)
+        try:
+            for base in range(0, a.size, GG_BFS_LANES):  # (an empty list: no batch, no rows)
+                part = np.ascontiguousarray(a[base:base + GG_BFS_LANES])
+                st, res = CheapestStats(), C.c_void_p()
+                self._chk(self.lib.gg_cheapest64(
+                    self.ctx, csr.handle, weights.handle, part.ctypes.data_as(C.POINTER(C.c_int64)), part.size,
+                    int(max_hops), tp, nt, C.byref(st), C.byref(res) if fetch else None))
+                if fetch:
+                    out.parts.append((res, base))
+                for k in d:
+                    d[k] += int(getattr(st, k))
+        except Exception:
+            out.close()
+            raise
+        return out
+
+    def cheapest64(self, csr: Csr, weights: "EdgeWeights", sources, max_hops: int = -1, targets=None,
+                   fetch: bool = True) -> "CheapestPaths":
+        """gg_cheapest64, one call: 1..64 sources, one row (index into `sources`, vertex id, cost, hops) per reached pair.
+        max_hops < 0: to the fixpoint.  targets: only these ids may have a row (None: every vertex; an empty list: no
+        rows).  fetch=False: the stats only, nothing is kept on the device."""
+        a = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        if not 1 <= a.size <= GG_BFS_LANES:
+            raise GGError(-1, f"cheapest64: {a.size} sources outside 1..{GG_BFS_LANES}")
+        return self._cheapest(csr, weights, a, max_hops, targets, fetch)
+
+    def cheapest_path_lengths(self, csr: Csr, weights: "EdgeWeights", sources=None, max_hops: int = -1, targets=None,
+                              fetch: bool = True) -> "CheapestPaths":
+        """gg_cheapest64 over any number of sources (None: every vertex in vertex-table order): batches of 64, one C call
+        each, the rows concatenated with the batch's offset added to the source index and the stats added."""
+        if sources is None:
+            a = np.ascontiguousarray(csr.export()[3], dtype=np.int64)
+        else:
+            a = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
+        return self._cheapest(csr, weights, a, max_hops, targets, fetch)
+
+    def debug_cheapest(self, long_row_entries: int = 0, gather_mode: int = 0):
+        """gg_cheapest64 gives in-rows of more than long_row_entries entries to a whole workgroup each (0: the default)
+        and with gather_mode 1 counts every entry as live whatever its mask."""
+        self._chk(self.lib.gg_debug_cheapest(self.ctx, int(long_row_entries), int(gather_mode)))
 
     # ---- weakly connected components
     def components(self, csr: Csr, fetch: bool = True) -> dict:

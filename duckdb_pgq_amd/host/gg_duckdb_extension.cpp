@@ -764,6 +764,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterValueRowsFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
+	GGRegisterCheapestFunctions(*con.context);
 	GGRegisterComponentFunctions(*con.context);
 	GGRegisterPlanRules(*con.context);
 	con.Commit();

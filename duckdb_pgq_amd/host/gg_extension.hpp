@@ -128,6 +128,9 @@ void GGRegisterAggregateFunctions(ClientContext &context);
 //! gg_pair_counts.cpp: registers gg_khop_pair_counts (inside the caller's transaction)
 void GGRegisterPairCountFunctions(ClientContext &context);
 
+//! gg_cheapest.cpp: registers gg_cheapest_path (inside the caller's transaction)
+void GGRegisterCheapestFunctions(ClientContext &context);
+
 //! gg_components.cpp: registers gg_components and gg_component_sizes (inside the caller's transaction)
 void GGRegisterComponentFunctions(ClientContext &context);
 

@@ -443,7 +443,7 @@ int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, int key_col,
  * set.  A row without a value behaves as SQL's NULL under a comparison: it passes no predicate in either mode and is never a
  * candidate of the top.  The message of an extended row is its last column and a vertex of the extension's CSR, so
  * m_creationdate per message is such a column; a person's property is one over the walk CSR.  Values keyed by edge rowid
- * (k_creationdate) are out of scope, and so is a device-resident value column shared between calls: each call uploads its
+ * (k_creationdate) are out of scope here (gg_edge_weights keys one by edge rowid, for gg_cheapest64 alone), and so is a device-resident value column shared between calls: each call uploads its
  * 8 V bytes (and V / 8 of valid), as gg_result_group_by does.
  * Predicate: GG_VALUE_IN keeps a row iff it has a value x and lo <= x <= hi (signed); GG_VALUE_NOT_IN iff it has a value x
  * and (x < lo or x > hi).  lo > hi: IN keeps nothing, NOT_IN every valued row.  `<` and `>=` are bounds +- 1 on the caller's
@@ -699,6 +699,75 @@ int gg_khop_pair_counts_rows(const gg_result *res, int hops, uint64_t *n_rows);
  * three may be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
 int gg_khop_pair_counts_fetch(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *src_index,
                               int64_t *vertex_id, uint64_t *walks, uint32_t *n_out);
+
+/* ---- cheapest paths over weighted edge rows, 64 sources a pass --------------------------------------- */
+/* The weighted half of the shortest-path family: cheapest_path_length / ANY SHORTEST ... COST, and the hop-bounded
+ * recursive CTE under min(cost).  Weights are int64 >= 0, one per kept edge row.  Lane i is src_ids[i] (1 <= n_src <=
+ * GG_BFS_LANES): each listed position is its own lane, so a duplicate id gives two lanes with equal rows, and a source that
+ * is no vertex has no rows.  For lane s and vertex x
+ *     cost_0(s, s) = 0, every other cell unreached;
+ *     cost_r(s, x) = min(cost_{r-1}(s, x), min over the entries u -> x of x's reverse row of cost_{r-1}(s, u) (+) w(entry))
+ * where (+) is addition saturating at INT64_MAX, so a reported cost of INT64_MAX means "at least".  Saturating add and min
+ * are monotone, associative and commutative: every route and every launch geometry gives the same bits.  The rounds are
+ * strict Jacobi rounds: a cell of round r is never computed from a cell already updated in round r.
+ * The answer is cost_R.  A round that lowers no cell is a fixpoint and ends the search; R is that round, or max_hops if
+ * max_hops >= 0 comes first (max_hops < 0: no bound; round V can lower nothing, non-negative weights).  So max_hops means
+ * exactly "the cheapest walk of at most max_hops edges" — the relation of a hop-bounded recursive CTE under min(cost) — and
+ * max_hops 0 reports the sources alone.  hops(s, x) = the round in which the final cost was first attained: the fewest edges
+ * of any cheapest walk within the bound (what a backward trace needs to terminate on zero-weight cycles).
+ * Parallel rows: the cheapest wins.  A self-loop never lowers anything.
+ * Targets: dst_ids NULL: every vertex may have a row; else only the vertices whose id is listed (ids that are no vertices
+ * are ignored, duplicates collapse, n_dst == 0 gives no rows — gg_khop_pair_counts' convention).  The filter applies to the
+ * rows reported, never to the recurrence.
+ * Rows: one (source index, vertex id, cost, hops) per lane and reached vertex that passes the filter, the source itself
+ * included (cost 0, hops 0); they ascend by (source index, dense index of the vertex), placed by count, scan, write: the
+ * same on every run, on every route and under every knob.
+ *
+ * gg_edge_weights: a device-resident weight column bound to one whole CSR, made once and used by any number of
+ * gg_cheapest64 calls.  GG_WEIGHTS_BY_ROWID: weights[r] belongs to the edge row whose reported rowid is r (the rowid the Sink
+ * passed, else the append position); needs a CSR built with rowids (GG_ERR_STATE otherwise, as gg_expand_khop_edges); a kept
+ * edge row whose rowid lies outside [0, n_weights) is GG_ERR_INVALID_ARG; weights of dropped edge rows are never read.
+ * GG_WEIGHTS_BY_ENTRY: n_weights == E (else GG_ERR_INVALID_ARG), in the order gg_csr_export shows; works without rowids.  A
+ * negative weight that is read is GG_ERR_INVALID_ARG (decided on the device by one reduction; the message names nothing but
+ * the fact).  The object holds E x 8 bytes, the weights in reverse-entry order, and makes the CSR keep its reverse rows by
+ * source and their forward positions (2 x 4 E bytes, shared with gg_bfs64_paths / gg_triangles_edges).  It must be destroyed
+ * before its CSR.  Other errors: GG_ERR_INVALID_ARG for NULL ctx / csr / out, weights NULL with n_weights != 0, a csr of
+ * another context, an unknown `by`; GG_ERR_STATE for a shard CSR. */
+#define GG_WEIGHTS_BY_ROWID 0
+#define GG_WEIGHTS_BY_ENTRY 1
+typedef struct gg_edge_weights gg_edge_weights; /* device-resident edge weights of one CSR; caller-owned */
+int gg_edge_weights_create(gg_ctx *ctx, const gg_csr *csr, const int64_t *weights, uint64_t n_weights, int by,
+                           gg_edge_weights **out);
+void gg_edge_weights_destroy(gg_edge_weights *weights);
+/* Cost: `rounds` passes over all E reverse entries whatever the source count, one host synchronisation per round; an entry
+ * none of whose 64 lanes was lowered in the round before costs its 4-byte index and an 8-byte mask, a live one its 8-byte
+ * weight and a 512-byte row.  State: about 1.8 KiB per vertex on the device.
+ * stats (nullable), all exact functions of the input: rounds = the pull rounds that ran (the last one of an unbounded search
+ * lowers nothing; 0 on a graph without kept edges); reached_pairs = the (lane, vertex) cells with a cost, the filter not
+ * applied; cells_lowered = the cell updates over all rounds, seeds not counted; entries_pulled = rounds x E; rows_gathered =
+ * of those, the entries whose source had a lane lowered in the round before (round 1: was seeded).
+ * out_result (NULL: stats only) answers gg_cheapest64_rows / gg_cheapest64_fetch only — every other reader refuses it with
+ * GG_ERR_STATE, and the two calls refuse every other result with GG_ERR_STATE.
+ * GG_ERR_INVALID_ARG: NULL ctx, csr, weights or src_ids, objects of another context, weights made for another CSR, n_src
+ * outside 1..GG_BFS_LANES, dst_ids NULL with n_dst != 0, stats and out_result both NULL; GG_ERR_STATE: a shard CSR;
+ * GG_ERR_TOO_LARGE: 2^32 rows or more (decided from a 64-bit count); GG_ERR_OOM: the state does not fit.  The context stays
+ * usable. */
+typedef struct gg_cheapest_stats {
+  uint64_t rounds;          /* pull rounds that ran */
+  uint64_t reached_pairs;   /* (lane, vertex) cells with a cost, sources included, before the target filter */
+  uint64_t cells_lowered;   /* cell updates over all rounds */
+  uint64_t entries_pulled;  /* reverse entries looked at over all rounds: rounds x E */
+  uint64_t rows_gathered;   /* of those, the ones whose 512-byte row of lowered values was read (mask != 0) */
+} gg_cheapest_stats;
+int gg_cheapest64(gg_ctx *ctx, const gg_csr *csr, const gg_edge_weights *weights, const int64_t *src_ids,
+                  int n_src /* 1..GG_BFS_LANES */, int64_t max_hops /* < 0: to the fixpoint */,
+                  const int64_t *dst_ids /* nullable */, uint64_t n_dst, gg_cheapest_stats *stats /* nullable */,
+                  gg_result **out_result /* NULL: stats only */);
+int gg_cheapest64_rows(const gg_result *res, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows), in row order, into host arrays of >= max_rows entries (any of the four may be NULL).
+ * *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
+int gg_cheapest64_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *src_index, int64_t *vertex_id,
+                        int64_t *cost, int32_t *hops, uint32_t *n_out);
 
 /* ---- weakly connected components: a label and a size per vertex ------------------------------------ */
 /* "Which vertices hang together, and how big is each piece."  In the reference that is a UNION recursive CTE under an
@@ -1065,6 +1134,12 @@ int gg_debug_aggregate_top_listed(gg_ctx *ctx, uint64_t *list_entries);
  * and entries_pulled must not depend on either; rows_gathered equals entries_pulled with gather_mode 1.  A gather_mode
  * outside 0..1 is GG_ERR_INVALID_ARG. */
 int gg_debug_pair_counts(gg_ctx *ctx, uint32_t long_row_entries /* 0: default */, int gather_mode /* 0 auto, 1 never skip */);
+/* Testing knob: what gg_debug_pair_counts is to gg_khop_pair_counts, for gg_cheapest64 (the default threshold is 512 as
+ * well).  With gather_mode 1 every entry counts as live and is walked whatever its mask; a lane still takes a value only
+ * where the entry's own mask bit is set, which is what keeps the rounds exact.  Rows and every stats field but rows_gathered
+ * must not depend on either; rows_gathered equals entries_pulled with gather_mode 1.  A gather_mode outside 0..1 is
+ * GG_ERR_INVALID_ARG. */
+int gg_debug_cheapest(gg_ctx *ctx, uint32_t long_row_entries /* 0: default */, int gather_mode /* 0 auto, 1 never skip */);
 /* Testing knob: gg_components looks at the flatten's changed word once per `jumps_per_check` pointer-doubling launches
  * (0: the default, 4).  init_mode 0 is the default start of the forest and 1 starts every vertex as its own root; the two
  * are the same start since the other candidate (under the first smaller out-neighbour) measured slower and was removed.
