@@ -812,6 +812,7 @@ __global__ __launch_bounds__(256) void k_copy_u32(const uint32_t *__restrict__ i
 
 static int ensure_push_in(gg_ctx *ctx, gg_csr *csr) {
   if (csr->pin_off) return GG_OK;
+  GG_TRY(ensure_reverse(ctx, csr));  // (the rows and the row index: k_pin_fill reads both)
   const uint64_t V = csr->V, n = csr->E_rev;
   hipStream_t s = ctx->stream;
   uint32_t *cnt = nullptr, *pin_off = nullptr, *pin_nbr = nullptr;
@@ -824,7 +825,7 @@ static int ensure_push_in(gg_ctx *ctx, gg_csr *csr) {
   GG_TRY(scan_exclusive_u32(ctx, cnt, pin_off, V + 1, nullptr));
   GG_LAUNCH(ctx, "pin_copy", k_copy_u32, dim3((unsigned)((V + 1 + 255) / 256)), dim3(256), 0, pin_off, cnt, V + 1);
   if (n)
-    GG_LAUNCH(ctx, "pin_fill", k_pin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr_rows, csr->rrow, n, cnt,
+    GG_LAUNCH(ctx, "pin_fill", k_pin_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->rnbr_rows, csr->rrow_index, n, cnt,
               pin_nbr);
   GG_TRY(sync_checked(ctx));
   ctx->dev_free(cnt);
@@ -934,7 +935,8 @@ extern "C" int gg_bfs_sharded_begin(gg_ctx *ctx, const gg_csr *csr_c, const int6
   GG_TRY(ctx->dev_alloc((void **)&run->acc, V * sizeof(uint64_t)));
   GG_TRY(ctx->dev_alloc((void **)&run->lv, 2 * sizeof(BfsLevel)));
   if (csr->V && csr->n_parts > 1) {  // (a whole CSR pushes along its forward rows)
-    if (!csr->rrow) {
+    GG_TRY(ensure_reverse_index(ctx, csr));
+    if (!csr->rrow_index) {
       set_error("gg_bfs_sharded: the shard has no reverse COO column");
       return GG_ERR_INVALID_ARG;
     }

@@ -234,9 +234,14 @@ extern "C" int gg_components(gg_ctx *ctx, const gg_csr *csr, gg_cc_stats *stats,
     if (E) {
       // whichever COO pair the build left: (row, nbr) of the multi-pass build, (rrow, rnbr) of the bucketed one
       const uint32_t *erow = csr->row, *enbr = csr->nbr;
-      // (a derived build: roff == off, so rrow is the row of every FORWARD entry as well, and no reverse rows are needed)
-      if (!erow && csr->rrow && csr->rev_derived) erow = csr->rrow;
-      else if (!erow && csr->rrow && csr->rnbr_rows) erow = csr->rrow, enbr = csr->rnbr_rows;
+      // (a derived build: roff == off, so the row index is the row of every FORWARD entry as well, and no reverse rows are
+      // needed; it is expanded from the offsets here if nobody asked for it before)
+      if (!erow && csr->rev_derived) {
+        GG_TRY(ensure_reverse_index(ctx, const_cast<gg_csr *>(csr)));
+        erow = csr->rrow_index;
+      } else if (!erow && csr->rrow_index && csr->rnbr_rows) {
+        erow = csr->rrow_index, enbr = csr->rnbr_rows;
+      }
       GG_LAUNCH(ctx, "cc_hook", k_cc_hook, stride_grid(ctx, E), dim3(256), 0, erow, enbr, (const uint32_t *)csr->off, V, E,
                 buf[0], words + CC_HOOKS);
     }

@@ -698,7 +698,7 @@ extern "C" void gg_csr_destroy(gg_csr *csr) {
     ctx->dev_free(csr->ht);
     ctx->dev_free(csr->roff);
     ctx->dev_free(csr->rnbr_rows);  // (null on a derived build that never rotated: dev_free takes a null)
-    ctx->dev_free(csr->rrow);
+    ctx->dev_free(csr->rrow_index);  // (null on a derived build whose index nobody asked for)
     ctx->dev_free(csr->rot);
     ctx->dev_free(csr->rnbr_by_src);
     ctx->dev_free(csr->rpos_by_src);
@@ -881,7 +881,7 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   ctx->dev_free(st);
   ctx->dev_free(kept_dev);
   ctx->dev_free(kept_rev_dev);
-  if (!fast) csr->rrow = rkey_sorted;  // null unless this is a shard build (ensure_reverse fills it lazily otherwise)
+  if (!fast) csr->rrow_index = rkey_sorted;  // null unless this is a shard build (ensure_reverse fills it lazily otherwise)
   if (hs.scan_error) {
     GG_HIP(hipMemsetAsync(ctx->dev_err, 0, sizeof(unsigned long long), s));
     set_error("CSR build: a chained prefix scan gave up waiting for a predecessor tile");
@@ -898,18 +898,20 @@ static int csr_build_impl(gg_ctx *ctx, int part, int n_parts, gg_csr **out) {
   csr->rev_derived = fast && hs.rev_derived != 0;
   csr->owned_vertices = shard ? hs.owned : V;
   csr->dropped = shard ? 0 : E - hs.kept;  // a shard cannot tell dropped edges from other shards' edges
-  // A build that may derive allocates both the plain form's reverse rows and the derived form's rotation counts,
-  // since its kernels are queued before the status says which form runs.  The unused one goes back to the pool here,
-  // behind the build's one wait (whoever takes the block next is queued behind the kernels that hold its address).
+  // A build that may derive allocates both the plain form's reverse rows and row index and the derived form's rotation
+  // counts, since its kernels are queued before the status says which form runs.  The unused ones go back to the pool
+  // here, behind the build's one wait (whoever takes a block next is queued behind the kernels that hold its address).
   if (csr->rev_derived) {
     ctx->dev_free(csr->rnbr_rows);
     csr->rnbr_rows = nullptr;  // ensure_reverse rotates the forward rows into a new block on first use
+    ctx->dev_free(csr->rrow_index);
+    csr->rrow_index = nullptr;  // ensure_reverse_index expands the offsets into a new block on first use
   } else {
     ctx->dev_free(csr->rot);
     csr->rot = nullptr;
   }
   for (void *p : {(void *)csr->off, (void *)csr->nbr, (void *)csr->row, (void *)csr->epos, (void *)csr->eid,
-                  (void *)csr->vid, (void *)csr->ht, (void *)csr->roff, (void *)csr->rnbr_rows, (void *)csr->rrow,
+                  (void *)csr->vid, (void *)csr->ht, (void *)csr->roff, (void *)csr->rnbr_rows, (void *)csr->rrow_index,
                   (void *)csr->rot})
     ctx->keep(p);  // (a null is ignored)
   *out = owner.release();
@@ -949,13 +951,13 @@ int ensure_ht(gg_ctx *ctx, gg_csr *csr) {
 // Reverse CSR from the forward COO view (row, nbr), which is sorted by (source, rowid): a stable sort
 // by destination leaves every in-neighbour list in ascending (source, rowid) order.
 //
-// A derived build (gg_csr_fast.hip "Derived reverse") left roff = off, rrow and rot = |A| per vertex, and no reverse
-// rows: row x of the reverse CSR is the forward row of x rotated by |A| (B ++ A), written here by one thread per entry
+// A derived build (gg_csr_fast.hip "Derived reverse") left roff = off and rot = |A| per vertex, no row index (rrow:
+// k_row_index below expands the offsets into it on first use) and no reverse rows: row x of the reverse CSR is the forward row of x rotated by |A| (B ++ A), written here by one thread per entry
 // on the context's stream, without a host synchronisation.  An entry is a chain of three dependent loads (rrow; off and
 // rot; nbr), so a thread takes ROT_EPT entries a block width apart and issues each stage for all of them together.
 constexpr int ROT_EPT = 4;
 __global__ __launch_bounds__(256) void k_rotate_rows(const uint32_t *__restrict__ off, const uint32_t *__restrict__ nbr,
-                                                     const uint32_t *__restrict__ rrow,
+                                                     const uint32_t *__restrict__ rrow /* the row index */,
                                                      const uint32_t *__restrict__ rot, uint64_t E,
                                                      uint32_t *__restrict__ rnbr) {
   const uint64_t p0 = (uint64_t)blockIdx.x * (256 * ROT_EPT) + threadIdx.x;
@@ -980,25 +982,76 @@ __global__ __launch_bounds__(256) void k_rotate_rows(const uint32_t *__restrict_
     if (p0 + k * 256 < E) rnbr[p0 + k * 256] = v[k];
 }
 
+// The row index of a derived build, which writes none (roff == off): rrow[p] = the x with off[x] <= p < off[x + 1].  A
+// workgroup takes RIX_EPT * 256 consecutive entries, two of its waves find the rows of the first and the last of them
+// (wave_find_row), and every entry then searches the few rows between the two.  Every probe stays inside [0, V).
+constexpr int RIX_EPT = 4;
+__global__ __launch_bounds__(256) void k_row_index(const uint32_t *__restrict__ off, uint32_t V, uint64_t E,
+                                                   uint32_t *__restrict__ rrow) {
+  __shared__ uint32_t s_x[2];
+  const uint64_t p0 = (uint64_t)blockIdx.x * (256 * RIX_EPT);  // (< E: the grid covers E entries)
+  const uint64_t pl = p0 + 256 * RIX_EPT - 1 < E ? p0 + 256 * RIX_EPT - 1 : E - 1;
+  const uint32_t wave = threadIdx.x >> 6;
+  if (wave < 2) {  // (uniform over a wave)
+    const uint32_t x = wave_find_row(off, V, (uint32_t)(wave ? pl : p0));
+    if ((threadIdx.x & 63) == 0) s_x[wave] = x;
+  }
+  __syncthreads();
+  const uint32_t xa = s_x[0], xb = s_x[1];
+#pragma unroll
+  for (int k = 0; k < RIX_EPT; k++) {
+    const uint64_t p = p0 + k * 256 + threadIdx.x;
+    if (p < E) {
+      uint32_t lo = xa, hi = xb;  // the last x in [xa, xb] with off[x] <= p
+      while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (off[mid] <= (uint32_t)p)
+          lo = mid;
+        else
+          hi = mid - 1;
+      }
+      rrow[p] = lo;
+    }
+  }
+}
+
+int ensure_reverse_offsets(gg_ctx *ctx, gg_csr *csr) {
+  if (csr->roff) return GG_OK;
+  return ensure_reverse(ctx, csr);
+}
+
 int ensure_reverse_index(gg_ctx *ctx, gg_csr *csr) {
-  if (csr->roff && csr->rrow) return GG_OK;
+  if (csr->roff && csr->rrow_index) return GG_OK;
+  if (csr->roff && csr->rev_derived) {
+    const uint64_t E = csr->E;
+    GG_HIP(hipSetDevice(ctx->device));
+    uint32_t *index = nullptr;
+    GG_TRY(ctx->dev_alloc((void **)&index, (E ? E : 1) * sizeof(uint32_t)));
+    if (E)
+      GG_LAUNCH(ctx, "row_index", k_row_index, dim3((unsigned)((E + 256 * RIX_EPT - 1) / (256 * RIX_EPT))), dim3(256), 0,
+                (const uint32_t *)csr->off, (uint32_t)csr->V, E, index);
+    ctx->keep(index);
+    csr->rrow_index = index;
+    return GG_OK;
+  }
   return ensure_reverse(ctx, csr);
 }
 
 int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
-  if (csr->roff && csr->rrow && csr->rnbr_rows) return GG_OK;
-  if (csr->roff && csr->rrow && csr->rev_derived) {
+  if (csr->roff && csr->rrow_index && csr->rnbr_rows) return GG_OK;
+  if (csr->roff && csr->rev_derived) {
     if (!csr->rot) {
       set_error("internal: a derived reverse CSR without its rotation counts");
       return GG_ERR_STATE;
     }
+    GG_TRY(ensure_reverse_index(ctx, csr));  // (k_rotate_rows reads it)
     const uint64_t E = csr->E;
     GG_HIP(hipSetDevice(ctx->device));
     uint32_t *rows = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&rows, (E ? E : 1) * sizeof(uint32_t)));
     if (E)
       GG_LAUNCH(ctx, "rotate_rows", k_rotate_rows, dim3((unsigned)((E + 256 * ROT_EPT - 1) / (256 * ROT_EPT))), dim3(256), 0,
-                (const uint32_t *)csr->off, (const uint32_t *)csr->nbr, (const uint32_t *)csr->rrow,
+                (const uint32_t *)csr->off, (const uint32_t *)csr->nbr, (const uint32_t *)csr->rrow_index,
                 (const uint32_t *)csr->rot, E, rows);
     ctx->keep(rows);
     csr->rnbr_rows = rows;
@@ -1011,7 +1064,7 @@ int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
       if (armed) {
         c->ctx->dev_free(c->roff);
         c->ctx->dev_free(c->rnbr_rows);
-        c->roff = c->rnbr_rows = c->rrow = nullptr;
+        c->roff = c->rnbr_rows = c->rrow_index = nullptr;
       }
     }
   } reset{csr};
@@ -1028,10 +1081,10 @@ int ensure_reverse(gg_ctx *ctx, gg_csr *csr) {
   GG_LAUNCH(ctx, "row_offsets", k_row_offsets, dim3((unsigned)(((E ? E : 1) + 1023) / 1024)), dim3(256), 0, rkey, E,
             (const unsigned long long *)nullptr, V, csr->roff, (const unsigned long long *)ctx->dev_err);
   GG_TRY(sync_checked(ctx));
-  csr->rrow = rkey;
+  csr->rrow_index = rkey;
   ctx->keep(csr->roff);
   ctx->keep(csr->rnbr_rows);
-  ctx->keep(csr->rrow);
+  ctx->keep(csr->rrow_index);
   reset.armed = false;
   return GG_OK;
 }
@@ -1774,7 +1827,9 @@ extern "C" int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, i
   if (derived) *derived = csr->rev_derived ? 1 : 0;
   if (!roff && !rnbr && !rrow) return GG_OK;
   GG_HIP(hipSetDevice(ctx->device));
-  GG_TRY(ensure_reverse(ctx, csr));  // (the multi-pass build of a whole graph leaves the reverse CSR to its first use)
+  // (the multi-pass build of a whole graph leaves the reverse CSR to its first use, a derived one its index and rows:
+  // no more is built than the arrays asked for need)
+  GG_TRY(rnbr ? ensure_reverse(ctx, csr) : rrow ? ensure_reverse_index(ctx, csr) : ensure_reverse_offsets(ctx, csr));
   GG_TRY(sync_checked(ctx));
   auto fetch = [&](int64_t *out, const uint32_t *dev, uint64_t n) -> int {
     if (!out || !n) return GG_OK;
@@ -1786,12 +1841,18 @@ extern "C" int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, i
   GG_TRY(fetch(roff, csr->roff, csr->V + 1));
   const uint64_t n_rev = csr->n_parts > 1 ? csr->E_rev : csr->E;
   GG_TRY(fetch(rnbr, csr->rnbr_rows, n_rev));
-  GG_TRY(fetch(rrow, csr->rrow, n_rev));
+  GG_TRY(fetch(rrow, csr->rrow_index, n_rev));
   return GG_OK;
 }
 
 extern "C" int gg_debug_csr_reverse_ready(const gg_csr *csr, int *ready) {
   if (!csr || !ready) return GG_ERR_INVALID_ARG;
-  *ready = csr->roff && csr->rrow && csr->rnbr_rows ? 1 : 0;  // (asks only: nothing is built or launched)
+  *ready = csr->roff && csr->rrow_index && csr->rnbr_rows ? 1 : 0;  // (asks only: nothing is built or launched)
+  return GG_OK;
+}
+
+extern "C" int gg_debug_csr_reverse_index_ready(const gg_csr *csr, int *ready) {
+  if (!csr || !ready) return GG_ERR_INVALID_ARG;
+  *ready = csr->roff && csr->rrow_index ? 1 : 0;  // (asks only: nothing is built or launched)
   return GG_OK;
 }

@@ -97,8 +97,8 @@ struct FastGeom {
 
 // Derived reverse.  Where EVERY row i + h is row i with source and destination swapped (E = 2 h), the reverse CSR holds
 // nothing new: with A / B the entries of x's forward row that come from first- / second-half rows (the row is A ++ B
-// in rowid order), roff == off, rrow is the row-index expansion of off, and x's reverse row in rowid order is B ++ A —
-// the forward row rotated by |A|.  The build then partitions and chunk-sorts the E forward entries only, first-half
+// in rowid order), roff == off, rrow is the row-index expansion of off (not written by the build: gg_csr.hip expands it
+// on first use), and x's reverse row in rowid order is B ++ A — the forward row rotated by |A|.  The build then partitions and chunk-sorts the E forward entries only, first-half
 // tiles into part_f and second-half tiles into part_r (the second set of nb columns, chunks and offset rows means
 // "forward entries of second-half tiles" instead of "reverse entries"), and k_vrows writes both CSRs from them.
 // The decision is made on the device: the sampled rows chose the paired densification, which sees every pair and
@@ -1755,16 +1755,18 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
 // second-half rows, in part_r); walking the chunks in that order, the running row positions put A then B into every
 // forward row exactly as above.  The offset rows of the two halves give |A| and |B| per vertex on the way, and the
 // reverse row is the forward row rotated by |A|: an A entry at forward position p lies at p + |B| in the reverse row, a
-// B entry at p - |A|.  roff = off; rrow[p] is the vertex whose row holds p, in either CSR.  The rotated rows are NOT
-// written here: the build's own consumer, the counting 2-hop expansion, only sums over a row and reads the forward one
-// in its place, so this step leaves rot[v] = |A| and ensure_reverse (gg_csr.hip) rotates on first use.  The staged path
-// writes nbr and rrow as whole lines; large groups store each entry straight to both.
+// B entry at p - |A|.  roff = off, and the row of entry p is the vertex whose row holds p, in either CSR.  Neither the
+// rotated rows nor that row index are written here: the build's own consumer, the counting 2-hop expansion, only sums
+// over a row, reads the forward one in its place and finds the row of an entry from the offsets (gg_khop.hip:
+// mid_stage_offsets), so this step leaves rot[v] = |A|; ensure_reverse_index expands the offsets into the index and
+// ensure_reverse rotates the rows, each on first use (gg_csr.hip).  The staged path writes nbr as whole lines; large
+// groups store each entry straight to it.
 __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                              const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
                                              const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
                                              FastGeom g, uint64_t V, uint32_t *__restrict__ off,
                                              uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
-                                             uint32_t *__restrict__ rot, uint32_t *__restrict__ rrow) {
+                                             uint32_t *__restrict__ rot) {
   __shared__ uint32_t s_delta[FB_VCG * FB_VG];
   __shared__ uint32_t s_run[2 * FB_VCG];  // [c]: first entry of the run inside chunk c, [FB_VCG + c]: its length
   __shared__ uint32_t s_stage[GG_FB_VCAP];
@@ -1779,7 +1781,6 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
   const uint32_t nch = nA + nB;  // chunk c of the group: chunk c of A, or chunk c - nA of B
   const uint32_t gs = gstart[(uint64_t)j * 64 + gi];
   const uint32_t pay_mask = (1u << g.key_bits) - 1u;
-  const uint32_t keep_mask = (vg << g.key_bits) - 1u;  // payload and the vertex inside the group
   // the vertices' |A| and |B| (sums over the chunks' offset rows of either half), the row offsets of both CSRs
   uint32_t degA = 0, degB = 0;
 #pragma unroll 1
@@ -1897,13 +1898,10 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
         if ((have >> q) & 1u) {
           const uint32_t d = (kw[q] >> g.key_bits) & (vg - 1u);
           const uint32_t pos = s_delta[(kx[q] >> 24) * vg + d] + (kx[q] & 0xFFFFFFu);
-          if (staged) {
-            s_stage[pos] = kw[q] & keep_mask;
-          } else {
-            const uint32_t pay = kw[q] & pay_mask;
-            nbr[pos] = pay;
-            rrow[pos] = (uint32_t)v0 + d;
-          }
+          if (staged)
+            s_stage[pos] = kw[q] & pay_mask;
+          else
+            nbr[pos] = kw[q] & pay_mask;
         }
       }
     }
@@ -1915,11 +1913,7 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
     const uint32_t hd = GG_FB_ALIGNW ? (t0 & 31u) : 0u;
     for (uint32_t x0 = 0; x0 < n + hd; x0 += 64) {
       const uint32_t x = x0 + lane - hd;  // (wraps below zero for the lanes before the first entry)
-      if (x < n) {
-        const uint32_t sw = s_stage[x];
-        nbr[t0 + x] = sw & pay_mask;
-        rrow[t0 + x] = (uint32_t)v0 + (sw >> g.key_bits);
-      }
+      if (x < n) nbr[t0 + x] = s_stage[x];
     }
   }
 }
@@ -1936,7 +1930,7 @@ __global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f
                                               uint32_t *__restrict__ rrow) {
   if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
   if (MIRROR)
-    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows, rrow);
+    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows);  // (writes no row index)
   else
     vrows_plain(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows, rrow);
 }
@@ -2093,12 +2087,12 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&part_r, E * words * sizeof(uint32_t)));
   if (rowid) GG_TRY(ctx->dev_alloc((void **)&epos_f, E * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&csr->roff, (V + 1) * sizeof(uint32_t)));
-  // (the plain form's reverse rows and, where the device may derive, the derived form's rotation counts: both launches
-  // are queued before the host knows which one works, and csr_build_impl returns the other block to the pool behind the
-  // status wait it has anyway)
+  // (the plain form's reverse rows and row index and, where the device may derive, the derived form's rotation counts:
+  // both launches are queued before the host knows which one works, and csr_build_impl returns the other form's blocks
+  // to the pool behind the status wait it has anyway; the derived form writes neither rows nor index)
   GG_TRY(ctx->dev_alloc((void **)&csr->rnbr_rows, E * sizeof(uint32_t)));
   if (g.derive) GG_TRY(ctx->dev_alloc((void **)&csr->rot, V * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&csr->rrow, E * sizeof(uint32_t)));
+  GG_TRY(ctx->dev_alloc((void **)&csr->rrow_index, E * sizeof(uint32_t)));
   const size_t lds_a = ((size_t)FB_TILE * (words + (rowid ? 1 : 0)) + (size_t)(FB_WAVES + 2) * nb + FB_WAVES + 2) *
                            sizeof(uint32_t) +
                        (size_t)FB_TILE * sizeof(uint16_t) + 16 + (0 ? (size_t)FB_WAVES * nb * 8 : 0);
@@ -2140,7 +2134,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_LAUNCH(ctx, "leaf_rows", (k_leaf_rows<P, R>), dim3(grid_l), dim3(LEAF_WAVES * 64), lds_l,                          \
             (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)epos_f, (const uint32_t *)bstart,     \
             (const uint32_t *)cstart, (const uint32_t *)offs, (const uint32_t *)substart, g, V, csr->off, csr->nbr,     \
-            csr->epos, csr->roff, csr->rnbr_rows, csr->rrow)
+            csr->epos, csr->roff, csr->rnbr_rows, csr->rrow_index)
 #define GG_FB_LAUNCH_B2(P, R)      \
   do {                             \
     if (g.sub > 6) {               \
@@ -2167,11 +2161,11 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
       GG_LAUNCH(ctx, "leaf_rows", k_vrows<true>, dim3((unsigned)((uint64_t)nb * (nk / vg))), dim3(64), 0,
                 (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart, (const uint32_t *)cstart,
                 (const uint16_t *)offs16, (const uint32_t *)gstart, g, V, (const BuildStatus *)st, csr->off, csr->nbr,
-                csr->roff, csr->rot, csr->rrow);
+                csr->roff, csr->rot, csr->rrow_index);
     GG_LAUNCH(ctx, g.derive ? "leaf_rows_plain" : "leaf_rows", k_vrows<false>, dim3((unsigned)(2ull * nb * (nk / vg))),
               dim3(64), 0, (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart,
               (const uint32_t *)cstart, (const uint16_t *)offs16, (const uint32_t *)gstart, g, V,
-              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr_rows, csr->rrow);
+              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr_rows, csr->rrow_index);
   } else if (g.pack && rowid) {
     GG_FB_LAUNCH_B2(true, true);
   } else if (g.pack && g.rank_atomic && GG_FB_SUBPIPE) {
@@ -2195,7 +2189,7 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_LAUNCH(ctx, "leaf_rows", (k_leaf_rows<true, false>), dim3(grid_l), dim3(LEAF_WAVES * 64), lds_l,
               (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)epos_f, (const uint32_t *)bstart,
               (const uint32_t *)cstart, (const uint32_t *)offs, (const uint32_t *)substart, g, V, csr->off, csr->nbr,
-              csr->epos, csr->roff, csr->rnbr_rows, csr->rrow);
+              csr->epos, csr->roff, csr->rnbr_rows, csr->rrow_index);
   } else if (g.pack) {
     GG_FB_LAUNCH_B2(true, false);
   } else if (rowid) {

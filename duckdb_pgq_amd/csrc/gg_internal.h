@@ -294,8 +294,11 @@ struct gg_csr {
   // E   source u of the reverse entry.  NULL on a derived build (rev_derived) until ensure_reverse() rotates the
   // forward rows into it: every reader goes through ensure_reverse() first; ensure_reverse_index() does not write it
   uint32_t *rnbr_rows = nullptr;
-  uint32_t *rrow = nullptr;    // E   destination x of the reverse entry (COO view, sorted by x)
-  bool rev_derived = false;    // the bucketed build derived roff / rrow from the forward rows (fully mirrored table)
+  // E   destination x of the reverse entry (COO view, sorted by x): the row-index expansion of roff.  NULL on a derived
+  // build until ensure_reverse_index() expands the offsets into it: every reader goes through that (or ensure_reverse())
+  // first; ensure_reverse_offsets() does not write it, and the counting 2-hop expansion never reads it
+  uint32_t *rrow_index = nullptr;
+  bool rev_derived = false;    // the bucketed build derived roff from the forward rows (fully mirrored table): roff == off
   // V   derived builds: |A| of every vertex, the first-half entries its forward row starts with.  The reverse row is
   // the forward row rotated by it (B ++ A), which is what ensure_reverse() writes on first use
   uint32_t *rot = nullptr;
@@ -527,11 +530,16 @@ int sort_triples_by_key(gg_ctx *ctx, const uint32_t *key, const uint32_t *a, con
 int grow_column(gg_ctx *ctx, Column &c, size_t live_rows, size_t need_rows);
 // GG_STAGING_TRACE=1: print and reset the edge staging's waiting-time counters (gg_runtime.hip)
 void staging_trace_print();
-// build csr->roff / csr->rrow / csr->rnbr_rows if absent (gg_csr.hip).  A derived build left the first two and
-// csr->rot: the rows are then one rotation kernel on the context's stream, no host synchronisation
-int ensure_reverse(gg_ctx *ctx, gg_csr *csr);
-// csr->roff / csr->rrow only, for callers that never read the reverse rows themselves: a derived build has both
+// The reverse CSR at three levels (gg_csr.hip); each builds what is absent and includes the levels above it.
+// offsets: csr->roff only, for callers that read nothing else (the counting 2-hop expansion, the work estimate of
+// gg_khop_partition_mid).  A derived build has them: nothing is launched.
+int ensure_reverse_offsets(gg_ctx *ctx, gg_csr *csr);
+// index: csr->roff and csr->rrow_index, for callers that read the COO column but not the reverse rows.  On a derived
+// build without the index: one kernel on the context's stream that expands the offsets into it, no host synchronisation
 int ensure_reverse_index(gg_ctx *ctx, gg_csr *csr);
+// rows: csr->roff, csr->rrow_index and csr->rnbr_rows.  A derived build left csr->rot: the rows are then the index
+// kernel and one rotation kernel on the context's stream, no host synchronisation
+int ensure_reverse(gg_ctx *ctx, gg_csr *csr);
 // build csr->rnbr_by_src if absent: the reverse rows with their sources ascending, under csr->roff (gg_paths.hip)
 int ensure_reverse_by_source(gg_ctx *ctx, gg_csr *csr);
 // build csr->rpos_by_src if absent: the same sort carrying the forward CSR position (gg_paths.hip)
@@ -650,6 +658,23 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
   v += dpp_or_zero<0x142, 0xA>(v);  // row_bcast:15 into rows 1 and 3
   v += dpp_or_zero<0x143, 0xC>(v);  // row_bcast:31 into rows 2 and 3
   return v;
+}
+
+// The last x in [0, V) with offs[x] <= p, for ascending offsets with offs[0] <= p < offs[V]: the row of a CSR that holds
+// entry p, rows without entries skipped.  A 64-way search by one wave (every lane probes, the ballot counts the probes at
+// or below p): 19 bits of V take four rounds.  Call with the whole wave active; the result is the same in every lane.
+__device__ __forceinline__ uint32_t wave_find_row(const uint32_t *__restrict__ offs, uint32_t V, uint32_t p) {
+  const uint32_t lane = threadIdx.x & 63;
+  uint32_t lo = 0, n = V;  // the answer lies in [lo, lo + n)
+  while (n > 1) {
+    const uint32_t step = (n + 63) >> 6;
+    const uint64_t k = (uint64_t)(lane + 1) * step;  // (64 steps may pass 2^32 where V nearly fills 32 bits)
+    const bool le = k < n && offs[lo + (uint32_t)k] <= p;  // (ascending: the yeses are a prefix)
+    const uint32_t c = (uint32_t)__popcll(__ballot(le));
+    lo += c * step;
+    n = n - c * step < step ? n - c * step : step;
+  }
+  return lo;
 }
 
 // sums over the wave with the DPP scan: the total is the last lane's prefix.  Call with the whole wave active.

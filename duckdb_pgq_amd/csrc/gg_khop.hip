@@ -279,16 +279,24 @@ constexpr int MID_EPT = GG_MID_EPT;    // reverse-CSR entries per thread
 constexpr int MT = XT * MID_EPT;       // entries per tile (workgroup): 768 (512: 797 us, 1024: 813 us, 768: 757 us at SF100)
 constexpr int MID_SEG = MID_EPT * (XT / 64);  // (entry slot, wave) segments of a tile, in position order
 
-struct alignas(16) MidShared {  // LDS image of one tile
+struct alignas(16) MidShared {  // LDS image of one tile: what the fold reads
   uint32_t q[MT];          // low half of the hash state q_1 of each 1-hop row of the tile
   uint32_t pq[MT + 1];     // prefix sums (mod 2^32) of q: pq[i] = sum of q[0..i)
-  uint32_t x[MT];          // middle vertex of each row
   uint32_t run[MT + 1];    // tile position where each run of equal x starts (+ end sentinel)
   uint32_t rst[MT];        // per run: start of out-row x in nbr
   uint32_t rdout[MT];      // per run: out-degree of x
   uint32_t wcnt[MID_SEG];
   uint32_t wsum[MID_SEG];
   uint64_t red[12];
+};
+constexpr int MID_WORDS = MT / 64;  // one 64-bit word of run starts per (entry slot, wave) segment
+static_assert(MID_WORDS == MID_SEG, "a segment is one wave's 64 consecutive tile positions");
+
+struct MidOffsets {  // k_expand_mid2's staging from the offsets (mid_stage_offsets)
+  uint32_t run_x[MT];                   // per run: the middle vertex itself
+  unsigned long long mask[MID_WORDS];   // bit i: a run starts at tile position i
+  uint32_t ccnt[2][XT / 64];            // runs found by each wave in a window chunk (by chunk parity)
+  uint32_t more[2];                     // the window goes on behind this chunk
 };
 
 struct MidRows {  // a thread's MID_EPT rows of one tile, as loaded from the reverse CSR
@@ -300,52 +308,130 @@ struct MidPrep {  // the same rows after hashing and the out-row lookups
   uint32_t st[MID_EPT], dout[MID_EPT];
 };
 
-// stage 1: reverse-CSR entry p is the 1-hop row u -> x with x = rrow[p] (COO view), u = rnbr[p]:
-// two coalesced loads, no search.  Tile position of thread t's e-th entry: e*XT + t.
-__device__ __forceinline__ void mid_load_rows(const uint32_t *__restrict__ rrow, const uint32_t *__restrict__ rnbr,
-                                              uint64_t fbase, uint64_t M, uint64_t tile, MidRows &r) {
-#pragma unroll
-  for (int e = 0; e < MID_EPT; e++) {
-    const uint64_t i = tile * MT + (uint64_t)(e * XT) + threadIdx.x;
-    r.valid[e] = i < M;
-    r.x[e] = INVALID_U32;
-    r.u[e] = 0;
-    if (r.valid[e]) {
-      r.x[e] = rrow[fbase + i];
-      r.u[e] = rnbr[fbase + i];
-    }
-  }
-}
+// ---- k_expand_mid2's tile, staged from the offsets --------------------------------------------------------------
+// Reverse-CSR entry p is the 1-hop row u -> x with u = rnbr[p] and x the row of `roff` that holds p.  The tile covers
+// entries [p0, p1); every non-empty row x with roff[x] < p1, from the row that holds p0 on, is one run of the tile: it
+// starts at max(roff[x], p0) - p0, and its out-row is off[x] .. off[x + 1] (the very words just read where roff == off,
+// a derived CSR).  The row that holds p0 comes from k_mid_tile_rows (tile_x); the runs are found one row per lane from a
+// window of the offsets; an entry then finds its run by counting run starts at or before its own position.  No
+// per-entry row index is read (tests/test_offset_runs_cpu.py holds the numpy model this is written from).
 
-// stage 2: row hashes (two fmix64 each) and the out-row extents of the middle vertices (gathers)
-__device__ __forceinline__ void mid_prepare(const uint32_t *__restrict__ off, const MidRows &r, int emit_mid,
-                                            MidPrep &p, uint64_t &mid_sum, uint64_t &rows_last) {
+// stages 1 to 3 of k_expand_mid2: the run table and the start mask from the offsets, then the states and their prefix
+// sums.  Returns the number of runs.  One barrier per window chunk (a chunk is XT rows; rows without entries are legal
+// and may be many, so the window is walked until roff[x] >= p1 or x == V) and three more.
+__device__ __forceinline__ uint32_t mid_stage_offsets(MidShared &sm, MidOffsets &so, const uint32_t *__restrict__ off,
+                                                      const uint32_t *__restrict__ roff,
+                                                      const uint32_t *__restrict__ rnbr, uint32_t V, uint64_t fbase,
+                                                      uint64_t M, uint64_t tile, int emit_mid, uint64_t &mid_sum,
+                                                      uint64_t &rows_last, const uint32_t *__restrict__ tile_x) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int uwave = __builtin_amdgcn_readfirstlane(wave);
+  const uint64_t remaining = M - tile * MT;
+  const uint32_t n = remaining < MT ? (uint32_t)remaining : (uint32_t)MT;  // entries of this tile
+  const uint32_t p0 = (uint32_t)(fbase + tile * MT), p1 = p0 + n;           // (offsets are 32-bit: so is every p)
+  // the in-row entries: independent of the run table, in flight while it is built
+  // (all loads first, one after the other: a position past the tile's end reads the tile's last entry, so that no
+  // load sits in a branch of its own and waits there)
+  uint32_t u[MID_EPT];
 #pragma unroll
   for (int e = 0; e < MID_EPT; e++) {
-    p.q[e] = 0;
-    p.st[e] = p.dout[e] = 0;
-    if (r.valid[e]) {
-      p.st[e] = off[r.x[e]];
-      p.dout[e] = off[r.x[e] + 1] - p.st[e];
-      const uint64_t P = dig_leaf(dig_q((uint64_t)r.u[e], 0), r.x[e]);
+    const uint32_t idx = e * XT + threadIdx.x;
+    u[e] = rnbr[(uint64_t)p0 + (idx < n ? idx : n - 1)];
+  }
+  if (threadIdx.x < MID_WORDS) so.mask[threadIdx.x] = 0;
+  const bool same = roff == off;
+  const uint64_t lt = (1ULL << lane) - 1ULL;
+  uint32_t nruns = 0;
+  int par = 0;
+  for (uint32_t xc = tile_x[tile];; xc += XT, par ^= 1) {
+    const uint32_t x = xc + threadIdx.x;
+    uint32_t a = 0, b = 0;
+    if (x < V) {
+      a = roff[x];
+      b = roff[x + 1];
+    }
+    const bool is_run = b > a && a < p1;  // (x >= the row that holds p0: a non-empty row ends behind p0)
+    uint32_t st = a, dout = b - a;
+    if (is_run && !same) {
+      st = off[x];
+      dout = off[x + 1] - st;
+    }
+    const uint64_t hm = __ballot(is_run);
+    if (lane == 0) so.ccnt[par][uwave] = (uint32_t)__popcll(hm);
+    if (threadIdx.x == XT - 1) so.more[par] = x < V && x + 1 < V && b < p1;
+    __syncthreads();
+    uint32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < XT / 64; w++) {
+      const uint32_t c = so.ccnt[par][w];
+      before += w < uwave ? c : 0u;
+      total += c;
+    }
+    if (is_run) {
+      const uint32_t rr = nruns + before + (uint32_t)__popcll(hm & lt);
+      const uint32_t s = (a > p0 ? a : p0) - p0, end = (b < p1 ? b : p1) - p0;
+      sm.run[rr] = s;
+      sm.rst[rr] = st;
+      sm.rdout[rr] = dout;
+      so.run_x[rr] = x;
+      atomicOr(&so.mask[s >> 6], 1ULL << (s & 63));
+      rows_last += (uint64_t)(end - s) * dout;
+    }
+    nruns += total;
+    if (!so.more[par]) break;  // (uniform; the slots of the other parity are free again behind the next barrier)
+  }
+  if (threadIdx.x == 0) sm.run[nruns] = n;
+  __syncthreads();
+  // an entry at tile position i lies in run (number of starts at positions <= i) - 1: its segment's word of the mask
+  // (the same word in every lane of the wave), one population count, and the starts of the segments before it
+  const unsigned long long mword = lane < MID_WORDS ? so.mask[lane] : 0ULL;
+  uint32_t m_incl;
+  const uint32_t m_cnt = (uint32_t)__popcll(mword);
+  m_incl = row_scan_incl(m_cnt);
+  static_assert(MID_WORDS <= 16, "segment scan covers 16 lanes");
+  const uint32_t m_excl = m_incl - m_cnt;
+  const uint64_t le = lt | (1ULL << lane);
+  uint32_t plo[MID_EPT];
+#pragma unroll
+  for (int e = 0; e < MID_EPT; e++) {
+    const uint32_t idx = e * XT + threadIdx.x;
+    const int seg = e * (XT / 64) + uwave;
+    uint64_t q = 0;
+    if (idx < n) {
+      const uint64_t w = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(mword >> 32), seg) << 32) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mword, seg);
+      const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)m_excl, seg) + (uint32_t)__popcll(w & le) - 1u;
+      const uint64_t P = dig_leaf(dig_q((uint64_t)u[e], 0), so.run_x[r]);
       if (emit_mid) mid_sum = dsum_add(mid_sum, P);
-      p.q[e] = dig_q(P, 1);
-      rows_last += (uint64_t)p.dout[e];
+      q = dig_q(P, 1);
     }
+    sm.q[idx] = (uint32_t)q;
+    plo[e] = wave_scan_incl((uint32_t)q);  // (mod 2^32)
+    if (lane == 63) sm.wsum[seg] = plo[e];
   }
+  __syncthreads();
+  const uint32_t sv = lane < MID_SEG ? sm.wsum[lane] : 0u;
+  const uint32_t s_excl = row_scan_incl(sv) - sv;  // sums of the segments before each segment
+#pragma unroll
+  for (int e = 0; e < MID_EPT; e++)
+    sm.pq[e * XT + threadIdx.x + 1] = (uint32_t)__builtin_amdgcn_readlane((int)s_excl, e * (XT / 64) + uwave) + plo[e];
+  if (threadIdx.x == 0) sm.pq[0] = 0;
+  __syncthreads();
+  return nruns;
 }
 
-// stage 3: LDS image of the tile (states, their prefix sums, runs of equal middle vertex).  Returns the
-// number of runs.  Contains three workgroup barriers; the caller must have finished reading the previous image.
-__device__ __forceinline__ uint32_t mid_stage(MidShared &sm, const MidRows &r, const MidPrep &p, uint64_t M,
-                                              uint64_t tile) {
+// The same image for the kernels whose middle vertices come entry by entry (k_expand_front, k_expand_mid3): runs are
+// found by comparing neighbours in `sx` (MT words of LDS).  Returns the number of runs.  Contains three workgroup
+// barriers; the caller must have finished reading the previous image.
+__device__ __forceinline__ uint32_t mid_stage(MidShared &sm, uint32_t *sx, const MidRows &r, const MidPrep &p,
+                                              uint64_t M, uint64_t tile) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   uint32_t plo[MID_EPT];
 #pragma unroll
   for (int e = 0; e < MID_EPT; e++) {
     const uint32_t idx = e * XT + threadIdx.x;
     sm.q[idx] = (uint32_t)p.q[e];
-    sm.x[idx] = r.x[e];
+    sx[idx] = r.x[e];
     plo[e] = wave_scan_incl((uint32_t)p.q[e]);  // (mod 2^32)
     if (lane == 63) sm.wsum[e * (XT / 64) + wave] = plo[e];
   }
@@ -365,7 +451,7 @@ __device__ __forceinline__ uint32_t mid_stage(MidShared &sm, const MidRows &r, c
 #pragma unroll
   for (int e = 0; e < MID_EPT; e++) {
     const uint32_t idx = e * XT + threadIdx.x;
-    head[e] = r.valid[e] && (idx == 0 || sm.x[idx - 1] != r.x[e]);
+    head[e] = r.valid[e] && (idx == 0 || sx[idx - 1] != r.x[e]);
     hm[e] = __ballot(head[e]);
     const int seg = e * (XT / 64) + uwave;
     if (lane == 0) sm.wcnt[seg] = (uint32_t)__popcll(hm[e]);
@@ -469,24 +555,49 @@ __device__ __forceinline__ void mid_fold_tile(const MidShared &sm, uint32_t nrun
   }
 }
 
+// tile_x[t] = the row of `roff` that holds the first entry of tile t: the last x with roff[x] <= p, rows without entries
+// skipped (roff[0] <= p < roff[V]).  One thread per tile, a 16-way search: fifteen independent probes a round, so 19
+// bits of V take five dependent rounds (a binary search takes 19 and ran 10 us at SF100; one wave per tile with 64
+// probes a round ran 17 us, its 52 000 waves standing in line).  In front of k_expand_mid2, not inside it: the search in
+// every workgroup cost that VALU-bound kernel 24 us (profiles/r23_bench_ab.json).
+constexpr int MID_WAYS = 16;
+__global__ __launch_bounds__(256) void k_mid_tile_rows(const uint32_t *__restrict__ roff, uint32_t V, uint64_t fbase,
+                                                       uint64_t n_tiles, uint32_t *__restrict__ tile_x) {
+  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_tiles) return;
+  const uint32_t p = (uint32_t)(fbase + t * MT);
+  uint32_t lo = 0, n = V;  // the answer lies in [lo, lo + n)
+  while (n > 1) {
+    const uint32_t step = (n + MID_WAYS - 1) / MID_WAYS;  // (at most 2^28: (MID_WAYS - 1) steps stay below 2^32)
+    uint32_t v[MID_WAYS - 1];
+#pragma unroll
+    for (int k = 1; k < MID_WAYS; k++)  // (a probe past the range reads its last row instead: no load in a branch)
+      v[k - 1] = roff[lo + ((uint32_t)k * step < n ? (uint32_t)k * step : n - 1)];
+    uint32_t c = 0;  // (roff ascends: the probes at or below p are a prefix)
+#pragma unroll
+    for (int k = 1; k < MID_WAYS; k++) c += (uint32_t)k * step < n && v[k - 1] <= p ? 1u : 0u;
+    lo += c * step;
+    n = n - c * step < step ? n - c * step : step;
+  }
+  tile_x[t] = lo;
+}
+
 // One tile per workgroup.
 __global__ __launch_bounds__(XT) void k_expand_mid2(const uint32_t *__restrict__ off, const uint32_t *__restrict__ nbr,
-                                                    const uint32_t *__restrict__ rrow, const uint32_t *__restrict__ rnbr,
-                                                    uint64_t fbase, uint64_t M, int emit_mid,
+                                                    const uint32_t *__restrict__ roff, const uint32_t *__restrict__ rnbr,
+                                                    uint32_t V, uint64_t fbase, uint64_t M, int emit_mid,
                                                     unsigned long long *__restrict__ partial,
-                                                    unsigned long long *__restrict__ zero3) {
+                                                    unsigned long long *__restrict__ zero3,
+                                                    const uint32_t *__restrict__ tile_x) {
   __shared__ MidShared sm;
+  __shared__ MidOffsets so;
   if (blockIdx.x == 0 && threadIdx.x < 3) zero3[threadIdx.x] = 0;  // k_reduce_partials' accumulators (next kernel)
   uint64_t mid_sum = 0, rows_last = 0;
   uint32_t corr = 0;
   uint32_t acc[MID_R];
 #pragma unroll
   for (int r = 0; r < MID_R; r++) acc[r] = 0;
-  MidRows rows;
-  MidPrep prep;
-  mid_load_rows(rrow, rnbr, fbase, M, blockIdx.x, rows);
-  mid_prepare(off, rows, emit_mid, prep, mid_sum, rows_last);
-  const uint32_t nruns = mid_stage(sm, rows, prep, M, blockIdx.x);
+  const uint32_t nruns = mid_stage_offsets(sm, so, off, roff, rnbr, V, fbase, M, blockIdx.x, emit_mid, mid_sum, rows_last, tile_x);
   mid_fold_tile(sm, nruns, nbr, acc, corr);
   uint32_t tsum = 0;
 #pragma unroll
@@ -578,6 +689,7 @@ __global__ __launch_bounds__(XT) void k_expand_front(const uint32_t *__restrict_
                                                      const uint32_t *__restrict__ fv, const uint32_t *__restrict__ fq32,
                                                      uint64_t M, unsigned long long *__restrict__ partial) {
   __shared__ MidShared sm;
+  __shared__ uint32_t s_x[MT];
   uint32_t corr = 0;
   uint32_t acc[MID_R];
 #pragma unroll
@@ -599,7 +711,7 @@ __global__ __launch_bounds__(XT) void k_expand_front(const uint32_t *__restrict_
       prep.dout[e] = off[rows.x[e] + 1] - prep.st[e];
     }
   }
-  const uint32_t nruns = mid_stage(sm, rows, prep, M, blockIdx.x);
+  const uint32_t nruns = mid_stage(sm, s_x, rows, prep, M, blockIdx.x);
   mid_fold_tile(sm, nruns, nbr, acc, corr);
   uint32_t tsum = 0;
 #pragma unroll
@@ -660,6 +772,7 @@ __global__ __launch_bounds__(XT) void k_expand_mid3(const uint32_t *__restrict__
   // frontier sorted by its last vertex: their hash states q_level), so the prefixes one hop longer that end in b are,
   // for every reverse entry (a -> b), those entries; their states are dig_q(dig_leaf(q, b), level + 1).
   __shared__ MidShared sm;
+  __shared__ uint32_t s_x[MT];
   __shared__ uint64_t s_foff[MT + 1];
   uint64_t mid_sum = 0, rows_last = 0;
   uint32_t acc[MID_R], corr = 0;
@@ -720,7 +833,7 @@ __global__ __launch_bounds__(XT) void k_expand_mid3(const uint32_t *__restrict__
       rows_last += (uint64_t)prep.dout[e];
     }
   }
-  const uint32_t nruns = mid_stage(sm, rows, prep, M2, tile);
+  const uint32_t nruns = mid_stage(sm, s_x, rows, prep, M2, tile);
   mid_fold_tile(sm, nruns, nbr, acc, corr);
   uint32_t tsum = 0;
 #pragma unroll
@@ -1149,7 +1262,7 @@ int khop_count(gg_ctx *ctx, const gg_csr *csr, bool ident, uint32_t lo, uint64_t
     for (uint64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {
       const uint64_t nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
       GG_LAUNCH(ctx, "expand_front3", k_expand_mid3, dim3((unsigned)nt), dim3(XT), 0, csr->off, csr->nbr,
-                (const uint32_t *)froff, csr->rrow, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
+                (const uint32_t *)froff, csr->rrow_index, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
                 (int)(j + 1 >= k_min), partial + t0 * 4, t0, (const uint64_t *)fqs, j);
     }
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
@@ -1299,6 +1412,20 @@ __global__ void k_pack_stats(const unsigned long long *__restrict__ tmp3, unsign
   }
 }
 
+// the tiles' first rows, then the tiles (M > 0 entries from fbase on; in_off == csr->off tells a derived CSR)
+static int launch_expand_mid2(gg_ctx *ctx, gg_csr *csr, const uint32_t *in_off, const uint32_t *in_rows, uint64_t fbase,
+                              uint64_t M, int k_min, unsigned long long *partial, unsigned long long *zero3) {
+  const uint64_t n_tiles = (M + MT - 1) / MT;
+  uint32_t *tile_x = nullptr;
+  GG_TRY(ctx->dev_alloc((void **)&tile_x, n_tiles * sizeof(uint32_t)));
+  GG_LAUNCH(ctx, "mid_tile_rows", k_mid_tile_rows, dim3((unsigned)((n_tiles + 255) / 256)), dim3(256), 0, in_off,
+            (uint32_t)csr->V, fbase, n_tiles, tile_x);
+  GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, in_off, in_rows,
+            (uint32_t)csr->V, fbase, M, (int)(k_min <= 1), partial, zero3, (const uint32_t *)tile_x);
+  ctx->dev_free(tile_x);  // (the pool keeps a freed block alive in stream order)
+  return GG_OK;
+}
+
 // st == nullptr: nothing comes back to the host and nothing waits — the six words are left in dev_out6
 int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, int k_min, gg_khop_stats *st,
                    unsigned long long *dev_out6 = nullptr) {
@@ -1306,11 +1433,14 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
   // The kernel only sums over the in-row of every middle vertex x (the 1-hop digest, one staged state per entry).  On a
   // derived CSR that row is the forward row of x in another order under the same offsets (roff == off), so the forward
   // rows stand in for it — the same counts and digests — and the reverse rows stay unwritten (gg_csr.hip: ensure_reverse).
+  // The row of an entry comes from the offsets (mid_stage_offsets): the row index is never read, and on a derived CSR
+  // never built here.  Its two offset arrays hold the same words: passing one for both tells the kernel so.
   if (csr->rev_derived)
-    GG_TRY(ensure_reverse_index(ctx, csr));
+    GG_TRY(ensure_reverse_offsets(ctx, csr));
   else
     GG_TRY(ensure_reverse(ctx, csr));
   const uint32_t *in_rows = csr->rev_derived ? csr->nbr : csr->rnbr_rows;
+  const uint32_t *in_off = csr->rev_derived ? csr->off : csr->roff;
   const uint64_t n_mid = mid_hi - mid_lo;
   uint64_t M = csr->E_rev, fbase = 0;
   if (!(mid_lo == 0 && mid_hi == csr->V)) {
@@ -1328,8 +1458,7 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
       const uint64_t n_tiles = (M + MT - 1) / MT;
       GG_TRY(ctx->dev_alloc((void **)&partial, n_tiles * 4 * sizeof(unsigned long long)));
       GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
-      GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, csr->rrow,
-                in_rows, fbase, M, (int)(k_min <= 1), partial, tmp);
+      GG_TRY(launch_expand_mid2(ctx, csr, in_off, in_rows, fbase, M, k_min, partial, tmp));
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
     }
     GG_LAUNCH(ctx, "pack_stats", k_pack_stats, dim3(1), dim3(64), 0, (const unsigned long long *)tmp, (unsigned long long)M,
@@ -1343,8 +1472,7 @@ int khop_count_mid(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mid_hi, i
     unsigned long long *partial = nullptr, *tmp = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&partial, n_tiles * 4 * sizeof(unsigned long long)));
     GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
-    GG_LAUNCH(ctx, "expand_mid2", k_expand_mid2, dim3((unsigned)n_tiles), dim3(XT), 0, csr->off, csr->nbr, csr->rrow,
-              in_rows, fbase, M, (int)(k_min <= 1), partial, tmp);
+    GG_TRY(launch_expand_mid2(ctx, csr, in_off, in_rows, fbase, M, k_min, partial, tmp));
     GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp, true));
     uint64_t h[3];
     GG_TRY(read_back(ctx, {{tmp, sizeof(h), h}}));
@@ -1378,7 +1506,7 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
     GG_TRY(ctx->dev_alloc((void **)&foff2, (E + 1) * sizeof(uint64_t)));
     GG_TRY(ctx->dev_alloc((void **)&partial, nb1 * 4 * sizeof(unsigned long long)));
     GG_TRY(ctx->dev_alloc((void **)&tmp, 3 * sizeof(unsigned long long)));
-    GG_LAUNCH(ctx, "mid3_prepare", k_mid3_prepare, dim3((unsigned)nb1), dim3(256), 0, csr->roff, csr->rrow, csr->rnbr_rows,
+    GG_LAUNCH(ctx, "mid3_prepare", k_mid3_prepare, dim3((unsigned)nb1), dim3(256), 0, csr->roff, csr->rrow_index, csr->rnbr_rows,
               E, foff2, partial);
     GG_TRY(reduce_partials(ctx, partial, nb1, tmp));
     GG_TRY(offsets_from_deg(ctx, foff2, E, &M2, {{tmp, sizeof(uint64_t), &dig1}}));  // (the 1-hop digest rides on its sync)
@@ -1400,7 +1528,7 @@ int khop_count_mid3(gg_ctx *ctx, gg_csr *csr, int k_min, gg_khop_stats *st) {
       for (uint64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {  // (one launch up to 1.3e10 2-hop rows)
         const uint64_t nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
         GG_LAUNCH(ctx, "expand_mid3", k_expand_mid3, dim3((unsigned)nt), dim3(XT), 0, csr->off, csr->nbr, csr->roff,
-                  csr->rrow, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
+                  csr->rrow_index, csr->rnbr_rows, (const uint64_t *)foff2, E, M2, (const uint32_t *)tile_entry,
                   (int)(k_min <= 2), partial + t0 * 4, t0, (const uint64_t *)nullptr, 0);
       }
       GG_TRY(reduce_partials(ctx, partial, n_tiles, tmp));
@@ -1815,7 +1943,7 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
   GG_TRY(ctx->dev_alloc((void **)&foff, (n + 1) * sizeof(uint64_t)));
   if (n)
     GG_LAUNCH(ctx, "mat_mid2_prepare", k_mat_mid2_prepare, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, csr->off,
-              csr->rrow, e0, n, foff);
+              csr->rrow_index, e0, n, foff);
   uint64_t M2 = 0;
   GG_TRY(offsets_from_deg(ctx, foff, n, &M2));
   res->rows[2] = M2;
@@ -1836,7 +1964,7 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
     GG_TRY(ctx->dev_alloc((void **)&tile_entry, (n_tiles + 1) * sizeof(uint32_t)));
     GG_LAUNCH(ctx, "mat_tile_entries", k_mat_tile_entries, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0,
               (const uint64_t *)foff, n, n_tiles, M2, tile_entry);
-    GG_LAUNCH(ctx, "mat_mid2", k_mat_mid2, dim3((unsigned)n_tiles), dim3(256), 0, csr->off, csr->nbr, csr->rrow,
+    GG_LAUNCH(ctx, "mat_mid2", k_mat_mid2, dim3((unsigned)n_tiles), dim3(256), 0, csr->off, csr->nbr, csr->rrow_index,
               csr->rnbr_rows, csr->vid, (const uint64_t *)foff, (const uint32_t *)tile_entry, e0, n, M2, res->cols[2][0],
               res->cols[2][1], res->cols[2][2], (uint32_t)n_tiles);
     ctx->dev_free(tile_entry);
@@ -1848,7 +1976,7 @@ int khop_materialise_mid2(gg_ctx *ctx, gg_csr *csr, uint64_t mid_lo, uint64_t mi
       ctx->keep(res->cols[1][c]);
       if (n)
         GG_LAUNCH(ctx, "gather_ids", k_gather_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                  (c ? csr->rrow : csr->rnbr_rows) + e0, csr->vid, n, res->cols[1][c]);
+                  (c ? csr->rrow_index : csr->rnbr_rows) + e0, csr->vid, n, res->cols[1][c]);
     }
   }
   ctx->dev_free(foff);
@@ -2102,7 +2230,7 @@ int khop_count_rows(gg_ctx *ctx, gg_csr *csr, const uint32_t *dense_src, uint64_
   if (all ? k_max >= 3 : k_max >= 2)
     GG_TRY(ensure_reverse(ctx, csr));
   else if (k_max >= 2 || (all && csr->n_parts > 1))
-    GG_TRY(ensure_reverse_index(ctx, csr));
+    GG_TRY(ensure_reverse_offsets(ctx, csr));
   unsigned long long *out = nullptr, *wa = nullptr, *wb = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&out, (GG_MAX_HOPS + 1) * sizeof(unsigned long long)));
   GG_HIP(hipMemsetAsync(out, 0, (GG_MAX_HOPS + 1) * sizeof(unsigned long long), ctx->stream));
@@ -2484,7 +2612,7 @@ extern "C" int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint
     for (int i = 1; i < n_parts; i++) bounds[i] = V;
     return GG_OK;
   }
-  GG_TRY(ensure_reverse_index(ctx, csr));  // (k_mid_work reads the two offset arrays only)
+  GG_TRY(ensure_reverse_offsets(ctx, csr));  // (k_mid_work reads the two offset arrays only)
   uint64_t *work = nullptr;
   GG_TRY(ctx->dev_alloc((void **)&work, (V + 1) * sizeof(uint64_t)));
   GG_LAUNCH(ctx, "mid_work", k_mid_work, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, csr->off, csr->roff, V,

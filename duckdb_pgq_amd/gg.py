@@ -20,7 +20,7 @@ SYMBOLS = [
     "gg_ctx_set_edge_rowid", "gg_csr_build", "gg_csr_build_shard", "gg_csr_destroy", "gg_csr_info", "gg_csr_export",
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
-    "gg_debug_csr_reverse", "gg_debug_csr_reverse_ready", "gg_debug_scan", "gg_debug_sort_pairs",
+    "gg_debug_csr_reverse", "gg_debug_csr_reverse_ready", "gg_debug_csr_reverse_index_ready", "gg_debug_scan", "gg_debug_sort_pairs",
     "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_pool", "gg_debug_reach_visited",
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
@@ -208,6 +208,7 @@ def load_library(path: str | None = None):
     lib.gg_debug_rank_mode.argtypes = [P, C.c_int]
     lib.gg_debug_csr_reverse.argtypes = [P, i64p, i64p, i64p, C.POINTER(C.c_int)]
     lib.gg_debug_csr_reverse_ready.argtypes = [P, C.POINTER(C.c_int)]
+    lib.gg_debug_csr_reverse_index_ready.argtypes = [P, C.POINTER(C.c_int)]
     lib.gg_debug_scan_fault.argtypes = [P, C.c_uint32, u64]
     lib.gg_debug_scan.argtypes = [P, C.c_void_p, u64, C.c_int, C.c_void_p, C.POINTER(u64)]
     lib.gg_debug_sort_pairs.argtypes = [P] + [C.c_void_p] * 3 + [u64, C.c_int] + [C.c_void_p] * 3 + [C.POINTER(u64)]
@@ -667,6 +668,23 @@ class Csr:
         r = C.c_int()
         self.gg._chk(self.gg.lib.gg_debug_csr_reverse_ready(self.handle, C.byref(r)))
         return bool(r.value)
+
+    @property
+    def reverse_index_ready(self) -> bool:
+        """True if the row index of the reverse entries (rrow) is written; asking does not write it
+        (gg_debug_csr_reverse_index_ready)."""
+        r = C.c_int()
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse_index_ready(self.handle, C.byref(r)))
+        return bool(r.value)
+
+    def export_reverse_index(self):
+        """rrow alone: builds the offsets and the row index if absent, not the reverse rows."""
+        p = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))  # noqa: E731
+        roff = np.empty(self.V + 1, np.int64)
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, p(roff), None, None, None))
+        rrow = np.empty(int(roff[-1]), np.int64)
+        self.gg._chk(self.gg.lib.gg_debug_csr_reverse(self.handle, None, None, p(rrow), None))
+        return rrow
 
     def export_reverse(self):
         """(roff, rnbr, rrow) of the reverse CSR as int64 arrays (gg_debug_csr_reverse)."""

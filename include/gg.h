@@ -1081,18 +1081,25 @@ int gg_debug_force_legacy_build(gg_ctx *ctx, int on);
 int gg_debug_rank_mode(gg_ctx *ctx, int mode);
 /* Testing hook: the reverse CSR (in-neighbours) as int64 arrays — roff[V + 1], and rnbr / rrow (source / destination
  * of every reverse entry) with as many entries as the CSR keeps edges (a shard: the edges whose destination it owns);
- * any of the three may be NULL.  Row x lists its sources in edge-rowid order where the bucketed build made the reverse
+ * any of the three may be NULL, and no more of the reverse CSR is built than the arrays asked for need (rnbr: all of it;
+ * rrow without rnbr: the offsets and the row index; roff alone: the offsets).  Row x lists its sources in edge-rowid order where the bucketed build made the reverse
  * CSR, in ascending (source, rowid) order where the multi-pass build of a whole graph left it to this call.
  * *derived (may be NULL): 1 if the build derived the reverse CSR from the forward rows of a fully mirrored edge table
  * (row i + E/2 = row i with source and destination swapped, for every i), which must give the same arrays as sorting;
  * GG_MIRROR_REVERSE=0 in the environment at gg_ctx_create (or GG_MIRROR_PAIRS=0) switches that off. */
 int gg_debug_csr_reverse(gg_csr *csr, int64_t *roff, int64_t *rnbr, int64_t *rrow, int *derived);
 /* *ready = 1 if the CSR holds its reverse rows (rnbr), 0 if they are still to be written.  A derived build keeps only
- * the row offsets, the COO column and one rotation count per vertex, and writes the rows when the first call that reads
+ * the row offsets and one rotation count per vertex, and writes the rows when the first call that reads
  * them arrives (counting 1- and 2-hop walks never does); every other build has them from the start or, for the
  * multi-pass build of a whole graph, from that first call.  This call asks only: it builds and launches nothing, where
  * gg_debug_csr_reverse with an array to fill writes the rows first. */
 int gg_debug_csr_reverse_ready(const gg_csr *csr, int *ready);
+/* *ready = 1 if the CSR holds the row index of its reverse entries (rrow, the COO column: the row-index expansion of
+ * roff), 0 if it is still to be written.  A derived build writes none: the first call that reads the column (2-hop rows
+ * through a middle vertex, 3-hop counts, connected components, a sharded BFS, gg_debug_csr_reverse with rnbr or rrow)
+ * has it expanded from the offsets by one kernel; counting 1- and 2-hop walks and gg_khop_partition_mid never do.  This
+ * call asks only: it builds and launches nothing. */
+int gg_debug_csr_reverse_index_ready(const gg_csr *csr, int *ready);
 /* Testing knob (fault injection): tile `mute_tile` of every chained prefix scan never publishes its sum and the
  * tiles behind it give up after `spin_limit` polls instead of 2^24; the call that ran the scan must then
  * fail with GG_ERR_HIP instead of returning a wrong result.  spin_limit 0 and mute_tile UINT64_MAX restore
