@@ -316,7 +316,8 @@ struct gg_csr {
 
 // What a device result holds and which calls read it.  The kinds from AGGREGATE on were born with a refusal contract:
 // every call but their own answers them with GG_ERR_STATE, and theirs answer every other kind so (gg::expect_kind).
-enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS, CHEAPEST };
+enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS, CHEAPEST,
+                        CHEAPEST_PATHS };
 
 // kind          tables and columns (h: a level in k_min..k_max)                     read by
 // TABLES        rows[h], cols[h][0..h] = ids v0..vh; ecols[h][j] = rowid of the     gg_result_rows / _fetch / _fetch_edges /
@@ -340,6 +341,10 @@ enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGAT
 //               asked for
 // CHEAPEST      rows[0], cols[0][0..3] = source index, vertex id, cost, hops (int32     gg_cheapest64_rows / _fetch
 //               cells)
+// CHEAPEST_PATHS  rows[CPP_PAIRS_TABLE], cols[..][0..3] = pair index, cost, hops,     gg_cheapest64_paths_rows / _fetch_pairs /
+//               traced (both int32 cells); rows[CPP_ROWS_TABLE], cols[..][0..4] =    _fetch
+//               pair index, step (int32 cells), vertex id, edge rowid if asked for,
+//               cost
 struct gg_result {
   gg_ctx *ctx = nullptr;
   ResultKind kind = ResultKind::TABLES;
@@ -402,7 +407,9 @@ constexpr KindName KIND_NAMES[] = {
     {"components", "gg_components_rows / gg_components_fetch[_sizes]"},
     {"all shortest paths", "gg_bfs64_all_paths_rows / _fetch_pairs / _fetch"},
     {"cheapest path costs", "gg_cheapest64_rows / gg_cheapest64_fetch"},
+    {"cheapest paths", "gg_cheapest64_paths_rows / _fetch_pairs / _fetch"},
 };
+static_assert(sizeof(KIND_NAMES) / sizeof(KIND_NAMES[0]) == (size_t)ResultKind::CHEAPEST_PATHS + 1, "a name per kind");
 inline int expect_kind(const gg_result *res, ResultKind want, const char *fn) {
   if (!res) return GG_ERR_INVALID_ARG;
   if (res->kind == want) return GG_OK;
@@ -828,5 +835,8 @@ int all_paths_emit(gg_ctx *ctx, gg_csr *csr, const void *dist, size_t cell_bytes
 // gg_bfs64's dispatch (8-bit cells, 16-bit rerun) with the request handed to bfs_run (gg_bfs.hip)
 int bfs64_all_paths_run(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids, int n_src, int max_hops,
                         gg_bfs_stats *stats, const AllPathsRequest &rq);
+
+// ---- the cheapest paths off a finished gg_cheapest64 batch (gg_cheapest.hip)
+constexpr int CPP_PAIRS_TABLE = 0, CPP_ROWS_TABLE = 1;  // the gg_result tables of the reached pairs and of the path rows
 
 }  // namespace gg

@@ -39,6 +39,7 @@ SYMBOLS = [
     "gg_khop_pair_counts", "gg_khop_pair_counts_rows", "gg_khop_pair_counts_fetch", "gg_debug_pair_counts",
     "gg_edge_weights_create", "gg_edge_weights_destroy", "gg_cheapest64", "gg_cheapest64_rows", "gg_cheapest64_fetch",
     "gg_debug_cheapest",
+    "gg_cheapest64_paths", "gg_cheapest64_paths_rows", "gg_cheapest64_paths_fetch_pairs", "gg_cheapest64_paths_fetch",
     "gg_components", "gg_components_rows", "gg_components_fetch", "gg_components_fetch_sizes", "gg_debug_components",
     "gg_result_extend_edge", "gg_debug_extend",
     "gg_result_group_by", "gg_debug_group",
@@ -132,6 +133,16 @@ class CheapestStats(C.Structure):
         ("cells_lowered", C.c_uint64),
         ("entries_pulled", C.c_uint64),
         ("rows_gathered", C.c_uint64),
+    ]
+
+
+class CheapestPathsStats(C.Structure):
+    _fields_ = [
+        ("search", CheapestStats),
+        ("pairs_reached", C.c_uint64),
+        ("pairs_saturated", C.c_uint64),
+        ("rows", C.c_uint64),
+        ("entries_scanned", C.c_uint64),
     ]
 
 
@@ -302,6 +313,11 @@ def load_library(path: str | None = None):
     lib.gg_cheapest64_rows.argtypes = [P, C.POINTER(u64)]
     lib.gg_cheapest64_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
     lib.gg_debug_cheapest.argtypes = [P, C.c_uint32, C.c_int]
+    lib.gg_cheapest64_paths.argtypes = [P, P, P, i64p, C.c_int, u32p, i64p, u64, C.c_int, C.POINTER(CheapestPathsStats),
+                                        C.POINTER(P)]
+    lib.gg_cheapest64_paths_rows.argtypes = [P, C.c_int, u64p]
+    lib.gg_cheapest64_paths_fetch_pairs.argtypes = [P, u64, C.c_uint32, i64p, i64p, i32p, i32p, u32p]
+    lib.gg_cheapest64_paths_fetch.argtypes = [P, u64, C.c_uint32, i64p, i32p, i64p, i64p, i64p, u32p]
     lib.gg_components.argtypes = [P, P, C.POINTER(CcStats), C.POINTER(P)]
     lib.gg_components_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
     lib.gg_components_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(u64), C.POINTER(C.c_uint32)]
@@ -1613,6 +1629,59 @@ class GG:
         else:
             a = np.ascontiguousarray(sources, dtype=np.int64).reshape(-1)
         return self._cheapest(csr, weights, a, max_hops, targets, fetch)
+
+    def cheapest64_paths(self, csr: Csr, weights: "EdgeWeights", sources, pair_lane, pair_dst, edges: bool = True):
+        """gg_cheapest64_paths: the pinned cheapest path of each (sources[pair_lane[i]], pair_dst[i]) of one <=64-source batch
+        run to the fixpoint.  Returns ((pair int64, step int32, vertex int64, edge int64, cost int64) ascending by (pair,
+        step), the pair table (pair int64, cost int64, hops int32, traced int32) of the reached pairs, stats): stats = the
+        call's gg_cheapest_paths_stats as a dict, the rounds' under "search"."""
+        i64p, i32p = C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        s, ps = _i64(sources)
+        d, pd = _i64(pair_dst)
+        lane = np.ascontiguousarray(pair_lane, dtype=np.uint32)
+        if lane.size != d.size:
+            raise ValueError("one source lane per target")
+        st, res = CheapestPathsStats(), C.c_void_p()
+        self._chk(self.lib.gg_cheapest64_paths(self.ctx, csr.handle, weights.handle, ps, s.size,
+                                               lane.ctypes.data_as(C.POINTER(C.c_uint32)), pd, d.size, 1 if edges else 0,
+                                               C.byref(st), C.byref(res)))
+        try:
+            def fetch_table(table, cols, call):
+                n = C.c_uint64()
+                self._chk(self.lib.gg_cheapest64_paths_rows(res, table, C.byref(n)))
+                n = int(n.value)
+                out = [np.empty(n, t) for t in cols]
+                done = 0
+                while done < n:
+                    got = C.c_uint32()
+                    ptrs = [a[done:].ctypes.data_as({np.int64: i64p, np.int32: i32p}[t]) for a, t in zip(out, cols)]
+                    self._chk(call(res, done, min(n - done, 1 << 30), *ptrs, C.byref(got)))
+                    assert got.value
+                    done += got.value
+                return tuple(out)
+            pairs = fetch_table(0, (np.int64, np.int64, np.int32, np.int32), self.lib.gg_cheapest64_paths_fetch_pairs)
+            rows = fetch_table(1, (np.int64, np.int32, np.int64, np.int64, np.int64), self.lib.gg_cheapest64_paths_fetch)
+        finally:
+            self.lib.gg_result_destroy(res)
+        stats = {k: int(getattr(st, k)) for k in ("pairs_reached", "pairs_saturated", "rows", "entries_scanned")}
+        stats["search"] = {name: int(getattr(st.search, name)) for name, _ in CheapestStats._fields_}
+        return rows, pairs, stats
+
+    def cheapest_paths(self, csr: Csr, weights: "EdgeWeights", src, dst, edges: bool = True):
+        """The pinned cheapest path (include/gg.h, gg_cheapest64_paths) of every pair (src[i], dst[i]), unnested: arrays
+        (pair_index int64, step int32, vertex int64, edge int64, cost int64), one row per step 0..hops of every pair that has
+        an unsaturated cost, ascending by (pair index, step); edge is the rowid of the edge into the step's vertex, -1 at step
+        0 (and everywhere with edges=False).  Any number of pairs, grouped by source into device batches of at most 64
+        distinct sources as shortest_paths groups them."""
+        parts = []
+        for sources, lanes, targets, members in self._all_paths_batches(src, dst):
+            rows, _, _ = self.cheapest64_paths(csr, weights, sources, lanes, targets, edges)
+            parts.append((members[rows[0]],) + rows[1:])
+        if not parts:
+            return tuple(np.empty(0, np.int32 if k == 1 else np.int64) for k in range(5))
+        cols = [np.concatenate([p[c] for p in parts]) for c in range(5)]
+        order = np.argsort(cols[0], kind="stable")  # batches interleave; inside a pair the steps already ascend
+        return tuple(c[order] for c in cols)
 
     def debug_cheapest(self, long_row_entries: int = 0, gather_mode: int = 0):
         """gg_cheapest64 gives in-rows of more than long_row_entries entries to a whole workgroup each (0: the default)

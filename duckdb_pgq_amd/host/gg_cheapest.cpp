@@ -18,6 +18,17 @@
 // and batch of 64 sources (gg_cheapest64, include/gg.h).
 // No planner rule recognises the shape.
 //
+//   gg_cheapest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, weight_column VARCHAR, pairs_sql VARCHAR)
+//        -> (src BIGINT, dst BIGINT, step INTEGER, vertex BIGINT, edge_rowid BIGINT, cost BIGINT)
+//
+// The cheapest paths themselves, unnested: for every pair (src, dst) `pairs_sql` yields (two integer columns; a row with a
+// NULL is no pair, duplicate pairs each get their rows) one row per step 0..hops of the pinned cheapest path
+// (gg_cheapest64_paths, include/gg.h: the fewest edges of a cheapest walk, the predecessor with the smallest vertex-table
+// position, among parallel rows the one appended first) with the rowid of the edge into the step's vertex (NULL at step 0)
+// and the cost up to it.  Always to the fixpoint: the state of a hop-bounded search cannot be traced.  A pair without a walk,
+// or whose cost saturates at INT64_MAX, has no rows.  Pairs are grouped by source, 64 distinct sources to a batch in
+// first-occurrence order, and drained as gg_shortest_path_rows drains them (ShortestPathRowsState, gg_operators.hpp).
+//
 // The graph comes from GGBuildGraphWithRowids — the rowid-carrying companion of the pinned graph of these tables if the
 // connection asked for pinned graphs.  (rowid, weight_column) is read in the statement's own transaction, laid out densely
 // by rowid and handed over as GG_WEIGHTS_BY_ROWID, once per statement; a NULL or negative weight and a column that is no
@@ -179,6 +190,134 @@ public:
 	}
 };
 
+//! The path rows of gg_cheapest64_paths, batch by batch.
+class PhysicalGGCheapestPathRows : public PhysicalOperator {
+public:
+	PhysicalGGCheapestPathRows(shared_ptr<GGGraph> graph_p, GGWeightsPtr weights_p, vector<int64_t> src_p,
+	                           vector<int64_t> dst_p)
+	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), 0), graph(move(graph_p)),
+	      weights(move(weights_p)), src(move(src_p)), dst(move(dst_p)) {
+		D_ASSERT(src.size() == dst.size());
+	}
+	static vector<LogicalType> OutputTypes() {
+		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER,
+		        LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT};
+	}
+
+	shared_ptr<GGGraph> graph;
+	GGWeightsPtr weights; // (declared after the graph: destroyed before it, as gg.h asks)
+	vector<int64_t> src, dst;
+
+	//! trace the pairs of a batch; caller holds graph->lock
+	GGResultPtr RunBatch(ShortestPathRowsState &state, idx_t batch, idx_t &rows) const {
+		const idx_t base = batch * GG_BFS_LANES;
+		const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - base);
+		auto &members = state.members[batch];
+		vector<int64_t> targets(members.size());
+		for (idx_t i = 0; i < members.size(); i++) {
+			targets[i] = dst[members[i]];
+		}
+		GGResultPtr owner;
+		GGGraph::Check(gg_cheapest64_paths(graph->ctx, graph->csr, weights.get(), state.uniq.data() + base, n,
+		                                   state.lanes[batch].data(), targets.data(), targets.size(), 1, nullptr,
+		                                   GGResultOut(owner)),
+		               "gg_cheapest64_paths");
+		uint64_t n_rows = 0;
+		GGGraph::Check(gg_cheapest64_paths_rows(owner.get(), 1, &n_rows), "gg_cheapest64_paths_rows");
+		rows = n_rows;
+		return owner;
+	}
+
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
+		auto state = make_unique<ShortestPathRowsState>();
+		lock_guard<mutex> guard(graph->lock);
+		if (!graph->csr) {
+			throw InternalException("GG_CHEAPEST_PATH_ROWS scheduled before the CSR was built");
+		}
+		state->Group(src);
+		if (!state->members.empty()) {
+			state->drain.Replace(context, 0, [&](idx_t &rows) { return RunBatch(*state, 0, rows); });
+		}
+		// the first batch's size is the only estimate there is of how much the threads will have to drain
+		state->max_threads = GGResultSlab::ThreadsFor(state->drain.Rows() * state->members.size());
+		return move(state);
+	}
+
+	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
+		return make_unique<GGResultSlab>(graph);
+	}
+
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+	             LocalSourceState &lstate) const override {
+		auto &gstate = (ShortestPathRowsState &)gstate_p;
+		auto &slab = (GGResultSlab &)lstate;
+		if (context.client.interrupted) {
+			throw InterruptException();
+		}
+		if (slab.pos >= slab.rows) {
+			auto &drain = gstate.drain;
+			auto advance = [&]() -> bool { // current batch claimed completely: run the next one
+				const idx_t next = (idx_t)drain.Table() + 1;
+				if (next >= gstate.members.size()) {
+					return false;
+				}
+				if (context.client.interrupted) {
+					throw InterruptException();
+				}
+				// (the drain's lock stays held through the rounds on purpose: the other threads have nothing to claim
+				// until the next batch's rows exist)
+				drain.Replace(context.client, (int)next, [&](idx_t &rows) {
+					lock_guard<mutex> device_guard(graph->lock);
+					return RunBatch(gstate, next, rows);
+				});
+				return true;
+			};
+			auto fetch = [](gg_result *result, int, idx_t offset, uint32_t want, GGResultSlab &slab) {
+				// columns 0..3: pair, vertex, edge rowid, cost; column 4's memory holds the int32 steps
+				auto columns = slab.Columns(5);
+				uint32_t got = 0;
+				GGGraph::Check(gg_cheapest64_paths_fetch(result, offset, want, columns[0], (int32_t *)columns[4], columns[1],
+				                                         columns[2], columns[3], &got),
+				               "gg_cheapest64_paths_fetch");
+				return got;
+			};
+			if (!drain.Refill(slab, advance, fetch)) { // (pair i of a slab's rows is members[slab.table][i])
+				return;
+			}
+		}
+		const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
+		auto out_src = FlatVector::GetData<int64_t>(chunk.data[0]);
+		auto out_dst = FlatVector::GetData<int64_t>(chunk.data[1]);
+		auto out_step = FlatVector::GetData<int32_t>(chunk.data[2]);
+		auto out_vertex = FlatVector::GetData<int64_t>(chunk.data[3]);
+		auto out_edge = FlatVector::GetData<int64_t>(chunk.data[4]);
+		auto out_cost = FlatVector::GetData<int64_t>(chunk.data[5]);
+		auto &edge_validity = FlatVector::Validity(chunk.data[4]);
+		auto &members = gstate.members[slab.table]; // (filled before the first batch ran; never changed afterwards)
+		const int64_t *pair = slab.column[0] + slab.pos, *vertex = slab.column[1] + slab.pos;
+		const int64_t *edge = slab.column[2] + slab.pos, *cost = slab.column[3] + slab.pos;
+		const int32_t *step = (const int32_t *)slab.column[4] + slab.pos;
+		for (idx_t i = 0; i < n; i++) {
+			const idx_t p = members[(idx_t)pair[i]];
+			out_src[i] = src[p];
+			out_dst[i] = dst[p];
+			out_step[i] = step[i];
+			out_vertex[i] = vertex[i];
+			out_edge[i] = edge[i];
+			out_cost[i] = cost[i];
+			if (step[i] == 0) { // no edge leads into the path's first vertex
+				edge_validity.SetInvalid(i);
+			}
+		}
+		slab.pos += n;
+		chunk.SetCardinality(n);
+	}
+
+	string GetName() const override {
+		return "GG_CHEAPEST_PATH_ROWS";
+	}
+};
+
 //! weight_column of edge_table as one weight per rowid (a rowid no row has weighs 0 and is never read), on the device
 static GGWeightsPtr WeightsByRowid(ClientContext &context, GGGraph &graph, const string &edge_table,
                                    const string &weight_column) {
@@ -259,6 +398,36 @@ static unique_ptr<FunctionData> CheapestPathBind(ClientContext &context, vector<
 	return move(data);
 }
 
+static unique_ptr<FunctionData> CheapestPathRowsBind(ClientContext &context, vector<Value> &inputs,
+                                                     unordered_map<string, Value> &named_parameters,
+                                                     vector<LogicalType> &input_table_types,
+                                                     vector<string> &input_table_names, vector<LogicalType> &return_types,
+                                                     vector<string> &names) {
+	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
+	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+	if (inputs[5].is_null || inputs[6].is_null) {
+		throw BinderException("gg_cheapest_path_rows: weight_column and pairs_sql must not be NULL");
+	}
+	const string weight_column = inputs[5].ToString(), pairs_sql = inputs[6].ToString();
+	auto data = make_unique<GGFunctionData>();
+	data->open = [=](ClientContext &ctx, GGOpened &opened) {
+		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
+		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
+		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, true);
+		spec.edges_with_rowid = true;
+		opened.graph = GGBuildGraphWithRowids(ctx, spec);
+		auto weights = WeightsByRowid(ctx, *opened.graph, edge_table, weight_column);
+		vector<int64_t> src, dst;
+		GGQueryInt64Pairs(ctx, pairs_sql, "gg_cheapest_path_rows: pairs", src, dst);
+		opened.source = make_unique<PhysicalGGCheapestPathRows>(opened.graph, move(weights), move(src), move(dst));
+	};
+	data->parallel_result = true;
+	data->description = "cheapest paths over " + edge_table + " weighted by " + weight_column;
+	return_types = PhysicalGGCheapestPathRows::OutputTypes();
+	names = {"src", "dst", "step", "vertex", "edge_rowid", "cost"};
+	return move(data);
+}
+
 void GGRegisterCheapestFunctions(ClientContext &context) {
 	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
 	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
@@ -266,6 +435,12 @@ void GGRegisterCheapestFunctions(ClientContext &context) {
 	auto fn = GGScanFunction("gg_cheapest_path", args, CheapestPathBind);
 	CreateTableFunctionInfo info(fn);
 	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
+	const vector<LogicalType> rows_args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
+	                                       LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
+	                                       LogicalType::VARCHAR};
+	auto rows_fn = GGScanFunction("gg_cheapest_path_rows", rows_args, CheapestPathRowsBind);
+	CreateTableFunctionInfo rows_info(rows_fn);
+	Catalog::GetCatalog(context).CreateTableFunction(context, &rows_info);
 }
 
 } // namespace duckdb

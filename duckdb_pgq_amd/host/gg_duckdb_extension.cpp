@@ -523,8 +523,8 @@ static unique_ptr<FunctionData> ShortestBind(ClientContext &context, vector<Valu
 }
 
 //! the two integer columns of a statement as (src, dst) pairs; a row with a NULL is no pair
-static void QueryInt64Pairs(ClientContext &context, const string &sql, const char *what, vector<int64_t> &src,
-                            vector<int64_t> &dst) {
+void GGQueryInt64Pairs(ClientContext &context, const string &sql, const char *what, vector<int64_t> &src,
+                       vector<int64_t> &dst) {
 	Connection con(*context.db);
 	auto result = con.Query(sql);
 	if (!result->success) {
@@ -559,7 +559,7 @@ static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<
 		spec.edges_with_rowid = true;
 		opened.graph = GGBuildGraphWithRowids(ctx, spec);
 		vector<int64_t> src, dst;
-		QueryInt64Pairs(ctx, pairs_sql, "gg_shortest_path_rows: pairs", src, dst);
+		GGQueryInt64Pairs(ctx, pairs_sql, "gg_shortest_path_rows: pairs", src, dst);
 		opened.source = make_unique<PhysicalGGShortestPathRows>(opened.graph, move(src), move(dst),
 		                                                        max_hops < 0 ? -1 : (int)max_hops, 0);
 	};
@@ -593,7 +593,7 @@ static unique_ptr<FunctionData> AllShortestBind(ClientContext &context, vector<V
 		spec.edges_with_rowid = true;
 		opened.graph = GGBuildGraphWithRowids(ctx, spec);
 		vector<int64_t> src, dst;
-		QueryInt64Pairs(ctx, pairs_sql, what, src, dst);
+		GGQueryInt64Pairs(ctx, pairs_sql, what, src, dst);
 		opened.source = make_unique<PhysicalGGAllShortestPaths>(opened.graph, move(src), move(dst),
 		                                                        max_hops < 0 ? -1 : (int)max_hops, (uint64_t)path_limit,
 		                                                        COUNT_ONLY, 0);

@@ -88,6 +88,9 @@ void GGDropPinsOfTable(idx_t table_oid);
 
 //! first column of `sql` (run on a side connection) as int64, NULLs skipped
 vector<int64_t> GGQueryInt64Column(ClientContext &context, const string &sql, const char *what);
+//! the two integer columns of `sql` (run on a side connection) as (src, dst) pairs; a row with a NULL is no pair
+void GGQueryInt64Pairs(ClientContext &context, const string &sql, const char *what, vector<int64_t> &src,
+                       vector<int64_t> &dst);
 
 //! The (key, value) rows of a two-column integer source (TINYINT .. BIGINT; anything else raises, naming `fn` and
 //! `value_name`), read through the ingest path in the statement's own transaction, order unspecified.  Rows with a NULL key
@@ -128,7 +131,7 @@ void GGRegisterAggregateFunctions(ClientContext &context);
 //! gg_pair_counts.cpp: registers gg_khop_pair_counts (inside the caller's transaction)
 void GGRegisterPairCountFunctions(ClientContext &context);
 
-//! gg_cheapest.cpp: registers gg_cheapest_path (inside the caller's transaction)
+//! gg_cheapest.cpp: registers gg_cheapest_path and gg_cheapest_path_rows (inside the caller's transaction)
 void GGRegisterCheapestFunctions(ClientContext &context);
 
 //! gg_components.cpp: registers gg_components and gg_component_sizes (inside the caller's transaction)

@@ -30,6 +30,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "duckdb.hpp"
@@ -191,6 +192,42 @@ private:
 	int table = 0;                   // the table of it being handed out
 	idx_t rows = 0, offset = 0;      // rows of that table, next unclaimed one
 	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result` (it may not be freed under them)
+};
+
+//! The global source state of the operators that answer (src, dst) pairs from 64-source device batches (gg_shortest_paths.cpp,
+//! gg_cheapest.cpp): the pairs grouped by source, and the drain of the batch that is resident.
+class ShortestPathRowsState : public GlobalSourceState {
+public:
+	idx_t MaxThreads() override {
+		return max_threads;
+	}
+	vector<int64_t> uniq;            // distinct sources, in first-occurrence order; batch b holds uniq[64 b ..]
+	vector<vector<idx_t>> members;   // per batch: the pairs (indices into src / dst) of its sources, ascending
+	vector<vector<uint32_t>> lanes;  // per batch and member: the source's lane
+	GGResultDrain drain;             // the path rows of the current batch; its table is the batch
+	idx_t max_threads = 1;
+
+	//! group the pairs by source, 64 distinct sources to a batch, in the order the sources first occur
+	void Group(const vector<int64_t> &src) {
+		std::unordered_map<int64_t, idx_t> position; // source id -> index into uniq
+		for (idx_t p = 0; p < src.size(); p++) {
+			auto found = position.find(src[p]);
+			idx_t at;
+			if (found == position.end()) {
+				at = uniq.size();
+				position.emplace(src[p], at);
+				uniq.push_back(src[p]);
+				if (at % GG_BFS_LANES == 0) {
+					members.emplace_back();
+					lanes.emplace_back();
+				}
+			} else {
+				at = found->second;
+			}
+			members[at / GG_BFS_LANES].push_back(p);
+			lanes[at / GG_BFS_LANES].push_back((uint32_t)(at % GG_BFS_LANES));
+		}
+	}
 };
 
 class PhysicalGGVertexSink : public PhysicalOperator {

@@ -21,50 +21,10 @@
 #include "duckdb/common/exception.hpp"
 #include "duckdb/main/client_context.hpp"
 
-#include <unordered_map>
-
 #include "gg_extension.hpp"
 #include "gg_operators.hpp"
 
 namespace duckdb {
-
-namespace {
-
-class ShortestPathRowsState : public GlobalSourceState {
-public:
-	idx_t MaxThreads() override {
-		return max_threads;
-	}
-	vector<int64_t> uniq;            // distinct sources, in first-occurrence order; batch b holds uniq[64 b ..]
-	vector<vector<idx_t>> members;   // per batch: the pairs (indices into src / dst) of its sources, ascending
-	vector<vector<uint32_t>> lanes;  // per batch and member: the source's lane
-	GGResultDrain drain;             // the path rows of the current batch; its table is the batch
-	idx_t max_threads = 1;
-
-	//! group the pairs by source, 64 distinct sources to a batch, in the order the sources first occur
-	void Group(const vector<int64_t> &src) {
-		std::unordered_map<int64_t, idx_t> position; // source id -> index into uniq
-		for (idx_t p = 0; p < src.size(); p++) {
-			auto found = position.find(src[p]);
-			idx_t at;
-			if (found == position.end()) {
-				at = uniq.size();
-				position.emplace(src[p], at);
-				uniq.push_back(src[p]);
-				if (at % GG_BFS_LANES == 0) {
-					members.emplace_back();
-					lanes.emplace_back();
-				}
-			} else {
-				at = found->second;
-			}
-			members[at / GG_BFS_LANES].push_back(p);
-			lanes[at / GG_BFS_LANES].push_back((uint32_t)(at % GG_BFS_LANES));
-		}
-	}
-};
-
-} // namespace
 
 PhysicalGGShortestPathRows::PhysicalGGShortestPathRows(shared_ptr<GGGraph> graph_p, vector<int64_t> src_p,
                                                        vector<int64_t> dst_p, int max_hops_p,

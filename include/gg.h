@@ -769,6 +769,72 @@ int gg_cheapest64_rows(const gg_result *res, uint64_t *n_rows);
 int gg_cheapest64_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *src_index, int64_t *vertex_id,
                         int64_t *cost, int32_t *hops, uint32_t *n_out);
 
+/* The cheapest paths themselves (ANY SHORTEST under a cost), read backwards off the cost and hops cells of one gg_cheapest64
+ * batch while they are still on the device: the weighted twin of gg_bfs64_paths.  The batch is gg_cheapest64(src_ids,
+ * n_src <= 64) run TO THE FIXPOINT; pair i asks for the path from src_ids[pair_lane[i]] to pair_dst_ids[i].  Which of the
+ * cheapest paths is pinned: for lane s and a vertex x with hops(s, x) = h >= 1 and cost(s, x) = c < INT64_MAX,
+ *     pred(s, x) = the first entry u -> x of x's reverse row that satisfies all of
+ *                    u has a cost in lane s;
+ *                    cost(s, u) (+) w(entry) == c, (+) the saturating add of gg_cheapest64;
+ *                    hops(s, u) == h - 1;
+ * "first" in ascending (dense index of the source u, forward CSR position of the entry) — the order of the reverse rows by
+ * source.  So among equally good predecessors the one with the smallest vertex-table position wins, and among parallel rows
+ * of one predecessor that qualify, the row appended first.  The step's edge is that entry, reported as the rowid the Sink
+ * passed with the edge row, or its append position if it passed none.  The path is p_h = t, p_{i-1} = pred(s, p_i), p_0 = s,
+ * and has exactly hops(s, t) edges: the fewest of any cheapest walk.  A zero-weight cycle cannot hold the trace, because
+ * hops falls by one per step.  A qualifying entry always exists at the fixpoint when c < INT64_MAX.
+ * Table 1, the path rows: one row per step i = 0..h,
+ *     (pair index, step i, vertex id p_i, rowid of the edge into p_i or -1 at step 0, cost(s, p_i)),
+ * ascending by (pair index, step), placed by length, scan, write.  The cost column is non-decreasing along a path and the
+ * difference of two steps is the weight of the later step's edge row.
+ * Table 0, the pair table: one row (pair index, cost, hops, traced) per pair whose target has a cost in the pair's lane,
+ * ascending by pair index; traced = 1 if the pair has path rows.
+ * Two cases are outside the relation on purpose.
+ *   No hop bound.  The state a bounded search ends in cannot be traced: with rows 0->3 (10), 0->1 (1), 1->2 (1), 2->3 (1),
+ *   3->4 (1) and max_hops = 3, gg_cheapest64 reports cost(4) = 11 in 2 hops, derived from cost_1(3) = 10 — which round 3 then
+ *   overwrote with 3, so no entry of 4's reverse row qualifies.  This call therefore takes no max_hops; bounded costs stay what
+ *   gg_cheapest64 reports.
+ *   Saturated pairs.  A cost of INT64_MAX means "at least", and under saturation a qualifying entry need not exist.  Such a
+ *   pair is never traced, whether or not it happens to be traceable: it is listed in table 0 with traced = 0 and has no path
+ *   rows.
+ * s == t and s a vertex: one row of step 0 with cost 0.  An unreached target, or s or t not a vertex: no rows in either
+ * table.  Duplicate pairs each get their rows; two lanes may carry one source.
+ * want_edges == 0: the edge column is not computed (gg_cheapest64_paths_fetch reports -1), which is how a CSR without edge
+ * rowids (GG_WEIGHTS_BY_ENTRY weights) is served; want_edges != 0 on such a CSR is GG_ERR_STATE.
+ * Cost: the rounds of gg_cheapest64, then per step the reverse row of the step's vertex up to the entry taken — per entry
+ * looked at 4 B of entry, 8 B of weight and one gathered 64-byte line of cost (one more of hops where the cost matched).
+ * Pairs are traced in parallel, the steps of one pair one after the other.
+ * stats (nullable): search = the batch's rounds, as gg_cheapest64(max_hops = -1) reports them; the other fields are exact
+ * functions of the input, entries_scanned included: per step the entries of the reverse row up to and including the one
+ * taken, whatever the launch geometry.
+ * The result answers gg_cheapest64_paths_rows / _fetch_pairs / _fetch only — every other reader refuses it with
+ * GG_ERR_STATE, and the three calls refuse every other result with GG_ERR_STATE.
+ * GG_ERR_INVALID_ARG: NULL ctx, csr, weights, src_ids or out_result, objects of another context, weights made for another
+ * CSR, n_src outside 1..GG_BFS_LANES, n_pairs != 0 with a NULL pair array, a pair_lane[i] >= n_src; GG_ERR_STATE: a shard
+ * CSR, want_edges on a CSR without rowids, and a reached vertex without a qualifying entry (the cost state and the CSR
+ * disagree: never a loop); GG_ERR_TOO_LARGE: n_pairs >= 2^32 (decided before the arrays are read), or 2^32 path rows or more
+ * (decided from a 64-bit total before anything is traced).  Both outputs are cleared first; the context stays usable. */
+typedef struct gg_cheapest_paths_stats {
+  gg_cheapest_stats search;   /* the batch's rounds, as gg_cheapest64(max_hops = -1) reports them */
+  uint64_t pairs_reached;     /* pairs whose target has a cost in the pair's lane */
+  uint64_t pairs_saturated;   /* of those, cost == INT64_MAX: listed, never traced */
+  uint64_t rows;              /* path rows */
+  uint64_t entries_scanned;   /* reverse entries the trace looked at (exact: a function of the input alone) */
+} gg_cheapest_paths_stats;
+int gg_cheapest64_paths(gg_ctx *ctx, const gg_csr *csr, const gg_edge_weights *weights, const int64_t *src_ids,
+                        int n_src /* 1..GG_BFS_LANES */, const uint32_t *pair_lane, const int64_t *pair_dst_ids,
+                        uint64_t n_pairs, int want_edges, gg_cheapest_paths_stats *stats /* nullable */,
+                        gg_result **out_result);
+/* rows of table 0 (the pair table) or 1 (the path rows); another table is GG_ERR_INVALID_ARG */
+int gg_cheapest64_paths_rows(const gg_result *res, int table, uint64_t *n_rows);
+/* Copy rows [offset, offset+max_rows) of table 0, in row order, into host arrays of >= max_rows entries (any of the four may
+ * be NULL).  *n_out = rows copied, 0 past the end (gg_result_fetch's conventions, its fetch lanes included). */
+int gg_cheapest64_paths_fetch_pairs(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index,
+                                    int64_t *cost, int32_t *hops, int32_t *traced, uint32_t *n_out);
+/* The same for table 1 (edge_rowid and cost may be NULL). */
+int gg_cheapest64_paths_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows, int64_t *pair_index, int32_t *step,
+                              int64_t *vertex_id, int64_t *edge_rowid, int64_t *cost, uint32_t *n_out);
+
 /* ---- weakly connected components: a label and a size per vertex ------------------------------------ */
 /* "Which vertices hang together, and how big is each piece."  In the reference that is a UNION recursive CTE under an
  * aggregate,
