@@ -206,6 +206,8 @@ struct gg_ctx {
   uint32_t group_lds_keys = 0;      // gg_debug_group: keys the workgroup-private table of gg_result_group_by may hold (0: the default)
   int val_top_route = 0;            // gg_debug_value_top: as agg_top_route, for gg_result_top_rows
   uint32_t val_top_floor = 0;       // gg_debug_value_top: as agg_top_floor
+  uint64_t distinct_slots = 0;      // gg_debug_distinct: slots of gg_result_distinct's table (0: the default), rounded up there
+  int distinct_combine = 0;         // gg_debug_distinct: 0 adjacent equal lanes are combined, 1 every row probes
   bool cc_size_fold = true;     // GG_CC_SIZE_FOLD=0 at context creation: gg_components adds sizes per lane, never per wave
                                 // (a measurement switch, scripts/bench_components.py; sizes are the same either way)
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
@@ -323,7 +325,7 @@ enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGAT
 // TABLES        rows[h], cols[h][0..h] = ids v0..vh; ecols[h][j] = rowid of the     gg_result_rows / _fetch / _fetch_edges /
 //               (j + 1)-th edge if asked for; tri_edges: ecols[2][0..2] = e1, e2,   _digest / _filter_* / _extend_edge,
 //               e3 of a triangle row                                                gg_triangles_fetch_edges, gg_result_group_by,
-//                                                                                   gg_result_top_rows
+//                                                                                   gg_result_top_rows, gg_result_distinct
 // WALK_CLOSURE  rows[0] walks level by level, level_rows[L - 1] those of L edges;   gg_walk_closure_levels / _fetch
 //               cols[0][0..1] = index of the seed, rowid of the last edge
 // REACH         the same; cols[0][0..1] = class, vertex id of level L's new pairs   gg_reach_closure_levels / _fetch

@@ -2694,7 +2694,7 @@ __global__ __launch_bounds__(256) void k_result_digest(IdColsIn cols, int hops, 
 extern "C" int gg_result_digest(gg_ctx *ctx, const gg_csr *csr, const gg_result *res, int hops, uint64_t *n_rows,
                                 uint64_t *digest) {
   if (!ctx || !csr || !res || !digest || res->ctx != ctx || csr->ctx != ctx) return GG_ERR_INVALID_ARG;
-  if (res->kind != ResultKind::TABLES || hops < res->k_min || hops > res->k_max || hops < 1 || hops > GG_MAX_HOPS) {
+  if (res->kind != ResultKind::TABLES || hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
     set_error("gg_result_digest: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
     return GG_ERR_INVALID_ARG;
   }

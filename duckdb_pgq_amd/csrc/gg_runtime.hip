@@ -461,6 +461,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->agg_top_floor = 0;
   ctx->val_top_route = 0;
   ctx->val_top_floor = 0;
+  ctx->distinct_slots = 0;
+  ctx->distinct_combine = 0;
   ctx->pc_long_row = 0;
   ctx->pc_gather_mode = 0;
   ctx->cp_long_row = 0;

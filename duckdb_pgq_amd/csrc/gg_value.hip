@@ -14,7 +14,7 @@
 //                   the valid word; the row's pass flag is one bit of a 64-row mask word — the wavefront's __ballot, stored
 //                   by lane 0 — and the valued and passing rows are counted per wavefront.  For the top it also writes the
 //                   value to an 8 B/row scratch column, so the digit passes never probe the dictionary again.
-// Filter (gg_result_filter_value), count, scan, write:
+// Filter (gg_result_filter_value), count, scan, write (gg_rows.h, shared with gg_distinct.hip):
 //   k_value_groups  one thread per group of 256 rows: the popcount of its four mask words
 //   scan            exclusive prefix of the groups' rows
 //   k_value_write   a row's place is the group's prefix + the popcounts of the group's mask words below its wavefront +
@@ -33,22 +33,13 @@
 // top); write 1/8 B mask + 8 (columns) B read per kept row + 8 (columns) B written; a digit pass before compaction 1/8 B
 // mask + 8 B per key word it needs for rows that are live, after it 4 B list entry + the same, gathered.
 #include "gg_internal.h"
+#include "gg_rows.h"
 #include "gg_top.h"
 
 using namespace gg;
 
 namespace gg {
 namespace {
-
-constexpr int VAL_MAX_COLS = 2 * GG_MAX_HOPS + 1;  // hops + 1 id columns and hops edge columns
-constexpr uint64_t VAL_MAX_GROUPS = 0xFFFFFFFFull / 256;  // workgroups per launch: GG_LAUNCH refuses 2^32 threads
-
-struct ValIn {
-  const int64_t *c[VAL_MAX_COLS];
-};
-struct ValOut {
-  int64_t *c[VAL_MAX_COLS];
-};
 
 struct ProbeArgs {
   const int64_t *cells;  // the value column's cells
@@ -93,52 +84,6 @@ __global__ __launch_bounds__(256) void k_value_probe(ProbeArgs a) {
     if (valued) atomicAdd(&a.counts[0], (unsigned long long)valued);
     if (passed) atomicAdd(&a.counts[1], (unsigned long long)passed);
   }
-}
-
-__device__ __forceinline__ uint64_t mask_word(const uint64_t *__restrict__ mask, uint64_t n_words, uint64_t i) {
-  return i < n_words ? mask[i] : 0;
-}
-
-// group[g] = rows of group g that pass
-__global__ __launch_bounds__(256) void k_value_groups(const uint64_t *__restrict__ mask, uint64_t n_words, uint64_t groups,
-                                                      uint64_t *__restrict__ group) {
-  for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t n = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) n += (uint32_t)__popcll(mask_word(mask, n_words, 4 * g + k));
-    group[g] = n;
-  }
-}
-
-// Workgroup g0 + blockIdx.x owns rows [256 g, 256 g + 256); group[g] is its first output row.
-__global__ __launch_bounds__(256) void k_value_write(ValIn in, int ncols, uint64_t g0, uint64_t n_rows,
-                                                     const uint64_t *__restrict__ mask, uint64_t n_words,
-                                                     const uint64_t *__restrict__ group, uint64_t total, ValOut out) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint64_t g = g0 + blockIdx.x, r = g * 256 + threadIdx.x;
-  uint64_t pos = group[g];
-  for (int k = 0; k < wave; k++) pos += (uint64_t)__popcll(mask_word(mask, n_words, 4 * g + k));
-  const uint64_t mine = mask_word(mask, n_words, 4 * g + wave);
-  pos += (uint64_t)__popcll(mine & ((1ull << lane) - 1));
-  // (a set bit is a row < n_rows, and pos < total: the groups' counts are the popcounts of the same words)
-  if (((mine >> lane) & 1ull) && r < n_rows && pos < total) {
-#pragma unroll
-    for (int c = 0; c < VAL_MAX_COLS; c++)
-      if (c < ncols) out.c[c][pos] = in.c[c][r];
-  }
-}
-
-// split under gg_debug_max_grid_tiles like the edge filter
-int value_write_launch(gg_ctx *ctx, const ValIn &in, int ncols, uint64_t n_rows, const uint64_t *mask, uint64_t n_words,
-                       const uint64_t *group, uint64_t total, const ValOut &out) {
-  const uint64_t groups = (n_rows + 255) / 256;
-  const uint64_t per_launch = ctx->max_grid_tiles && ctx->max_grid_tiles < VAL_MAX_GROUPS ? ctx->max_grid_tiles : VAL_MAX_GROUPS;
-  for (uint64_t g0 = 0; g0 < groups; g0 += per_launch) {
-    const uint64_t ng = groups - g0 < per_launch ? groups - g0 : per_launch;
-    GG_LAUNCH(ctx, "k_value_write", k_value_write, dim3((unsigned)ng), dim3(256), 0, in, ncols, g0, n_rows, mask, n_words,
-              group, total, out);
-  }
-  return GG_OK;
 }
 
 struct ValueKeys {  // the key source of gg_top.h: the rows' values, the tie column (null: none) and the pass mask

@@ -44,6 +44,7 @@ SYMBOLS = [
     "gg_result_extend_edge", "gg_debug_extend",
     "gg_result_group_by", "gg_debug_group",
     "gg_result_filter_value", "gg_result_top_rows", "gg_debug_value_top",
+    "gg_result_distinct", "gg_debug_distinct",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -107,6 +108,10 @@ class ValueFilterStats(C.Structure):
 class ValueTopStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_valued", C.c_uint64), ("candidates", C.c_uint64), ("rows_out", C.c_uint64),
                 ("select_passes", C.c_uint32), ("sort_route", C.c_uint32)]
+
+
+class DistinctStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("slots", C.c_uint64), ("probe_steps", C.c_uint64)]
 
 
 class AggStats(C.Structure):
@@ -278,6 +283,9 @@ def load_library(path: str | None = None):
     lib.gg_result_top_rows.argtypes = [P, P, C.c_int, C.c_int, P, i64p, C.POINTER(u64), C.c_int64, C.c_int64, C.c_int,
                                        C.c_int, C.c_int, u64, C.POINTER(ValueTopStats), C.POINTER(P)]
     lib.gg_debug_value_top.argtypes = [P, C.c_int, C.c_uint32]
+    lib.gg_result_distinct.argtypes = [P, P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(DistinctStats),
+                                       C.POINTER(P)]
+    lib.gg_debug_distinct.argtypes = [P, u64, C.c_int]
     lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
@@ -1034,6 +1042,24 @@ class GG:
         """top_rows orders its survivors in LDS (1) or by the global passes (2) and compacts the selection's candidates at
         candidate_floor or fewer (0: the defaults).  Results must not depend on it."""
         self._chk(self.lib.gg_debug_value_top(self.ctx, int(sort_route), int(candidate_floor)))
+
+    def distinct(self, res: KhopResult, hops: int, cols, materialise: bool = True):
+        """gg_result_distinct: SELECT DISTINCT over the columns `cols` (pairwise different numbers in 0..hops, in output
+        order) of res's `hops`-hop table.  Cells are compared as raw int64 values.  One row per distinct tuple — the first
+        input row that holds it — in input order.  Returns {"rows_in", "rows_out", "slots", "probe_steps"}; with
+        materialise, (that dict, KhopResult whose table len(cols) - 1 holds the rows — the caller closes it)."""
+        cs = [int(c) for c in cols]
+        arr = (C.c_int * max(len(cs), 1))(*cs)
+        st, out = DistinctStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_distinct(self.ctx, res.handle, hops, arr, len(cs), int(materialise), C.byref(st),
+                                              C.byref(out) if materialise else None))
+        d = {f: int(getattr(st, f)) for f, _ in DistinctStats._fields_}
+        return (d, KhopResult(self, out, d)) if materialise else d
+
+    def debug_distinct(self, slots: int = 0, combine: int = 0):
+        """distinct uses a table of `slots` slots (0: the default; rounded up to a power of two above the row count) and,
+        with combine = 1, never combines adjacent equal lanes.  Results must not depend on it."""
+        self._chk(self.lib.gg_debug_distinct(self.ctx, int(slots), int(combine)))
 
     def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
         """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows

@@ -762,6 +762,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterExtendFunctions(*con.context);
 	GGRegisterGroupFunctions(*con.context);
 	GGRegisterValueRowsFunctions(*con.context);
+	GGRegisterDistinctFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterCheapestFunctions(*con.context);

@@ -73,6 +73,13 @@
  *           benchmark/ldbc/queries/interactive-complex-2.sql:5,8-9, interactive-complex-9.sql:16-18; a date range before the
  *           GROUP BY, interactive-complex-4.sql:9,18, interactive-complex-3.sql:20,27; k2.k_person2id <> :person,
  *           interactive-complex-9.sql:12)
+ *   gg_result_distinct
+ *        <- PhysicalHashAggregate without aggregates above a join chain (SELECT DISTINCT / UNION)
+ *                                                               src/execution/physical_plan/plan_distinct.cpp:12-78,
+ *                                                               physical_hash_aggregate.cpp:152-266
+ *           (SELECT DISTINCT k2.k_person2id, benchmark/ldbc/queries/interactive-complex-10.sql:19-24; the friends UNION of
+ *           interactive-complex-6.sql:3-12 before it is joined with message; SELECT DISTINCT p1.personid, p2.personid,
+ *           bi-14.sql:30-102; count(DISTINCT m_messageid), interactive-complex-10.sql:2-9)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -288,7 +295,8 @@ int gg_expand_khop_edges(gg_ctx *ctx, const gg_csr *csr, const int64_t *src_ids,
 /* Copy rows [offset, offset+max_rows) of the edge columns e1..e_hops into ecols[0..hops-1]. */
 int gg_result_fetch_edges(const gg_result *res, int hops, uint64_t offset, uint32_t max_rows, int64_t *const *ecols,
                           uint32_t *n_out);
-/* Checksum of the `hops`-hop rows (k_min <= hops <= k_max of the result, so up to GG_MAX_HOPS) as they stand in HBM:
+/* Checksum of the `hops`-hop rows (k_min <= hops <= k_max of the result, so 0 — a one-column table of
+ * gg_result_distinct, whose row hash is the dense index itself — up to GG_MAX_HOPS) as they stand in HBM:
  * every id of every row is mapped back to its dense index and the rows' hashes are summed exactly as
  * gg_khop_stats.digest[hops] sums them, so a materialising expansion can be compared with the count-only expansion (and
  * with the oracle) over ALL its rows without fetching them.  Fails with GG_ERR_STATE if a row holds an id that is not a
@@ -512,6 +520,47 @@ int gg_result_top_rows(gg_ctx *ctx, const gg_result *res, int hops, int value_co
                        const int64_t *values, const uint64_t *valid /* nullable */, int64_t lo, int64_t hi, int mode,
                        int descending, int tie_col /* -1: none */, uint64_t n, gg_value_top_stats *stats /* nullable */,
                        gg_result **out_result);
+/* SELECT DISTINCT over chosen columns of a materialised walk table: projection plus DISTINCT, on the device.
+ * What it replaces in the reference: the hash aggregate without aggregates that SELECT DISTINCT and UNION plan
+ * (src/execution/physical_plan/plan_distinct.cpp:12-78) above a join chain — `SELECT DISTINCT k2.k_person2id`
+ * (benchmark/ldbc/queries/interactive-complex-10.sql:19-24), the friends UNION of interactive-complex-3/5/6/9/11 before it
+ * is joined with message, `SELECT DISTINCT p1.personid, p2.personid` above chains that leave knows (bi-14.sql:30-102), and
+ * count(DISTINCT m_messageid) per person (interactive-complex-10.sql:2-9): this call over (person, message), then
+ * gg_result_group_by.  A 2-hop walk table holds a friend of a friend once per middle vertex; without this call every later
+ * join and count sees that person once per walk.
+ * Input: the `hops`-hop table of `res` — whatever gg_result_filter_value accepts: plain, filtered, extended and
+ * gg_result_top_rows tables and this call's own output.
+ * Columns: `cols` holds n_cols pairwise different column numbers in 0..hops, in any order, 1 <= n_cols <= hops + 1.  Their
+ * order is the output's column order: the call is a projection too.
+ * Equality: two rows are equal iff their int64 cells are equal in every chosen column — raw 64-bit values, no id
+ * dictionary, no CSR; a cell that is a vertex of nothing, INT64_MIN and -1 are values like any other.
+ * Output: table n_cols - 1 of *out_result (k_min = k_max = n_cols - 1), whose column j is the input's column cols[j]; no
+ * edge columns (the projection drops them).  n_cols == 1 gives a one-column table 0.  One row per distinct tuple: the first
+ * input row that holds it, and the rows stay in input order — placed by count, scan, write, so they are identical on every
+ * run, for every slot count and under every testing knob.  The result answers every reader of a walk table: gg_result_rows,
+ * gg_result_fetch, gg_result_digest, both filters, gg_result_extend_edge, gg_result_group_by, gg_result_filter_value,
+ * gg_result_top_rows and this call.
+ * materialise == 0: only `stats` is filled (out_result may be NULL) — count(DISTINCT ...) in 64-bit counters.  stats may be
+ * NULL when materialising.  One host synchronisation when counting, two when rows are written.
+ * How: an open-addressing table of 32-bit row numbers (4 bytes per slot whatever n_cols is, no sentinel among the ids), a
+ * power of two strictly greater than rows_in — the next power of two >= 2 rows_in by default, at most 2^32 — so an empty
+ * slot always exists; the probe loop is bounded by the slot count all the same, and a row that exhausts it makes the call
+ * GG_ERR_STATE.
+ * Errors: NULL ctx / res / cols, an object of another context, hops outside the result's k_min..k_max, n_cols outside
+ * 1..hops + 1, a column outside 0..hops or repeated, materialise != 0 with NULL out_result, stats and out_result both NULL:
+ * GG_ERR_INVALID_ARG.  A result of another kind: GG_ERR_INVALID_ARG or GG_ERR_STATE by the rule of gg_result's kinds
+ * (above).  An input of 2^32 rows or more: GG_ERR_TOO_LARGE — row numbers are 32-bit here, as in gg_result_top_rows.  A
+ * table that does not fit: GG_ERR_OOM.  After every error the context stays usable.  An empty input gives GG_OK, an empty
+ * table and slots == 0. */
+typedef struct gg_distinct_stats {
+  uint64_t rows_in;      /* rows of the input table */
+  uint64_t rows_out;     /* distinct tuples over the chosen columns */
+  uint64_t slots;        /* slots of the table the call used (0: nothing to do) */
+  uint64_t probe_steps;  /* slots inspected by the insert pass, a diagnostic: may differ from run to run */
+} gg_distinct_stats;
+int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, const int *cols, int n_cols,
+                       int materialise, gg_distinct_stats *stats /* nullable when materialising */,
+                       gg_result **out_result /* NULL allowed iff materialise == 0 */);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
@@ -1234,6 +1283,11 @@ int gg_debug_group(gg_ctx *ctx, int route /* 0 auto, 1 LDS where the table fits,
  * passes (csrc/gg_top.h) but not this setting, so a test of one never moves the other.  sort_route 1 is taken while min(n,
  * rows_in) <= GG_CHUNK_ROWS.  Results must not depend on it.  A sort_route outside 0..2 is GG_ERR_INVALID_ARG. */
 int gg_debug_value_top(gg_ctx *ctx, int sort_route /* 0 auto, 1 LDS, 2 global */, uint32_t candidate_floor /* 0: default */);
+/* Testing knob: gg_result_distinct uses a table of `slots` slots (0: the default, the next power of two >= 2 rows_in).
+ * slots is rounded up to a power of two and raised to the smallest power of two above rows_in where it is lower, so a forced
+ * load of almost 1 stays legal and an empty slot always exists.  combine = 1: no lanes of a wavefront are combined, every
+ * row probes.  Results must not depend on either.  A combine outside 0..1 is GG_ERR_INVALID_ARG. */
+int gg_debug_distinct(gg_ctx *ctx, uint64_t slots /* 0: default */, int combine /* 0 auto, 1 never combine adjacent lanes */);
 /* Testing hook, stateless: the library's shared exclusive prefix scan over a host array.  `in` and `out` are n values of
  * `width` bytes (4: uint32, 8: uint64); out[i] = in[0] + ... + in[i-1] — the width-4 form mod 2^32 — and *total is the
  * exact sum in 64 bits, which must stay below 2^62 (the scan's status words keep two flag bits; a larger sum is not
