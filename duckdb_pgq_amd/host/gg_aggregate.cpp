@@ -33,32 +33,14 @@
 //
 // The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
 // The weights are read in the statement's own transaction and brought into the order of the graph's vertex table.  The
-// groups stay on the device and the pipeline's threads drain them together (GGResultDrain, gg_operators.hpp).
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
+// groups stay on the device and the pipeline's threads drain them together.
 #include <unordered_map>
 
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
 namespace {
-
-class AggregateState : public GlobalSourceState {
-public:
-	idx_t MaxThreads() override {
-		return max_threads;
-	}
-	gg_agg_stats stats {};
-	GGResultDrain drain;
-	idx_t max_threads = 1;
-	idx_t next_rank = 0; // gg_khop_aggregate_top: the rank of the next row to leave
-};
 
 //! a sink that collects (key, value) pairs on the host (GGKeyedValues, gg_extension.hpp): rows with a NULL key are skipped,
 //! a NULL value is kept as 0 with has = 0
@@ -174,53 +156,53 @@ static vector<int64_t> WeightsInVertexOrder(ClientContext &context, GGGraph &gra
 	return weights;
 }
 
-} // namespace
-
-PhysicalGGKhopAggregate::PhysicalGGKhopAggregate(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p,
-                                                 bool all_sources_p, int group_by_p, vector<int64_t> weights_p,
-                                                 bool weighted_p, idx_t estimated_cardinality)
-    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), estimated_cardinality), graph(move(graph_p)),
-      hops(hops_p), sources(move(sources_p)), all_sources(all_sources_p), group_by(group_by_p), weights(move(weights_p)),
-      weighted(weighted_p) {
-}
-
-vector<LogicalType> PhysicalGGKhopAggregate::OutputTypes() {
-	return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::HUGEINT};
-}
-
-unique_ptr<GlobalSourceState> PhysicalGGKhopAggregate::GetGlobalSourceState(ClientContext &context) const {
-	auto state = make_unique<AggregateState>();
-	lock_guard<mutex> guard(graph->lock);
-	if (!graph->csr) {
-		throw InternalException("GG_KHOP_AGGREGATE scheduled before the CSR was built");
+//! Source: one row (vertex BIGINT, walks BIGINT, total HUGEINT) per vertex that starts (group_by GG_GROUP_START) or ends
+//! (GG_GROUP_END) a `hops`-hop walk from the sources: the number of such walks and the sum of the weights at their other
+//! end (gg_khop_aggregate, include/gg.h).  weights: one per vertex in the graph's vertex-table order (weighted false:
+//! counts only, total = walks).
+class PhysicalGGKhopAggregate : public GGWalkSource {
+public:
+	PhysicalGGKhopAggregate(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p, bool all_sources_p,
+	                        int group_by_p, vector<int64_t> weights_p, bool weighted_p,
+	                        vector<LogicalType> types = OutputTypes())
+	    : GGWalkSource(move(types), move(graph_p), hops_p, move(sources_p), all_sources_p), group_by(group_by_p),
+	      weights(move(weights_p)), weighted(weighted_p) {
 	}
-	static const int64_t none = 0; // an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex)
-	const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
-	state->drain.Replace(context, hops, [&](idx_t &rows) {
-		GGResultPtr owner;
-		GGGraph::Check(gg_khop_aggregate(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops, hops,
-		                                 group_by, weighted ? weights.data() : nullptr, &state->stats, GGResultOut(owner)),
+	static vector<LogicalType> OutputTypes() {
+		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::HUGEINT};
+	}
+	typedef GGDrainStateOf<gg_agg_stats> State;
+
+	int group_by; // GG_GROUP_START / GG_GROUP_END
+	vector<int64_t> weights;
+	bool weighted;
+
+	//! the groups, on the device; caller holds graph->lock
+	void Aggregate(State &state, GGResultPtr &out) const {
+		GGGraph::Check(gg_khop_aggregate(graph->ctx, graph->csr, SourceIds(), SourceCount(), hops, hops, group_by,
+		                                 weighted ? weights.data() : nullptr, &state.stats, GGResultOut(out)),
 		               "gg_khop_aggregate");
-		rows = state->stats.groups[hops];
-		return owner;
-	});
-	state->max_threads = GGResultSlab::ThreadsFor(state->stats.groups[hops]);
-	return move(state);
-}
-
-unique_ptr<LocalSourceState> PhysicalGGKhopAggregate::GetLocalSourceState(ExecutionContext &context,
-                                                                          GlobalSourceState &gstate) const {
-	return make_unique<GGResultSlab>(graph);
-}
-
-void PhysicalGGKhopAggregate::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
-                                      LocalSourceState &lstate) const {
-	auto &gstate = (AggregateState &)gstate_p;
-	if (context.client.interrupted) {
-		throw InterruptException();
 	}
-	auto &slab = (GGResultSlab &)lstate;
-	if (slab.pos >= slab.rows) {
+
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
+		auto state = make_unique<State>();
+		lock_guard<mutex> guard(graph->lock);
+		if (!graph->csr) {
+			throw InternalException("GG_KHOP_AGGREGATE scheduled before the CSR was built");
+		}
+		state->drain.Replace(context, hops, [&](idx_t &rows) {
+			GGResultPtr owner;
+			Aggregate(*state, owner);
+			rows = state->stats.groups[hops];
+			return owner;
+		});
+		state->max_threads = GGResultSlab::ThreadsFor(state->stats.groups[hops]);
+		return move(state);
+	}
+
+	//! Serves the next groups: vertex and walks as they are into chunk.data[first ..], then the total, whose halves lie
+	//! side by side in the slab.  Returns their number (0: nothing is left).
+	idx_t EmitGroups(State &gstate, GGResultSlab &slab, DataChunk &chunk, idx_t first) const {
 		auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
 			uint32_t got = 0;
 			auto columns = slab.Columns(4); // vertex id, walks, low and high half of the total
@@ -229,71 +211,29 @@ void PhysicalGGKhopAggregate::GetData(ExecutionContext &context, DataChunk &chun
 			               "gg_khop_aggregate_fetch");
 			return got;
 		};
-		if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
-			return;
+		if (!Refill(gstate, slab, fetch)) {
+			return 0;
 		}
+		const idx_t at = slab.pos;
+		const idx_t n = slab.Emit(chunk, first, 2);
+		auto total = FlatVector::GetData<hugeint_t>(chunk.data[first + 2]);
+		for (idx_t i = 0; i < n; i++) {
+			total[i].lower = (uint64_t)slab.column[2][at + i];
+			total[i].upper = slab.column[3][at + i];
+		}
+		return n;
 	}
-	// the two BIGINT columns as they are; the total's halves side by side
-	const idx_t first = slab.pos;
-	const idx_t n = slab.Emit(chunk, 0, 2);
-	auto total = FlatVector::GetData<hugeint_t>(chunk.data[2]);
-	for (idx_t i = 0; i < n; i++) {
-		total[i].lower = (uint64_t)slab.column[2][first + i];
-		total[i].upper = slab.column[3][first + i];
-	}
-}
 
-static unique_ptr<FunctionData> KhopAggregateBind(ClientContext &context, vector<Value> &inputs,
-                                                  unordered_map<string, Value> &named_parameters,
-                                                  vector<LogicalType> &input_table_types,
-                                                  vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                  vector<string> &names) {
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
-	if (inputs[6].is_null || inputs[7].is_null) {
-		throw BinderException("gg_khop_aggregate: hops and group_by must not be NULL");
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
+	             LocalSourceState &lstate) const override {
+		PollInterrupt(context);
+		EmitGroups((State &)gstate, (GGResultSlab &)lstate, chunk, 0);
 	}
-	const auto hops = inputs[6].GetValue<int64_t>();
-	const string group_name = inputs[7].ToString();
-	const bool weighted = !inputs[8].is_null;
-	const string weight_column = weighted ? inputs[8].ToString() : string();
-	if (hops < 1 || hops > GG_MAX_HOPS) {
-		throw BinderException("gg_khop_aggregate: need 1 <= hops <= " + to_string(GG_MAX_HOPS));
-	}
-	int group_by;
-	if (group_name == "start") {
-		group_by = GG_GROUP_START;
-	} else if (group_name == "end") {
-		group_by = GG_GROUP_END;
-	} else {
-		throw BinderException("gg_khop_aggregate: group_by '" + group_name + "' (one of 'start', 'end')");
-	}
-	auto data = make_unique<GGFunctionData>();
-	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
-		opened.graph = GGBuildGraph(ctx, spec);
-		vector<int64_t> sources, weights;
-		if (!sources_sql.empty()) {
-			sources = GGQueryInt64Column(ctx, sources_sql, "gg_khop_aggregate: sources");
-		}
-		if (weighted) {
-			weights = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, weight_column);
-		}
-		opened.source = make_unique<PhysicalGGKhopAggregate>(opened.graph, (int)hops, move(sources), sources_sql.empty(),
-		                                                     group_by, move(weights), weighted, 0);
-	};
-	data->parallel_result = true;
-	data->description = (weighted ? "count, sum(" + weight_column + ")" : string("count")) + " by " + group_name + " over " +
-	                    to_string(hops) + "-hop walks of " + edge_table;
-	return_types = PhysicalGGKhopAggregate::OutputTypes();
-	names = {"vertex", "walks", "total"};
-	return move(data);
-}
 
-namespace {
+	string GetName() const override {
+		return "GG_KHOP_AGGREGATE";
+	}
+};
 
 //! The first n groups of PhysicalGGKhopAggregate's answer in rank order: gg_khop_aggregate_top behind gg_khop_aggregate
 class PhysicalGGKhopAggregateTop : public PhysicalGGKhopAggregate {
@@ -302,9 +242,8 @@ public:
 	                           int group_by_p, vector<int64_t> weights_p, bool weighted_p, int order_by_p, bool descending_p,
 	                           vector<int64_t> bias_p, bool biased_p, uint64_t n_p)
 	    : PhysicalGGKhopAggregate(move(graph_p), hops_p, move(sources_p), all_sources_p, group_by_p, move(weights_p),
-	                              weighted_p, 0),
+	                              weighted_p, OutputTypes()),
 	      order_by(order_by_p), descending(descending_p), bias(move(bias_p)), biased(biased_p), n(n_p) {
-		types = OutputTypes();
 	}
 	static vector<LogicalType> OutputTypes() {
 		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::HUGEINT};
@@ -317,19 +256,14 @@ public:
 	uint64_t n;
 
 	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
-		auto state = make_unique<AggregateState>();
+		auto state = make_unique<State>(); // (max_threads stays 1: the rows leave in rank order)
 		lock_guard<mutex> guard(graph->lock);
 		if (!graph->csr) {
 			throw InternalException("GG_KHOP_AGGREGATE_TOP scheduled before the CSR was built");
 		}
-		static const int64_t none = 0; // (an EMPTY list must not arrive as a null pointer)
-		const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
 		state->drain.Replace(context, hops, [&](idx_t &rows) {
 			GGResultPtr groups, owner;
-			GGGraph::Check(gg_khop_aggregate(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops, hops,
-			                                 group_by, weighted ? weights.data() : nullptr, &state->stats,
-			                                 GGResultOut(groups)),
-			               "gg_khop_aggregate");
+			Aggregate(*state, groups);
 			gg_top_stats top {};
 			GGGraph::Check(gg_khop_aggregate_top(graph->ctx, groups.get(), hops, order_by, descending ? 1 : 0, n,
 			                                     biased ? graph->csr : nullptr, biased ? bias.data() : nullptr, &top,
@@ -338,40 +272,13 @@ public:
 			rows = top.rows_out;
 			return owner; // (the groups go back to the pool here: only the top rows stay in HBM)
 		});
-		state->max_threads = 1; // the rows leave in rank order
 		return move(state);
 	}
 
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
 	             LocalSourceState &lstate) const override {
-		auto &gstate = (AggregateState &)gstate_p;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
-		auto &slab = (GGResultSlab &)lstate;
-		if (slab.pos >= slab.rows) {
-			auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
-				uint32_t got = 0;
-				auto columns = slab.Columns(4);
-				GGGraph::Check(gg_khop_aggregate_fetch(result, table, offset, want, columns[0], (uint64_t *)columns[1],
-				                                       (uint64_t *)columns[2], columns[3], &got),
-				               "gg_khop_aggregate_fetch");
-				return got;
-			};
-			if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) {
-				return;
-			}
-		}
-		const idx_t first = slab.pos;
-		const idx_t count = slab.Emit(chunk, 1, 2);
-		auto rank = FlatVector::GetData<int64_t>(chunk.data[0]);
-		auto total = FlatVector::GetData<hugeint_t>(chunk.data[3]);
-		for (idx_t i = 0; i < count; i++) {
-			rank[i] = (int64_t)(gstate.next_rank + i); // (one thread: the slabs are claimed and emitted in order)
-			total[i].lower = (uint64_t)slab.column[2][first + i];
-			total[i].upper = slab.column[3][first + i];
-		}
-		gstate.next_rank += count;
+		PollInterrupt(context);
+		EmitRank((State &)gstate, chunk, EmitGroups((State &)gstate, (GGResultSlab &)lstate, chunk, 1));
 	}
 
 	string GetName() const override {
@@ -379,94 +286,87 @@ public:
 	}
 };
 
-} // namespace
+enum { GROUPS, TOP };
 
-static unique_ptr<FunctionData> KhopAggregateTopBind(ClientContext &context, vector<Value> &inputs,
-                                                     unordered_map<string, Value> &named_parameters,
-                                                     vector<LogicalType> &input_table_types,
-                                                     vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                     vector<string> &names) {
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
-	if (inputs[6].is_null || inputs[7].is_null || inputs[9].is_null || inputs[10].is_null || inputs[12].is_null) {
-		throw BinderException("gg_khop_aggregate_top: hops, group_by, order_by, descending and n must not be NULL");
-	}
-	const auto hops = inputs[6].GetValue<int64_t>();
+//! gg_khop_aggregate, and with four more arguments gg_khop_aggregate_top
+unique_ptr<FunctionData> KhopAggregateBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                           vector<string> &names, int kind) {
+	const bool top = kind == TOP;
+	const GGWalkArguments args = top ? GGWalkArguments("gg_khop_aggregate_top", inputs, GGWalkArguments::NO_EXTENSION,
+	                                                   {6, 7, 9, 10, 12}, "hops, group_by, order_by, descending and n")
+	                                 : GGWalkArguments("gg_khop_aggregate", inputs, GGWalkArguments::NO_EXTENSION, {6, 7},
+	                                                   "hops and group_by");
+	const string &fn = args.fn;
 	const string group_name = inputs[7].ToString();
 	const bool weighted = !inputs[8].is_null;
 	const string weight_column = weighted ? inputs[8].ToString() : string();
-	const string order_name = inputs[9].ToString();
-	const bool descending = inputs[10].GetValue<bool>();
-	const bool biased = !inputs[11].is_null;
+	const string order_name = top ? inputs[9].ToString() : string();
+	const bool descending = top && inputs[10].GetValue<bool>();
+	const bool biased = top && !inputs[11].is_null;
 	const string bias_column = biased ? inputs[11].ToString() : string();
-	const auto n = inputs[12].GetValue<int64_t>();
-	if (hops < 1 || hops > GG_MAX_HOPS) {
-		throw BinderException("gg_khop_aggregate_top: need 1 <= hops <= " + to_string(GG_MAX_HOPS));
-	}
+	const auto n = top ? inputs[12].GetValue<int64_t>() : 0;
 	if (n < 0) {
-		throw BinderException("gg_khop_aggregate_top: n must not be negative");
+		throw BinderException(fn + ": n must not be negative");
 	}
-	int group_by, order_by;
+	int group_by, order_by = GG_TOP_BY_TOTAL;
 	if (group_name == "start") {
 		group_by = GG_GROUP_START;
 	} else if (group_name == "end") {
 		group_by = GG_GROUP_END;
 	} else {
-		throw BinderException("gg_khop_aggregate_top: group_by '" + group_name + "' (one of 'start', 'end')");
+		throw BinderException(fn + ": group_by '" + group_name + "' (one of 'start', 'end')");
 	}
-	if (order_name == "total") {
-		order_by = GG_TOP_BY_TOTAL;
-	} else if (order_name == "walks") {
+	if (top && order_name == "walks") {
 		order_by = GG_TOP_BY_WALKS;
-	} else {
-		throw BinderException("gg_khop_aggregate_top: order_by '" + order_name + "' (one of 'total', 'walks')");
+	} else if (top && order_name != "total") {
+		throw BinderException(fn + ": order_by '" + order_name + "' (one of 'total', 'walks')");
 	}
 	if (biased && order_by == GG_TOP_BY_WALKS) {
-		throw BinderException("gg_khop_aggregate_top: a bias_column is added to the total only");
+		throw BinderException(fn + ": a bias_column is added to the total only");
 	}
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
-		opened.graph = GGBuildGraph(ctx, spec);
-		vector<int64_t> sources, weights, bias;
-		if (!sources_sql.empty()) {
-			sources = GGQueryInt64Column(ctx, sources_sql, "gg_khop_aggregate_top: sources");
-		}
+		opened.graph = args.BuildGraph(ctx);
+		vector<int64_t> sources = args.Sources(ctx), weights, bias;
 		if (weighted) {
-			weights = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, weight_column);
+			weights = WeightsInVertexOrder(ctx, *opened.graph, args.vertex_table, args.vertex_key, weight_column);
 		}
 		if (biased) {
-			bias = WeightsInVertexOrder(ctx, *opened.graph, vertex_table, vertex_key, bias_column);
+			bias = WeightsInVertexOrder(ctx, *opened.graph, args.vertex_table, args.vertex_key, bias_column);
 		}
-		opened.source = make_unique<PhysicalGGKhopAggregateTop>(opened.graph, (int)hops, move(sources), sources_sql.empty(),
-		                                                        group_by, move(weights), weighted, order_by, descending,
-		                                                        move(bias), biased, (uint64_t)n);
+		if (top) {
+			opened.source = make_unique<PhysicalGGKhopAggregateTop>(opened.graph, (int)args.hops, move(sources),
+			                                                        args.AllSources(), group_by, move(weights), weighted,
+			                                                        order_by, descending, move(bias), biased, (uint64_t)n);
+		} else {
+			opened.source = make_unique<PhysicalGGKhopAggregate>(opened.graph, (int)args.hops, move(sources), args.AllSources(),
+			                                                     group_by, move(weights), weighted);
+		}
 	};
-	data->parallel_result = false; // the rows leave in rank order
-	data->description = "top " + to_string(n) + " by " + (biased ? bias_column + " + " : string()) + order_name +
-	                    (descending ? " desc" : "") + " of " +
-	                    (weighted ? "count, sum(" + weight_column + ")" : string("count")) + " by " + group_name + " over " +
-	                    to_string(hops) + "-hop walks of " + edge_table;
-	return_types = PhysicalGGKhopAggregateTop::OutputTypes();
-	names = {"rank", "vertex", "walks", "total"};
+	data->parallel_result = !top; // (the top's rows leave in rank order)
+	data->description = (weighted ? "count, sum(" + weight_column + ")" : string("count")) + " by " + group_name + " over " +
+	                    args.Describe();
+	if (top) {
+		data->description = "top " + to_string(n) + " by " + (biased ? bias_column + " + " : string()) + order_name +
+		                    (descending ? " desc" : "") + " of " + data->description;
+		return_types = PhysicalGGKhopAggregateTop::OutputTypes();
+		names = {"rank", "vertex", "walks", "total"};
+	} else {
+		return_types = PhysicalGGKhopAggregate::OutputTypes();
+		names = {"vertex", "walks", "total"};
+	}
 	return move(data);
 }
 
+} // namespace
+
 void GGRegisterAggregateFunctions(ClientContext &context) {
-	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::BIGINT,  LogicalType::VARCHAR, LogicalType::VARCHAR};
-	auto fn = GGScanFunction("gg_khop_aggregate", args, KhopAggregateBind);
-	CreateTableFunctionInfo info(fn);
-	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
-	vector<LogicalType> top_args = args;
+	auto args = GGWalkArguments::Types(false);
+	args.insert(args.end(), {LogicalType::VARCHAR, LogicalType::VARCHAR});
+	auto top_args = args;
 	top_args.insert(top_args.end(), {LogicalType::VARCHAR, LogicalType::BOOLEAN, LogicalType::VARCHAR, LogicalType::BIGINT});
-	auto top_fn = GGScanFunction("gg_khop_aggregate_top", top_args, KhopAggregateTopBind);
-	CreateTableFunctionInfo top_info(top_fn);
-	Catalog::GetCatalog(context).CreateTableFunction(context, &top_info);
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_khop_aggregate", args, GGBind<KhopAggregateBind, GROUPS>),
+	                                   GGScanFunction("gg_khop_aggregate_top", top_args, GGBind<KhopAggregateBind, TOP>)});
 }
 
 } // namespace duckdb

@@ -34,16 +34,9 @@
 // by rowid and handed over as GG_WEIGHTS_BY_ROWID, once per statement; a NULL or negative weight and a column that is no
 // integer raise.  One batch of 64 sources is resident at a time: the pipeline's threads drain its rows together
 // (GGResultDrain, gg_operators.hpp), and whoever claims the last of them runs the next batch under the graph's lock.
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
 #include <unordered_set>
 
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
@@ -79,20 +72,18 @@ struct GGWeightsDestroy {
 };
 typedef std::unique_ptr<gg_edge_weights, GGWeightsDestroy> GGWeightsPtr;
 
-class PhysicalGGCheapestPath : public PhysicalOperator {
+class PhysicalGGCheapestPath : public GGResultSource {
 public:
 	PhysicalGGCheapestPath(shared_ptr<GGGraph> graph_p, GGWeightsPtr weights_p, int64_t max_hops_p,
 	                       vector<int64_t> sources_p, bool all_sources_p, vector<int64_t> targets_p, bool all_targets_p)
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), 0), graph(move(graph_p)),
-	      weights(move(weights_p)), max_hops(max_hops_p), sources(move(sources_p)), all_sources(all_sources_p),
-	      targets(move(targets_p)), all_targets(all_targets_p) {
+	    : GGResultSource(OutputTypes(), move(graph_p)), weights(move(weights_p)), max_hops(max_hops_p),
+	      sources(move(sources_p)), all_sources(all_sources_p), targets(move(targets_p)), all_targets(all_targets_p) {
 	}
 	static vector<LogicalType> OutputTypes() {
 		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::INTEGER};
 	}
 
-	shared_ptr<GGGraph> graph;
-	GGWeightsPtr weights; // (declared after the graph: destroyed before it, as gg.h asks)
+	GGWeightsPtr weights; // (a member of the derived class: destroyed before the base's graph, as gg.h asks)
 	int64_t max_hops;
 	vector<int64_t> sources; // distinct (ignored if all_sources)
 	bool all_sources;
@@ -102,8 +93,7 @@ public:
 	//! the rows of the batch starting at source batch_base; caller holds graph->lock
 	GGResultPtr RunBatch(CheapestState &state, idx_t batch_base, idx_t &rows) const {
 		const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - batch_base);
-		static const int64_t none = 0; // an EMPTY target list must not arrive as a null pointer (gg.h: null means every vertex)
-		const int64_t *dst = all_targets ? nullptr : targets.empty() ? &none : targets.data();
+		const int64_t *dst = all_targets ? nullptr : GGSourceIds(targets);
 		GGResultPtr owner;
 		GGGraph::Check(gg_cheapest64(graph->ctx, graph->csr, weights.get(), state.uniq.data() + batch_base, n, max_hops, dst,
 		                             all_targets ? 0 : targets.size(), nullptr, GGResultOut(owner)),
@@ -134,17 +124,11 @@ public:
 		return move(state);
 	}
 
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
-		return make_unique<GGResultSlab>(graph);
-	}
-
 	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
 	             LocalSourceState &lstate) const override {
 		auto &gstate = (CheapestState &)gstate_p;
 		auto &slab = (GGResultSlab &)lstate;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
+		PollInterrupt(context);
 		if (slab.pos >= slab.rows) {
 			auto &drain = gstate.drain;
 			auto advance = [&]() -> bool { // current batch claimed completely: run the next one
@@ -191,12 +175,11 @@ public:
 };
 
 //! The path rows of gg_cheapest64_paths, batch by batch.
-class PhysicalGGCheapestPathRows : public PhysicalOperator {
+class PhysicalGGCheapestPathRows : public GGResultSource {
 public:
 	PhysicalGGCheapestPathRows(shared_ptr<GGGraph> graph_p, GGWeightsPtr weights_p, vector<int64_t> src_p,
 	                           vector<int64_t> dst_p)
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), 0), graph(move(graph_p)),
-	      weights(move(weights_p)), src(move(src_p)), dst(move(dst_p)) {
+	    : GGResultSource(OutputTypes(), move(graph_p)), weights(move(weights_p)), src(move(src_p)), dst(move(dst_p)) {
 		D_ASSERT(src.size() == dst.size());
 	}
 	static vector<LogicalType> OutputTypes() {
@@ -204,8 +187,7 @@ public:
 		        LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT};
 	}
 
-	shared_ptr<GGGraph> graph;
-	GGWeightsPtr weights; // (declared after the graph: destroyed before it, as gg.h asks)
+	GGWeightsPtr weights; // (a member of the derived class: destroyed before the base's graph, as gg.h asks)
 	vector<int64_t> src, dst;
 
 	//! trace the pairs of a batch; caller holds graph->lock
@@ -243,17 +225,11 @@ public:
 		return move(state);
 	}
 
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
-		return make_unique<GGResultSlab>(graph);
-	}
-
 	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
 	             LocalSourceState &lstate) const override {
 		auto &gstate = (ShortestPathRowsState &)gstate_p;
 		auto &slab = (GGResultSlab &)lstate;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
+		PollInterrupt(context);
 		if (slab.pos >= slab.rows) {
 			auto &drain = gstate.drain;
 			auto advance = [&]() -> bool { // current batch claimed completely: run the next one
@@ -357,29 +333,18 @@ static GGWeightsPtr WeightsByRowid(ClientContext &context, GGGraph &graph, const
 	return GGWeightsPtr(made);
 }
 
-} // namespace
-
-static unique_ptr<FunctionData> CheapestPathBind(ClientContext &context, vector<Value> &inputs,
-                                                 unordered_map<string, Value> &named_parameters,
-                                                 vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                                 vector<LogicalType> &return_types, vector<string> &names) {
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	if (inputs[5].is_null) {
-		throw BinderException("gg_cheapest_path: weight_column must not be NULL");
-	}
+unique_ptr<FunctionData> CheapestPathBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                          vector<string> &names, int kind) {
+	const GraphArguments args(inputs);
+	GGRequireArguments("gg_cheapest_path", inputs, {5}, "weight_column");
 	const string weight_column = inputs[5].ToString();
 	const string sources_sql = inputs[6].is_null ? string() : inputs[6].ToString();
 	const string targets_sql = inputs[7].is_null ? string() : inputs[7].ToString();
 	const int64_t max_hops = inputs[8].is_null ? -1 : MaxValue<int64_t>(-1, inputs[8].GetValue<int64_t>());
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, true);
-		spec.edges_with_rowid = true;
-		opened.graph = GGBuildGraphWithRowids(ctx, spec);
-		auto weights = WeightsByRowid(ctx, *opened.graph, edge_table, weight_column);
+		opened.graph = args.Build(ctx, true);
+		auto weights = WeightsByRowid(ctx, *opened.graph, args.edge_table, weight_column);
 		vector<int64_t> sources, targets;
 		if (!sources_sql.empty()) {
 			sources = Distinct(GGQueryInt64Column(ctx, sources_sql, "gg_cheapest_path: sources"));
@@ -392,55 +357,41 @@ static unique_ptr<FunctionData> CheapestPathBind(ClientContext &context, vector<
 	};
 	data->parallel_result = true;
 	data->description = "cheapest walks of " + (max_hops < 0 ? string("any length") : "at most " + to_string(max_hops) + " hops") +
-	                    " over " + edge_table + " weighted by " + weight_column;
+	                    " over " + args.edge_table + " weighted by " + weight_column;
 	return_types = PhysicalGGCheapestPath::OutputTypes();
 	names = {"source", "vertex", "cost", "hops"};
 	return move(data);
 }
 
-static unique_ptr<FunctionData> CheapestPathRowsBind(ClientContext &context, vector<Value> &inputs,
-                                                     unordered_map<string, Value> &named_parameters,
-                                                     vector<LogicalType> &input_table_types,
-                                                     vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                     vector<string> &names) {
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	if (inputs[5].is_null || inputs[6].is_null) {
-		throw BinderException("gg_cheapest_path_rows: weight_column and pairs_sql must not be NULL");
-	}
+unique_ptr<FunctionData> CheapestPathRowsBind(ClientContext &context, vector<Value> &inputs,
+                                              vector<LogicalType> &return_types, vector<string> &names, int kind) {
+	const GraphArguments args(inputs);
+	GGRequireArguments("gg_cheapest_path_rows", inputs, {5, 6}, "weight_column and pairs_sql");
 	const string weight_column = inputs[5].ToString(), pairs_sql = inputs[6].ToString();
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, true);
-		spec.edges_with_rowid = true;
-		opened.graph = GGBuildGraphWithRowids(ctx, spec);
-		auto weights = WeightsByRowid(ctx, *opened.graph, edge_table, weight_column);
+		opened.graph = args.Build(ctx, true);
+		auto weights = WeightsByRowid(ctx, *opened.graph, args.edge_table, weight_column);
 		vector<int64_t> src, dst;
 		GGQueryInt64Pairs(ctx, pairs_sql, "gg_cheapest_path_rows: pairs", src, dst);
 		opened.source = make_unique<PhysicalGGCheapestPathRows>(opened.graph, move(weights), move(src), move(dst));
 	};
 	data->parallel_result = true;
-	data->description = "cheapest paths over " + edge_table + " weighted by " + weight_column;
+	data->description = "cheapest paths over " + args.edge_table + " weighted by " + weight_column;
 	return_types = PhysicalGGCheapestPathRows::OutputTypes();
 	names = {"src", "dst", "step", "vertex", "edge_rowid", "cost"};
 	return move(data);
 }
 
+} // namespace
+
 void GGRegisterCheapestFunctions(ClientContext &context) {
-	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BIGINT};
-	auto fn = GGScanFunction("gg_cheapest_path", args, CheapestPathBind);
-	CreateTableFunctionInfo info(fn);
-	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
-	const vector<LogicalType> rows_args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                       LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                       LogicalType::VARCHAR};
-	auto rows_fn = GGScanFunction("gg_cheapest_path_rows", rows_args, CheapestPathRowsBind);
-	CreateTableFunctionInfo rows_info(rows_fn);
-	Catalog::GetCatalog(context).CreateTableFunction(context, &rows_info);
+	auto rows_args = GraphArguments::Types();
+	rows_args.insert(rows_args.end(), {LogicalType::VARCHAR, LogicalType::VARCHAR});
+	auto args = rows_args;
+	args.insert(args.end(), {LogicalType::VARCHAR, LogicalType::BIGINT});
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_cheapest_path", args, GGBind<CheapestPathBind>),
+	                                   GGScanFunction("gg_cheapest_path_rows", rows_args, GGBind<CheapestPathRowsBind>)});
 }
 
 } // namespace duckdb

@@ -16,45 +16,27 @@
 //
 // The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
 // The call runs under the graph's lock; the rows stay on the device and the pipeline's threads drain them together, each
-// through its own page-locked slab (GGResultDrain, gg_operators.hpp: one result, one table of it).
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+// through its own page-locked slab.
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
 namespace {
 
-class ComponentsState : public GlobalSourceState {
-public:
-	idx_t MaxThreads() override {
-		return max_threads;
-	}
-	gg_cc_stats stats {};
-	GGResultDrain drain;
-	idx_t max_threads = 1;
-};
-
-class PhysicalGGComponents : public PhysicalOperator {
+class PhysicalGGComponents : public GGResultSource {
 public:
 	PhysicalGGComponents(shared_ptr<GGGraph> graph_p, bool sizes_only_p)
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(sizes_only_p), 0), graph(move(graph_p)),
-	      sizes_only(sizes_only_p) {
+	    : GGResultSource(OutputTypes(sizes_only_p), move(graph_p)), sizes_only(sizes_only_p) {
 	}
 	static vector<LogicalType> OutputTypes(bool sizes_only) {
 		return vector<LogicalType>(sizes_only ? 2 : 3, LogicalType::BIGINT);
 	}
+	typedef GGDrainStateOf<gg_cc_stats> State;
 
-	shared_ptr<GGGraph> graph;
 	bool sizes_only; // table 1 of the result, not table 0
 
 	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
-		auto state = make_unique<ComponentsState>();
+		auto state = make_unique<State>();
 		lock_guard<mutex> guard(graph->lock);
 		if (!graph->csr) {
 			throw InternalException("GG_COMPONENTS scheduled before the CSR was built");
@@ -69,37 +51,26 @@ public:
 		return move(state);
 	}
 
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
-		return make_unique<GGResultSlab>(graph);
-	}
-
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
 	             LocalSourceState &lstate) const override {
-		auto &gstate = (ComponentsState &)gstate_p;
 		auto &slab = (GGResultSlab &)lstate;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
-		if (slab.pos >= slab.rows) {
-			auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
-				uint32_t got = 0;
-				if (table == 1) {
-					auto columns = slab.Columns(2);
-					GGGraph::Check(gg_components_fetch_sizes(result, offset, want, columns[0], (uint64_t *)columns[1], &got),
-					               "gg_components_fetch_sizes");
-				} else {
-					auto columns = slab.Columns(3);
-					GGGraph::Check(gg_components_fetch(result, offset, want, columns[0], columns[1],
-					                                   (uint64_t *)columns[2], &got),
-					               "gg_components_fetch");
-				}
-				return got;
-			};
-			if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
-				return;
+		PollInterrupt(context);
+		auto fetch = [](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
+			uint32_t got = 0;
+			if (table == 1) {
+				auto columns = slab.Columns(2);
+				GGGraph::Check(gg_components_fetch_sizes(result, offset, want, columns[0], (uint64_t *)columns[1], &got),
+				               "gg_components_fetch_sizes");
+			} else {
+				auto columns = slab.Columns(3);
+				GGGraph::Check(gg_components_fetch(result, offset, want, columns[0], columns[1], (uint64_t *)columns[2], &got),
+				               "gg_components_fetch");
 			}
+			return got;
+		};
+		if (Refill((State &)gstate, slab, fetch)) {
+			slab.Emit(chunk, 0, sizes_only ? 2 : 3);
 		}
-		slab.Emit(chunk, 0, sizes_only ? 2 : 3);
 	}
 
 	string GetName() const override {
@@ -107,28 +78,20 @@ public:
 	}
 };
 
-} // namespace
+enum { ROWS, SIZES };
 
-static unique_ptr<FunctionData> ComponentsBindInternal(vector<Value> &inputs, vector<LogicalType> &return_types,
-                                                       vector<string> &names, bool sizes_only) {
-	const char *fn = sizes_only ? "gg_component_sizes" : "gg_components";
-	for (idx_t i = 0; i < 5; i++) {
-		if (inputs[i].is_null) {
-			throw BinderException(string(fn) + ": table and column names must not be NULL");
-		}
-	}
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+unique_ptr<FunctionData> ComponentsBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                        vector<string> &names, int kind) {
+	const bool sizes_only = kind == SIZES;
+	GGRequireArguments(sizes_only ? "gg_component_sizes" : "gg_components", inputs, {0, 1, 2, 3, 4}, "table and column names");
+	const GraphArguments args(inputs);
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
-		opened.graph = GGBuildGraph(ctx, spec);
+		opened.graph = args.Build(ctx);
 		opened.source = make_unique<PhysicalGGComponents>(opened.graph, sizes_only);
 	};
 	data->parallel_result = true;
-	data->description = string(sizes_only ? "component sizes of " : "components of ") + edge_table;
+	data->description = string(sizes_only ? "component sizes of " : "components of ") + args.edge_table;
 	return_types = PhysicalGGComponents::OutputTypes(sizes_only);
 	if (sizes_only) {
 		names = {"component", "size"};
@@ -138,29 +101,12 @@ static unique_ptr<FunctionData> ComponentsBindInternal(vector<Value> &inputs, ve
 	return move(data);
 }
 
-static unique_ptr<FunctionData> ComponentsBind(ClientContext &context, vector<Value> &inputs,
-                                               unordered_map<string, Value> &named_parameters,
-                                               vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                               vector<LogicalType> &return_types, vector<string> &names) {
-	return ComponentsBindInternal(inputs, return_types, names, false);
-}
-
-static unique_ptr<FunctionData> ComponentSizesBind(ClientContext &context, vector<Value> &inputs,
-                                                   unordered_map<string, Value> &named_parameters,
-                                                   vector<LogicalType> &input_table_types,
-                                                   vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                   vector<string> &names) {
-	return ComponentsBindInternal(inputs, return_types, names, true);
-}
+} // namespace
 
 void GGRegisterComponentFunctions(ClientContext &context) {
-	const vector<LogicalType> args(5, LogicalType::VARCHAR);
-	auto rows = GGScanFunction("gg_components", args, ComponentsBind);
-	auto sizes = GGScanFunction("gg_component_sizes", args, ComponentSizesBind);
-	CreateTableFunctionInfo rows_info(rows), sizes_info(sizes);
-	auto &catalog = Catalog::GetCatalog(context);
-	catalog.CreateTableFunction(context, &rows_info);
-	catalog.CreateTableFunction(context, &sizes_info);
+	const auto args = GraphArguments::Types();
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_components", args, GGBind<ComponentsBind, ROWS>),
+	                                   GGScanFunction("gg_component_sizes", args, GGBind<ComponentsBind, SIZES>)});
 }
 
 } // namespace duckdb

@@ -64,7 +64,7 @@
 #include "duckdb/parallel/thread_context.hpp"
 #include "duckdb/parser/parsed_data/create_table_function_info.hpp"
 #include "duckdb/transaction/transaction.hpp"
-#include "gg_extension.hpp"
+#include "gg_table_function.hpp"
 
 #include <csignal>
 #include <execinfo.h>
@@ -286,21 +286,6 @@ void GGSetConnectionFlags(ClientContext &context, const GGConnectionFlags &flags
 	g_flags.emplace_back(weak_ptr<ClientContext>(context.shared_from_this()), flags);
 }
 
-//! (vertex_table, vertex_key, edge_table, src_col, dst_col) arguments -> scans, resolved at execution time
-struct GraphArguments {
-	string vertex_table, vertex_key, edge_table, edge_src, edge_dst;
-	explicit GraphArguments(vector<Value> &inputs)
-	    : vertex_table(inputs[0].ToString()), vertex_key(inputs[1].ToString()), edge_table(inputs[2].ToString()),
-	      edge_src(inputs[3].ToString()), edge_dst(inputs[4].ToString()) {
-	}
-	GGGraphSpec Resolve(ClientContext &context) const {
-		GGGraphSpec spec;
-		spec.vertices = GGTableSource(context, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(context, edge_table, {edge_src, edge_dst}, false);
-		return spec;
-	}
-};
-
 static GGScanSource Statement(const string &sql) {
 	GGScanSource source;
 	source.sql = sql;
@@ -422,14 +407,8 @@ vector<int64_t> GGQueryInt64Column(ClientContext &context, const string &sql, co
 //! gg_same_neighbour_paths(vertices_sql, sources_sql, path_table, path_src, path_dst,
 //!                         filter_table, filter_src, filter_dst, hops) -> (w, v0..v{hops})
 static unique_ptr<FunctionData> FilteredPathsBind(ClientContext &context, vector<Value> &inputs,
-                                                  unordered_map<string, Value> &named_parameters,
-                                                  vector<LogicalType> &input_table_types,
-                                                  vector<string> &input_table_names,
-                                                  vector<LogicalType> &return_types, vector<string> &names) {
-	const auto hops = inputs[8].GetValue<int64_t>();
-	if (hops < 1 || hops + 1 > GG_MAX_HOPS) {
-		throw BinderException("gg_same_neighbour_paths: need 1 <= hops <= " + to_string(GG_MAX_HOPS - 1));
-	}
+                                                  vector<LogicalType> &return_types, vector<string> &names, int kind) {
+	const auto hops = GGHopsArgument("gg_same_neighbour_paths", inputs[8], GG_MAX_HOPS - 1);
 	const string vertices_sql = inputs[0].ToString(), sources_sql = inputs[1].ToString();
 	const string path_table = inputs[2].ToString(), path_src = inputs[3].ToString(), path_dst = inputs[4].ToString();
 	const string filter_table = inputs[5].ToString(), filter_src = inputs[6].ToString(),
@@ -448,9 +427,7 @@ static unique_ptr<FunctionData> FilteredPathsBind(ClientContext &context, vector
 	};
 	return_types = vector<LogicalType>(hops + 2, LogicalType::BIGINT);
 	names.push_back("w");
-	for (int64_t c = 0; c <= hops; c++) {
-		names.push_back("v" + to_string(c));
-	}
+	GGWalkColumnNames(names, hops);
 	return move(data);
 }
 
@@ -460,15 +437,18 @@ static void CheckHops(int64_t k_min, int64_t k_max) {
 	}
 }
 
-static unique_ptr<FunctionData> KhopBindInternal(ClientContext &context, vector<Value> &inputs,
-                                                 vector<LogicalType> &return_types, vector<string> &names,
-                                                 bool count_only) {
+enum { ROWS, COUNT };
+
+//! gg_khop / gg_khop_count
+static unique_ptr<FunctionData> KhopBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                         vector<string> &names, int kind) {
+	const bool count_only = kind == COUNT;
 	const auto k_min = inputs[5].GetValue<int64_t>(), k_max = inputs[6].GetValue<int64_t>();
 	CheckHops(k_min, k_max);
 	const GraphArguments graph(inputs);
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		opened.graph = GGBuildGraph(ctx, graph.Resolve(ctx));
+		opened.graph = graph.Build(ctx);
 		opened.source = make_unique<PhysicalGGPathExpand>(opened.graph, (int)k_min, (int)k_max, count_only,
 		                                                  vector<int64_t>(), true, 0);
 	};
@@ -480,39 +460,19 @@ static unique_ptr<FunctionData> KhopBindInternal(ClientContext &context, vector<
 		names.push_back("digest");
 		names.push_back("traversed_edges");
 	} else {
-		for (int64_t c = 0; c <= k_max; c++) {
-			names.push_back("v" + to_string(c));
-		}
+		GGWalkColumnNames(names, k_max);
 	}
 	return move(data);
 }
 
-static unique_ptr<FunctionData> KhopBind(ClientContext &context, vector<Value> &inputs,
-                                         unordered_map<string, Value> &named_parameters,
-                                         vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                         vector<LogicalType> &return_types, vector<string> &names) {
-	return KhopBindInternal(context, inputs, return_types, names, false);
-}
-
-static unique_ptr<FunctionData> KhopCountBind(ClientContext &context, vector<Value> &inputs,
-                                              unordered_map<string, Value> &named_parameters,
-                                              vector<LogicalType> &input_table_types,
-                                              vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                              vector<string> &names) {
-	return KhopBindInternal(context, inputs, return_types, names, true);
-}
-
 static unique_ptr<FunctionData> ShortestBind(ClientContext &context, vector<Value> &inputs,
-                                             unordered_map<string, Value> &named_parameters,
-                                             vector<LogicalType> &input_table_types,
-                                             vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                             vector<string> &names) {
+                                             vector<LogicalType> &return_types, vector<string> &names, int kind) {
 	const GraphArguments graph(inputs);
 	const string sources_sql = inputs[5].ToString();
 	const auto max_hops = inputs[6].GetValue<int64_t>();
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		opened.graph = GGBuildGraph(ctx, graph.Resolve(ctx));
+		opened.graph = graph.Build(ctx);
 		auto sources = GGQueryInt64Column(ctx, sources_sql, "gg_shortest_path: sources");
 		opened.source = make_unique<PhysicalGGShortestPath>(opened.graph, move(sources), (int)max_hops, 0);
 	};
@@ -544,20 +504,13 @@ void GGQueryInt64Pairs(ClientContext &context, const string &sql, const char *wh
 
 //! gg_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
 static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<Value> &inputs,
-                                                 unordered_map<string, Value> &named_parameters,
-                                                 vector<LogicalType> &input_table_types,
-                                                 vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                 vector<string> &names) {
+                                                 vector<LogicalType> &return_types, vector<string> &names, int kind) {
 	const GraphArguments graph(inputs);
 	const string pairs_sql = inputs[5].ToString();
 	const auto max_hops = inputs[6].GetValue<int64_t>();
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec;
-		spec.vertices = GGTableSource(ctx, graph.vertex_table, {graph.vertex_key}, false);
-		spec.edges = GGTableSource(ctx, graph.edge_table, {graph.edge_src, graph.edge_dst}, true);
-		spec.edges_with_rowid = true;
-		opened.graph = GGBuildGraphWithRowids(ctx, spec);
+		opened.graph = graph.Build(ctx, true);
 		vector<int64_t> src, dst;
 		GGQueryInt64Pairs(ctx, pairs_sql, "gg_shortest_path_rows: pairs", src, dst);
 		opened.source = make_unique<PhysicalGGShortestPathRows>(opened.graph, move(src), move(dst),
@@ -571,12 +524,9 @@ static unique_ptr<FunctionData> ShortestRowsBind(ClientContext &context, vector<
 
 //! gg_all_shortest_path_rows(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops, path_limit) and
 //! gg_shortest_path_counts(vertex_table, vertex_key, edge_table, src_col, dst_col, pairs_sql, max_hops)
-template <bool COUNT_ONLY>
 static unique_ptr<FunctionData> AllShortestBind(ClientContext &context, vector<Value> &inputs,
-                                                unordered_map<string, Value> &named_parameters,
-                                                vector<LogicalType> &input_table_types,
-                                                vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                vector<string> &names) {
+                                                vector<LogicalType> &return_types, vector<string> &names, int kind) {
+	const bool COUNT_ONLY = kind == COUNT;
 	const GraphArguments graph(inputs);
 	const string pairs_sql = inputs[5].ToString();
 	const auto max_hops = inputs[6].GetValue<int64_t>();
@@ -587,11 +537,7 @@ static unique_ptr<FunctionData> AllShortestBind(ClientContext &context, vector<V
 	const char *what = COUNT_ONLY ? "gg_shortest_path_counts: pairs" : "gg_all_shortest_path_rows: pairs";
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec;
-		spec.vertices = GGTableSource(ctx, graph.vertex_table, {graph.vertex_key}, false);
-		spec.edges = GGTableSource(ctx, graph.edge_table, {graph.edge_src, graph.edge_dst}, true);
-		spec.edges_with_rowid = true;
-		opened.graph = GGBuildGraphWithRowids(ctx, spec);
+		opened.graph = graph.Build(ctx, true);
 		vector<int64_t> src, dst;
 		GGQueryInt64Pairs(ctx, pairs_sql, what, src, dst);
 		opened.source = make_unique<PhysicalGGAllShortestPaths>(opened.graph, move(src), move(dst),
@@ -617,15 +563,13 @@ struct PinResultData : public TableFunctionData {
 };
 
 static unique_ptr<FunctionData> GraphPinBind(ClientContext &context, vector<Value> &inputs,
-                                             unordered_map<string, Value> &named_parameters,
-                                             vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                             vector<LogicalType> &return_types, vector<string> &names) {
-	const string vertex_table = inputs[0].ToString();
+                                             vector<LogicalType> &return_types, vector<string> &names, int kind) {
+	const GraphArguments args(inputs);
 	GGGraphSpec spec;
-	if (!vertex_table.empty()) {
-		spec.vertices = GGTableSource(context, vertex_table, {inputs[1].ToString()}, false);
+	if (!args.vertex_table.empty()) {
+		spec.vertices = GGTableSource(context, args.vertex_table, {args.vertex_key}, false);
 	}
-	spec.edges = GGTableSource(context, inputs[2].ToString(), {inputs[3].ToString(), inputs[4].ToString()}, false);
+	spec.edges = GGTableSource(context, args.edge_table, {args.edge_src, args.edge_dst}, false);
 	PinnedGraph pin;
 	if (!PinKey(spec, pin)) {
 		throw BinderException("gg_graph_pin: only base tables can be pinned");
@@ -673,10 +617,7 @@ static void GraphPinFunction(ClientContext &context, const FunctionData *bind_da
 }
 
 static unique_ptr<FunctionData> GraphUnpinBind(ClientContext &context, vector<Value> &inputs,
-                                               unordered_map<string, Value> &named_parameters,
-                                               vector<LogicalType> &input_table_types,
-                                               vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                               vector<string> &names) {
+                                               vector<LogicalType> &return_types, vector<string> &names, int kind) {
 	auto result = make_unique<PinResultData>();
 	{
 		lock_guard<mutex> guard(g_pinned_lock);
@@ -701,9 +642,7 @@ static void GraphUnpinFunction(ClientContext &context, const FunctionData *bind_
 
 //! gg_graph_pins() -> number of graphs currently pinned (tests; monitoring)
 static unique_ptr<FunctionData> GraphPinsBind(ClientContext &context, vector<Value> &inputs,
-                                              unordered_map<string, Value> &named_parameters,
-                                              vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                              vector<LogicalType> &return_types, vector<string> &names) {
+                                              vector<LogicalType> &return_types, vector<string> &names, int kind) {
 	auto result = make_unique<PinResultData>();
 	{
 		lock_guard<mutex> guard(g_pinned_lock);
@@ -715,48 +654,30 @@ static unique_ptr<FunctionData> GraphPinsBind(ClientContext &context, vector<Val
 }
 
 static void LoadInternal(DatabaseInstance &db) {
-	const vector<LogicalType> graph_args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                        LogicalType::VARCHAR, LogicalType::VARCHAR};
+	const auto graph_args = GraphArguments::Types();
 	auto khop_args = graph_args;
-	khop_args.push_back(LogicalType::BIGINT);
-	khop_args.push_back(LogicalType::BIGINT);
+	khop_args.insert(khop_args.end(), {LogicalType::BIGINT, LogicalType::BIGINT});
 	auto sp_args = graph_args;
-	sp_args.push_back(LogicalType::VARCHAR);
-	sp_args.push_back(LogicalType::BIGINT);
-
-	auto khop = GGScanFunction("gg_khop", khop_args, KhopBind);
-	auto khop_count = GGScanFunction("gg_khop_count", khop_args, KhopCountBind);
-	auto shortest = GGScanFunction("gg_shortest_path", sp_args, ShortestBind);
-	auto shortest_rows = GGScanFunction("gg_shortest_path_rows", sp_args, ShortestRowsBind);
+	sp_args.insert(sp_args.end(), {LogicalType::VARCHAR, LogicalType::BIGINT});
 	auto all_args = sp_args;
 	all_args.push_back(LogicalType::BIGINT);
-	auto all_shortest_rows = GGScanFunction("gg_all_shortest_path_rows", all_args, AllShortestBind<false>);
-	auto shortest_counts = GGScanFunction("gg_shortest_path_counts", sp_args, AllShortestBind<true>);
-	auto filtered = GGScanFunction("gg_same_neighbour_paths",
-	                               {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BIGINT},
-	                               FilteredPathsBind);
-	TableFunction pin("gg_graph_pin", graph_args, GraphPinFunction, GraphPinBind);
-	TableFunction unpin("gg_graph_unpin", {}, GraphUnpinFunction, GraphUnpinBind);
-	TableFunction pins("gg_graph_pins", {}, GraphUnpinFunction, GraphPinsBind);
-	CreateTableFunctionInfo khop_info(khop), khop_count_info(khop_count), shortest_info(shortest), shortest_rows_info(shortest_rows),
-	    filtered_info(filtered), pin_info(pin), unpin_info(unpin), pins_info(pins),
-	    all_shortest_rows_info(all_shortest_rows), shortest_counts_info(shortest_counts);
+	auto filtered_args = vector<LogicalType>(8, LogicalType::VARCHAR);
+	filtered_args.push_back(LogicalType::BIGINT);
 
 	Connection con(db);
 	con.BeginTransaction();
-	auto &catalog = Catalog::GetCatalog(*con.context);
-	catalog.CreateTableFunction(*con.context, &khop_info);
-	catalog.CreateTableFunction(*con.context, &khop_count_info);
-	catalog.CreateTableFunction(*con.context, &shortest_info);
-	catalog.CreateTableFunction(*con.context, &shortest_rows_info);
-	catalog.CreateTableFunction(*con.context, &all_shortest_rows_info);
-	catalog.CreateTableFunction(*con.context, &shortest_counts_info);
-	catalog.CreateTableFunction(*con.context, &filtered_info);
-	catalog.CreateTableFunction(*con.context, &pin_info);
-	catalog.CreateTableFunction(*con.context, &unpin_info);
-	catalog.CreateTableFunction(*con.context, &pins_info);
+	GGRegisterTableFunctions(
+	    *con.context,
+	    {GGScanFunction("gg_khop", khop_args, GGBind<KhopBind, ROWS>),
+	     GGScanFunction("gg_khop_count", khop_args, GGBind<KhopBind, COUNT>),
+	     GGScanFunction("gg_shortest_path", sp_args, GGBind<ShortestBind>),
+	     GGScanFunction("gg_shortest_path_rows", sp_args, GGBind<ShortestRowsBind>),
+	     GGScanFunction("gg_all_shortest_path_rows", all_args, GGBind<AllShortestBind, ROWS>),
+	     GGScanFunction("gg_shortest_path_counts", sp_args, GGBind<AllShortestBind, COUNT>),
+	     GGScanFunction("gg_same_neighbour_paths", filtered_args, GGBind<FilteredPathsBind>),
+	     TableFunction("gg_graph_pin", graph_args, GraphPinFunction, GGBind<GraphPinBind>),
+	     TableFunction("gg_graph_unpin", {}, GraphUnpinFunction, GGBind<GraphUnpinBind>),
+	     TableFunction("gg_graph_pins", {}, GraphUnpinFunction, GGBind<GraphPinsBind>)});
 	GGRegisterTriangleFunctions(*con.context);
 	GGRegisterEdgeFilterFunctions(*con.context);
 	GGRegisterExtendFunctions(*con.context);

@@ -23,128 +23,84 @@
 //
 // The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
 // The walk table is expanded on the device, filtered there and dropped before the first row leaves; the surviving rows
-// stay on the device and the pipeline's threads drain them together (GGResultDrain, gg_operators.hpp).
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+// stay on the device and the pipeline's threads drain them together.
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
 namespace {
 
-class EdgeFilterState : public GlobalSourceState {
+//! Source: the `hops`-hop walks from the sources, kept by the number m of edge rows that lead from column from_col to
+//! column to_col of the walk (gg_result_filter_edge, include/gg.h).
+//! Output: (v0 BIGINT, ..., v{hops} BIGINT); count_only: the one row (rows BIGINT, walks BIGINT, matches BIGINT).
+class PhysicalGGEdgeFilter : public GGWalkSource {
 public:
-	idx_t MaxThreads() override {
-		return max_threads;
+	PhysicalGGEdgeFilter(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p, bool all_sources_p,
+	                     int from_col_p, int to_col_p, int mode_p, bool count_only_p)
+	    : GGWalkSource(OutputTypes(hops_p, count_only_p), move(graph_p), hops_p, move(sources_p), all_sources_p),
+	      from_col(from_col_p), to_col(to_col_p), mode(mode_p), count_only(count_only_p) {
 	}
-	gg_edge_filter_stats stats {};
-	GGResultDrain drain;  // the rows (count_only: none)
-	bool counted = false; // count_only: the one row went out (under drain.lock)
-	idx_t max_threads = 1;
+	static vector<LogicalType> OutputTypes(int hops, bool count_only) {
+		return vector<LogicalType>(count_only ? 3 : hops + 1, LogicalType::BIGINT);
+	}
+	typedef GGDrainStateOf<gg_edge_filter_stats> State;
+
+	int from_col, to_col;
+	int mode; // GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
+	bool count_only;
+
+	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
+		auto state = make_unique<State>();
+		lock_guard<mutex> guard(graph->lock);
+		if (!graph->csr) {
+			throw InternalException("GG_EDGE_FILTER scheduled before the CSR was built");
+		}
+		state->drain.Replace(context, hops, [&](idx_t &rows) {
+			GGResultPtr owner;
+			GGResultPtr walks; // (gone once filtered: dropped before the rows drain)
+			ExpandWalks(walks);
+			GGGraph::Check(gg_result_filter_edge(graph->ctx, walks.get(), hops, graph->csr, from_col, to_col, mode,
+			                                     count_only ? 0 : 1, &state->stats,
+			                                     count_only ? nullptr : static_cast<gg_result **>(GGResultOut(owner))),
+			               "gg_result_filter_edge");
+			rows = count_only ? 0 : state->stats.rows_out;
+			return owner;
+		});
+		state->max_threads = GGResultSlab::ThreadsFor(count_only ? 0 : state->stats.rows_out);
+		return move(state);
+	}
+
+	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
+	             LocalSourceState &lstate) const override {
+		auto &gstate = (State &)gstate_p;
+		PollInterrupt(context);
+		if (count_only) {
+			EmitCountRow(gstate, chunk, {gstate.stats.rows_out, gstate.stats.rows_in, gstate.stats.matches});
+			return;
+		}
+		auto &slab = (GGResultSlab &)lstate;
+		const idx_t columns = (idx_t)hops + 1;
+		if (FetchIds(gstate, slab, columns)) {
+			slab.Emit(chunk, 0, columns);
+		}
+	}
+
+	string GetName() const override {
+		return "GG_EDGE_FILTER";
+	}
 };
 
-} // namespace
+enum { ROWS, COUNT };
 
-PhysicalGGEdgeFilter::PhysicalGGEdgeFilter(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p,
-                                           bool all_sources_p, int from_col_p, int to_col_p, int mode_p, bool count_only_p,
-                                           idx_t estimated_cardinality)
-    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(hops_p, count_only_p), estimated_cardinality),
-      graph(move(graph_p)), hops(hops_p), sources(move(sources_p)), all_sources(all_sources_p), from_col(from_col_p),
-      to_col(to_col_p), mode(mode_p), count_only(count_only_p) {
-}
-
-vector<LogicalType> PhysicalGGEdgeFilter::OutputTypes(int hops, bool count_only) {
-	return vector<LogicalType>(count_only ? 3 : hops + 1, LogicalType::BIGINT);
-}
-
-unique_ptr<GlobalSourceState> PhysicalGGEdgeFilter::GetGlobalSourceState(ClientContext &context) const {
-	auto state = make_unique<EdgeFilterState>();
-	lock_guard<mutex> guard(graph->lock);
-	if (!graph->csr) {
-		throw InternalException("GG_EDGE_FILTER scheduled before the CSR was built");
-	}
-	static const int64_t none = 0; // an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex)
-	const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
-	state->drain.Replace(context, hops, [&](idx_t &rows) {
-		GGResultPtr owner;
-		gg_khop_stats walk_stats;
-		GGResultPtr walks; // (gone once filtered: dropped before the rows drain)
-		GGGraph::Check(gg_expand_khop_result(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops, hops,
-		                                     &walk_stats, GGResultOut(walks)),
-		               "gg_expand_khop_result");
-		GGGraph::Check(gg_result_filter_edge(graph->ctx, walks.get(), hops, graph->csr, from_col, to_col, mode,
-		                                     count_only ? 0 : 1, &state->stats,
-		                                     count_only ? nullptr : static_cast<gg_result **>(GGResultOut(owner))),
-		               "gg_result_filter_edge");
-		rows = count_only ? 0 : state->stats.rows_out;
-		return owner;
-	});
-	state->max_threads = GGResultSlab::ThreadsFor(count_only ? 0 : state->stats.rows_out);
-	return move(state);
-}
-
-unique_ptr<LocalSourceState> PhysicalGGEdgeFilter::GetLocalSourceState(ExecutionContext &context,
-                                                                       GlobalSourceState &gstate) const {
-	return make_unique<GGResultSlab>(graph);
-}
-
-void PhysicalGGEdgeFilter::GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
-                                   LocalSourceState &lstate) const {
-	auto &gstate = (EdgeFilterState &)gstate_p;
-	if (context.client.interrupted) {
-		throw InterruptException();
-	}
-	if (count_only) {
-		lock_guard<mutex> guard(gstate.drain.lock);
-		if (gstate.counted) {
-			return;
-		}
-		gstate.counted = true;
-		FlatVector::GetData<int64_t>(chunk.data[0])[0] = (int64_t)gstate.stats.rows_out;
-		FlatVector::GetData<int64_t>(chunk.data[1])[0] = (int64_t)gstate.stats.rows_in;
-		FlatVector::GetData<int64_t>(chunk.data[2])[0] = (int64_t)gstate.stats.matches;
-		chunk.SetCardinality(1);
-		return;
-	}
-	auto &slab = (GGResultSlab &)lstate;
-	const idx_t columns = (idx_t)hops + 1;
-	if (slab.pos >= slab.rows) {
-		auto fetch = [columns](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
-			uint32_t got = 0;
-			GGGraph::Check(gg_result_fetch(result, table, offset, want, slab.Columns(columns), &got), "gg_result_fetch");
-			return got;
-		};
-		if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
-			return;
-		}
-	}
-	slab.Emit(chunk, 0, columns);
-}
-
-static unique_ptr<FunctionData> EdgeFilterBindInternal(vector<Value> &inputs, vector<LogicalType> &return_types,
-                                                       vector<string> &names, bool count_only) {
-	const char *fn = count_only ? "gg_khop_edge_filter_count" : "gg_khop_edge_filter";
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
-	for (idx_t i = 6; i <= 9; i++) {
-		if (inputs[i].is_null) {
-			throw BinderException(string(fn) + ": hops, from_col, to_col and mode must not be NULL");
-		}
-	}
-	const auto hops = inputs[6].GetValue<int64_t>(), from_col = inputs[7].GetValue<int64_t>(),
-	           to_col = inputs[8].GetValue<int64_t>();
+unique_ptr<FunctionData> EdgeFilterBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                        vector<string> &names, int kind) {
+	const bool count_only = kind == COUNT;
+	const GGWalkArguments args(count_only ? "gg_khop_edge_filter_count" : "gg_khop_edge_filter", inputs,
+	                           GGWalkArguments::NO_EXTENSION, {6, 7, 8, 9}, "hops, from_col, to_col and mode");
+	const auto hops = args.hops, from_col = inputs[7].GetValue<int64_t>(), to_col = inputs[8].GetValue<int64_t>();
 	const string mode_name = inputs[9].ToString();
-	if (hops < 1 || hops > GG_MAX_HOPS) {
-		throw BinderException(string(fn) + ": need 1 <= hops <= " + to_string(GG_MAX_HOPS));
-	}
 	if (from_col < 0 || from_col > hops || to_col < 0 || to_col > hops) {
-		throw BinderException(string(fn) + ": from_col and to_col must lie in 0.." + to_string(hops));
+		throw BinderException(args.fn + ": from_col and to_col must lie in 0.." + to_string(hops));
 	}
 	int mode;
 	if (mode_name == "inner") {
@@ -154,62 +110,32 @@ static unique_ptr<FunctionData> EdgeFilterBindInternal(vector<Value> &inputs, ve
 	} else if (mode_name == "anti") {
 		mode = GG_EDGE_ANTI;
 	} else {
-		throw BinderException(string(fn) + ": mode '" + mode_name + "' (one of 'inner', 'semi', 'anti')");
+		throw BinderException(args.fn + ": mode '" + mode_name + "' (one of 'inner', 'semi', 'anti')");
 	}
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
-		opened.graph = GGBuildGraph(ctx, spec);
-		vector<int64_t> sources;
-		if (!sources_sql.empty()) {
-			sources = GGQueryInt64Column(ctx, sources_sql, count_only ? "gg_khop_edge_filter_count: sources"
-			                                                          : "gg_khop_edge_filter: sources");
-		}
-		opened.source = make_unique<PhysicalGGEdgeFilter>(opened.graph, (int)hops, move(sources), sources_sql.empty(),
-		                                                  (int)from_col, (int)to_col, mode, count_only, 0);
+		opened.graph = args.BuildGraph(ctx);
+		opened.source = make_unique<PhysicalGGEdgeFilter>(opened.graph, (int)hops, args.Sources(ctx), args.AllSources(),
+		                                                  (int)from_col, (int)to_col, mode, count_only);
 	};
 	data->parallel_result = !count_only;
-	data->description = mode_name + " edge v" + to_string(from_col) + " -> v" + to_string(to_col) + " over " +
-	                    to_string(hops) + "-hop walks of " + edge_table;
+	data->description = mode_name + " edge v" + to_string(from_col) + " -> v" + to_string(to_col) + " over " + args.Describe();
 	return_types = PhysicalGGEdgeFilter::OutputTypes((int)hops, count_only);
 	if (count_only) {
 		names = {"rows", "walks", "matches"};
 	} else {
-		for (int64_t c = 0; c <= hops; c++) {
-			names.push_back("v" + to_string(c));
-		}
+		GGWalkColumnNames(names, hops);
 	}
 	return move(data);
 }
 
-static unique_ptr<FunctionData> EdgeFilterBind(ClientContext &context, vector<Value> &inputs,
-                                               unordered_map<string, Value> &named_parameters,
-                                               vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                               vector<LogicalType> &return_types, vector<string> &names) {
-	return EdgeFilterBindInternal(inputs, return_types, names, false);
-}
-
-static unique_ptr<FunctionData> EdgeFilterCountBind(ClientContext &context, vector<Value> &inputs,
-                                                    unordered_map<string, Value> &named_parameters,
-                                                    vector<LogicalType> &input_table_types,
-                                                    vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                    vector<string> &names) {
-	return EdgeFilterBindInternal(inputs, return_types, names, true);
-}
+} // namespace
 
 void GGRegisterEdgeFilterFunctions(ClientContext &context) {
-	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::BIGINT,  LogicalType::BIGINT,  LogicalType::BIGINT,
-	                                  LogicalType::VARCHAR};
-	auto rows = GGScanFunction("gg_khop_edge_filter", args, EdgeFilterBind);
-	auto count = GGScanFunction("gg_khop_edge_filter_count", args, EdgeFilterCountBind);
-	CreateTableFunctionInfo rows_info(rows), count_info(count);
-	auto &catalog = Catalog::GetCatalog(context);
-	catalog.CreateTableFunction(context, &rows_info);
-	catalog.CreateTableFunction(context, &count_info);
+	auto args = GGWalkArguments::Types(false);
+	args.insert(args.end(), {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::VARCHAR});
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_khop_edge_filter", args, GGBind<EdgeFilterBind, ROWS>),
+	                                   GGScanFunction("gg_khop_edge_filter_count", args, GGBind<EdgeFilterBind, COUNT>)});
 }
 
 } // namespace duckdb

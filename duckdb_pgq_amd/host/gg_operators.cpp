@@ -591,10 +591,16 @@ PhysicalGGPathExpand::PhysicalGGPathExpand(shared_ptr<GGGraph> graph_p, int k_mi
       all_sources(all_sources_p), rows_only(rows_only_p && count_only_p) {
 }
 
-//! A source list for the C-ABI: an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex).
-static const int64_t *SourceIds(const vector<int64_t> &sources) {
+const int64_t *GGSourceIds(const vector<int64_t> &sources) {
 	static const int64_t none = 0;
 	return sources.empty() ? &none : sources.data();
+}
+
+void GGExpandWalks(GGGraph &graph, const vector<int64_t> &sources, bool all_sources, int hops, GGResultPtr &out) {
+	gg_khop_stats stats;
+	GGGraph::Check(gg_expand_khop_result(graph.ctx, graph.csr, all_sources ? nullptr : GGSourceIds(sources),
+	                                     all_sources ? 0 : sources.size(), hops, hops, &stats, GGResultOut(out)),
+	               "gg_expand_khop_result");
 }
 
 //! Row counts per walk length from degrees (gg_khop_count) in the shape the counting expansion reports them:
@@ -603,7 +609,7 @@ static void CountRowsFromDegrees(gg_ctx *ctx, const gg_csr *csr, const vector<in
                                  int k_min, int k_max, gg_khop_stats &stats) {
 	memset(&stats, 0, sizeof(stats));
 	uint64_t rows[GG_MAX_HOPS + 1];
-	GGGraph::Check(gg_khop_count(ctx, csr, all_sources ? nullptr : SourceIds(sources), sources.size(), 1, k_max, rows),
+	GGGraph::Check(gg_khop_count(ctx, csr, all_sources ? nullptr : GGSourceIds(sources), sources.size(), 1, k_max, rows),
 	               "gg_khop_count");
 	for (int h = 1; h <= k_max; h++) {
 		stats.traversed_edges += rows[h];
@@ -712,7 +718,7 @@ unique_ptr<GlobalSourceState> PhysicalGGPathExpand::GetGlobalSourceState(ClientC
 	// count first: cheap (nothing is written), and it tells how much HBM the walks would take — from degrees when
 	// the rows are wanted (their digest is nobody's business then), by the counting expansion for gg_path_count
 	if (count_only) {
-		GGGraph::Check(gg_expand_khop(graph->ctx, graph->csr, all_sources ? nullptr : SourceIds(sources), sources.size(),
+		GGGraph::Check(gg_expand_khop(graph->ctx, graph->csr, all_sources ? nullptr : GGSourceIds(sources), sources.size(),
 		                              k_min, k_max, 0, &state->stats, nullptr),
 		               "gg_expand_khop");
 		state->hop = k_min;
@@ -1077,12 +1083,9 @@ unique_ptr<GlobalSourceState> PhysicalGGFilteredPaths::GetGlobalSourceState(Clie
 	if (!graph->csr || !graph->filter_csr) {
 		throw InternalException("GG_FILTERED_PATHS scheduled before both CSRs were built");
 	}
-	gg_khop_stats stats;
 	{
 		GGResultPtr paths; // (gone once filtered)
-		GGGraph::Check(gg_expand_khop_result(graph->ctx, graph->csr, all_sources ? nullptr : SourceIds(sources),
-		                                     all_sources ? 0 : sources.size(), hops, hops, &stats, GGResultOut(paths)),
-		               "gg_expand_khop_result");
+		GGExpandWalks(*graph, sources, all_sources, hops, paths);
 		GGGraph::Check(gg_result_filter_common_neighbour(graph->ctx, paths.get(), hops, graph->filter_csr,
 		                                                 GGResultOut(state->result)),
 		               "gg_result_filter_common_neighbour");
@@ -1173,7 +1176,7 @@ unique_ptr<GlobalSourceState> PhysicalGGPathEdges::GetGlobalSourceState(ClientCo
 	// count first (from degrees: nothing is written) — the walks with their edges take (2 * hops + 1) int64 columns
 	// at the last level plus the level tables below it (dense u32 columns: about half as much again)
 	uint64_t rows[GG_MAX_HOPS + 1];
-	GGGraph::Check(gg_khop_count(graph->ctx, graph->csr, all_sources ? nullptr : SourceIds(sources), sources.size(), 1, hops,
+	GGGraph::Check(gg_khop_count(graph->ctx, graph->csr, all_sources ? nullptr : GGSourceIds(sources), sources.size(), 1, hops,
 	                             rows),
 	               "gg_khop_count");
 	uint64_t bytes = rows[hops] * (uint64_t)(2 * hops + 1) * sizeof(int64_t);

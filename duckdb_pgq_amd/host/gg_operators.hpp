@@ -10,17 +10,15 @@
 //        <=1024-row DataChunks, Finalize once.
 //   PhysicalGGPathExpand                         <->  the chain of PhysicalHashJoin::Execute probes
 //        (physical_hash_join.cpp:217-254) of a k-hop pattern; a source that emits the walks.
-//   PhysicalGGTriangles                          <->  three PhysicalHashJoin probes, the last on two conditions
-//        (physical_hash_join.cpp:217-254) of the cyclic pattern a -> b -> c -> a (benchmark/ldbc/queries/bi-11.sql:22-33).
-//   PhysicalGGEdgeFilter                         <->  the last PhysicalHashJoin probe of a chain on two conditions, or the
-//        semi / anti join of an EXISTS / NOT EXISTS over the edge table (src/execution/join_hashtable.cpp:304-540).
 //   PhysicalGGShortestPath                       <->  PhysicalRecursiveCTE + min(hop) aggregate
 //   PhysicalGGShortestPathRows                   <->  (no counterpart: the paths behind those hop counts, unnested)
 //   PhysicalGGAllShortestPaths                   <->  PhysicalRecursiveCTE (UNION ALL) over friends_shortest x knows [+ count]
 //        (src/execution/operator/set/physical_recursive_cte.cpp:48-139) for the bi-10 friends CTE.
 //
-// The six sources whose rows stay on the device (path expansion, triangles, the edge filter, the grouped aggregate, the two shortest-path ones) hand them to
-// the pipeline's threads through one helper, GGResultDrain + GGResultSlab below: claim under a lock, fetch without one.
+// The sources whose rows stay on the device (here path expansion and the shortest-path ones) hand them to the pipeline's
+// threads through one helper, GGResultDrain + GGResultSlab below: claim under a lock, fetch without one.  The sources
+// behind the later table functions (triangles, the edge filter, the extension and what follows it, the aggregates, ...)
+// are declared in the .cpp that registers their function, over the bases of gg_table_function.hpp.
 //
 // Compiled against the reference's headers; duckdb symbols are resolved by the hosting libduckdb at
 // load time (the library is loaded as an extension: gg_duckdb_extension.cpp).
@@ -193,6 +191,12 @@ private:
 	idx_t rows = 0, offset = 0;      // rows of that table, next unclaimed one
 	std::atomic<idx_t> fetching {0}; // slab fetches still reading `result` (it may not be freed under them)
 };
+
+//! A source list for the C-ABI: an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex).
+const int64_t *GGSourceIds(const vector<int64_t> &sources);
+//! The `hops`-hop walk table from `sources` (all_sources: from every vertex), left on the device (gg_expand_khop_result,
+//! include/gg.h).  Caller holds graph.lock.
+void GGExpandWalks(GGGraph &graph, const vector<int64_t> &sources, bool all_sources, int hops, GGResultPtr &out);
 
 //! The global source state of the operators that answer (src, dst) pairs from 64-source device batches (gg_shortest_paths.cpp,
 //! gg_cheapest.cpp): the pairs grouped by source, and the drain of the batch that is resident.
@@ -455,116 +459,6 @@ public:
 	}
 };
 
-//! Source: the `hops`-hop walks from the sources, kept by the number m of edge rows that lead from column from_col to
-//! column to_col of the walk (gg_result_filter_edge, include/gg.h): mode GG_EDGE_INNER m copies — the last hash join of a
-//! chain carrying two conditions, e.g. the edge that closes a walk (src/execution/join_hashtable.cpp:304-476) —
-//! GG_EDGE_SEMI the row if m > 0 (EXISTS, NextSemiJoin, join_hashtable.cpp:522), GG_EDGE_ANTI the row if m == 0 (NOT
-//! EXISTS, benchmark/ldbc/queries/interactive-complex-10.sql:19-24, NextAntiJoin, join_hashtable.cpp:478-540).
-//! Output: (v0 BIGINT, ..., v{hops} BIGINT); count_only: the one row (rows BIGINT, walks BIGINT, matches BIGINT).
-class PhysicalGGEdgeFilter : public PhysicalOperator {
-public:
-	PhysicalGGEdgeFilter(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int from_col,
-	                     int to_col, int mode, bool count_only, idx_t estimated_cardinality);
-	static vector<LogicalType> OutputTypes(int hops, bool count_only);
-
-	shared_ptr<GGGraph> graph;
-	int hops;
-	vector<int64_t> sources;
-	bool all_sources; // walks may start at any vertex
-	int from_col, to_col;
-	int mode; // GG_EDGE_INNER / GG_EDGE_SEMI / GG_EDGE_ANTI
-	bool count_only;
-
-public:
-	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
-	                                                 GlobalSourceState &gstate) const override;
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
-	             LocalSourceState &lstate) const override;
-	bool IsSource() const override {
-		return true;
-	}
-	bool ParallelSource() const override {
-		return true;
-	}
-	string GetName() const override {
-		return "GG_EDGE_FILTER";
-	}
-};
-
-//! Source: the `hops`-hop walks from the sources joined with the rows of a second edge table (GGGraph::filter_csr, built
-//! with rowids) whose key is column from_col of the walk (gg_result_extend_edge, include/gg.h) — the next hash join of a
-//! chain over a different build table with its payload gathered by rowid (src/execution/join_hashtable.cpp:304-476;
-//! benchmark/ldbc/queries/interactive-complex-2.sql:2-7).
-//! Output: (v0 BIGINT, ..., v{hops} BIGINT, w BIGINT, ext_rowid BIGINT); count_only: the one row (rows BIGINT, walks
-//! BIGINT, matched BIGINT).
-class PhysicalGGExtend : public PhysicalOperator {
-public:
-	PhysicalGGExtend(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int from_col,
-	                 bool count_only, idx_t estimated_cardinality);
-	static vector<LogicalType> OutputTypes(int hops, bool count_only);
-
-	shared_ptr<GGGraph> graph;
-	int hops;
-	vector<int64_t> sources;
-	bool all_sources; // walks may start at any vertex
-	int from_col;
-	bool count_only;
-
-public:
-	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
-	                                                 GlobalSourceState &gstate) const override;
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
-	             LocalSourceState &lstate) const override;
-	bool IsSource() const override {
-		return true;
-	}
-	bool ParallelSource() const override {
-		return true;
-	}
-	string GetName() const override {
-		return "GG_EXTEND";
-	}
-};
-
-//! Source: one row (vertex BIGINT, walks BIGINT, total HUGEINT) per vertex that starts (group_by GG_GROUP_START) or ends
-//! (GG_GROUP_END) a `hops`-hop walk from the sources: the number of such walks and the sum of the weights at their other
-//! end (gg_khop_aggregate, include/gg.h) — PhysicalHashAggregate above a chain of hash joins
-//! (src/execution/operator/aggregate/physical_hash_aggregate.cpp:152-266), the shape of
-//! benchmark/ldbc/queries/bi-8.sql:41-53.  weights: one per vertex in the graph's vertex-table order (weighted false:
-//! counts only, total = walks).
-class PhysicalGGKhopAggregate : public PhysicalOperator {
-public:
-	PhysicalGGKhopAggregate(shared_ptr<GGGraph> graph, int hops, vector<int64_t> sources, bool all_sources, int group_by,
-	                        vector<int64_t> weights, bool weighted, idx_t estimated_cardinality);
-	static vector<LogicalType> OutputTypes();
-
-	shared_ptr<GGGraph> graph;
-	int hops;
-	vector<int64_t> sources;
-	bool all_sources; // walks may start at any vertex
-	int group_by;     // GG_GROUP_START / GG_GROUP_END
-	vector<int64_t> weights;
-	bool weighted;
-
-public:
-	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
-	                                                 GlobalSourceState &gstate) const override;
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
-	             LocalSourceState &lstate) const override;
-	bool IsSource() const override {
-		return true;
-	}
-	bool ParallelSource() const override {
-		return true;
-	}
-	string GetName() const override {
-		return "GG_KHOP_AGGREGATE";
-	}
-};
-
 //! Source: (vertex id BIGINT, h1 BIGINT, ..., hk BIGINT) — one row per vertex that ends a walk of 1..k_max edges from
 //! one of the sources; h = 1 iff a walk of exactly h edges ends there (gg_walk_endpoints).  The device form of the
 //! reference's hash-aggregate dedupe above a UNION of endpoint sets (interactive-complex-3.sql:3-12).
@@ -695,39 +589,6 @@ public:
 	}
 	string GetName() const override {
 		return count_only ? "GG_SHORTEST_PATH_COUNTS" : "GG_ALL_SHORTEST_PATH_ROWS";
-	}
-};
-
-//! Source: the triangle rows (closed 3-edge walks, include/gg.h gg_triangles) of the graph from every vertex.
-//! Output: (v0 BIGINT, v1 BIGINT, v2 BIGINT), one row per triple of edge rows v0->v1, v1->v2, v2->v0; ordered: only
-//! id(v0) < id(v1) < id(v2).  count_only: the one row (rows BIGINT, digest BIGINT, wedges BIGINT).  with_edges
-//! (gg_triangles_edges; the graph carries edge rowids): three more columns (e1 BIGINT, e2 BIGINT, e3 BIGINT), the rowids
-//! of those three edge rows.
-class PhysicalGGTriangles : public PhysicalOperator {
-public:
-	PhysicalGGTriangles(shared_ptr<GGGraph> graph, bool ordered, bool count_only, bool with_edges,
-	                    idx_t estimated_cardinality);
-	static vector<LogicalType> OutputTypes(bool count_only, bool with_edges);
-
-	shared_ptr<GGGraph> graph;
-	bool ordered;
-	bool count_only;
-	bool with_edges;
-
-public:
-	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override;
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context,
-	                                                 GlobalSourceState &gstate) const override;
-	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate,
-	             LocalSourceState &lstate) const override;
-	bool IsSource() const override {
-		return true;
-	}
-	bool ParallelSource() const override {
-		return true;
-	}
-	string GetName() const override {
-		return "GG_TRIANGLES";
 	}
 };
 

@@ -20,16 +20,9 @@
 // The graph comes from GGBuildGraph — or is the pinned graph of these tables if the connection asked for pinned graphs.
 // One batch of 64 sources is resident at a time: the pipeline's threads drain its rows together (GGResultDrain,
 // gg_operators.hpp), and whoever claims the last of them runs the next batch under the graph's lock.
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
 #include <unordered_set>
 
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
@@ -58,18 +51,17 @@ static vector<int64_t> Distinct(const vector<int64_t> &ids) {
 	return out;
 }
 
-class PhysicalGGKhopPairCounts : public PhysicalOperator {
+class PhysicalGGKhopPairCounts : public GGResultSource {
 public:
 	PhysicalGGKhopPairCounts(shared_ptr<GGGraph> graph_p, int hops_p, vector<int64_t> sources_p, bool all_sources_p,
 	                         vector<int64_t> targets_p, bool all_targets_p)
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(), 0), graph(move(graph_p)), hops(hops_p),
-	      sources(move(sources_p)), all_sources(all_sources_p), targets(move(targets_p)), all_targets(all_targets_p) {
+	    : GGResultSource(OutputTypes(), move(graph_p)), hops(hops_p), sources(move(sources_p)), all_sources(all_sources_p),
+	      targets(move(targets_p)), all_targets(all_targets_p) {
 	}
 	static vector<LogicalType> OutputTypes() {
 		return {LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT};
 	}
 
-	shared_ptr<GGGraph> graph;
 	int hops;
 	vector<int64_t> sources; // distinct (ignored if all_sources)
 	bool all_sources;
@@ -79,8 +71,7 @@ public:
 	//! the pair counts of the batch starting at source batch_base; caller holds graph->lock
 	GGResultPtr RunBatch(PairCountsState &state, idx_t batch_base, idx_t &rows) const {
 		const int n = (int)MinValue<idx_t>(GG_BFS_LANES, state.uniq.size() - batch_base);
-		static const int64_t none = 0; // an EMPTY target list must not arrive as a null pointer (gg.h: null means every vertex)
-		const int64_t *dst = all_targets ? nullptr : targets.empty() ? &none : targets.data();
+		const int64_t *dst = all_targets ? nullptr : GGSourceIds(targets);
 		gg_pair_stats stats {};
 		GGResultPtr owner;
 		GGGraph::Check(gg_khop_pair_counts(graph->ctx, graph->csr, state.uniq.data() + batch_base, n, hops, hops, dst,
@@ -110,17 +101,11 @@ public:
 		return move(state);
 	}
 
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
-		return make_unique<GGResultSlab>(graph);
-	}
-
 	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
 	             LocalSourceState &lstate) const override {
 		auto &gstate = (PairCountsState &)gstate_p;
 		auto &slab = (GGResultSlab &)lstate;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
+		PollInterrupt(context);
 		if (slab.pos >= slab.rows) {
 			auto &drain = gstate.drain;
 			auto advance = [&]() -> bool { // current batch claimed completely: run the next one
@@ -163,30 +148,17 @@ public:
 	}
 };
 
-} // namespace
-
-static unique_ptr<FunctionData> KhopPairCountsBind(ClientContext &context, vector<Value> &inputs,
-                                                   unordered_map<string, Value> &named_parameters,
-                                                   vector<LogicalType> &input_table_types,
-                                                   vector<string> &input_table_names, vector<LogicalType> &return_types,
-                                                   vector<string> &names) {
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
+unique_ptr<FunctionData> KhopPairCountsBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                            vector<string> &names, int kind) {
+	const string fn = "gg_khop_pair_counts";
+	const GraphArguments args(inputs);
 	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
 	const string targets_sql = inputs[6].is_null ? string() : inputs[6].ToString();
-	if (inputs[7].is_null) {
-		throw BinderException("gg_khop_pair_counts: hops must not be NULL");
-	}
-	const auto hops = inputs[7].GetValue<int64_t>();
-	if (hops < 1 || hops > GG_MAX_HOPS) {
-		throw BinderException("gg_khop_pair_counts: need 1 <= hops <= " + to_string(GG_MAX_HOPS));
-	}
+	GGRequireArguments(fn, inputs, {7}, "hops");
+	const auto hops = GGHopsArgument(fn, inputs[7], GG_MAX_HOPS);
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		GGGraphSpec spec; // (tables and columns are resolved at execution time: a missing one raises here)
-		spec.vertices = GGTableSource(ctx, vertex_table, {vertex_key}, false);
-		spec.edges = GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false);
-		opened.graph = GGBuildGraph(ctx, spec);
+		opened.graph = args.Build(ctx);
 		vector<int64_t> sources, targets;
 		if (!sources_sql.empty()) {
 			sources = Distinct(GGQueryInt64Column(ctx, sources_sql, "gg_khop_pair_counts: sources"));
@@ -198,19 +170,18 @@ static unique_ptr<FunctionData> KhopPairCountsBind(ClientContext &context, vecto
 		                                                      move(targets), targets_sql.empty());
 	};
 	data->parallel_result = true;
-	data->description = "count by (source, end) over " + to_string(hops) + "-hop walks of " + edge_table;
+	data->description = "count by (source, end) over " + to_string(hops) + "-hop walks of " + args.edge_table;
 	return_types = PhysicalGGKhopPairCounts::OutputTypes();
 	names = {"source", "vertex", "walks"};
 	return move(data);
 }
 
+} // namespace
+
 void GGRegisterPairCountFunctions(ClientContext &context) {
-	const vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                                  LogicalType::VARCHAR, LogicalType::BIGINT};
-	auto fn = GGScanFunction("gg_khop_pair_counts", args, KhopPairCountsBind);
-	CreateTableFunctionInfo info(fn);
-	Catalog::GetCatalog(context).CreateTableFunction(context, &info);
+	auto args = GraphArguments::Types();
+	args.insert(args.end(), {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BIGINT});
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_khop_pair_counts", args, GGBind<KhopPairCountsBind>)});
 }
 
 } // namespace duckdb

@@ -25,25 +25,16 @@
 // m_creationdate DESC, m_messageid LIMIT 20), the date range of interactive-complex-4.sql:9,18.  No planner rule recognises
 // these shapes.
 // The walk table and the extended table are dropped before the first row leaves; only the answer's rows stay on the device.
-#include "duckdb.hpp"
-#include "duckdb/catalog/catalog.hpp"
-#include "duckdb/common/exception.hpp"
-#include "duckdb/main/client_context.hpp"
-#include "duckdb/parser/parsed_data/create_table_function_info.hpp"
-
-#include "gg_extension.hpp"
-#include "gg_operators.hpp"
+#include "gg_table_function.hpp"
 
 namespace duckdb {
 
 namespace {
 
-enum class ValueRowsKind { FILTER, COUNT, TOP };
+enum ValueRowsKind { FILTER, COUNT, TOP };
 
-const char *FunctionName(ValueRowsKind kind) {
-	return kind == ValueRowsKind::FILTER ? "gg_khop_extend_filter"
-	       : kind == ValueRowsKind::COUNT ? "gg_khop_extend_filter_count"
-	                                      : "gg_khop_extend_top";
+const char *FunctionName(int kind) {
+	return kind == FILTER ? "gg_khop_extend_filter" : kind == COUNT ? "gg_khop_extend_filter_count" : "gg_khop_extend_top";
 }
 
 //! a value per vertex of one CSR, in its vertex-table order (include/gg.h, "the value of a row")
@@ -96,20 +87,8 @@ ValueColumn ValuesInVertexOrder(ClientContext &context, GGGraph &graph, gg_csr *
 	return out;
 }
 
-class ValueRowsState : public GlobalSourceState {
-public:
-	idx_t MaxThreads() override {
-		return max_threads;
-	}
-	gg_value_filter_stats stats {};
-	GGResultDrain drain;  // the rows (COUNT: none)
-	bool counted = false; // COUNT: the one row went out (under drain.lock)
-	idx_t max_threads = 1;
-	idx_t next_rank = 0;  // TOP: the rank of the next row to leave
-};
-
 struct ValueRowsSpec {
-	ValueRowsKind kind;
+	int kind; // ValueRowsKind
 	int hops, from_col, value_of;
 	int64_t lo, hi;
 	bool negate, descending;
@@ -117,49 +96,36 @@ struct ValueRowsSpec {
 	uint64_t n;  // TOP: UINT64_MAX: every row
 };
 
-class PhysicalGGValueRows : public PhysicalOperator {
+class PhysicalGGValueRows : public GGWalkSource {
 public:
 	PhysicalGGValueRows(shared_ptr<GGGraph> graph_p, ValueRowsSpec spec_p, vector<int64_t> sources_p, bool all_sources_p,
 	                    ValueColumn column_p)
-	    : PhysicalOperator(PhysicalOperatorType::INVALID, OutputTypes(spec_p), 0), graph(move(graph_p)), spec(spec_p),
-	      sources(move(sources_p)), all_sources(all_sources_p), column(move(column_p)) {
+	    : GGWalkSource(OutputTypes(spec_p), move(graph_p), spec_p.hops, move(sources_p), all_sources_p), spec(spec_p),
+	      column(move(column_p)) {
 	}
 	static vector<LogicalType> OutputTypes(const ValueRowsSpec &spec) {
-		const idx_t n = spec.kind == ValueRowsKind::COUNT ? 3 : spec.hops + 3 + (spec.kind == ValueRowsKind::TOP ? 1 : 0);
+		const idx_t n = spec.kind == COUNT ? 3 : spec.hops + 3 + (spec.kind == TOP ? 1 : 0);
 		return vector<LogicalType>(n, LogicalType::BIGINT);
 	}
+	typedef GGDrainStateOf<gg_value_filter_stats> State;
 
-	shared_ptr<GGGraph> graph;
 	ValueRowsSpec spec;
-	vector<int64_t> sources;
-	bool all_sources;
 	ValueColumn column;
 
 	unique_ptr<GlobalSourceState> GetGlobalSourceState(ClientContext &context) const override {
-		auto state = make_unique<ValueRowsState>();
+		auto state = make_unique<State>();
 		lock_guard<mutex> guard(graph->lock);
 		if (!graph->csr || !graph->filter_csr) {
 			throw InternalException("GG_VALUE_ROWS scheduled before both CSRs were built");
 		}
-		static const int64_t none = 0; // an EMPTY list must not arrive as a null pointer (gg.h: null means every vertex)
-		const int64_t *ids = all_sources ? nullptr : sources.empty() ? &none : sources.data();
-		const int hops = spec.hops, out_hops = hops + 1;
+		const int out_hops = hops + 1;
 		const gg_csr *value_csr = spec.value_of == out_hops ? graph->filter_csr : graph->csr;
 		const int mode = spec.negate ? GG_VALUE_NOT_IN : GG_VALUE_IN;
 		state->drain.Replace(context, out_hops, [&](idx_t &rows) {
 			GGResultPtr owner, extended;
-			{
-				GGResultPtr walks; // (gone once extended)
-				gg_khop_stats walk_stats;
-				GGGraph::Check(gg_expand_khop_result(graph->ctx, graph->csr, ids, all_sources ? 0 : sources.size(), hops,
-				                                     hops, &walk_stats, GGResultOut(walks)),
-				               "gg_expand_khop_result");
-				gg_extend_stats extend_stats {};
-				GGGraph::Check(gg_result_extend_edge(graph->ctx, walks.get(), hops, graph->filter_csr, spec.from_col, 1, 1,
-				                                     &extend_stats, GGResultOut(extended)),
-				               "gg_result_extend_edge");
-			}
-			if (spec.kind == ValueRowsKind::TOP) {
+			gg_extend_stats extend_stats {};
+			ExpandExtended(spec.from_col, true, true, extend_stats, &extended);
+			if (spec.kind == TOP) {
 				gg_value_top_stats top {};
 				GGGraph::Check(gg_result_top_rows(graph->ctx, extended.get(), out_hops, spec.value_of, value_csr,
 				                                  column.values.data(), column.valid.data(), spec.lo, spec.hi, mode,
@@ -168,75 +134,40 @@ public:
 				state->stats.rows_in = top.rows_in, state->stats.rows_valued = top.rows_valued;
 				state->stats.rows_out = top.rows_out;
 			} else {
-				const bool count = spec.kind == ValueRowsKind::COUNT;
+				const bool count = spec.kind == COUNT;
 				GGGraph::Check(gg_result_filter_value(graph->ctx, extended.get(), out_hops, spec.value_of, value_csr,
 				                                      column.values.data(), column.valid.data(), spec.lo, spec.hi, mode,
 				                                      count ? 0 : 1, &state->stats,
 				                                      count ? nullptr : static_cast<gg_result **>(GGResultOut(owner))),
 				               "gg_result_filter_value");
 			}
-			rows = spec.kind == ValueRowsKind::COUNT ? 0 : state->stats.rows_out;
+			rows = spec.kind == COUNT ? 0 : state->stats.rows_out;
 			return owner; // (the extended table goes back to the pool here: only the answer's rows stay in HBM)
 		});
-		if (spec.kind == ValueRowsKind::FILTER) {
+		if (spec.kind == FILTER) {
 			state->max_threads = GGResultSlab::ThreadsFor(state->stats.rows_out);
 		}
 		return move(state);
 	}
 
-	unique_ptr<LocalSourceState> GetLocalSourceState(ExecutionContext &context, GlobalSourceState &gstate) const override {
-		return make_unique<GGResultSlab>(graph);
-	}
-
 	void GetData(ExecutionContext &context, DataChunk &chunk, GlobalSourceState &gstate_p,
 	             LocalSourceState &lstate) const override {
-		auto &gstate = (ValueRowsState &)gstate_p;
-		if (context.client.interrupted) {
-			throw InterruptException();
-		}
-		if (spec.kind == ValueRowsKind::COUNT) {
-			lock_guard<mutex> guard(gstate.drain.lock);
-			if (gstate.counted) {
-				return;
-			}
-			gstate.counted = true;
-			FlatVector::GetData<int64_t>(chunk.data[0])[0] = (int64_t)gstate.stats.rows_out;
-			FlatVector::GetData<int64_t>(chunk.data[1])[0] = (int64_t)gstate.stats.rows_in;
-			FlatVector::GetData<int64_t>(chunk.data[2])[0] = (int64_t)gstate.stats.rows_valued;
-			chunk.SetCardinality(1);
+		auto &gstate = (State &)gstate_p;
+		PollInterrupt(context);
+		if (spec.kind == COUNT) {
+			EmitCountRow(gstate, chunk, {gstate.stats.rows_out, gstate.stats.rows_in, gstate.stats.rows_valued});
 			return;
 		}
+		// the slab: the id columns v0..v{hops}, w, then the edge columns e1..e{hops+1}, the last of which is ext_rowid
 		auto &slab = (GGResultSlab &)lstate;
-		// the slab: the id columns v0..v{hops}, w, then the edge columns e1..e{hops+1} — of which only the last, the joined
-		// row's rowid, goes out (the walk carries no edge columns: the others hold -1)
-		const idx_t ids = (idx_t)spec.hops + 2, edges = (idx_t)spec.hops + 1;
-		if (slab.pos >= slab.rows) {
-			auto fetch = [ids, edges](gg_result *result, int table, idx_t offset, uint32_t want, GGResultSlab &slab) {
-				uint32_t got = 0, got_edges = 0;
-				auto columns = slab.Columns(ids + edges);
-				GGGraph::Check(gg_result_fetch(result, table, offset, want, columns, &got), "gg_result_fetch");
-				GGGraph::Check(gg_result_fetch_edges(result, table, offset, want, columns + ids, &got_edges),
-				               "gg_result_fetch_edges");
-				if (got_edges != got) {
-					throw InternalException("gg_khop_extend_filter: id and edge columns of different lengths");
-				}
-				return got;
-			};
-			if (!gstate.drain.Refill(slab, [] { return false; }, fetch)) { // (one table: nothing to advance to)
-				return;
-			}
+		const idx_t ids = (idx_t)hops + 2, edges = (idx_t)hops + 1;
+		if (!FetchIdsAndEdges(gstate, slab, ids, edges, "gg_khop_extend_filter")) {
+			return;
 		}
-		const idx_t first = spec.kind == ValueRowsKind::TOP ? 1 : 0;
-		const idx_t n = MinValue<idx_t>(STANDARD_VECTOR_SIZE, slab.rows - slab.pos);
-		memcpy(FlatVector::GetData<int64_t>(chunk.data[first + ids]), slab.column[ids + edges - 1] + slab.pos,
-		       n * sizeof(int64_t));
-		const idx_t count = slab.Emit(chunk, first, ids);
-		if (first) {
-			auto rank = FlatVector::GetData<int64_t>(chunk.data[0]);
-			for (idx_t i = 0; i < count; i++) {
-				rank[i] = (int64_t)(gstate.next_rank + i); // (one thread: the slabs are claimed and emitted in order)
-			}
-			gstate.next_rank += count;
+		if (spec.kind == TOP) {
+			EmitRank(gstate, chunk, EmitIdsAndRowid(slab, chunk, 1, ids, edges));
+		} else {
+			EmitIdsAndRowid(slab, chunk, 0, ids, edges);
 		}
 	}
 
@@ -245,40 +176,26 @@ public:
 	}
 };
 
-unique_ptr<FunctionData> ValueRowsBindInternal(vector<Value> &inputs, vector<LogicalType> &return_types,
-                                               vector<string> &names, ValueRowsKind kind) {
-	const string fn = FunctionName(kind);
-	const string vertex_table = inputs[0].ToString(), vertex_key = inputs[1].ToString();
-	const string edge_table = inputs[2].ToString(), edge_src = inputs[3].ToString(), edge_dst = inputs[4].ToString();
-	const string sources_sql = inputs[5].is_null ? string() : inputs[5].ToString();
-	for (idx_t i = 6; i <= 12; i++) {
-		if (inputs[i].is_null) {
-			throw BinderException(fn + ": hops, ext_table, ext_key_col, ext_next_col, from_col, value_column and value_of "
-			                           "must not be NULL");
-		}
-	}
-	const auto hops = inputs[6].GetValue<int64_t>(), from_col = inputs[10].GetValue<int64_t>();
-	const string ext_table = inputs[7].ToString(), ext_key = inputs[8].ToString(), ext_next = inputs[9].ToString();
+unique_ptr<FunctionData> ValueRowsBind(ClientContext &context, vector<Value> &inputs, vector<LogicalType> &return_types,
+                                       vector<string> &names, int kind) {
+	const GGWalkArguments args(FunctionName(kind), inputs, GGWalkArguments::EXTENSION, {6, 7, 8, 9, 10, 11, 12},
+	                           "hops, ext_table, ext_key_col, ext_next_col, from_col, value_column and value_of");
+	const string &fn = args.fn;
+	const auto hops = args.hops;
 	const string value_column = inputs[11].ToString();
 	const auto value_of = inputs[12].GetValue<int64_t>();
-	if (hops < 1 || hops + 1 > GG_MAX_HOPS) {
-		throw BinderException(fn + ": need 1 <= hops <= " + to_string(GG_MAX_HOPS - 1));
-	}
-	if (from_col < 0 || from_col > hops) {
-		throw BinderException(fn + ": from_col must lie in 0.." + to_string(hops));
-	}
 	if (value_of < 0 || value_of > hops + 1) {
 		throw BinderException(fn + ": value_of must lie in 0.." + to_string(hops + 1));
 	}
 	ValueRowsSpec spec {};
 	spec.kind = kind;
-	spec.hops = (int)hops, spec.from_col = (int)from_col, spec.value_of = (int)value_of;
+	spec.hops = (int)hops, spec.from_col = (int)args.from_col, spec.value_of = (int)value_of;
 	spec.lo = inputs[13].is_null ? INT64_MIN : inputs[13].GetValue<int64_t>();
 	spec.hi = inputs[14].is_null ? INT64_MAX : inputs[14].GetValue<int64_t>();
 	spec.negate = !inputs[15].is_null && inputs[15].GetValue<bool>();
 	spec.tie_col = -1;
 	spec.n = UINT64_MAX;
-	if (kind == ValueRowsKind::TOP) {
+	if (kind == TOP) {
 		spec.descending = !inputs[16].is_null && inputs[16].GetValue<bool>();
 		if (!inputs[17].is_null) {
 			const auto tie = inputs[17].GetValue<int64_t>();
@@ -297,65 +214,38 @@ unique_ptr<FunctionData> ValueRowsBindInternal(vector<Value> &inputs, vector<Log
 	}
 	auto data = make_unique<GGFunctionData>();
 	data->open = [=](ClientContext &ctx, GGOpened &opened) {
-		// (tables and columns are resolved at execution time: a missing one raises here)
-		opened.graph = GGBuildExtendGraph(ctx, GGTableSource(ctx, vertex_table, {vertex_key}, false),
-		                                  GGTableSource(ctx, edge_table, {edge_src, edge_dst}, false),
-		                                  GGTableSource(ctx, ext_table, {ext_key, ext_next}, true));
-		vector<int64_t> sources;
-		if (!sources_sql.empty()) {
-			sources = GGQueryInt64Column(ctx, sources_sql, (fn + ": sources").c_str());
-		}
-		const bool of_ext = value_of == hops + 1;
+		opened.graph = args.BuildGraph(ctx);
+		auto sources = args.Sources(ctx);
+		const bool of_ext = value_of == args.hops + 1;
 		auto column = ValuesInVertexOrder(ctx, *opened.graph, of_ext ? opened.graph->filter_csr : opened.graph->csr,
-		                                  of_ext ? ext_table : vertex_table, of_ext ? ext_next : vertex_key, value_column,
-		                                  fn.c_str());
-		opened.source = make_unique<PhysicalGGValueRows>(opened.graph, spec, move(sources), sources_sql.empty(), move(column));
+		                                  of_ext ? args.ext_table : args.vertex_table, of_ext ? args.ext_next : args.vertex_key,
+		                                  value_column, args.fn.c_str());
+		opened.source = make_unique<PhysicalGGValueRows>(opened.graph, spec, move(sources), args.AllSources(), move(column));
 	};
-	data->parallel_result = kind == ValueRowsKind::FILTER; // (the top's rows leave in rank order)
-	data->description = to_string(hops) + "-hop walks of " + edge_table + " joined with " + ext_table + " on v" +
-	                    to_string(from_col) + " = " + ext_key + ", " + value_column + " of column " + to_string(value_of) +
+	data->parallel_result = kind == FILTER; // (the top's rows leave in rank order)
+	data->description = args.Describe() + ", " + value_column + " of column " + to_string(value_of) +
 	                    (spec.negate ? " outside [" : " in [") + to_string(spec.lo) + ", " + to_string(spec.hi) + "]" +
-	                    (kind == ValueRowsKind::TOP ? string(", ordered") + (spec.descending ? " descending" : "") : string());
+	                    (kind == TOP ? string(", ordered") + (spec.descending ? " descending" : "") : string());
 	return_types = PhysicalGGValueRows::OutputTypes(spec);
-	if (kind == ValueRowsKind::COUNT) {
+	if (kind == COUNT) {
 		names = {"rows", "walks", "valued"};
 	} else {
-		if (kind == ValueRowsKind::TOP) {
-			names.push_back("rank");
-		}
-		for (int64_t c = 0; c <= hops; c++) {
-			names.push_back("v" + to_string(c));
-		}
-		names.push_back("w");
-		names.push_back("ext_rowid");
+		GGWalkColumnNames(names, hops, true, kind == TOP);
 	}
 	return move(data);
-}
-
-template <ValueRowsKind KIND>
-unique_ptr<FunctionData> ValueRowsBind(ClientContext &context, vector<Value> &inputs,
-                                       unordered_map<string, Value> &named_parameters,
-                                       vector<LogicalType> &input_table_types, vector<string> &input_table_names,
-                                       vector<LogicalType> &return_types, vector<string> &names) {
-	return ValueRowsBindInternal(inputs, return_types, names, KIND);
 }
 
 } // namespace
 
 void GGRegisterValueRowsFunctions(ClientContext &context) {
-	vector<LogicalType> args = {LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::VARCHAR,
-	                            LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BIGINT,  LogicalType::VARCHAR,
-	                            LogicalType::VARCHAR, LogicalType::VARCHAR, LogicalType::BIGINT,  LogicalType::VARCHAR,
-	                            LogicalType::BIGINT,  LogicalType::BIGINT,  LogicalType::BIGINT,  LogicalType::BOOLEAN};
-	auto filter = GGScanFunction("gg_khop_extend_filter", args, ValueRowsBind<ValueRowsKind::FILTER>);
-	auto count = GGScanFunction("gg_khop_extend_filter_count", args, ValueRowsBind<ValueRowsKind::COUNT>);
-	args.insert(args.end(), {LogicalType::BOOLEAN, LogicalType::BIGINT, LogicalType::BIGINT});
-	auto top = GGScanFunction("gg_khop_extend_top", args, ValueRowsBind<ValueRowsKind::TOP>);
-	CreateTableFunctionInfo filter_info(filter), count_info(count), top_info(top);
-	auto &catalog = Catalog::GetCatalog(context);
-	catalog.CreateTableFunction(context, &filter_info);
-	catalog.CreateTableFunction(context, &count_info);
-	catalog.CreateTableFunction(context, &top_info);
+	auto args = GGWalkArguments::Types(true);
+	args.insert(args.end(), {LogicalType::VARCHAR, LogicalType::BIGINT, LogicalType::BIGINT, LogicalType::BIGINT,
+	                         LogicalType::BOOLEAN});
+	auto top_args = args;
+	top_args.insert(top_args.end(), {LogicalType::BOOLEAN, LogicalType::BIGINT, LogicalType::BIGINT});
+	GGRegisterTableFunctions(context, {GGScanFunction("gg_khop_extend_filter", args, GGBind<ValueRowsBind, FILTER>),
+	                                   GGScanFunction("gg_khop_extend_filter_count", args, GGBind<ValueRowsBind, COUNT>),
+	                                   GGScanFunction("gg_khop_extend_top", top_args, GGBind<ValueRowsBind, TOP>)});
 }
 
 } // namespace duckdb
