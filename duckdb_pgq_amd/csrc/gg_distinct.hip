@@ -11,6 +11,7 @@
 // The table: `cap` slots of 32-bit ROW NUMBERS, not of keys — 4 bytes per slot whatever the number of chosen columns, no
 // sentinel among the ids (every int64 value is an ordinary cell), one code path for 1 to 9 columns.  A slot holds the
 // smallest row number seen so far among the rows of ONE tuple; the tuple is read from the input columns through it.
+// The two kernels live in gg_tuples.h, which gg_group_tuples.hip includes as well.
 //   k_distinct_insert  one thread per row, striding by workgroups of 256 rows: the chosen cells, their hash (fmix64 folded
 //                      over the columns in their chosen order, so (a, b) and (b, a) differ), linear probing from the home
 //                      slot.  An empty slot (0xFFFFFFFF) is claimed by a 32-bit atomicCAS of the own row number; on an
@@ -44,112 +45,9 @@
 // as gg_rows.h.  The table itself: 4 cap B set to 0xFF.
 #include "gg_internal.h"
 #include "gg_rows.h"
+#include "gg_tuples.h"
 
 using namespace gg;
-
-namespace gg {
-namespace {
-
-constexpr int DST_MAX_COLS = GG_MAX_HOPS + 1;
-constexpr uint32_t DST_EMPTY = 0xFFFFFFFFu;  // no row: row numbers are below 2^32 - 1 (n_rows < 2^32)
-constexpr uint64_t DST_MAX_SLOTS = 1ull << 32;
-
-struct DistinctArgs {
-  const int64_t *c[DST_MAX_COLS];  // the chosen columns, in their chosen order
-  int ncols;
-  uint64_t n_rows;
-  uint32_t *tab;      // cap slots
-  uint64_t cap;       // a power of two > n_rows
-  uint32_t *slot_of;  // n_rows: the slot the row ended in (0 for a row that did not probe: no slot ever holds such a row)
-  int combine;        // adjacent equal lanes of a wavefront are combined
-  uint64_t *mask;     // ceil(n_rows / 64) words (k_distinct_flag)
-  unsigned long long *words;  // [0] probe steps, [1] error (a row exhausted the probe bound), [2] rows that pass
-};
-
-// Workgroup g owns rows [256 g, 256 g + 256); the grid strides over the groups.
-__global__ __launch_bounds__(256) void k_distinct_insert(DistinctArgs a) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t groups = (a.n_rows + 255) / 256, smask = a.cap - 1;
-  uint64_t steps = 0;
-  bool failed = false;
-  for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-    const uint64_t r = g * 256 + threadIdx.x;
-    const bool live = r < a.n_rows;
-    int64_t mine[DST_MAX_COLS];
-    uint64_t h = 0;
-    bool same = true;  // as the row of the lane below
-#pragma unroll
-    for (int c = 0; c < DST_MAX_COLS; c++) {
-      if (c < a.ncols) {  // (uniform: every lane shuffles)
-        mine[c] = live ? a.c[c][r] : 0;
-        h = fmix64((h ^ (uint64_t)mine[c]) + DIG_GOLD);
-        const int64_t below = (int64_t)__shfl_up((unsigned long long)mine[c], 1, 64);
-        same = same && below == mine[c];
-      }
-    }
-    // (lane l - 1 holds row r - 1 < n_rows whenever lane l is live)
-    const bool probes = live && !(a.combine && lane != 0 && same);
-    uint32_t my_slot = 0;
-    if (probes) {
-      const uint32_t me = (uint32_t)r;
-      uint64_t s = h & smask;
-      bool done = false;
-      for (uint64_t t = 0; t < a.cap && !done; t++, s = (s + 1) & smask) {  // (s < cap: the table's bound)
-        steps++;
-        uint32_t occ = __atomic_load_n(&a.tab[s], __ATOMIC_RELAXED);  // (may be stale: see the file comment)
-        if (occ == DST_EMPTY) {
-          occ = atomicCAS(&a.tab[s], DST_EMPTY, me);
-          if (occ == DST_EMPTY) {
-            my_slot = (uint32_t)s, done = true;
-            break;
-          }
-        }
-        if (occ >= a.n_rows) break;  // (cannot happen: a slot holds empty or a row number; never gather out of bounds)
-        bool eq = true;
-#pragma unroll
-        for (int c = 0; c < DST_MAX_COLS; c++)
-          if (c < a.ncols) eq = eq && a.c[c][occ] == mine[c];
-        if (eq) {
-          if (me < occ) atomicMin(&a.tab[s], me);
-          my_slot = (uint32_t)s, done = true;
-        }
-      }
-      if (!done) failed = true, my_slot = 0;
-    }
-    if (live) a.slot_of[r] = my_slot;
-  }
-  steps = wave_reduce_add_u64(steps);
-  if (lane == 0 && steps) atomicAdd(&a.words[0], (unsigned long long)steps);
-  if (failed) atomicMax(&a.words[1], 1ull);
-}
-
-// row r passes iff its slot holds r; mask word r / 64 is the wavefront's ballot, as k_value_probe writes it
-__global__ __launch_bounds__(256) void k_distinct_flag(DistinctArgs a) {
-  const int lane = threadIdx.x & 63;
-  const uint64_t groups = (a.n_rows + 255) / 256;
-  uint64_t passed = 0;  // (uniform over the wavefront)
-  for (uint64_t g = blockIdx.x; g < groups; g += gridDim.x) {
-    const uint64_t r = g * 256 + threadIdx.x;
-    bool pass = false;
-    if (r < a.n_rows) {
-      const uint32_t s = a.slot_of[r];  // (< cap)
-      pass = a.tab[s] == (uint32_t)r;
-    }
-    const uint64_t pm = __ballot(pass);
-    passed += (uint64_t)__popcll(pm);
-    if (lane == 0 && (r & ~63ull) < a.n_rows) a.mask[r >> 6] = pm;  // (r >> 6 < ceil(n_rows / 64))
-  }
-  if (lane == 0 && passed) atomicAdd(&a.words[2], (unsigned long long)passed);
-}
-
-uint64_t pow2_at_least(uint64_t n) {
-  uint64_t p = 1;
-  while (p < n) p <<= 1;
-  return p;
-}
-
-}  // namespace
-}  // namespace gg
 
 extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, const int *cols, int n_cols,
                                   int materialise, gg_distinct_stats *stats, gg_result **out_result) {
@@ -168,33 +66,8 @@ extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, c
     set_error("gg_result_distinct: neither stats nor out_result is asked for");
     return GG_ERR_INVALID_ARG;
   }
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
-    set_error("gg_result_distinct: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
-    return GG_ERR_INVALID_ARG;
-  }
-  if (n_cols < 1 || n_cols > hops + 1) {
-    set_error("gg_result_distinct: %d columns chosen, outside 1..%d", n_cols, hops + 1);
-    return GG_ERR_INVALID_ARG;
-  }
-  uint32_t seen = 0;
-  for (int j = 0; j < n_cols; j++) {
-    if (cols[j] < 0 || cols[j] > hops || ((seen >> cols[j]) & 1u)) {
-      set_error("gg_result_distinct: column %d (place %d) outside 0..%d or chosen twice", cols[j], j, hops);
-      return GG_ERR_INVALID_ARG;
-    }
-    seen |= 1u << cols[j];
-  }
+  GG_TRY(tuple_columns_check("gg_result_distinct", res, hops, cols, n_cols));
   const uint64_t n_rows = res->rows[hops], n_words = (n_rows + 63) / 64;
-  if (n_rows >= (1ull << 32)) {
-    set_error("gg_result_distinct: a table of %llu rows (2^32 or more); filter it first", (unsigned long long)n_rows);
-    return GG_ERR_TOO_LARGE;
-  }
-  if (n_rows)
-    for (int j = 0; j < n_cols; j++)
-      if (!res->cols[hops][cols[j]]) {
-        set_error("gg_result_distinct: table %d of the result has rows but no id columns", hops);
-        return GG_ERR_STATE;
-      }
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
   const int out_hops = n_cols - 1;
@@ -203,11 +76,7 @@ extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, c
   uint64_t words_host[3] = {0, 0, 0}, total = 0, cap = 0;  // probe steps, error, rows that pass
   if (n_rows) {
     hipStream_t st = ctx->stream;
-    // a power of two strictly above n_rows: an empty slot always exists (n_rows < 2^32, so 2^32 slots always do)
-    const uint64_t want = ctx->distinct_slots ? ctx->distinct_slots : 2 * n_rows;
-    cap = pow2_at_least(want < DST_MAX_SLOTS ? want : DST_MAX_SLOTS);
-    const uint64_t least = pow2_at_least(n_rows + 1);  // (<= 2^32)
-    if (cap < least) cap = least;
+    cap = tuple_slots(ctx, n_rows);
     DistinctArgs a{};
     for (int j = 0; j < n_cols; j++) a.c[j] = res->cols[hops][cols[j]];
     a.ncols = n_cols;

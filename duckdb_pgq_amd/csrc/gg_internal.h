@@ -208,6 +208,8 @@ struct gg_ctx {
   uint32_t val_top_floor = 0;       // gg_debug_value_top: as agg_top_floor
   uint64_t distinct_slots = 0;      // gg_debug_distinct: slots of gg_result_distinct's table (0: the default), rounded up there
   int distinct_combine = 0;         // gg_debug_distinct: 0 adjacent equal lanes are combined, 1 every row probes
+  int tuple_route = 0;              // gg_debug_group_tuples: 0 the group count decides, 1 the LDS cells where they fit, 2 the global cells
+  uint32_t tuple_lds_groups = 0;    // gg_debug_group_tuples: groups the workgroup-private cells of gg_result_group_tuples may hold (0: the default)
   bool cc_size_fold = true;     // GG_CC_SIZE_FOLD=0 at context creation: gg_components adds sizes per lane, never per wave
                                 // (a measurement switch, scripts/bench_components.py; sizes are the same either way)
   uint64_t agg_top_listed = 0;  // gg_debug_aggregate_top_listed: list entries the last gg_khop_aggregate_top compacted to
@@ -319,13 +321,14 @@ struct gg_csr {
 // What a device result holds and which calls read it.  The kinds from AGGREGATE on were born with a refusal contract:
 // every call but their own answers them with GG_ERR_STATE, and theirs answer every other kind so (gg::expect_kind).
 enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGATE, PAIR_COUNTS, COMPONENTS, ALL_PATHS, CHEAPEST,
-                        CHEAPEST_PATHS };
+                        CHEAPEST_PATHS, TUPLE_GROUPS };
 
 // kind          tables and columns (h: a level in k_min..k_max)                     read by
 // TABLES        rows[h], cols[h][0..h] = ids v0..vh; ecols[h][j] = rowid of the     gg_result_rows / _fetch / _fetch_edges /
 //               (j + 1)-th edge if asked for; tri_edges: ecols[2][0..2] = e1, e2,   _digest / _filter_* / _extend_edge,
 //               e3 of a triangle row                                                gg_triangles_fetch_edges, gg_result_group_by,
-//                                                                                   gg_result_top_rows, gg_result_distinct
+//                                                                                   gg_result_top_rows, gg_result_distinct,
+//                                                                                   gg_result_group_tuples
 // WALK_CLOSURE  rows[0] walks level by level, level_rows[L - 1] those of L edges;   gg_walk_closure_levels / _fetch
 //               cols[0][0..1] = index of the seed, rowid of the last edge
 // REACH         the same; cols[0][0..1] = class, vertex id of level L's new pairs   gg_reach_closure_levels / _fetch
@@ -347,6 +350,9 @@ enum class ResultKind { TABLES, WALK_CLOSURE, REACH, LEVEL_SETS, PATHS, AGGREGAT
 //               traced (both int32 cells); rows[CPP_ROWS_TABLE], cols[..][0..4] =    _fetch
 //               pair index, step (int32 cells), vertex id, edge rowid if asked for,
 //               cost
+// TUPLE_GROUPS  rows[0] groups, k_min = k_max = key columns - 1; cols[0][j] = key      gg_tuple_groups_rows / _fetch
+//               column j; cols[1][0..5] = rows, valued, sum low, sum high, min, max
+//               (the count form has cols[1][0] alone: the others read as 0)
 struct gg_result {
   gg_ctx *ctx = nullptr;
   ResultKind kind = ResultKind::TABLES;
@@ -410,8 +416,9 @@ constexpr KindName KIND_NAMES[] = {
     {"all shortest paths", "gg_bfs64_all_paths_rows / _fetch_pairs / _fetch"},
     {"cheapest path costs", "gg_cheapest64_rows / gg_cheapest64_fetch"},
     {"cheapest paths", "gg_cheapest64_paths_rows / _fetch_pairs / _fetch"},
+    {"aggregates per key tuple", "gg_tuple_groups_rows / gg_tuple_groups_fetch"},
 };
-static_assert(sizeof(KIND_NAMES) / sizeof(KIND_NAMES[0]) == (size_t)ResultKind::CHEAPEST_PATHS + 1, "a name per kind");
+static_assert(sizeof(KIND_NAMES) / sizeof(KIND_NAMES[0]) == (size_t)ResultKind::TUPLE_GROUPS + 1, "a name per kind");
 inline int expect_kind(const gg_result *res, ResultKind want, const char *fn) {
   if (!res) return GG_ERR_INVALID_ARG;
   if (res->kind == want) return GG_OK;

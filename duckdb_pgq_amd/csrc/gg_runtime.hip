@@ -472,6 +472,8 @@ extern "C" int gg_debug_reset(gg_ctx *ctx) {
   ctx->extend_tile_rows = 0;
   ctx->group_route = 0;
   ctx->group_lds_keys = 0;
+  ctx->tuple_route = 0;
+  ctx->tuple_lds_groups = 0;
   ctx->keep_edge_rowid = true;
   ctx->bfs_steps.clear();
   ctx->bfs_cell_bytes = 0;

@@ -45,6 +45,7 @@ SYMBOLS = [
     "gg_result_group_by", "gg_debug_group",
     "gg_result_filter_value", "gg_result_top_rows", "gg_debug_value_top",
     "gg_result_distinct", "gg_debug_distinct",
+    "gg_result_group_tuples", "gg_tuple_groups_rows", "gg_tuple_groups_fetch", "gg_debug_group_tuples",
     "gg_profile_enable", "gg_profile_select", "gg_profile_reset", "gg_profile_count", "gg_profile_get",
 ]
 
@@ -112,6 +113,11 @@ class ValueTopStats(C.Structure):
 
 class DistinctStats(C.Structure):
     _fields_ = [("rows_in", C.c_uint64), ("rows_out", C.c_uint64), ("slots", C.c_uint64), ("probe_steps", C.c_uint64)]
+
+
+class GroupTuplesStats(C.Structure):
+    _fields_ = [("rows_in", C.c_uint64), ("rows_valued", C.c_uint64), ("groups", C.c_uint64), ("slots", C.c_uint64),
+                ("probe_steps", C.c_uint64), ("route", C.c_uint32)]
 
 
 class AggStats(C.Structure):
@@ -286,6 +292,12 @@ def load_library(path: str | None = None):
     lib.gg_result_distinct.argtypes = [P, P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(DistinctStats),
                                        C.POINTER(P)]
     lib.gg_debug_distinct.argtypes = [P, u64, C.c_int]
+    lib.gg_result_group_tuples.argtypes = [P, P, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, P, i64p, C.POINTER(u64),
+                                           C.POINTER(GroupTuplesStats), C.POINTER(P)]
+    lib.gg_tuple_groups_rows.argtypes = [P, C.POINTER(u64), C.POINTER(C.c_int)]
+    lib.gg_tuple_groups_fetch.argtypes = [P, u64, C.c_uint32, C.POINTER(i64p), C.POINTER(u64), C.POINTER(u64), i64p, i64p,
+                                          i64p, i64p, C.POINTER(C.c_uint32)]
+    lib.gg_debug_group_tuples.argtypes = [P, C.c_int, C.c_uint32]
     lib.gg_debug_level_sets.argtypes = [P, C.c_int, C.c_int]
     lib.gg_reach_closure_levels.argtypes = [P, C.POINTER(u64), C.c_int, C.POINTER(C.c_int)]
     lib.gg_reach_closure_fetch.argtypes = [P, u64, C.c_uint32, i64p, i64p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
@@ -494,6 +506,54 @@ class KhopAggregate:
         totals = np.empty(n, object)
         totals[:] = [(int(h_) << 64) + int(l_) for l_, h_ in zip(lo.tolist(), hi.tolist())]
         return ids, walks, totals
+
+    def close(self):
+        if self.handle:
+            self.gg.lib.gg_result_destroy(self.handle)
+            self.handle = None
+
+
+class TupleGroups:
+    """Aggregates per key tuple (gg_result_group_tuples), left in HBM: one row per distinct tuple over the chosen columns,
+    in input order of the tuples' first rows.  stats: {"rows_in", "rows_valued", "groups", "slots", "probe_steps",
+    "route"}; handle None: the call asked for the stats only."""
+
+    COLUMNS = ("rows", "valued", "sum", "min", "max")
+
+    def __init__(self, gg: "GG", handle, stats):
+        self.gg, self.handle, self.stats = gg, handle, stats
+
+    def shape(self):
+        """(groups, key columns)"""
+        n, k = C.c_uint64(), C.c_int()
+        self.gg._chk(self.gg.lib.gg_tuple_groups_rows(self.handle, C.byref(n), C.byref(k)))
+        return int(n.value), int(k.value)
+
+    def rows(self) -> int:
+        return self.shape()[0]
+
+    def fetch(self, offset: int = 0, n=None) -> dict:
+        """rows [offset, offset + n) (None: to the end) as {"keys": int64 [m, key columns], "rows" / "valued": uint64 [m],
+        "sum": an object array of Python ints put together from the two halves, "min" / "max": int64 [m]}"""
+        total, k = self.shape()
+        m = max(0, min(total - offset, total if n is None else int(n)))
+        keys = np.empty((k, m), np.int64)
+        rows, valued, lo = np.empty(m, np.uint64), np.empty(m, np.uint64), np.empty(m, np.uint64)
+        hi, mn, mx = np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64)
+        i64p, u64p = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+        got, o = C.c_uint32(), 0
+        while o < m:
+            kp = (i64p * max(k, 1))(*[keys[j, o:].ctypes.data_as(i64p) for j in range(k)])
+            self.gg._chk(self.gg.lib.gg_tuple_groups_fetch(
+                self.handle, offset + o, min(m - o, 1 << 20), kp, rows[o:].ctypes.data_as(u64p),
+                valued[o:].ctypes.data_as(u64p), lo[o:].view(np.int64).ctypes.data_as(i64p), hi[o:].ctypes.data_as(i64p),
+                mn[o:].ctypes.data_as(i64p), mx[o:].ctypes.data_as(i64p), C.byref(got)))
+            if not got.value:
+                raise GGError(-6, f"gg_tuple_groups_fetch: no row at offset {offset + o} of {total}")
+            o += got.value
+        sums = np.empty(m, object)
+        sums[:] = [(int(h_) << 64) + int(l_) for l_, h_ in zip(lo.tolist(), hi.tolist())]
+        return {"keys": np.ascontiguousarray(keys.T), "rows": rows, "valued": valued, "sum": sums, "min": mn, "max": mx}
 
     def close(self):
         if self.handle:
@@ -1060,6 +1120,33 @@ class GG:
         """distinct uses a table of `slots` slots (0: the default; rounded up to a power of two above the row count) and,
         with combine = 1, never combines adjacent equal lanes.  Results must not depend on it."""
         self._chk(self.lib.gg_debug_distinct(self.ctx, int(slots), int(combine)))
+
+    def group_tuples(self, res: KhopResult, hops: int, cols, value_col=None, value_csr=None, values=None, valid=None,
+                     fetch: bool = True) -> "TupleGroups":
+        """gg_result_group_tuples: GROUP BY the columns `cols` (as distinct's) of res's `hops`-hop table, cells compared as
+        raw int64 values: per distinct tuple count(*), and over the value of a row (filter_value's: the cell of value_col
+        looked up in value_csr, values, valid) count(x), sum(x) as a Python int mod 2^128, min(x) and max(x).  value_col
+        None: the count form, the value columns are 0.  The answer is a TupleGroups whose rows are distinct's rows in
+        distinct's order; fetch=False: the stats only, nothing is kept on the device."""
+        cs = [int(c) for c in cols]
+        arr = (C.c_int * max(len(cs), 1))(*cs)
+        v, vp, b, bp = (None, None, None, None)
+        if value_col is not None:
+            v, vp, b, bp = self._value_args(value_csr, values, valid)
+        elif value_csr is not None or values is not None or valid is not None:
+            raise ValueError("value_csr, values and valid go with a value column")
+        st, out = GroupTuplesStats(), C.c_void_p()
+        self._chk(self.lib.gg_result_group_tuples(self.ctx, res.handle, hops, arr, len(cs),
+                                                  -1 if value_col is None else int(value_col),
+                                                  value_csr.handle if value_csr is not None else None, vp, bp,
+                                                  C.byref(st), C.byref(out) if fetch else None))
+        d = {f: int(getattr(st, f)) for f, _ in GroupTuplesStats._fields_}
+        return TupleGroups(self, out if fetch else None, d)
+
+    def debug_group_tuples(self, route: int = 0, lds_groups: int = 0):
+        """group_tuples accumulates in the workgroup-private LDS cells where the groups fit (1) or in the global cells (2);
+        lds_groups shrinks the groups those cells may hold (0: the defaults).  Results must not depend on it."""
+        self._chk(self.lib.gg_debug_group_tuples(self.ctx, int(route), int(lds_groups)))
 
     def closed_walks(self, csr: Csr, k: int, sources=None, materialise: bool = True):
         """Closed walks of k edges v0 -> v1 -> ... -> v_{k-1} -> v0 with v0 from `sources` (None: every vertex), as rows

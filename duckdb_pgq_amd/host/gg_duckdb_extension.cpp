@@ -684,6 +684,7 @@ static void LoadInternal(DatabaseInstance &db) {
 	GGRegisterGroupFunctions(*con.context);
 	GGRegisterValueRowsFunctions(*con.context);
 	GGRegisterDistinctFunctions(*con.context);
+	GGRegisterGroupTuplesFunctions(*con.context);
 	GGRegisterAggregateFunctions(*con.context);
 	GGRegisterPairCountFunctions(*con.context);
 	GGRegisterCheapestFunctions(*con.context);

@@ -128,6 +128,9 @@ void GGRegisterValueRowsFunctions(ClientContext &context);
 //! gg_distinct.cpp: registers gg_khop_extend_distinct / gg_khop_extend_distinct_count (inside the caller's transaction)
 void GGRegisterDistinctFunctions(ClientContext &context);
 
+//! gg_group_tuples.cpp: registers gg_khop_extend_group_columns (inside the caller's transaction)
+void GGRegisterGroupTuplesFunctions(ClientContext &context);
+
 //! gg_aggregate.cpp: registers gg_khop_aggregate (inside the caller's transaction)
 void GGRegisterAggregateFunctions(ClientContext &context);
 

@@ -37,56 +37,6 @@ const char *FunctionName(int kind) {
 	return kind == FILTER ? "gg_khop_extend_filter" : kind == COUNT ? "gg_khop_extend_filter_count" : "gg_khop_extend_top";
 }
 
-//! a value per vertex of one CSR, in its vertex-table order (include/gg.h, "the value of a row")
-struct ValueColumn {
-	vector<int64_t> values;
-	vector<uint64_t> valid;
-};
-
-//! value_column of `table` per vertex of `csr`, keyed by key_column.  A vertex no row names, or whose value is NULL, has
-//! no value; two rows of one key with different values are refused.
-ValueColumn ValuesInVertexOrder(ClientContext &context, GGGraph &graph, gg_csr *csr, const string &table,
-                                const string &key_column, const string &value_column, const char *fn) {
-	const auto rows = GGCollectKeyedValues(context, GGTableSource(context, table, {key_column, value_column}, false), fn,
-	                                       "value_column");
-	const idx_t n = rows.keys.size();
-	vector<uint32_t> dense(n ? n : 1);
-	uint64_t V = 0, kept = 0, dropped = 0;
-	{
-		lock_guard<mutex> guard(graph.lock);
-		GGGraph::Check(gg_csr_info(csr, &V, &kept, &dropped), "gg_csr_info");
-		if (n) {
-			GGGraph::Check(gg_csr_lookup(graph.ctx, csr, rows.keys.data(), n, dense.data()), "gg_csr_lookup");
-		}
-	}
-	ValueColumn out;
-	out.values.assign(V ? V : 1, 0);
-	out.valid.assign((V + 63) / 64 + 1, 0);
-	vector<uint64_t> seen((V + 63) / 64 + 1, 0);
-	for (idx_t i = 0; i < n; i++) {
-		const uint32_t d = dense[i];
-		if (d == UINT32_MAX) {
-			continue; // (a key that is no vertex of the CSR: no row of the walk table can hold it)
-		}
-		const uint64_t bit = 1ull << (d & 63);
-		if (seen[d >> 6] & bit) {
-			const bool had = out.valid[d >> 6] & bit;
-			if (had != (bool)rows.has[i] || (had && out.values[d] != rows.values[i])) {
-				throw InvalidInputException(string(fn) + ": two rows of " + table + " share " + key_column + " = " +
-				                            to_string(rows.keys[i]) + " and carry different values of " + value_column +
-				                            "; a value per " + key_column + " cannot express that");
-			}
-			continue;
-		}
-		seen[d >> 6] |= bit;
-		if (rows.has[i]) {
-			out.valid[d >> 6] |= bit;
-			out.values[d] = rows.values[i];
-		}
-	}
-	return out;
-}
-
 struct ValueRowsSpec {
 	int kind; // ValueRowsKind
 	int hops, from_col, value_of;

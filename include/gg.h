@@ -80,6 +80,12 @@
  *           (SELECT DISTINCT k2.k_person2id, benchmark/ldbc/queries/interactive-complex-10.sql:19-24; the friends UNION of
  *           interactive-complex-6.sql:3-12 before it is joined with message; SELECT DISTINCT p1.personid, p2.personid,
  *           bi-14.sql:30-102; count(DISTINCT m_messageid), interactive-complex-10.sql:2-9)
+ *   gg_result_group_tuples / gg_tuple_groups_rows / gg_tuple_groups_fetch
+ *        <- PhysicalHashAggregate above a join chain: GROUP BY several columns of the joined rows, raw cells as keys,
+ *           count / sum / min / max                             physical_hash_aggregate.cpp:152-266
+ *           (GROUP BY m.friendid, t.t_name, benchmark/ldbc/queries/bi-10-shortestpath.sql:74; min(hopCount) GROUP BY
+ *           startPerson, friend, bi-10-shortestpath.sql:28-30; GROUP BY person1id, person2id, bi-14.sql:111;
+ *           max(l_creationdate) GROUP BY l_personid, interactive-complex-7.sql:7-12)
  *   gg_csr_lookup
  *        <- JoinHashTable::Probe of plain keys                 join_hashtable.cpp:304-330
  *   gg_walk_closure / gg_walk_closure_levels / gg_walk_closure_fetch
@@ -274,7 +280,8 @@ int gg_khop_partition_mid(gg_ctx *ctx, gg_csr *csr, int n_parts, uint64_t *bound
 
 /* A result answers the calls of its own kind only.  The five older kinds — fixed-length walk tables, walk closure, reach
  * closure, level sets, paths — refuse one another with GG_ERR_INVALID_ARG; the kinds that state a refusal contract of their
- * own (grouped aggregates, pair counts, components, all shortest paths) are refused by every other call, and their calls
+ * own (grouped aggregates, pair counts, components, all shortest paths, cheapest costs and paths, aggregates per key
+ * tuple) are refused by every other call, and their calls
  * refuse every other result, with GG_ERR_STATE.  A fixed-length walk table (a result of gg_expand_khop*, gg_bfs64_pairs*,
  * gg_walk_endpoints, gg_join_probe, gg_triangles*, the filters or gg_result_extend_edge) answers gg_result_rows,
  * gg_result_fetch, gg_result_fetch_edges and gg_result_digest for the levels it holds; a closure, level-set or paths result
@@ -561,6 +568,70 @@ typedef struct gg_distinct_stats {
 int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, const int *cols, int n_cols,
                        int materialise, gg_distinct_stats *stats /* nullable when materialising */,
                        gg_result **out_result /* NULL allowed iff materialise == 0 */);
+/* GROUP BY several columns of a materialised walk table: count(*), count(x), sum(x), min(x) and max(x) per tuple, on the
+ * device.
+ * What it replaces in the reference: PhysicalHashAggregate (src/execution/operator/aggregate/physical_hash_aggregate.cpp:
+ * 152-266) above a join chain whose statement groups by more than one column, by a cell that is a vertex of no CSR, or
+ * under min / max — `GROUP BY m.friendid, t.t_name` under count(*) (benchmark/ldbc/queries/bi-10-shortestpath.sql:74),
+ * `min(hopCount) ... GROUP BY startPerson, friend` (bi-10-shortestpath.sql:28-30), `GROUP BY person1id, person2id` with a
+ * summed score (bi-14.sql:111) and `max(l_creationdate) ... GROUP BY l_personid` (interactive-complex-7.sql:7-12).
+ * gg_result_group_by groups by exactly one column whose cells are vertices of a CSR and forms count(*) and sum only.
+ * Input, cols, equality: exactly gg_result_distinct's — whatever walk table that call accepts, its own output included;
+ * `cols` holds n_cols pairwise different column numbers in 0..hops, 1 <= n_cols <= hops + 1, in output order; cells are raw
+ * int64 values, no dictionary, no CSR.
+ * The value of a row: exactly gg_result_filter_value's — `values` is V(value_csr) int64 in vertex-table order, host memory,
+ * `valid` (nullable) its bits; the cell of value_col is looked up as gg_csr_lookup does, and the row has the value iff the
+ * cell is a vertex whose valid bit is set.  value_col may be one of the key columns or any other column in 0..hops.
+ * value_col == -1 is the count form and requires value_csr, values and valid all NULL: no lookup, no sum / min / max state.
+ * Aggregates per group, by SQL's NULL rules: rows = count(*); valued = count(x), the group's rows that have a value; sum
+ * over the valued rows as a 128-bit two's-complement integer mod 2^128 (sum_lo, sum_hi), like gg_result_group_by's total;
+ * min / max signed over the valued rows.  A group with valued == 0 reports sum 0 and min = max = 0: the reader tells NULL
+ * from valued.  In the count form valued, sum_lo, sum_hi, min and max are all 0 (no sum is formed); fetching them gives
+ * zeros.
+ * Output: a result of the kind "aggregates per key tuple", one row per distinct tuple.  Key column j is the input's column
+ * cols[j], taken from the first input row that holds the tuple, and the rows are in input order of those first rows:
+ * exactly the rows and the order gg_result_distinct returns for the same cols.  Placement is count, scan, write.  The rows
+ * and every aggregate are identical on every run, on both routes, for every slot count, under gg_debug_distinct's and
+ * gg_debug_group_tuples' knobs and under gg_debug_max_grid_tiles: everything is integer addition mod 2^64 / 2^128 and
+ * integer min / max.  Only gg_tuple_groups_rows / gg_tuple_groups_fetch answer the result; every other reader refuses it
+ * with GG_ERR_STATE, and those two refuse every other kind so (gg_result's kinds, above).
+ * How: gg_result_distinct's table of 32-bit row numbers gives every tuple one slot and its first row; count and scan give
+ * a first row its rank; a second pass over the rows adds each run of equal adjacent rows of a wavefront to the cell of
+ * its tuple's rank — state is sized by the number of groups, not of slots.  Two routes, chosen per call
+ * (stats->route): workgroup-private cells in LDS when the groups fit 48 KiB (1024 valued cells, 6144 count cells), flushed
+ * with one set of global atomics per touched cell and workgroup; global cells otherwise.
+ * stats (nullable) and out_result (NULL: stats only — then no aggregate is formed, rows_valued is counted by a pass of its
+ * own and route says what the groups would have taken).  One host synchronisation when only stats are asked for, two when
+ * rows are written.
+ * Errors: NULL ctx / res / cols, an object of another context, hops outside the result's k_min..k_max, n_cols outside
+ * 1..hops + 1, a column outside 0..hops or repeated, value_col outside -1..hops, value_col >= 0 with NULL value_csr or
+ * values, value_col == -1 with a non-NULL value_csr, values or valid, stats and out_result both NULL:
+ * GG_ERR_INVALID_ARG.  A result of another kind: GG_ERR_INVALID_ARG or GG_ERR_STATE by the rule of gg_result's kinds.  A
+ * shard CSR: GG_ERR_STATE.  An input of 2^32 rows or more: GG_ERR_TOO_LARGE.  State that does not fit: GG_ERR_OOM.  A row
+ * that exhausts the probe bound of the tuple table (which always has an empty slot): GG_ERR_STATE.  After every error the
+ * context stays usable.  An empty input gives GG_OK, zero groups and slots == 0. */
+typedef struct gg_group_tuples_stats {
+  uint64_t rows_in;      /* rows of the input table */
+  uint64_t rows_valued;  /* of those, rows that have a value (0 without a value column) */
+  uint64_t groups;       /* rows of the output = distinct tuples over the chosen columns */
+  uint64_t slots;        /* slots of the tuple table (0: nothing to do) */
+  uint64_t probe_steps;  /* diagnostic, may differ from run to run */
+  uint32_t route;        /* 0 nothing to do, 1 workgroup-private LDS cells, 2 global cells */
+} gg_group_tuples_stats;
+int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hops, const int *cols, int n_cols,
+                           int value_col /* -1: none */, const gg_csr *value_csr, const int64_t *values,
+                           const uint64_t *valid /* nullable */, gg_group_tuples_stats *stats /* nullable */,
+                           gg_result **out_result /* NULL: stats only */);
+/* The readers of gg_result_group_tuples' result.  _rows: the number of groups and of key columns (either pointer may be
+ * NULL, not both).  _fetch: rows [offset, offset + max_rows) clamped to the result, *n_out their number; `keys` holds
+ * n_key_cols pointers (NULL: no key column is asked for), each nullable, and every other column pointer is nullable too.
+ * The 128-bit sum of a row is sum_hi * 2^64 + (uint64_t)sum_lo.  A result of another kind: GG_ERR_STATE; NULL res or
+ * n_out: GG_ERR_INVALID_ARG. */
+int gg_tuple_groups_rows(const gg_result *res, uint64_t *n_rows, int *n_key_cols);
+int gg_tuple_groups_fetch(const gg_result *res, uint64_t offset, uint32_t max_rows,
+                          int64_t *const *keys /* n_key_cols pointers, each nullable */,
+                          uint64_t *rows, uint64_t *valued, int64_t *sum_lo, int64_t *sum_hi,
+                          int64_t *min, int64_t *max /* each nullable */, uint32_t *n_out);
 /* Forget the staged edge rows but keep the staged vertex table (several edge tables, one vertex set). */
 int gg_staging_clear_edges(gg_ctx *ctx);
 /* Replace the staged vertex table by the distinct endpoint ids of the staged edge rows, in ascending
@@ -1288,6 +1359,13 @@ int gg_debug_value_top(gg_ctx *ctx, int sort_route /* 0 auto, 1 LDS, 2 global */
  * load of almost 1 stays legal and an empty slot always exists.  combine = 1: no lanes of a wavefront are combined, every
  * row probes.  Results must not depend on either.  A combine outside 0..1 is GG_ERR_INVALID_ARG. */
 int gg_debug_distinct(gg_ctx *ctx, uint64_t slots /* 0: default */, int combine /* 0 auto, 1 never combine adjacent lanes */);
+/* Testing knob: gg_result_group_tuples accumulates in workgroup-private LDS cells wherever the groups fit them (1; where
+ * they do not, the global cells run all the same) or in the global cells whatever their number (2); lds_groups shrinks the
+ * number of groups those cells may hold (0: the default, 6144 in the count form and 1024 in the valued form; larger values
+ * change nothing), so both routes and the boundary occur at small sizes.  The call's tuple table obeys gg_debug_distinct.
+ * stats->route says which route ran.  Results must not depend on it.  A route outside 0..2 is GG_ERR_INVALID_ARG. */
+int gg_debug_group_tuples(gg_ctx *ctx, int route /* 0 auto, 1 LDS where the groups fit, 2 global */,
+                          uint32_t lds_groups /* 0: default capacity */);
 /* Testing hook, stateless: the library's shared exclusive prefix scan over a host array.  `in` and `out` are n values of
  * `width` bytes (4: uint32, 8: uint64); out[i] = in[0] + ... + in[i-1] — the width-4 form mod 2^32 — and *total is the
  * exact sum in 64 bits, which must stay below 2^62 (the scan's status words keep two flag bits; a larger sum is not
