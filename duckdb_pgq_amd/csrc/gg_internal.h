@@ -172,7 +172,7 @@ struct gg_ctx {
   // ---- caching device allocator ----
   // pool_mu: compute calls on one context are externally serialised, but results of earlier calls are
   // destroyed (their blocks freed) from whatever thread finishes with them
-  std::mutex pool_mu;
+  mutable std::mutex pool_mu;  // (mutable: gg_debug_pool_fill reads the counters of a const context under it)
   std::vector<gg::DevBlock> blocks;
   size_t bytes_allocated = 0;
 
@@ -255,6 +255,11 @@ struct gg_ctx {
   int fetch_columns(void *const *dst, const void *const *src, int n_cols, size_t bytes);
 
   uint64_t next_serial = 1;
+  // GG_POOL_FILL=<0..255> at context creation: every block dev_alloc hands out, fresh or recycled, is set to that byte over
+  // its whole size first (DESIGN.md "Scratch is never assumed zero"); -1: off.  gg_debug_reset leaves it alone.
+  int pool_fill = -1;
+  uint64_t pool_blocks_filled = 0, pool_bytes_filled = 0;  // since the context was created (gg_debug_pool_fill)
+  int fill_block(void *p, size_t size);
   int dev_alloc(void **out, size_t bytes);
   // Three result columns of col_bytes each that will be written in lockstep (k_mat_mid2).  Small ones share one pooled
   // block; large ones are three blocks chosen so that they lie in different memory ranks (gg_runtime.hip "Placement"),

@@ -65,6 +65,7 @@ int gg_ctx::dev_alloc(void **out, size_t bytes) {
     blocks[best].serial = next_serial++;
     blocks[best].keep = false;
     *out = blocks[best].ptr;
+    if (pool_fill >= 0) return fill_block(blocks[best].ptr, blocks[best].size);
     return GG_OK;
   }
   void *p = nullptr;
@@ -100,6 +101,18 @@ int gg_ctx::dev_alloc(void **out, size_t bytes) {
   bytes_allocated += bytes;
   blocks.push_back({p, bytes, true, next_serial++, false});
   *out = p;
+  if (pool_fill >= 0) return fill_block(p, bytes);
+  return GG_OK;
+}
+
+// GG_POOL_FILL: the whole block (not only the bytes asked for) set to the context's byte, on the library's stream.  Every
+// earlier user of a recycled block is behind it there: compute runs on that stream alone, and a fetch lane's copy is
+// waited for before the fetch returns (fetch_columns), which is before its result can be destroyed.  Caller holds pool_mu.
+int gg_ctx::fill_block(void *p, size_t size) {
+  GG_HIP(hipSetDevice(device));
+  GG_HIP(hipMemsetAsync(p, pool_fill, size, stream));
+  pool_blocks_filled++;
+  pool_bytes_filled += size;
   return GG_OK;
 }
 
@@ -442,6 +455,15 @@ extern "C" int gg_debug_pool(gg_ctx *ctx, uint64_t *blocks, uint64_t *in_use) {
   return GG_OK;
 }
 
+extern "C" int gg_debug_pool_fill(const gg_ctx *ctx, int *fill, uint64_t *blocks_filled, uint64_t *bytes_filled) {
+  if (!ctx) return GG_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(ctx->pool_mu);
+  if (fill) *fill = ctx->pool_fill;
+  if (blocks_filled) *blocks_filled = ctx->pool_blocks_filled;
+  if (bytes_filled) *bytes_filled = ctx->pool_bytes_filled;
+  return GG_OK;
+}
+
 extern "C" int gg_debug_reset(gg_ctx *ctx) {
   if (!ctx) return GG_ERR_INVALID_ARG;
   ctx->force_frontier = 0;
@@ -541,6 +563,13 @@ extern "C" int gg_ctx_create(int device, gg_ctx **out) {
   if (const char *e = getenv("GG_MIRROR_PAIRS")) ctx->mirror_pairs = atoi(e) != 0;
   if (const char *e = getenv("GG_MIRROR_REVERSE")) ctx->mirror_reverse = atoi(e) != 0;
   if (const char *e = getenv("GG_CC_SIZE_FOLD")) ctx->cc_size_fold = atoi(e) != 0;
+  if (const char *e = getenv("GG_POOL_FILL")) {  // 0..255, decimal or 0x..; anything else: off
+    char *end = nullptr;
+    const bool hex = e[0] == '0' && (e[1] == 'x' || e[1] == 'X');
+    const long v = strtol(e, &end, hex ? 16 : 10);
+    const bool digit = hex ? isxdigit((unsigned char)e[2]) != 0 : isdigit((unsigned char)e[0]) != 0;
+    if (digit && end && *end == 0 && v >= 0 && v <= 255) ctx->pool_fill = (int)v;
+  }
   for (int i = 0; i < 2; i++) {
     GG_HIP(hipHostMalloc((void **)&ctx->pin_v[i], gg_ctx::STAGE_ROWS * sizeof(int64_t), hipHostMallocDefault));
     GG_HIP(hipEventCreateWithFlags(&ctx->pin_v_free[i], hipEventDisableTiming));
@@ -703,6 +732,10 @@ int grow_column(gg_ctx *ctx, Column &c, size_t live_rows, size_t need_rows) {
   while (ncap < need_rows) ncap *= 2;
   int64_t *p = nullptr;
   GG_HIP(hipMalloc((void **)&p, ncap * sizeof(int64_t)));
+  if (ctx->pool_fill >= 0) {  // GG_POOL_FILL: the staging column beyond the rows it keeps
+    const size_t live = c.dev ? live_rows : 0;
+    GG_HIP(hipMemsetAsync(p + live, ctx->pool_fill, (ncap - live) * sizeof(int64_t), ctx->stream));
+  }
   if (c.dev && live_rows)
     GG_HIP(hipMemcpyAsync(p, c.dev, live_rows * sizeof(int64_t), hipMemcpyDeviceToDevice, ctx->stream));
   if (c.dev) {

@@ -21,7 +21,7 @@ SYMBOLS = [
     "gg_expand_khop", "gg_expand_khop_range", "gg_khop_count", "gg_expand_khop_dev", "gg_stream_wait", "gg_join_probe", "gg_khop_partition", "gg_expand_khop_mid", "gg_khop_partition_mid", "gg_expand_khop_mid_result",
     "gg_debug_force_frontier", "gg_debug_force_legacy_build", "gg_debug_scan_fault", "gg_debug_rank_mode",
     "gg_debug_csr_reverse", "gg_debug_csr_reverse_ready", "gg_debug_csr_reverse_index_ready", "gg_debug_scan", "gg_debug_sort_pairs",
-    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_pool", "gg_debug_reach_visited",
+    "gg_debug_max_grid_tiles", "gg_debug_reset", "gg_debug_placement", "gg_debug_pool", "gg_debug_pool_fill", "gg_debug_reach_visited",
     "gg_debug_level_sets", "gg_level_sets", "gg_level_sets_levels", "gg_level_sets_fetch",
     "gg_result_rows", "gg_result_fetch", "gg_result_destroy", "gg_expand_khop_result", "gg_result_digest",
     "gg_expand_khop_edges", "gg_result_fetch_edges",
@@ -238,6 +238,7 @@ def load_library(path: str | None = None):
     lib.gg_debug_reset.argtypes = [P]
     lib.gg_debug_placement.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
     lib.gg_debug_pool.argtypes = [P, C.POINTER(u64), C.POINTER(u64)]
+    lib.gg_debug_pool_fill.argtypes = [P, C.POINTER(C.c_int), C.POINTER(u64), C.POINTER(u64)]
     lib.gg_debug_reach_visited.argtypes = [P, C.c_int, u64]
     lib.gg_debug_bfs_steps.argtypes = [P, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.gg_result_rows.argtypes = [P, C.c_int, C.POINTER(u64)]
@@ -1247,6 +1248,13 @@ class GG:
         a, b = C.c_uint64(), C.c_uint64()
         self._chk(self.lib.gg_debug_pool(self.ctx, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def pool_fill(self):
+        """(the byte GG_POOL_FILL gave this context or -1, blocks filled, bytes filled since it was created)
+        (gg_debug_pool_fill)."""
+        f, a, b = C.c_int(), C.c_uint64(), C.c_uint64()
+        self._chk(self.lib.gg_debug_pool_fill(self.ctx, C.byref(f), C.byref(a), C.byref(b)))
+        return int(f.value), int(a.value), int(b.value)
 
     def khop_partition(self, csr: Csr, n_parts: int):
         b = (C.c_uint64 * (n_parts + 1))()

@@ -1392,6 +1392,12 @@ int gg_debug_placement(gg_ctx *ctx, uint64_t *sets_built, uint64_t *fast_pairs_o
  * result, or inside a running call).  A block that is never given back shows as in_use growing from call to call, one
  * given back twice or lost as the counts of two identical rounds of calls differing.  Read-only; either may be NULL. */
 int gg_debug_pool(gg_ctx *ctx, uint64_t *blocks, uint64_t *in_use);
+/* The pool's fill mode.  GG_POOL_FILL=<0..255, decimal or 0x..> in the environment of gg_ctx_create makes the context set
+ * every device block it hands out, fresh or recycled, to that byte over the block's whole size before its first use (and
+ * the staging columns beyond the rows they hold), so that a test decides what scratch memory holds when an operation
+ * starts; unset or anything else: off.  gg_debug_reset leaves the mode alone.  *fill = the byte, or -1 when off;
+ * *blocks_filled / *bytes_filled = blocks and bytes filled since the context was created.  Read-only; any may be NULL. */
+int gg_debug_pool_fill(const gg_ctx *ctx, int *fill, uint64_t *blocks_filled, uint64_t *bytes_filled);
 /* Diagnostics of the LAST 64-lane BFS of this context (gg_bfs64 and every call that runs one: pairs, paths, all paths):
  * what its levels recorded about themselves on the device, as the host read it back when the search ended.  *n_levels =
  * stats.levels + 1 entries (entry 0: the seed; entry l: level l), 0 if no BFS ran since gg_ctx_create / gg_debug_reset or
