@@ -248,6 +248,9 @@ __device__ __forceinline__ void mid_accumulate(const uint32_t *s_q, int ia, int 
       mid_fold<NREG>(c0.y, t, acc);
       mid_fold<NREG>(c0.z, t, acc);
       mid_fold<NREG>(c0.w, t, acc);
+      // (the read may not move up among the folds of the group it replaces: it then lands in four other registers and
+      // is copied into c0's at the end of every trip, two v_mov_b64 per eight states)
+      __builtin_amdgcn_sched_barrier(0);
       c0 = *reinterpret_cast<const uint4 *>(s_q + i + 8);
       mid_fold<NREG>(c1.x, t, acc);
       mid_fold<NREG>(c1.y, t, acc);
