@@ -27,6 +27,7 @@
 // 24 B written).  The gathered table is 24 V bytes; whether its lines are served from L2 / Infinity Cache is not
 // measured here.
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 using namespace gg;
 
@@ -376,10 +377,7 @@ extern "C" int gg_khop_aggregate(gg_ctx *ctx, const gg_csr *csr_c, const int64_t
       if (res) {
         // V entries per column: a level has at most V groups, and their number stays on the device until the call's
         // one read-back
-        for (int c = 0; c < 4; c++) {
-          GG_TRY(ctx->dev_alloc((void **)&res->cols[h][c], V * sizeof(int64_t)));
-          ctx->keep(res->cols[h][c]);
-        }
+        GG_TRY(alloc_kept_columns(ctx, res->cols[h], 4, V));
         GG_LAUNCH(ctx, "agg_write", k_agg_write, vgrid, dim3(256), 0, cur, (int)weighted, final_mult, V,
                   (const uint32_t *)flag, (const int64_t *)csr->vid, res->cols[h][0], res->cols[h][1], res->cols[h][2],
                   res->cols[h][3]);

@@ -53,20 +53,22 @@ extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, c
                                   int materialise, gg_distinct_stats *stats, gg_result **out_result) {
   if (out_result) *out_result = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (!ctx || !res || !cols || res->ctx != ctx) {
-    set_error("gg_result_distinct: bad context / result / cols argument");
+  const char *fn = "gg_result_distinct";
+  GG_TRY(result_arg(fn, ctx, res));
+  if (!cols) {
+    set_error("%s: NULL cols", fn);
     return GG_ERR_INVALID_ARG;
   }
-  GG_TRY(expect_kind(res, ResultKind::TABLES, "gg_result_distinct"));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::EXPECT));
   if (materialise && !out_result) {
-    set_error("gg_result_distinct: materialise without out_result");
+    set_error("%s: materialise without out_result", fn);
     return GG_ERR_INVALID_ARG;
   }
   if (!stats && !out_result) {
-    set_error("gg_result_distinct: neither stats nor out_result is asked for");
+    set_error("%s: neither stats nor out_result is asked for", fn);
     return GG_ERR_INVALID_ARG;
   }
-  GG_TRY(tuple_columns_check("gg_result_distinct", res, hops, cols, n_cols));
+  GG_TRY(tuple_columns_check(fn, res, hops, cols, n_cols));
   const uint64_t n_rows = res->rows[hops], n_words = (n_rows + 63) / 64;
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
@@ -98,11 +100,7 @@ extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, c
       GG_TRY(read_back(ctx, {{a.words, sizeof(words_host), words_host}}));
       total = words_host[2];
     } else {
-      const uint64_t groups = (n_rows + 255) / 256;
-      GG_TRY(ctx->dev_alloc((void **)&group, groups * sizeof(uint64_t)));
-      GG_LAUNCH(ctx, "k_value_groups", k_value_groups, stride_grid(ctx, groups), dim3(256), 0, (const uint64_t *)a.mask,
-                n_words, groups, group);
-      GG_TRY(scan_total_u64(ctx, group, group, groups, &total, false, {{a.words, sizeof(words_host), words_host}}));
+      GG_TRY(mask_prefix(ctx, a.mask, n_rows, {{a.words, sizeof(words_host), words_host}}, &group, &total));
     }
     if (words_host[1]) {
       set_error("internal: gg_result_distinct found no slot for a row in a table of %llu slots for %llu rows",
@@ -117,12 +115,8 @@ extern "C" int gg_result_distinct(gg_ctx *ctx, const gg_result *res, int hops, c
     if (materialise && total) {
       ValIn in{};
       ValOut out{};
-      for (int j = 0; j < n_cols; j++) {
-        in.c[j] = a.c[j];
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[out_hops][j], total * sizeof(int64_t)));
-        ctx->keep(o->cols[out_hops][j]);
-        out.c[j] = o->cols[out_hops][j];
-      }
+      GG_TRY(alloc_kept_columns(ctx, o->cols[out_hops], n_cols, total));
+      for (int j = 0; j < n_cols; j++) in.c[j] = a.c[j], out.c[j] = o->cols[out_hops][j];
       GG_TRY(value_write_launch(ctx, in, n_cols, n_rows, a.mask, n_words, group, total, out));
       GG_TRY(sync_checked(ctx));
     }

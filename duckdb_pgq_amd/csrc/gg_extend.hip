@@ -28,6 +28,7 @@
 // through L2 / L1 among the copies of one parent), 4 B of nbr, 8 B of vid (a gather), 8 (hops + 2) B written; with edge
 // columns 4 or 8 B of rowid read, 8 hops B of the parent's edge cells read and 8 (hops + 1) B written.
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 using namespace gg;
 
@@ -36,7 +37,6 @@ namespace gg {
 constexpr uint32_t EX_TILE_ROWS = 1024;  // output rows per workgroup of the write pass
 constexpr int EX_PER = EX_TILE_ROWS / 256;  // output rows per lane of a full tile
 constexpr uint32_t EX_WIN = 1024;        // input rows whose prefixes a tile stages in LDS
-constexpr uint64_t EX_MAX_GROUPS = 0xFFFFFFFFull / 256;  // workgroups per launch: GG_LAUNCH refuses 2^32 threads
 
 struct ExIn {
   const int64_t *c[GG_MAX_HOPS + 1];  // id columns v0..v_hops of the input (hops + 1 <= GG_MAX_HOPS: c[GG_MAX_HOPS] stays null)
@@ -51,8 +51,7 @@ struct ExOut {
 // per row) get the dense index of the row's cell and the sum of the degrees of the workgroup's earlier rows; group[g] the
 // workgroup's total, *matched += its rows with an edge row.
 __global__ __launch_bounds__(256) void k_extend_count(const int64_t *__restrict__ from, uint64_t g0, uint64_t n_rows,
-                                                      const HtSlot *__restrict__ ht, uint64_t cap, int64_t min_idx,
-                                                      const uint32_t *__restrict__ off, uint32_t *__restrict__ u_rows,
+                                                      DictView dict, const uint32_t *__restrict__ off, uint32_t *__restrict__ u_rows,
                                                       uint32_t *__restrict__ pre, uint64_t *__restrict__ group,
                                                       unsigned long long *__restrict__ matched) {
   __shared__ uint64_t s_sum[4];
@@ -62,7 +61,7 @@ __global__ __launch_bounds__(256) void k_extend_count(const int64_t *__restrict_
   const bool live = r < n_rows;
   uint32_t u = INVALID_U32, deg = 0;
   if (live) {
-    u = ht_lookup(ht, cap, min_idx, from[r]);
+    u = dict.lookup(from[r]);
     if (u != INVALID_U32) deg = off[u + 1] - off[u];  // (u < V: off has V + 1 entries)
   }
   // (the prefixes are exact whenever they are used: rows are only written if fewer than 2^32 come out in all)
@@ -199,29 +198,19 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
                                      int want_edges, int materialise, gg_extend_stats *stats, gg_result **out_result) {
   if (out_result) *out_result = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (!ctx || !res || !csr_c || res->ctx != ctx || csr_c->ctx != ctx || (materialise && !out_result)) {
-    set_error("gg_result_extend_edge: bad context / result / csr / out_result argument");
+  const char *fn = "gg_result_extend_edge";
+  GG_TRY(result_arg(fn, ctx, res));
+  GG_TRY(csr_arg(fn, ctx, csr_c));
+  if (materialise && !out_result) {
+    set_error("%s: materialise without out_result", fn);
     return GG_ERR_INVALID_ARG;
   }
-  if (csr_c->n_parts > 1) {
-    set_error("gg_result_extend_edge: a CSR shard (gg_csr_build_shard) cannot be the joined table");
-    return GG_ERR_STATE;
-  }
-  if (res->kind != ResultKind::TABLES) {
-    set_error("gg_result_extend_edge: the result has no fixed-length table (a closure, level sets or paths)");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops + 1 > GG_MAX_HOPS) {
-    set_error("gg_result_extend_edge: hops %d outside the result's range [%d, %d], or hops + 1 > %d", hops, res->k_min,
-              res->k_max, GG_MAX_HOPS);
-    return GG_ERR_INVALID_ARG;
-  }
-  if (from_col < 0 || from_col > hops) {
-    set_error("gg_result_extend_edge: column %d outside 0..%d", from_col, hops);
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(whole_csr(fn, csr_c, "the joined table"));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::STATE));
+  GG_TRY(hops_arg(fn, res, hops, GG_MAX_HOPS - 1));  // (the output has hops + 1)
+  GG_TRY(column_arg(fn, "from", from_col, 0, hops));
   if (want_edges && !csr_c->has_rowid) {
-    set_error("gg_result_extend_edge: edge columns need a CSR built with edge rowids (gg_ctx_set_edge_rowid(ctx, 1))");
+    set_error("%s: edge columns need a CSR built with edge rowids (gg_ctx_set_edge_rowid(ctx, 1))", fn);
     return GG_ERR_STATE;
   }
   ApiScope scope(ctx);
@@ -234,7 +223,8 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
   if (materialise) o = make_result(ctx, ResultKind::TABLES, out_hops, out_hops);
   uint64_t total = 0, matched = 0;
   if (n_rows && csr->V && csr->E) {  // (without an edge row nothing matches: nothing to look up)
-    GG_TRY(ensure_ht(ctx, csr));
+    DictView dict;
+    GG_TRY(dict_view(ctx, csr, &dict));
     const uint64_t groups = (n_rows + 255) / 256;
     uint32_t *u_rows = nullptr, *pre = nullptr;
     uint64_t *group = nullptr;
@@ -246,14 +236,11 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
     GG_TRY(ctx->dev_alloc((void **)&group, groups * sizeof(uint64_t)));
     GG_TRY(ctx->dev_alloc((void **)&matched_dev, sizeof(unsigned long long)));
     GG_HIP(hipMemsetAsync(matched_dev, 0, sizeof(unsigned long long), ctx->stream));
-    // split under gg_debug_max_grid_tiles like the expansion and filter kernels
-    const uint64_t per_launch = ctx->max_grid_tiles && ctx->max_grid_tiles < EX_MAX_GROUPS ? ctx->max_grid_tiles : EX_MAX_GROUPS;
-    for (uint64_t g0 = 0; g0 < groups; g0 += per_launch) {
-      const uint64_t ng = groups - g0 < per_launch ? groups - g0 : per_launch;
+    GG_TRY(split_groups(ctx, groups, [&](uint64_t g0, uint64_t ng) -> int {
       GG_LAUNCH(ctx, "k_extend_count", k_extend_count, dim3((unsigned)ng), dim3(256), 0, res->cols[hops][from_col], g0,
-                n_rows, (const HtSlot *)csr->ht, csr->ht_cap, csr->ht_min_idx, (const uint32_t *)csr->off, u_rows, pre,
-                group, matched_dev);
-    }
+                n_rows, dict, (const uint32_t *)csr->off, u_rows, pre, group, matched_dev);
+      return GG_OK;
+    }));
     GG_TRY(scan_total_u64(ctx, group, group, groups, &total, false, {{matched_dev, sizeof(uint64_t), &matched}}));
     if (materialise && total) {
       if (total >= (1ull << 32)) {
@@ -268,33 +255,26 @@ extern "C" int gg_result_extend_edge(gg_ctx *ctx, const gg_result *res, int hops
       X.tile_rows = ctx->extend_tile_rows && ctx->extend_tile_rows < EX_TILE_ROWS ? ctx->extend_tile_rows : EX_TILE_ROWS;
       X.group = group, X.pre = pre, X.u_rows = u_rows;
       X.off = csr->off, X.nbr = csr->nbr, X.vid = csr->vid, X.epos = csr->epos, X.eid = csr->eid;
-      bool in_edges = want_edges && hops > 0;
-      for (int c = 0; c < hops; c++) in_edges = in_edges && res->ecols[hops][c];
+      const bool in_edges = want_edges && walk_edge_columns(res, hops);
       for (int c = 0; c <= hops; c++) X.in.c[c] = res->cols[hops][c];
       for (int c = 0; c < hops; c++) X.in.e[c] = in_edges ? res->ecols[hops][c] : nullptr;
-      for (int c = 0; c <= out_hops; c++) {
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[out_hops][c], total * sizeof(int64_t)));
-        ctx->keep(o->cols[out_hops][c]);
-        X.out.c[c] = o->cols[out_hops][c];
-      }
-      for (int c = 0; want_edges && c < out_hops; c++) {
-        GG_TRY(ctx->dev_alloc((void **)&o->ecols[out_hops][c], total * sizeof(int64_t)));
-        ctx->keep(o->ecols[out_hops][c]);
-        X.out.e[c] = o->ecols[out_hops][c];
-      }
+      GG_TRY(alloc_kept_columns(ctx, o->cols[out_hops], out_hops + 1, total));
+      for (int c = 0; c <= out_hops; c++) X.out.c[c] = o->cols[out_hops][c];
+      if (want_edges) GG_TRY(alloc_kept_columns(ctx, o->ecols[out_hops], out_hops, total));
+      for (int c = 0; want_edges && c < out_hops; c++) X.out.e[c] = o->ecols[out_hops][c];
       const uint64_t n_tiles = (total + X.tile_rows - 1) / X.tile_rows;
       uint64_t *tile_row = nullptr;
       GG_TRY(ctx->dev_alloc((void **)&tile_row, (n_tiles + 1) * sizeof(uint64_t)));
       X.tile_row = tile_row;
       GG_LAUNCH(ctx, "k_extend_tiles", k_extend_tiles, dim3((unsigned)((n_tiles + 1 + 255) / 256)), dim3(256), 0,
                 (const uint64_t *)group, (const uint32_t *)pre, n_rows, X.total, X.tile_rows, n_tiles, tile_row);
-      for (uint64_t t0 = 0; t0 < n_tiles; t0 += per_launch) {
-        const uint64_t nt = n_tiles - t0 < per_launch ? n_tiles - t0 : per_launch;
+      GG_TRY(split_groups(ctx, n_tiles, [&](uint64_t t0, uint64_t nt) -> int {
         if (want_edges)
           GG_LAUNCH(ctx, "k_extend_write_edges", (k_extend_write<true>), dim3((unsigned)nt), dim3(256), 0, X, t0);
         else
           GG_LAUNCH(ctx, "k_extend_write", (k_extend_write<false>), dim3((unsigned)nt), dim3(256), 0, X, t0);
-      }
+        return GG_OK;
+      }));
       GG_TRY(sync_checked(ctx));
     }
   }

@@ -30,6 +30,7 @@
 // 4 B (the first ones of a hub's row shared through L2), 4 B of m written and read once each, 8 (hops + 1) B read per
 // kept row and 8 (hops + 1) B written per output row.
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 using namespace gg;
 
@@ -51,8 +52,7 @@ __device__ __forceinline__ uint32_t mult_of(const uint32_t *__restrict__ off, co
 }
 
 template <bool FILL>
-__global__ __launch_bounds__(256) void k_filter(RowCols in, int ncols, uint64_t n_rows, const HtSlot *__restrict__ ht,
-                                                uint64_t cap, int64_t min_idx,
+__global__ __launch_bounds__(256) void k_filter(RowCols in, int ncols, uint64_t n_rows, DictView dict,
                                                 const uint32_t *__restrict__ off, const uint32_t *__restrict__ nbr,
                                                 const int64_t *__restrict__ vid, uint64_t *__restrict__ counts,
                                                 const uint64_t *__restrict__ offsets, OutCols out) {
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void k_filter(RowCols in, int ncols, uint64_t 
   uint32_t d[GG_MAX_HOPS + 1];
   bool ok = true;
   for (int c = 0; c < ncols; c++) {
-    d[c] = ht_lookup(ht, cap, min_idx, in.c[c][r]);  // row vertex -> dense index in the FILTER graph
+    d[c] = dict.lookup(in.c[c][r]);  // row vertex -> dense index in the FILTER graph
     ok = ok && d[c] != INVALID_U32;
   }
   uint64_t n = 0, o = FILL ? offsets[r] : 0;
@@ -86,9 +86,12 @@ __global__ __launch_bounds__(256) void k_filter(RowCols in, int ncols, uint64_t 
 
 extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *res, int hops, const gg_csr *filter,
                                                  gg_result **out) {
-  if (!ctx || !res || !filter || !out || res->ctx != ctx || filter->ctx != ctx || res->kind != ResultKind::TABLES ||
-      hops < res->k_min || hops > res->k_max || hops + 1 > GG_MAX_HOPS || filter->n_parts > 1) {
-    set_error("gg_result_filter_common_neighbour: bad argument");
+  const char *fn = "gg_result_filter_common_neighbour";
+  // (this entry point has one code for every fault, a shard included)
+  GG_TRY(walk_table_arg(fn, ctx, res, hops, KindRule::INVALID_ARG, GG_MAX_HOPS - 1));
+  GG_TRY(csr_arg(fn, ctx, filter));
+  if (!out || filter->n_parts > 1) {
+    set_error("%s: NULL out, or a CSR shard (gg_csr_build_shard) as the filter graph", fn);
     return GG_ERR_INVALID_ARG;
   }
   *out = nullptr;
@@ -102,30 +105,23 @@ extern "C" int gg_result_filter_common_neighbour(gg_ctx *ctx, const gg_result *r
   OutCols oc;
   for (int c = 0; c < GG_MAX_HOPS + 2; c++) oc.c[c] = nullptr;
   uint64_t total = 0;
-  if (n_rows) {
-    GG_TRY(ensure_ht(ctx, const_cast<gg_csr *>(filter)));
+  DictView dict{};
+  if (n_rows) GG_TRY(dict_view(ctx, filter, &dict));
+  if (dict.ht) {  // (rows to filter, and a filter graph with vertices: without one no row is kept)
     uint64_t *counts = nullptr;
     GG_TRY(ctx->dev_alloc((void **)&counts, (n_rows + 1) * sizeof(uint64_t)));
     const unsigned grid = (unsigned)((n_rows + 255) / 256);
-    GG_LAUNCH(ctx, "filter_count", (k_filter<false>), dim3(grid), dim3(256), 0, in, ncols, n_rows, filter->ht,
-              filter->ht_cap, filter->ht_min_idx, filter->off, filter->nbr, filter->vid, counts,
-              (const uint64_t *)nullptr, oc);
+    GG_LAUNCH(ctx, "filter_count", (k_filter<false>), dim3(grid), dim3(256), 0, in, ncols, n_rows, dict, filter->off,
+              filter->nbr, filter->vid, counts, (const uint64_t *)nullptr, oc);
     GG_TRY(scan_total_u64(ctx, counts, counts, n_rows, &total));
-    for (int c = 0; c <= ncols; c++) {
-      GG_TRY(ctx->dev_alloc((void **)&o->cols[hops + 1][c], (total ? total : 1) * sizeof(int64_t)));
-      ctx->keep(o->cols[hops + 1][c]);
-      oc.c[c] = o->cols[hops + 1][c];
-    }
+    GG_TRY(alloc_kept_columns(ctx, o->cols[hops + 1], ncols + 1, total ? total : 1));
+    for (int c = 0; c <= ncols; c++) oc.c[c] = o->cols[hops + 1][c];
     if (total)
-      GG_LAUNCH(ctx, "filter_fill", (k_filter<true>), dim3(grid), dim3(256), 0, in, ncols, n_rows, filter->ht,
-                filter->ht_cap, filter->ht_min_idx, filter->off, filter->nbr, filter->vid,
-                (uint64_t *)nullptr, (const uint64_t *)counts, oc);
+      GG_LAUNCH(ctx, "filter_fill", (k_filter<true>), dim3(grid), dim3(256), 0, in, ncols, n_rows, dict, filter->off,
+                filter->nbr, filter->vid, (uint64_t *)nullptr, (const uint64_t *)counts, oc);
     GG_TRY(sync_checked(ctx));
   } else {
-    for (int c = 0; c <= ncols; c++) {
-      GG_TRY(ctx->dev_alloc((void **)&o->cols[hops + 1][c], sizeof(int64_t)));
-      ctx->keep(o->cols[hops + 1][c]);
-    }
+    GG_TRY(alloc_kept_columns(ctx, o->cols[hops + 1], ncols + 1, 1));
   }
   o->rows[hops + 1] = total;
   *out = o.release();
@@ -138,8 +134,6 @@ namespace gg {
 struct EdgeOut {
   int64_t *c[GG_MAX_HOPS + 1];
 };
-
-constexpr uint64_t EF_MAX_GROUPS = 0xFFFFFFFFull / 256;  // workgroups per launch: GG_LAUNCH refuses 2^32 threads
 
 // how often u occurs in the ascending row[0..n): upper bound - lower bound (the search of tri_run in gg_triangles.hip, which
 // stays private to its kernel; only the length is wanted here)
@@ -164,13 +158,12 @@ __device__ __forceinline__ uint32_t edge_keep(int mode, uint32_t m) {
 }
 
 // Workgroup g0 + blockIdx.x owns rows [256 g, 256 g + 256).  Count (FILL false): `from` / `to` are the condition columns,
-// ht == null says the condition graph has no edge (m = 0 everywhere); m_rows (nullable) gets m, group[g] the workgroup's
+// dict.ht == null says the condition graph has no edge (m = 0 everywhere); m_rows (nullable) gets m, group[g] the workgroup's
 // output rows, *matches += its sum of m.  Write (FILL true): m_rows is read, group[g] is the workgroup's first output row.
 template <bool FILL>
 __global__ __launch_bounds__(256) void k_edge_filter(RowCols in, int ncols, const int64_t *__restrict__ from,
                                                      const int64_t *__restrict__ to, int mode, uint64_t g0,
-                                                     uint64_t n_rows, const HtSlot *__restrict__ ht, uint64_t cap,
-                                                     int64_t min_idx, const uint32_t *__restrict__ roff,
+                                                     uint64_t n_rows, DictView dict, const uint32_t *__restrict__ roff,
                                                      const uint32_t *__restrict__ rin, uint32_t *__restrict__ m_rows,
                                                      uint64_t *__restrict__ group, unsigned long long *__restrict__ matches,
                                                      EdgeOut out) {
@@ -180,8 +173,8 @@ __global__ __launch_bounds__(256) void k_edge_filter(RowCols in, int ncols, cons
   const bool live = r < n_rows;
   if (!FILL) {
     uint32_t m = 0;
-    if (live && ht) {
-      const uint32_t u = ht_lookup(ht, cap, min_idx, from[r]), t = ht_lookup(ht, cap, min_idx, to[r]);
+    if (live && dict.ht) {
+      const uint32_t u = dict.lookup(from[r]), t = dict.lookup(to[r]);
       if (u != INVALID_U32 && t != INVALID_U32) {  // (t < V: roff has V + 1 entries, the row lies inside rin)
         const uint32_t lo = roff[t];
         m = edge_run(rin + lo, roff[t + 1] - lo, u);
@@ -231,9 +224,7 @@ struct EdgeArgs {
   const int64_t *from, *to;
   int mode;
   uint64_t n_rows;
-  const HtSlot *ht;  // null: the condition graph has no edge
-  uint64_t cap;
-  int64_t min_idx;
+  DictView dict;  // ht null: the condition graph has no edge
   const uint32_t *roff, *rin;
   uint32_t *m_rows;
   uint64_t *group;
@@ -244,15 +235,12 @@ struct EdgeArgs {
 // split under gg_debug_max_grid_tiles like the expansion and triangle kernels
 template <bool FILL>
 int edge_filter_launch(gg_ctx *ctx, const EdgeArgs &a) {
-  const uint64_t groups = (a.n_rows + 255) / 256;
-  const uint64_t per_launch = ctx->max_grid_tiles && ctx->max_grid_tiles < EF_MAX_GROUPS ? ctx->max_grid_tiles : EF_MAX_GROUPS;
-  for (uint64_t g0 = 0; g0 < groups; g0 += per_launch) {
-    const uint64_t ng = groups - g0 < per_launch ? groups - g0 : per_launch;
+  return split_groups(ctx, (a.n_rows + 255) / 256, [&](uint64_t g0, uint64_t ng) -> int {
     GG_LAUNCH(ctx, FILL ? "k_edge_filter_write" : "k_edge_filter_count", (k_edge_filter<FILL>), dim3((unsigned)ng),
-              dim3(256), 0, a.in, a.ncols, a.from, a.to, a.mode, g0, a.n_rows, a.ht, a.cap, a.min_idx, a.roff, a.rin,
-              a.m_rows, a.group, a.matches, a.out);
-  }
-  return GG_OK;
+              dim3(256), 0, a.in, a.ncols, a.from, a.to, a.mode, g0, a.n_rows, a.dict, a.roff, a.rin, a.m_rows, a.group,
+              a.matches, a.out);
+    return GG_OK;
+  });
 }
 
 }  // namespace gg
@@ -262,28 +250,20 @@ extern "C" int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops
                                      gg_result **out_result) {
   if (out_result) *out_result = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (!ctx || !res || !csr_c || res->ctx != ctx || csr_c->ctx != ctx || (materialise && !out_result)) {
-    set_error("gg_result_filter_edge: bad context / result / csr / out_result argument");
+  const char *fn = "gg_result_filter_edge";
+  GG_TRY(result_arg(fn, ctx, res));
+  GG_TRY(csr_arg(fn, ctx, csr_c));
+  if (materialise && !out_result) {
+    set_error("%s: materialise without out_result", fn);
     return GG_ERR_INVALID_ARG;
   }
-  if (csr_c->n_parts > 1) {
-    set_error("gg_result_filter_edge: a CSR shard (gg_csr_build_shard) cannot be the condition graph");
-    return GG_ERR_STATE;
-  }
-  if (res->kind != ResultKind::TABLES) {
-    set_error("gg_result_filter_edge: the result has no fixed-length table (a closure, level sets or paths)");
-    return GG_ERR_STATE;
-  }
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
-    set_error("gg_result_filter_edge: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
-    return GG_ERR_INVALID_ARG;
-  }
-  if (from_col < 0 || from_col > hops || to_col < 0 || to_col > hops) {
-    set_error("gg_result_filter_edge: columns %d -> %d outside 0..%d", from_col, to_col, hops);
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(whole_csr(fn, csr_c, "the condition graph"));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::STATE));
+  GG_TRY(hops_arg(fn, res, hops));
+  GG_TRY(column_arg(fn, "from", from_col, 0, hops));
+  GG_TRY(column_arg(fn, "to", to_col, 0, hops));
   if (mode != GG_EDGE_INNER && mode != GG_EDGE_SEMI && mode != GG_EDGE_ANTI) {
-    set_error("gg_result_filter_edge: mode %d (0: inner, 1: semi, 2: anti)", mode);
+    set_error("%s: mode %d (0: inner, 1: semi, 2: anti)", fn, mode);
     return GG_ERR_INVALID_ARG;
   }
   ApiScope scope(ctx);
@@ -302,9 +282,8 @@ extern "C" int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops
     a.mode = mode;
     a.n_rows = n_rows;
     if (csr->V && csr->E) {  // (without an edge every m is 0: nothing to look up)
-      GG_TRY(ensure_ht(ctx, csr));
+      GG_TRY(dict_view(ctx, csr, &a.dict));
       GG_TRY(ensure_reverse_by_source(ctx, csr));
-      a.ht = csr->ht, a.cap = csr->ht_cap, a.min_idx = csr->ht_min_idx;
       a.roff = csr->roff, a.rin = csr->rnbr_by_src;
     }
     const uint64_t groups = (n_rows + 255) / 256;
@@ -320,11 +299,8 @@ extern "C" int gg_result_filter_edge(gg_ctx *ctx, const gg_result *res, int hops
                   (unsigned long long)total);
         return GG_ERR_TOO_LARGE;
       }
-      for (int c = 0; c < a.ncols; c++) {
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[hops][c], total * sizeof(int64_t)));
-        ctx->keep(o->cols[hops][c]);
-        a.out.c[c] = o->cols[hops][c];
-      }
+      GG_TRY(alloc_kept_columns(ctx, o->cols[hops], a.ncols, total));
+      for (int c = 0; c < a.ncols; c++) a.out.c[c] = o->cols[hops][c];
       GG_TRY(edge_filter_launch<true>(ctx, a));
       GG_TRY(sync_checked(ctx));
     }

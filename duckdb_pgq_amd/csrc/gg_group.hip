@@ -20,7 +20,8 @@
 //   scan            exclusive prefix of the flags: the groups' places, their number
 //   k_group_write   (vertex id, walks, lo, hi) of every group at its place: ascending dense index
 // The 128-bit sum from 64-bit atomics: a row's weight w is the pair (lo = w, hi = w >> 63).  lo is added to the low cell
-// with a RETURNING atomic; the add carried iff old + lo < lo (mod 2^64), and hi + that carry is added to the high cell.
+// with a RETURNING atomic; the add carried iff (old + lo) mod 2^64 < lo, and hi + that carry is added to the high cell
+// (atomic_add128, gg_walk_table.h).
 // The atomics on one cell are applied in some serial order, and along it the low cell runs through the partial sums of
 // the low words mod 2^64: it wraps once each time the exact partial sum passes a multiple of 2^64, so the carries counted
 // are floor(exact sum of the low words / 2^64) whatever the order, and the high cell ends as the sum of the high words
@@ -32,6 +33,7 @@
 // two with weights.  Per key: 8 B (24 B with weights) zeroed, read twice (flag, write), 4 B of flag written, scanned and
 // read, and 32 B written per group; on the LDS route 8 / 24 B of global atomics per non-zero cell and workgroup.
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 using namespace gg;
 
@@ -49,23 +51,16 @@ struct GroupCell {  // the global state of a key with weights: 24 bytes
 };
 
 struct GroupArgs {
-  const int64_t *key_cells, *weight_cells;  // the two columns (weight_cells null: the count form)
+  const int64_t *key_cells;  // the key column
   uint64_t n_rows;
-  const HtSlot *kht, *wht;  // wht null: reuse the key's dense index (the same column of the same CSR), or no vertex at all
-  uint64_t kcap, wcap;
-  int64_t kmin, wmin;
-  int same_cell;            // the weight cell is the key cell and its CSR the key's
-  const int64_t *weights;   // device, V(weight_csr)
+  DictView key;             // the key table's dictionary
+  ValueColumn w;            // the weight column (cells null: the count form), its table's dictionary and the weights;
+                            // dict.ht null: no vertex at all, or unused because of same_cell
+  int same_cell;            // the weight cell is the key cell and its CSR the key's: the key's dense index serves
   uint32_t V;               // keys
   unsigned long long *cnt;  // count form: V u64
   GroupCell *cell;          // weighted form: V cells
 };
-
-// (lo, hi) += (blo, bhi) mod 2^128
-__device__ __forceinline__ void add128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
-  lo += blo;
-  hi += bhi + (uint64_t)(lo < blo);
-}
 
 // Both tables are indexed by dense key.  LDS layout: cnt[V], then lo[V], hi[V] with weights.
 template <bool LDS, bool WEIGHTED>
@@ -86,15 +81,15 @@ __global__ __launch_bounds__(256) void k_group_accum(GroupArgs A) {
       uint64_t lo = 0, hi = 0;
       if (r < A.n_rows) {
         const int64_t cell = A.key_cells[r];
-        u = ht_lookup(A.kht, A.kcap, A.kmin, cell);
+        u = A.key.lookup(cell);
         if (WEIGHTED && u != INVALID_U32) {  // (a row without a group needs no weight)
           uint32_t wv = INVALID_U32;
           if (A.same_cell)
             wv = u;
-          else if (A.wht)
-            wv = ht_lookup(A.wht, A.wcap, A.wmin, A.weight_cells[r]);
+          else if (A.w.dict.ht)
+            wv = A.w.dict.lookup(A.w.cells[r]);
           if (wv != INVALID_U32) {  // (wv < V(weight_csr): the weights have that many entries)
-            const int64_t w = A.weights[wv];
+            const int64_t w = A.w.values[wv];
             lo = (uint64_t)w, hi = (uint64_t)(w >> 63);
           }
         }
@@ -102,8 +97,7 @@ __global__ __launch_bounds__(256) void k_group_accum(GroupArgs A) {
       // runs of equal keys in adjacent lanes: lane l heads one iff its key differs from lane l - 1's
       const uint32_t prev = (uint32_t)__shfl_up((int)u, 1, 64);
       const uint64_t heads = __ballot(lane == 0 || prev != u);
-      const uint64_t after = lane == 63 ? 0 : heads >> (lane + 1);
-      const int end = after ? lane + 1 + __builtin_ctzll(after) : 64;  // one past the last lane of this lane's run
+      const int end = run_end(heads, lane);  // one past the last lane of this lane's run
       if (WEIGHTED) {  // segmented suffix sums: lane l ends with the sum over [l, end)
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -115,14 +109,10 @@ __global__ __launch_bounds__(256) void k_group_accum(GroupArgs A) {
         const unsigned long long cnt = (unsigned long long)(end - lane);
         if (LDS) {
           atomicAdd(&s_tab[u], cnt);
-          if (WEIGHTED) {
-            const unsigned long long old = atomicAdd(&s_tab[A.V + u], (unsigned long long)lo);
-            atomicAdd(&s_tab[2u * A.V + u], (unsigned long long)(hi + (uint64_t)(old + lo < lo)));
-          }
+          if (WEIGHTED) atomic_add128(&s_tab[A.V + u], &s_tab[2u * A.V + u], lo, hi);
         } else if (WEIGHTED) {
           atomicAdd(&A.cell[u].cnt, cnt);
-          const unsigned long long old = atomicAdd(&A.cell[u].lo, (unsigned long long)lo);
-          atomicAdd(&A.cell[u].hi, (unsigned long long)(hi + (uint64_t)(old + lo < lo)));
+          atomic_add128(&A.cell[u].lo, &A.cell[u].hi, lo, hi);
         } else {
           atomicAdd(&A.cnt[u], cnt);
         }
@@ -135,10 +125,8 @@ __global__ __launch_bounds__(256) void k_group_accum(GroupArgs A) {
       const unsigned long long cnt = s_tab[k];
       if (!cnt) continue;  // (no row of this workgroup had the key: its sums are 0 too)
       if (WEIGHTED) {
-        const unsigned long long lo = s_tab[A.V + k], hi = s_tab[2u * A.V + k];
         atomicAdd(&A.cell[k].cnt, cnt);
-        const unsigned long long old = atomicAdd(&A.cell[k].lo, lo);
-        atomicAdd(&A.cell[k].hi, hi + (unsigned long long)(old + lo < lo));
+        atomic_add128(&A.cell[k].lo, &A.cell[k].hi, s_tab[A.V + k], s_tab[2u * A.V + k]);
       } else {
         atomicAdd(&A.cnt[k], cnt);
       }
@@ -198,34 +186,23 @@ extern "C" int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, i
                                   gg_group_stats *stats, gg_result **out_result) {
   if (out_result) *out_result = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
+  const char *fn = "gg_result_group_by";
+  GG_TRY(result_arg(fn, ctx, res));
+  GG_TRY(csr_arg(fn, ctx, key_csr_c));
   if (!weight_csr_c) weight_csr_c = key_csr_c;
-  if (!ctx || !res || !key_csr_c || res->ctx != ctx || key_csr_c->ctx != ctx || weight_csr_c->ctx != ctx) {
-    set_error("gg_result_group_by: bad context / result / csr argument");
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(csr_arg(fn, ctx, weight_csr_c));
   if (!stats && !out_result) {
-    set_error("gg_result_group_by: neither stats nor out_result is asked for");
+    set_error("%s: neither stats nor out_result is asked for", fn);
     return GG_ERR_INVALID_ARG;
   }
-  if (key_csr_c->n_parts > 1 || weight_csr_c->n_parts > 1) {
-    set_error("gg_result_group_by: a CSR shard (gg_csr_build_shard) cannot be the key's or the weight's table");
-    return GG_ERR_STATE;
-  }
-  if (res->kind != ResultKind::TABLES) {
-    set_error("gg_result_group_by: the result has no fixed-length table (%s)", KIND_NAMES[(int)res->kind].holds);
-    return GG_ERR_STATE;
-  }
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
-    set_error("gg_result_group_by: hops %d outside the result's range [%d, %d]", hops, res->k_min, res->k_max);
-    return GG_ERR_INVALID_ARG;
-  }
-  if (key_col < 0 || key_col > hops || weight_col < -1 || weight_col > hops) {
-    set_error("gg_result_group_by: key column %d outside 0..%d or weight column %d outside -1..%d", key_col, hops,
-              weight_col, hops);
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(whole_csr(fn, key_csr_c, "the key's table"));
+  GG_TRY(whole_csr(fn, weight_csr_c, "the weight's table"));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::STATE));
+  GG_TRY(hops_arg(fn, res, hops));
+  GG_TRY(column_arg(fn, "key", key_col, 0, hops));
+  GG_TRY(column_arg(fn, "weight", weight_col, -1, hops));
   if ((weight_col >= 0) != (weights != nullptr)) {
-    set_error("gg_result_group_by: weights go with a weight column, and only with one");
+    set_error("%s: weights go with a weight column, and only with one", fn);
     return GG_ERR_INVALID_ARG;
   }
   ApiScope scope(ctx);
@@ -237,30 +214,18 @@ extern "C" int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, i
   if (out_result) o = make_result(ctx, ResultKind::AGGREGATE, hops, hops);
   uint64_t words_host[2] = {0, 0};  // groups, rows grouped
   uint32_t route = 0;
-  if (n_rows && (!res->cols[hops][key_col] || (weighted && !res->cols[hops][weight_col]))) {
-    set_error("gg_result_group_by: table %d of the result has rows but no id columns", hops);
-    return GG_ERR_STATE;
-  }
+  const int id_cols[2] = {key_col, weight_col};  // (weight_col -1: none)
+  GG_TRY(id_columns_present(fn, res, hops, id_cols, 2));
   if (n_rows && V) {
     hipStream_t st = ctx->stream;
-    GG_TRY(ensure_ht(ctx, kcsr));
     GroupArgs A{};
     A.key_cells = res->cols[hops][key_col];
     A.n_rows = n_rows;
-    A.kht = kcsr->ht, A.kcap = kcsr->ht_cap, A.kmin = kcsr->ht_min_idx;
+    GG_TRY(dict_view(ctx, kcsr, &A.key));
     A.V = (uint32_t)V;  // (a CSR has fewer than 2^32 vertices)
     if (weighted) {
-      A.weight_cells = res->cols[hops][weight_col];
-      A.same_cell = wcsr == kcsr && weight_col == key_col;
-      if (!A.same_cell && wcsr->V) {
-        GG_TRY(ensure_ht(ctx, wcsr));
-        A.wht = wcsr->ht, A.wcap = wcsr->ht_cap, A.wmin = wcsr->ht_min_idx;
-      }
-      int64_t *w_dev = nullptr;
-      GG_TRY(ctx->dev_alloc((void **)&w_dev, (wcsr->V ? wcsr->V : 1) * sizeof(int64_t)));
-      // (caller memory: the read_back below synchronises the stream before this call returns)
-      if (wcsr->V) GG_HIP(hipMemcpyAsync(w_dev, weights, wcsr->V * sizeof(int64_t), hipMemcpyHostToDevice, st));
-      A.weights = w_dev;
+      A.same_cell = wcsr == kcsr && weight_col == key_col;  // (then the weight table's dictionary is never asked)
+      GG_TRY(value_column(ctx, wcsr, res->cols[hops][weight_col], weights, nullptr, &A.w));
     }
     const size_t key_bytes = weighted ? sizeof(GroupCell) : sizeof(unsigned long long);
     void *state = nullptr;
@@ -298,10 +263,7 @@ extern "C" int gg_result_group_by(gg_ctx *ctx, const gg_result *res, int hops, i
     if (o) {
       // a level has at most min(V, rows) groups; their number stays on the device until the call's one read-back
       const uint64_t slots = V < n_rows ? V : n_rows;
-      for (int c = 0; c < 4; c++) {
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[hops][c], slots * sizeof(int64_t)));
-        ctx->keep(o->cols[hops][c]);
-      }
+      GG_TRY(alloc_kept_columns(ctx, o->cols[hops], 4, slots));
       GG_LAUNCH(ctx, "k_group_write", k_group_write, vgrid, dim3(256), 0, (const unsigned long long *)A.cnt,
                 (const GroupCell *)A.cell, V, (const uint32_t *)flag, slots, (const int64_t *)kcsr->vid, o->cols[hops][0],
                 o->cols[hops][1], o->cols[hops][2], o->cols[hops][3]);

@@ -64,40 +64,17 @@ struct TupleCell {  // the global state of a group in the valued form: 48 bytes
   long long mn, mx;
 };
 
-struct TupleValue {  // the value of a row, as gg_value.hip's k_value_probe forms it
-  const int64_t *cells;  // the value column's cells
-  const HtSlot *ht;      // null: value_csr has no vertex, no row has a value
-  uint64_t cap;
-  int64_t min_idx;
-  const int64_t *values;
-  const uint64_t *valid;  // null: every vertex has a value
-};
-
 struct TupleArgs {
   DistinctArgs d;         // the key columns, the tuple table, slot_of, the mask and the combine flag of the insert pass
   const uint64_t *group;  // the exclusive prefix of the first rows per 256-row group
   uint64_t groups;
-  TupleValue v;
+  ValueColumn v;          // the value of a row (gg_walk_table.h), as gg_value.hip's k_value_probe forms it
   unsigned long long *cnt;  // count form: groups u64
   TupleCell *cell;          // valued form: groups cells
 };
 
-__device__ __forceinline__ bool row_value(const TupleValue &v, uint64_t r, int64_t &x) {
-  if (!v.ht) return false;
-  const uint32_t d = ht_lookup(v.ht, v.cap, v.min_idx, v.cells[r]);
-  // (d < V: values has V entries and valid ceil(V / 64) words)
-  if (d == INVALID_U32 || (v.valid && !((v.valid[d >> 6] >> (d & 63)) & 1ull))) return false;
-  x = v.values[d];
-  return true;
-}
-
-__device__ __forceinline__ void add128(uint64_t &lo, uint64_t &hi, uint64_t blo, uint64_t bhi) {
-  lo += blo;
-  hi += bhi + (uint64_t)(lo < blo);
-}
-
 // rows that have a value -> *valued
-__global__ __launch_bounds__(256) void k_tuple_valued(TupleValue v, uint64_t n_rows, unsigned long long *valued) {
+__global__ __launch_bounds__(256) void k_tuple_valued(ValueColumn v, uint64_t n_rows, unsigned long long *valued) {
   const uint64_t tiles = (n_rows + 255) / 256;
   uint64_t n = 0;  // (uniform over the wavefront)
   for (uint64_t g = blockIdx.x; g < tiles; g += gridDim.x) {
@@ -146,8 +123,7 @@ __global__ __launch_bounds__(256) void k_tuple_accum(TupleArgs A) {
     }
     // lane l heads a run iff the insert pass made it probe; a lane past the table ends the run before it
     const uint64_t heads = __ballot(!live || !(a.combine && lane != 0 && same));
-    const uint64_t after = lane == 63 ? 0 : heads >> (lane + 1);
-    const int end = after ? lane + 1 + __builtin_ctzll(after) : 64;  // one past the last lane of this lane's run
+    const int end = run_end(heads, lane);  // one past the last lane of this lane's run
     uint64_t lo = 0, hi = 0;
     uint32_t nv = 0;
     int64_t mn = INT64_MAX, mx = INT64_MIN;
@@ -184,8 +160,7 @@ __global__ __launch_bounds__(256) void k_tuple_accum(TupleArgs A) {
           atomicAdd(&s_cell[rank], cnt);
           if (VALUED && nv) {
             atomicAdd(&s_cell[G + rank], (unsigned long long)nv);
-            const unsigned long long old = atomicAdd(&s_cell[2 * G + rank], (unsigned long long)lo);
-            atomicAdd(&s_cell[3 * G + rank], (unsigned long long)(hi + (uint64_t)(old + lo < lo)));
+            atomic_add128(&s_cell[2 * G + rank], &s_cell[3 * G + rank], lo, hi);
             atomicMin((long long *)&s_cell[4 * G + rank], (long long)mn);
             atomicMax((long long *)&s_cell[5 * G + rank], (long long)mx);
           }
@@ -194,8 +169,7 @@ __global__ __launch_bounds__(256) void k_tuple_accum(TupleArgs A) {
           atomicAdd(&cell->rows, cnt);
           if (nv) {
             atomicAdd(&cell->valued, (unsigned long long)nv);
-            const unsigned long long old = atomicAdd(&cell->lo, (unsigned long long)lo);
-            atomicAdd(&cell->hi, (unsigned long long)(hi + (uint64_t)(old + lo < lo)));
+            atomic_add128(&cell->lo, &cell->hi, lo, hi);
             atomicMin(&cell->mn, (long long)mn);
             atomicMax(&cell->mx, (long long)mx);
           }
@@ -215,10 +189,8 @@ __global__ __launch_bounds__(256) void k_tuple_accum(TupleArgs A) {
         atomicAdd(&cell->rows, cnt);
         const unsigned long long nv = s_cell[G + k];
         if (nv) {
-          const unsigned long long lo = s_cell[2 * G + k], hi = s_cell[3 * G + k];
           atomicAdd(&cell->valued, nv);
-          const unsigned long long old = atomicAdd(&cell->lo, lo);
-          atomicAdd(&cell->hi, hi + (unsigned long long)(old + lo < lo));
+          atomic_add128(&cell->lo, &cell->hi, s_cell[2 * G + k], s_cell[3 * G + k]);
           atomicMin(&cell->mn, (long long)s_cell[4 * G + k]);
           atomicMax(&cell->mx, (long long)s_cell[5 * G + k]);
         }
@@ -267,11 +239,12 @@ extern "C" int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hop
   const char *fn = "gg_result_group_tuples";
   if (out_result) *out_result = nullptr;
   if (stats) memset(stats, 0, sizeof(*stats));
-  if (!ctx || !res || !cols || res->ctx != ctx) {
-    set_error("%s: bad context / result / cols argument", fn);
+  GG_TRY(result_arg(fn, ctx, res));
+  if (!cols) {
+    set_error("%s: NULL cols", fn);
     return GG_ERR_INVALID_ARG;
   }
-  GG_TRY(expect_kind(res, ResultKind::TABLES, fn));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::EXPECT));
   if (!stats && !out_result) {
     set_error("%s: neither stats nor out_result is asked for", fn);
     return GG_ERR_INVALID_ARG;
@@ -283,24 +256,15 @@ extern "C" int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hop
     return GG_ERR_INVALID_ARG;
   }
   if (valued) {
-    if (value_col < 0 || value_col > hops) {
-      set_error("%s: value column %d outside -1..%d", fn, value_col, hops);
+    GG_TRY(column_arg(fn, "value", value_col, -1, hops));
+    if (!values) {
+      set_error("%s: NULL values", fn);
       return GG_ERR_INVALID_ARG;
     }
-    if (!value_csr || value_csr->ctx != ctx || !values) {
-      set_error("%s: bad csr / values argument", fn);
-      return GG_ERR_INVALID_ARG;
-    }
-    if (value_csr->n_parts > 1) {
-      set_error("%s: a CSR shard (gg_csr_build_shard) cannot be the values' table", fn);
-      return GG_ERR_STATE;
-    }
+    GG_TRY(whole_csr_arg(fn, ctx, value_csr, "the values' table"));
+    GG_TRY(id_columns_present(fn, res, hops, &value_col, 1));
   }
   const uint64_t n_rows = res->rows[hops], n_words = (n_rows + 63) / 64;
-  if (valued && n_rows && !res->cols[hops][value_col]) {
-    set_error("%s: table %d of the result has rows but no id columns", fn, hops);
-    return GG_ERR_STATE;
-  }
   ApiScope scope(ctx);
   GG_HIP(hipSetDevice(ctx->device));
   ResultOwner o;
@@ -324,27 +288,7 @@ extern "C" int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hop
     GG_TRY(ctx->dev_alloc((void **)&a.mask, n_words * sizeof(uint64_t)));
     GG_TRY(ctx->dev_alloc((void **)&a.words, sizeof(words_host)));
     GG_HIP(hipMemsetAsync(a.words, 0, sizeof(words_host), st));
-    if (valued) {
-      gg_csr *csr = const_cast<gg_csr *>(value_csr);
-      const uint64_t V = csr->V;
-      A.v.cells = res->cols[hops][value_col];
-      if (V) {
-        GG_TRY(ensure_ht(ctx, csr));
-        A.v.ht = csr->ht, A.v.cap = csr->ht_cap, A.v.min_idx = csr->ht_min_idx;
-        int64_t *v_dev = nullptr;
-        GG_TRY(ctx->dev_alloc((void **)&v_dev, V * sizeof(int64_t)));
-        // (caller memory: the call's first read_back synchronises the stream before it returns)
-        GG_HIP(hipMemcpyAsync(v_dev, values, V * sizeof(int64_t), hipMemcpyHostToDevice, st));
-        A.v.values = v_dev;
-        if (valid) {
-          uint64_t *b_dev = nullptr;
-          const size_t bytes = ((V + 63) / 64) * sizeof(uint64_t);
-          GG_TRY(ctx->dev_alloc((void **)&b_dev, bytes));
-          GG_HIP(hipMemcpyAsync(b_dev, valid, bytes, hipMemcpyHostToDevice, st));
-          A.v.valid = b_dev;
-        }
-      }
-    }
+    if (valued) GG_TRY(value_column(ctx, value_csr, res->cols[hops][value_col], values, valid, &A.v));
     dim3 grid = stride_grid(ctx, n_rows);
     if (ctx->max_grid_tiles && ctx->max_grid_tiles < grid.x) grid.x = (unsigned)ctx->max_grid_tiles;
     GG_LAUNCH(ctx, "k_distinct_insert", k_distinct_insert, grid, dim3(256), 0, a);
@@ -353,10 +297,7 @@ extern "C" int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hop
       GG_LAUNCH(ctx, "k_tuple_valued", k_tuple_valued, grid, dim3(256), 0, A.v, n_rows, a.words + 3);
     const uint64_t tiles = (n_rows + 255) / 256;
     uint64_t *group = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&group, tiles * sizeof(uint64_t)));
-    GG_LAUNCH(ctx, "k_value_groups", k_value_groups, stride_grid(ctx, tiles), dim3(256), 0, (const uint64_t *)a.mask, n_words,
-              tiles, group);
-    GG_TRY(scan_total_u64(ctx, group, group, tiles, &groups, false, {{a.words, 4 * sizeof(uint64_t), words_host}}));
+    GG_TRY(mask_prefix(ctx, a.mask, n_rows, {{a.words, 4 * sizeof(uint64_t), words_host}}, &group, &groups));
     if (words_host[1]) {
       set_error("internal: %s found no slot for a row in a table of %llu slots for %llu rows", fn, (unsigned long long)cap,
                 (unsigned long long)n_rows);
@@ -398,19 +339,13 @@ extern "C" int gg_result_group_tuples(gg_ctx *ctx, const gg_result *res, int hop
         GG_LAUNCH(ctx, "k_tuple_accum", (k_tuple_accum<false, false>), dim3((unsigned)agrid), dim3(256), 0, A);
       ValIn in{};
       ValOut keys{};
-      for (int j = 0; j < n_cols; j++) {
-        in.c[j] = a.c[j];
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[TG_KEYS_TABLE][j], groups * sizeof(int64_t)));
-        ctx->keep(o->cols[TG_KEYS_TABLE][j]);
-        keys.c[j] = o->cols[TG_KEYS_TABLE][j];
-      }
+      GG_TRY(alloc_kept_columns(ctx, o->cols[TG_KEYS_TABLE], n_cols, groups));
+      for (int j = 0; j < n_cols; j++) in.c[j] = a.c[j], keys.c[j] = o->cols[TG_KEYS_TABLE][j];
       GG_TRY(value_write_launch(ctx, in, n_cols, n_rows, a.mask, n_words, group, groups, keys));
       TupleOut out{};
-      for (int c = 0; c < (valued ? TG_AGG_COLS : 1); c++) {
-        GG_TRY(ctx->dev_alloc((void **)&o->cols[TG_AGG_TABLE][c], groups * sizeof(int64_t)));
-        ctx->keep(o->cols[TG_AGG_TABLE][c]);
-        out.c[c] = o->cols[TG_AGG_TABLE][c];
-      }
+      const int agg_cols = valued ? TG_AGG_COLS : 1;
+      GG_TRY(alloc_kept_columns(ctx, o->cols[TG_AGG_TABLE], agg_cols, groups));
+      for (int c = 0; c < agg_cols; c++) out.c[c] = o->cols[TG_AGG_TABLE][c];
       GG_LAUNCH(ctx, "k_tuple_write", k_tuple_write, stride_grid(ctx, groups), dim3(256), 0,
                 (const unsigned long long *)A.cnt, (const TupleCell *)A.cell, groups, out, a.words + 4);
       GG_TRY(read_back(ctx, {{a.words + 4, 2 * sizeof(uint64_t), words_host + 4}}));

@@ -383,6 +383,10 @@ namespace gg {
 // of a compute call is read_back / sync_checked, which test the chained scans' error word whenever a scan ran.  An
 // explicit dev_free is only worth writing where it lowers the pool's peak, i.e. before a later allocation in the same
 // call.
+// An operator over the rows of a walk table (gg_walk_table.h) checks its table through result_arg / walk_kind_arg / hops_arg
+// / whole_csr_arg / column_arg / id_columns_present, in the order its checks always had (two faults at once are answered
+// with the first check's code); takes a dictionary as a DictView from dict_view and a value column from value_column;
+// allocates its result's columns with alloc_kept_columns and splits a launch with split_groups.
 struct ApiScope {
   gg_ctx *ctx;
   uint64_t mark;

@@ -3,7 +3,7 @@
 //
 // The mask holds one bit per input row, word i the rows [64 i, 64 i + 64) — a wavefront's __ballot, stored by its lane 0.
 //   k_value_groups  one thread per group of 256 rows: the popcount of its four mask words
-//   scan            exclusive prefix of the groups' rows (the caller's: scan_total_u64)
+//   scan            exclusive prefix of the groups' rows (mask_prefix runs both; the caller's read-back items ride on it)
 //   k_value_write   a row's place is the group's prefix + the popcounts of the group's mask words below its wavefront +
 //                   the popcount of its own word below its lane: no LDS, no barrier.  It copies the cells of the columns
 //                   it is given; the kept lanes of a wavefront write consecutive cells of every column, in input order,
@@ -11,12 +11,12 @@
 // Bytes per row (model): 1/8 B mask + 8 (columns) B read per kept row + 8 (columns) B written.
 #pragma once
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 namespace gg {
 namespace {
 
 constexpr int VAL_MAX_COLS = 2 * GG_MAX_HOPS + 1;  // hops + 1 id columns and hops edge columns
-constexpr uint64_t VAL_MAX_GROUPS = 0xFFFFFFFFull / 256;  // workgroups per launch: GG_LAUNCH refuses 2^32 threads
 
 struct ValIn {
   const int64_t *c[VAL_MAX_COLS];
@@ -58,17 +58,23 @@ __global__ __launch_bounds__(256) void k_value_write(ValIn in, int ncols, uint64
   }
 }
 
-// split under gg_debug_max_grid_tiles like the edge filter
+// The mask's prefix: *group (from the pool) gets the exclusive prefix of the passing rows per group of 256 rows, *total
+// their number.  One host synchronisation, the scan's read-back, on which the caller's `extra` items ride.
+int mask_prefix(gg_ctx *ctx, const uint64_t *mask, uint64_t n_rows, std::initializer_list<ReadBack> extra, uint64_t **group,
+                uint64_t *total) {
+  const uint64_t groups = (n_rows + 255) / 256, n_words = (n_rows + 63) / 64;
+  GG_TRY(ctx->dev_alloc((void **)group, groups * sizeof(uint64_t)));
+  GG_LAUNCH(ctx, "k_value_groups", k_value_groups, stride_grid(ctx, groups), dim3(256), 0, mask, n_words, groups, *group);
+  return scan_total_u64(ctx, *group, *group, groups, total, false, extra);
+}
+
 int value_write_launch(gg_ctx *ctx, const ValIn &in, int ncols, uint64_t n_rows, const uint64_t *mask, uint64_t n_words,
                        const uint64_t *group, uint64_t total, const ValOut &out) {
-  const uint64_t groups = (n_rows + 255) / 256;
-  const uint64_t per_launch = ctx->max_grid_tiles && ctx->max_grid_tiles < VAL_MAX_GROUPS ? ctx->max_grid_tiles : VAL_MAX_GROUPS;
-  for (uint64_t g0 = 0; g0 < groups; g0 += per_launch) {
-    const uint64_t ng = groups - g0 < per_launch ? groups - g0 : per_launch;
+  return split_groups(ctx, (n_rows + 255) / 256, [&](uint64_t g0, uint64_t ng) -> int {
     GG_LAUNCH(ctx, "k_value_write", k_value_write, dim3((unsigned)ng), dim3(256), 0, in, ncols, g0, n_rows, mask, n_words,
               group, total, out);
-  }
-  return GG_OK;
+    return GG_OK;
+  });
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 // gg_distinct.hip's file comment; the kernels are the ones that file held, moved here unchanged.
 #pragma once
 #include "gg_internal.h"
+#include "gg_walk_table.h"
 
 namespace gg {
 namespace {
@@ -117,10 +118,7 @@ uint64_t tuple_slots(const gg_ctx *ctx, uint64_t n_rows) {
 
 // gg_result_distinct's argument checks on (hops, cols, n_cols) and the table's size, under the caller's name
 int tuple_columns_check(const char *fn, const gg_result *res, int hops, const int *cols, int n_cols) {
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
-    set_error("%s: hops %d outside the result's range [%d, %d]", fn, hops, res->k_min, res->k_max);
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(hops_arg(fn, res, hops));
   if (n_cols < 1 || n_cols > hops + 1) {
     set_error("%s: %d columns chosen, outside 1..%d", fn, n_cols, hops + 1);
     return GG_ERR_INVALID_ARG;
@@ -138,13 +136,7 @@ int tuple_columns_check(const char *fn, const gg_result *res, int hops, const in
     set_error("%s: a table of %llu rows (2^32 or more); filter it first", fn, (unsigned long long)n_rows);
     return GG_ERR_TOO_LARGE;
   }
-  if (n_rows)
-    for (int j = 0; j < n_cols; j++)
-      if (!res->cols[hops][cols[j]]) {
-        set_error("%s: table %d of the result has rows but no id columns", fn, hops);
-        return GG_ERR_STATE;
-      }
-  return GG_OK;
+  return id_columns_present(fn, res, hops, cols, n_cols);
 }
 
 }  // namespace

@@ -42,13 +42,8 @@ namespace gg {
 namespace {
 
 struct ProbeArgs {
-  const int64_t *cells;  // the value column's cells
+  ValueColumn v;  // the value of a row (gg_walk_table.h)
   uint64_t n_rows;
-  const HtSlot *ht;      // null: value_csr has no vertex, no row has a value
-  uint64_t cap;
-  int64_t min_idx;
-  const int64_t *values;
-  const uint64_t *valid;  // null: every vertex has a value
   int64_t lo, hi;
   int negate;
   uint64_t *mask;         // ceil(n_rows / 64) words
@@ -65,15 +60,10 @@ __global__ __launch_bounds__(256) void k_value_probe(ProbeArgs a) {
     const uint64_t r = g * 256 + threadIdx.x;
     bool has = false, pass = false;
     int64_t x = 0;
-    if (r < a.n_rows && a.ht) {
-      const uint32_t d = ht_lookup(a.ht, a.cap, a.min_idx, a.cells[r]);
-      // (d < V: values has V entries and valid ceil(V / 64) words)
-      if (d != INVALID_U32 && (!a.valid || ((a.valid[d >> 6] >> (d & 63)) & 1ull))) {
-        has = true;
-        x = a.values[d];
-        const bool in = a.lo <= x && x <= a.hi;
-        pass = in != (a.negate != 0);
-      }
+    if (r < a.n_rows && row_value(a.v, r, x)) {
+      has = true;
+      const bool in = a.lo <= x && x <= a.hi;
+      pass = in != (a.negate != 0);
     }
     if (a.xs && r < a.n_rows) a.xs[r] = x;
     const uint64_t hm = __ballot(has), pm = __ballot(pass);
@@ -117,40 +107,22 @@ __global__ __launch_bounds__(256) void k_value_gather(ValIn in, const uint32_t *
 // the checks both entry points share; *edges: the input carries walk edge columns e1..e_hops
 int value_check(const char *fn, gg_ctx *ctx, const gg_result *res, int hops, int value_col, const gg_csr *csr,
                 const int64_t *values, int mode, bool *edges) {
-  if (!ctx || !res || !csr || res->ctx != ctx || csr->ctx != ctx || !values) {
-    set_error("%s: bad context / result / csr / values argument", fn);
+  GG_TRY(result_arg(fn, ctx, res));
+  if (!values) {
+    set_error("%s: NULL values", fn);
     return GG_ERR_INVALID_ARG;
   }
-  if (csr->n_parts > 1) {
-    set_error("%s: a CSR shard (gg_csr_build_shard) cannot be the values' table", fn);
-    return GG_ERR_STATE;
-  }
-  if (res->kind != ResultKind::TABLES) {
-    set_error("%s: the result has no fixed-length table (%s)", fn, KIND_NAMES[(int)res->kind].holds);
-    return GG_ERR_STATE;
-  }
-  if (hops < res->k_min || hops > res->k_max || hops < 0 || hops > GG_MAX_HOPS) {
-    set_error("%s: hops %d outside the result's range [%d, %d]", fn, hops, res->k_min, res->k_max);
-    return GG_ERR_INVALID_ARG;
-  }
-  if (value_col < 0 || value_col > hops) {
-    set_error("%s: value column %d outside 0..%d", fn, value_col, hops);
-    return GG_ERR_INVALID_ARG;
-  }
+  GG_TRY(whole_csr_arg(fn, ctx, csr, "the values' table"));
+  GG_TRY(walk_kind_arg(fn, res, KindRule::STATE));
+  GG_TRY(hops_arg(fn, res, hops));
+  GG_TRY(column_arg(fn, "value", value_col, 0, hops));
   if (mode != GG_VALUE_IN && mode != GG_VALUE_NOT_IN) {
     set_error("%s: mode %d (0: in the range, 1: outside it)", fn, mode);
     return GG_ERR_INVALID_ARG;
   }
-  if (res->rows[hops]) {
-    for (int c = 0; c <= hops; c++)
-      if (!res->cols[hops][c]) {
-        set_error("%s: table %d of the result has rows but no id columns", fn, hops);
-        return GG_ERR_STATE;
-      }
-  }
-  bool e = hops > 0 && !res->tri_edges;  // (a triangle table's e1..e3 are no walk edge columns: dropped, as by every filter)
-  for (int c = 0; c < hops; c++) e = e && res->ecols[hops][c];
-  *edges = e;
+  GG_TRY(id_columns_present(fn, res, hops, nullptr, hops + 1));
+  // (a triangle table's e1..e3 are no walk edge columns: dropped, as by every filter)
+  *edges = !res->tri_edges && walk_edge_columns(res, hops);
   return GG_OK;
 }
 
@@ -159,27 +131,11 @@ int value_probe(gg_ctx *ctx, const gg_result *res, int hops, int value_col, gg_c
                 const uint64_t *valid, int64_t lo, int64_t hi, int mode, bool want_xs, uint64_t **mask, int64_t **xs,
                 unsigned long long **counts) {
   hipStream_t st = ctx->stream;
-  const uint64_t n_rows = res->rows[hops], n_words = (n_rows + 63) / 64, V = csr->V;
+  const uint64_t n_rows = res->rows[hops], n_words = (n_rows + 63) / 64;
   ProbeArgs a{};
-  a.cells = res->cols[hops][value_col];
+  GG_TRY(value_column(ctx, csr, res->cols[hops][value_col], values, valid, &a.v));
   a.n_rows = n_rows;
   a.lo = lo, a.hi = hi, a.negate = mode == GG_VALUE_NOT_IN;
-  if (V) {
-    GG_TRY(ensure_ht(ctx, csr));
-    a.ht = csr->ht, a.cap = csr->ht_cap, a.min_idx = csr->ht_min_idx;
-    int64_t *v_dev = nullptr;
-    GG_TRY(ctx->dev_alloc((void **)&v_dev, V * sizeof(int64_t)));
-    // (caller memory: the call's read_back synchronises the stream before it returns)
-    GG_HIP(hipMemcpyAsync(v_dev, values, V * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    a.values = v_dev;
-    if (valid) {
-      uint64_t *b_dev = nullptr;
-      const size_t bytes = ((V + 63) / 64) * sizeof(uint64_t);
-      GG_TRY(ctx->dev_alloc((void **)&b_dev, bytes));
-      GG_HIP(hipMemcpyAsync(b_dev, valid, bytes, hipMemcpyHostToDevice, st));
-      a.valid = b_dev;
-    }
-  }
   GG_TRY(ctx->dev_alloc((void **)&a.mask, n_words * sizeof(uint64_t)));
   if (want_xs) GG_TRY(ctx->dev_alloc((void **)&a.xs, n_rows * sizeof(int64_t)));
   GG_TRY(ctx->dev_alloc((void **)&a.counts, 2 * sizeof(unsigned long long)));
@@ -202,17 +158,12 @@ int value_columns(const gg_result *res, int hops, bool edges, ValIn *in) {
 // the kept columns of `rows` rows each for table hops of o, in value_columns' order
 int value_alloc_out(gg_ctx *ctx, gg_result *o, int hops, bool edges, uint64_t rows, ValOut *out) {
   int n = 0;
-  for (int c = 0; c <= hops; c++) {
-    GG_TRY(ctx->dev_alloc((void **)&o->cols[hops][c], rows * sizeof(int64_t)));
-    ctx->keep(o->cols[hops][c]);
-    out->c[n++] = o->cols[hops][c];
+  GG_TRY(alloc_kept_columns(ctx, o->cols[hops], hops + 1, rows));
+  for (int c = 0; c <= hops; c++) out->c[n++] = o->cols[hops][c];
+  if (edges) {
+    GG_TRY(alloc_kept_columns(ctx, o->ecols[hops], hops, rows));
+    for (int c = 0; c < hops; c++) out->c[n++] = o->ecols[hops][c];
   }
-  if (edges)
-    for (int c = 0; c < hops; c++) {
-      GG_TRY(ctx->dev_alloc((void **)&o->ecols[hops][c], rows * sizeof(int64_t)));
-      ctx->keep(o->ecols[hops][c]);
-      out->c[n++] = o->ecols[hops][c];
-    }
   return GG_OK;
 }
 
@@ -246,12 +197,8 @@ extern "C" int gg_result_filter_value(gg_ctx *ctx, const gg_result *res, int hop
       GG_TRY(read_back(ctx, {{counts, sizeof(counts_host), counts_host}}));
       total = counts_host[1];
     } else {
-      const uint64_t groups = (n_rows + 255) / 256;
       uint64_t *group = nullptr;
-      GG_TRY(ctx->dev_alloc((void **)&group, groups * sizeof(uint64_t)));
-      GG_LAUNCH(ctx, "k_value_groups", k_value_groups, stride_grid(ctx, groups), dim3(256), 0, (const uint64_t *)mask, n_words,
-                groups, group);
-      GG_TRY(scan_total_u64(ctx, group, group, groups, &total, false, {{counts, sizeof(counts_host), counts_host}}));
+      GG_TRY(mask_prefix(ctx, mask, n_rows, {{counts, sizeof(counts_host), counts_host}}, &group, &total));
       if (total >= (1ull << 32)) {
         set_error("gg_result_filter_value: %llu rows to materialise (2^32 or more); count them, or filter a smaller table",
                   (unsigned long long)total);
