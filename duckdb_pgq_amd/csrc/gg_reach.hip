@@ -89,6 +89,14 @@ __global__ __launch_bounds__(XT) void k_reach_expand(const uint32_t *__restrict_
   }
 }
 
+// the high piece of every class index, as a sort key of its own (expand_claim_sorted, more than 2^31 classes)
+constexpr int REACH_CLASS_PIECE_BITS = 16;
+__global__ __launch_bounds__(256) void k_reach_class_high(const uint32_t *__restrict__ cls, uint64_t n,
+                                                          uint32_t *__restrict__ high) {
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
+    high[i] = cls[i] >> REACH_CLASS_PIECE_BITS;
+}
+
 // rows of one level -> the result's int64 columns at their offset
 __global__ __launch_bounds__(256) void k_reach_emit(const uint32_t *__restrict__ cls, const uint32_t *__restrict__ vtx,
                                                     uint64_t n, const int64_t *__restrict__ vid,
@@ -160,10 +168,23 @@ int expand_claim_sorted(gg_ctx *ctx, const gg_csr *csr, const uint32_t *fcls, co
   GG_TRY(ctx->dev_alloc((void **)&l.cls, n_new * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&l.vtx, n_new * sizeof(uint32_t)));
   GG_TRY(sort_pairs_by_key(ctx, new_vtx, new_cls, n_new, bits_for(csr->V), l.vtx, l.cls));
-  if (n_classes > 1) {
+  if (n_classes > 1 && bits_for(n_classes) < 32) {
     GG_TRY(sort_pairs_by_key(ctx, l.cls, l.vtx, n_new, bits_for(n_classes), new_cls, new_vtx));
     std::swap(l.cls, new_cls);
     std::swap(l.vtx, new_vtx);
+  } else if (n_classes > 1) {
+    // more than 2^31 classes: a class index may fill 32 bits, which the radix sort does not take as one key (its
+    // 0xFFFFFFFF is "no element"; a class is at most 2^32 - 2, so no class is that key).  Two stable sorts by 16-bit
+    // pieces, the low one first: the sort ignores the class's high half, then the high half is a key of its own
+    GG_TRY(sort_pairs_by_key(ctx, l.cls, l.vtx, n_new, REACH_CLASS_PIECE_BITS, new_cls, new_vtx));
+    uint32_t *high = nullptr, *high_sorted = nullptr;
+    GG_TRY(ctx->dev_alloc((void **)&high, n_new * sizeof(uint32_t)));
+    GG_TRY(ctx->dev_alloc((void **)&high_sorted, n_new * sizeof(uint32_t)));
+    GG_LAUNCH(ctx, "reach_class_high", k_reach_class_high, stride_grid(ctx, n_new), dim3(256), 0,
+              (const uint32_t *)new_cls, (uint64_t)n_new, high);
+    GG_TRY(sort_triples_by_key(ctx, high, new_cls, new_vtx, n_new, 32 - REACH_CLASS_PIECE_BITS, high_sorted, l.cls, l.vtx));
+    ctx->dev_free(high_sorted);
+    ctx->dev_free(high);
   }
   ctx->dev_free(new_vtx);
   ctx->dev_free(new_cls);

@@ -1181,7 +1181,8 @@ int gg_walk_closure_fetch(const gg_result *res, uint64_t offset, uint32_t max_ro
  * (class, the vertex's dense index in the CSR) — the same on every run and whichever visited set is used.
  * The visited set is a bitmap of n_classes x V bits while that fits a budget, else a hash set of keys
  * class << 32 | vertex (gg_debug_reach_visited forces either).  A level of 2^32 children or more fails with
- * GG_ERR_TOO_LARGE, as do 2^32 seeds or more; a class >= n_classes with GG_ERR_INVALID_ARG; a shard CSR with
+ * GG_ERR_TOO_LARGE, as do 2^32 seeds or more; a class >= n_classes with GG_ERR_INVALID_ARG (n_classes may be any
+ * uint32_t value, on either form); a shard CSR with
  * GG_ERR_STATE.  The result answers gg_reach_closure_levels / gg_reach_closure_fetch (not gg_result_rows /
  * gg_result_fetch, nor the walk closure's calls): those two refuse another of the older kinds with GG_ERR_INVALID_ARG and an
  * aggregate, pair-count, component or all-paths result with GG_ERR_STATE. */
