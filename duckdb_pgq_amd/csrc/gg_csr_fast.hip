@@ -741,10 +741,12 @@ constexpr int LEAF_MAXS = GG_FB_LEAF_MAXS;  // 64-entry steps a wave of k_leaf_r
 // ---- column kernels: counters -> global positions ----------------------------------------------------------------
 // counts[tile][2 nb] (tile-major) must become bases[tile][c] = start of column c (its direction's bucket start)
 // + the counts of the earlier tiles in column c.  Three small kernels over groups of `gsz` tiles:
-//   k_col_partial  partial[g][c] = sum of the group's counts in column c
-//   k_col_scan     (one workgroup) partial[g][c] <- bucket start + sums of the earlier groups; bucket starts, chunk
-//                  table and kept-edge count on the way (every figure the kernels below need)
-//   k_col_apply    counts[tile][c] <- partial[g][c] + counts of the group's earlier tiles, in place
+//   k_col_partial  partial[g][c] = sum of the group's counts in column c, added into super[g / 16][c] (the sums of
+//                  supergroups of COL_SUPER groups) and into the column's total
+//   k_col_scan     (one workgroup) column totals -> bucket starts; chunk table and kept-edge count on the way (every
+//                  figure the kernels below need)
+//   k_col_apply    counts[tile][c] <- bucket start + the earlier supergroups' sums + the partial sums of the earlier
+//                  groups of its own supergroup + counts of the group's earlier tiles, in place
 // Derived reverse: column set 0 takes the FORWARD counts of the first-half tiles, set 1 the FORWARD counts of the
 // second-half tiles (col_live); a tile counts nothing in the other set and its base there is not written.
 // Every access is a coalesced row.  (The first version kept the counters bucket-major for a chained scan: D wrote
@@ -752,11 +754,15 @@ constexpr int LEAF_MAXS = GG_FB_LEAF_MAXS;  // 64-entry steps a wave of k_leaf_r
 //   bstart[dir * (nb + 1) + j]   first position of bucket j in that direction's partitioned array
 //   cstart[i], i = dir * nb + j  first chunk of bucket i (cstart[2 nb] = number of chunks)
 //   part_of[p]                   chunk p: {first entry, end, bucket i} (one load in k_sub_sort instead of a chain)
+constexpr uint32_t COL_SUPER = 16;       // groups per supergroup, whatever the group's size
+constexpr uint32_t COL_MAX_GROUPS = 512;  // (csr_build_fast sizes the groups so): at most 32 supergroups
+constexpr uint32_t COL_APPLY_THREADS = 256;  // columns per workgroup of k_col_apply (grid: groups x column blocks)
 __device__ __forceinline__ bool col_live(uint64_t tile, uint32_t c, uint32_t nb, uint32_t nt1) {
   return (c >= nb) == (tile >= nt1);
 }
 __global__ __launch_bounds__(1024) void k_col_partial(const uint32_t *__restrict__ counts, uint64_t nblocks,
                                                      uint32_t ncol, uint32_t gsz, uint32_t *__restrict__ partial,
+                                                     uint32_t *__restrict__ super /* [nsuper][ncol], zeroed */,
                                                      uint32_t *__restrict__ coltot /* [ncol], zeroed */, uint32_t derive,
                                                      uint32_t nt1, const uint32_t *__restrict__ tally) {
   const bool mirror = reverse_derivable(derive, tally);  // uniform over the grid
@@ -776,7 +782,10 @@ __global__ __launch_bounds__(1024) void k_col_partial(const uint32_t *__restrict
       for (int q = 0; q < 16; q++) sum += v[q];
     }
     partial[(uint64_t)blockIdx.x * ncol + c] = sum;
-    if (sum) atomicAdd(&coltot[c], sum);  // integer adds: the total does not depend on their order
+    if (sum) {  // integer adds: the totals do not depend on their order
+      atomicAdd(&super[(uint64_t)(blockIdx.x / COL_SUPER) * ncol + c], sum);
+      atomicAdd(&coltot[c], sum);
+    }
   }
 }
 
@@ -872,26 +881,52 @@ __global__ __launch_bounds__(1024) void k_col_scan(uint32_t *__restrict__ coltot
   if (threadIdx.x == 1023) cstart[2 * nb] = cex;
 }
 
-// bases in place: counts[tile][c] <- bucket start + counts of every earlier tile in column c.  A group adds up the
-// partial rows of the groups before it (L2-resident: the whole matrix is ~1 MB) instead of waiting for a scan.
-__global__ __launch_bounds__(1024) void k_col_apply(uint32_t *__restrict__ counts, uint64_t nblocks, uint32_t ncol,
+// Words [0, n) of a column (stride ncol) into v[0 .. 2 B - 2], n < 2 B: one unrolled batch of B, B / 2, ... 1 loads
+// per set bit of n (uniform branches, B the highest), so every load is issued before the first is waited for and no
+// row past the n-th is touched.  Slots of the batches not taken keep what they held.
+template <uint32_t B>
+__device__ __forceinline__ void col_rows(const uint32_t *__restrict__ p, uint32_t ncol, uint32_t n, uint32_t *v) {
+  if (n & B) {
+    const uint32_t r0 = n & ~(2u * B - 1u);  // (the rows of the larger batches)
+#pragma unroll
+    for (uint32_t q = 0; q < B; q++) v[q] = p[(r0 + q) * ncol];
+  }
+  if constexpr (B > 1) col_rows<B / 2>(p, ncol, n, v + B);
+}
+
+// bases in place: counts[tile][c] <- bucket start + counts of every earlier tile in column c.  A group adds up what
+// lies before it instead of waiting for a scan, in two levels: the sums of the supergroups before its own (at most
+// 31 rows) and the partial rows of the earlier groups of its own supergroup (at most 15).  Every load is independent
+// of the others and they go out in unrolled batches of 16 and less (col_rows), none waited for before the last is
+// issued: a group's way to its own tiles is one round trip to L2 however many groups precede it.  (One level, a chain over
+// ALL earlier partial rows, made the last of 304 groups at SF100 — 1.2 MB of partial sums at 1024 buckets — wait
+// for 38 dependent batches, 190 MB of L2 reads over the grid, and the kernel lasted as long as that group: 27 us.)
+// A workgroup takes 256 columns of its group: at 121 VGPRs a workgroup of 1024 threads filled a CU by itself, so 304
+// groups ran as a full round of 256 and a round of 48 (18 us between events; 11 with four workgroups a CU).
+__global__ __launch_bounds__(COL_APPLY_THREADS) void k_col_apply(uint32_t *__restrict__ counts, uint64_t nblocks, uint32_t ncol,
                                                     uint32_t gsz, const uint32_t *__restrict__ partial,
+                                                    const uint32_t *__restrict__ super,
                                                     const uint32_t *__restrict__ colstart, uint32_t nt1,
                                                     const BuildStatus *__restrict__ st) {
   const bool mirror = st->rev_derived != 0;  // uniform over the grid
   const uint32_t nb = ncol / 2;
   const uint64_t t0 = (uint64_t)blockIdx.x * gsz, t1 = t0 + gsz < nblocks ? t0 + gsz : nblocks;
-  for (uint32_t c = threadIdx.x; c < ncol; c += 1024) {
+  const uint32_t sg = blockIdx.x / COL_SUPER, g0 = sg * COL_SUPER, ng = blockIdx.x - g0;  // ng earlier groups in sg
+  static_assert(COL_MAX_GROUPS <= 2 * COL_SUPER * COL_SUPER, "two batches of supergroup rows");
+  for (uint32_t c = blockIdx.y * COL_APPLY_THREADS + threadIdx.x; c < ncol; c += gridDim.y * COL_APPLY_THREADS) {
     uint32_t run = colstart[c];
-    uint32_t g = 0;
-    for (; g + 8 <= blockIdx.x; g += 8) {  // eight independent row reads in flight
-      uint32_t v[8];
+    // (32-bit indices: both tables together are at most 545 rows of 2048 words)
+    uint32_t sv[2 * COL_SUPER - 1], pv[COL_SUPER - 1];
 #pragma unroll
-      for (int q = 0; q < 8; q++) v[q] = partial[(uint64_t)(g + q) * ncol + c];
+    for (uint32_t q = 0; q < 2 * COL_SUPER - 1; q++) sv[q] = 0u;
 #pragma unroll
-      for (int q = 0; q < 8; q++) run += v[q];
-    }
-    for (; g < blockIdx.x; g++) run += partial[(uint64_t)g * ncol + c];
+    for (uint32_t q = 0; q < COL_SUPER - 1; q++) pv[q] = 0u;
+    col_rows<COL_SUPER>(super + c, ncol, sg, sv);
+    col_rows<COL_SUPER / 2>(partial + g0 * ncol + c, ncol, ng, pv);
+#pragma unroll
+    for (uint32_t q = 0; q < 2 * COL_SUPER - 1; q++) run += sv[q];
+#pragma unroll
+    for (uint32_t q = 0; q < COL_SUPER - 1; q++) run += pv[q];
     uint32_t v[16];
     for (uint64_t tb = t0; tb < t1; tb += 16) {
 #pragma unroll
@@ -1408,9 +1443,11 @@ __global__ __launch_bounds__(LEAF_WAVES * 64) void k_leaf_rows(
 // all of it known from the offset rows; one pass, one LDS read per entry for the per-(chunk, vertex) term.
 //   k_vsort_pipe  persistent workgroups, next chunk's loads in flight (as k_sub_sort_pipe); cursors of up to 1024
 //                 keys: every thread owns keys t and t + 512, two scans over the workgroup
-//   k_vgroups     per bucket: where the rows of every group of VG vertices start (sums over the chunks' rows)
 //   k_vrows       one wave per group of VG consecutive vertices: the group's row offsets (its piece of the CSR's
-//                 offset array), then the group's run of every chunk copied to its rows
+//                 offset array), then the group's run of every chunk copied to its rows.  Where the group's rows
+//                 start needs no kernel of its own: a chunk's offset row is an exclusive prefix from 0, so the word
+//                 of the group's first vertex IS the chunk's entries before the group, and the wave loads that word
+//                 of every chunk anyway (bucket start + their sum)
 // Measured at SF100 against the sub-bucket form (k_sub_sort_pipe + k_sub_totals + k_leaf_rows): DESIGN.md §4.1.
 #ifndef GG_FB_VLOW
 #define GG_FB_VLOW 10  // vertices per bucket (log2) in this form: a wave's cursor row is 4 << GG_FB_VLOW bytes of LDS
@@ -1420,7 +1457,7 @@ constexpr int FB_VLOW = GG_FB_VLOW;
 #define GG_FB_VG 16    // vertices per wave of k_vrows (<= 32)
 #endif
 constexpr int FB_VG = GG_FB_VG;
-static_assert(FB_VG <= 32 && (1 << FB_VLOW) / FB_VG <= 64, "k_vgroups: one lane per group of a bucket");
+static_assert(FB_VG <= 32, "k_vrows: lanes 0 .. VG read one offset row of the group");
 #ifndef GG_FB_VCG
 #define GG_FB_VCG 16
 #endif
@@ -1563,30 +1600,6 @@ __global__ __launch_bounds__(FB_THREADS) void k_vsort_pipe(uint32_t *__restrict_
   }
 }
 
-// where the rows of every group of VG vertices start: one wave per bucket, lane = group (at most 64 groups)
-// mirror (derived reverse, read from the status block: one launch of 2 nb workgroups serves either form, and the
-// upper nb return): bucket j's rows take the entries of BOTH half-buckets j and nb + j
-__global__ __launch_bounds__(64) void k_vgroups(const uint16_t *__restrict__ offs, const uint32_t *__restrict__ bstart,
-                                                const uint32_t *__restrict__ cstart, FastGeom g,
-                                                uint32_t *__restrict__ gstart /* [2 nb][64] */,
-                                                const BuildStatus *__restrict__ st) {
-  const uint32_t mirror = g.derive && st->rev_derived != 0;  // (uniform over the grid)
-  const uint32_t nb = 1u << g.hb, nk = 1u << g.low, i = blockIdx.x, dir = i / nb, j = i % nb;
-  if (mirror && i >= nb) return;
-  const uint32_t vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG, groups = nk / vg;
-  const int lane = threadIdx.x;
-  const uint32_t k0 = (uint32_t)lane * vg;
-  uint32_t tot = 0, b0 = bstart[dir * (nb + 1) + j];
-  for (uint32_t half = 0; half < (mirror ? 2u : 1u); half++) {
-    const uint32_t ih = i + half * nb, p0 = cstart[ih], p1 = cstart[ih + 1];
-    if (half) b0 += bstart[nb + 1 + j];
-    if ((uint32_t)lane < groups)
-      for (uint32_t p = p0; p < p1; p++) tot += (uint32_t)offs[(uint64_t)p * g.ss + k0 + vg] - offs[(uint64_t)p * g.ss + k0];
-  }
-  const uint32_t incl = wave_scan_incl(tot);  // (DPP moves, gg_internal.h)
-  gstart[(uint64_t)i * 64 + lane] = b0 + incl - tot;
-}
-
 // One wave per (direction, bucket, group of VG vertices).  Chunks are taken FB_VCG at a time: for chunk c the lanes
 // d <= VG read the chunk's offsets of the group's vertices (one coalesced load), lane d keeps the running row
 // position of vertex d, and LDS gets   delta[c][d] = (row position of d's first entry in chunk c) - (index of that
@@ -1601,8 +1614,8 @@ __global__ __launch_bounds__(64) void k_vgroups(const uint16_t *__restrict__ off
 #endif
 __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                             const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
-                                            const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
-                                            FastGeom g, uint64_t V, uint32_t *__restrict__ off,
+                                            const uint16_t *__restrict__ offs, FastGeom g, uint64_t V,
+                                            uint32_t *__restrict__ off,
                                             uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
                                             uint32_t *__restrict__ rnbr, uint32_t *__restrict__ rrow) {
   __shared__ uint32_t s_delta[FB_VCG * FB_VG];
@@ -1617,13 +1630,14 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
   const uint64_t v0 = ((uint64_t)j << g.low) + k0;  // first vertex of the group
   if (v0 >= V) return;                              // (the table ends before this group: uniform)
   const uint32_t b0 = bstart[dir * (nb + 1) + j], p0 = cstart[i], nch = cstart[i + 1] - p0;
-  const uint32_t gs = gstart[(uint64_t)i * 64 + gi];
   const uint32_t pay_mask = (1u << g.key_bits) - 1u;  // (this form packs: key_bits + low <= 32)
   const uint32_t keep_mask = (vg << g.key_bits) - 1u;   // payload and the vertex inside the group
   // Pass over the offset rows of ALL the bucket's chunks: the vertices' degrees (sum over the chunks), and with them the
   // row offsets — this wave's piece of the CSR's offset array.  The rows of the first FB_VCG chunks (normally all
   // of them) are parked in the LDS tables as they stand, so the placing pass below does not load them again.
-  uint32_t deg = 0;
+  // Lane 0's words are the chunks' entries of the bucket's vertices BEFORE the group (a row is an exclusive prefix
+  // that starts at 0): their sum is where the group's rows start inside the bucket.
+  uint32_t deg = 0, acc = 0;
 #pragma unroll 1
   for (uint32_t c0 = 0; c0 < nch; c0 += 8) {
     uint32_t sv[8];
@@ -1637,6 +1651,7 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
       const uint32_t c = c0 + q;
       if (c >= nch) continue;  // uniform
       const uint32_t nxt = (uint32_t)__shfl_down((int)sv[q], 1, 64);  // (by the whole wave: lane vg feeds lane vg - 1)
+      acc += sv[q];
       if ((uint32_t)lane < vg) deg += nxt - sv[q];
       if (c < (uint32_t)FB_VCG) {
         if ((uint32_t)lane < vg) s_delta[c * vg + lane] = sv[q];
@@ -1645,6 +1660,7 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
       }
     }
   }
+  const uint32_t gs = b0 + (uint32_t)__builtin_amdgcn_readlane((int)acc, 0);  // (no chunks: the bucket's start)
   const uint32_t dincl = wave_scan_incl(deg);  // (DPP moves, gg_internal.h)
   uint32_t base = gs + dincl - deg;            // lane d < vg: row position of vertex d's next entry; lane vg: the end
   {
@@ -1763,8 +1779,8 @@ __device__ __forceinline__ void vrows_plain(const uint32_t *__restrict__ buf_f, 
 // groups store each entry straight to it.
 __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                              const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
-                                             const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
-                                             FastGeom g, uint64_t V, uint32_t *__restrict__ off,
+                                             const uint16_t *__restrict__ offs, FastGeom g, uint64_t V,
+                                             uint32_t *__restrict__ off,
                                              uint32_t *__restrict__ nbr, uint32_t *__restrict__ roff,
                                              uint32_t *__restrict__ rot) {
   __shared__ uint32_t s_delta[FB_VCG * FB_VG];
@@ -1779,10 +1795,10 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
   const uint32_t bA = bstart[j], bB = bstart[nb + 1 + j];
   const uint32_t pA = cstart[j], nA = cstart[j + 1] - pA, pB = cstart[nb + j], nB = cstart[nb + j + 1] - pB;
   const uint32_t nch = nA + nB;  // chunk c of the group: chunk c of A, or chunk c - nA of B
-  const uint32_t gs = gstart[(uint64_t)j * 64 + gi];
   const uint32_t pay_mask = (1u << g.key_bits) - 1u;
-  // the vertices' |A| and |B| (sums over the chunks' offset rows of either half), the row offsets of both CSRs
-  uint32_t degA = 0, degB = 0;
+  // the vertices' |A| and |B| (sums over the chunks' offset rows of either half), the row offsets of both CSRs; lane
+  // 0's words add up to the entries of both half-buckets that lie before the group (as in vrows_plain)
+  uint32_t degA = 0, degB = 0, acc = 0;
 #pragma unroll 1
   for (uint32_t c0 = 0; c0 < nch; c0 += 8) {
     uint32_t sv[8];
@@ -1797,6 +1813,7 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
       const uint32_t c = c0 + q;
       if (c >= nch) continue;  // uniform
       const uint32_t nxt = (uint32_t)__shfl_down((int)sv[q], 1, 64);  // (by the whole wave: lane vg feeds lane vg - 1)
+      acc += sv[q];
       if ((uint32_t)lane < vg) {
         if (c < nA)  // uniform
           degA += nxt - sv[q];
@@ -1811,6 +1828,7 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
     }
   }
   const uint32_t deg = degA + degB;
+  const uint32_t gs = bA + bB + (uint32_t)__builtin_amdgcn_readlane((int)acc, 0);  // (the group's first row)
   const uint32_t dincl = wave_scan_incl(deg);  // (DPP moves, gg_internal.h)
   uint32_t base = gs + dincl - deg;            // lane d < vg: row position of vertex d's next entry; lane vg: the end
   {
@@ -1923,16 +1941,16 @@ __device__ __forceinline__ void vrows_mirror(const uint32_t *__restrict__ buf_f,
 template <bool MIRROR>
 __global__ __launch_bounds__(64) void k_vrows(const uint32_t *__restrict__ buf_f, const uint32_t *__restrict__ buf_r,
                                               const uint32_t *__restrict__ bstart, const uint32_t *__restrict__ cstart,
-                                              const uint16_t *__restrict__ offs, const uint32_t *__restrict__ gstart,
-                                              FastGeom g, uint64_t V, const BuildStatus *__restrict__ st,
+                                              const uint16_t *__restrict__ offs, FastGeom g, uint64_t V,
+                                              const BuildStatus *__restrict__ st,
                                               uint32_t *__restrict__ off, uint32_t *__restrict__ nbr,
                                               uint32_t *__restrict__ roff, uint32_t *__restrict__ rows,
                                               uint32_t *__restrict__ rrow) {
   if (g.derive && (st->rev_derived != 0) != MIRROR) return;  // (uniform over the grid) the other form's work
   if (MIRROR)
-    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows);  // (writes no row index)
+    vrows_mirror(buf_f, buf_r, bstart, cstart, offs, g, V, off, nbr, roff, rows);  // (writes no row index)
   else
-    vrows_plain(buf_f, buf_r, bstart, cstart, offs, gstart, g, V, off, nbr, roff, rows, rrow);
+    vrows_plain(buf_f, buf_r, bstart, cstart, offs, g, V, off, nbr, roff, rows, rrow);
 }
 
 static int bits_of(uint64_t v) {  // bits needed for values 0..v
@@ -2013,12 +2031,14 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&tab, 2 * npairs * sizeof(unsigned long long)));
   // column totals of the counter matrix (zeroed by k_dict_init): allocated here, used by the column kernels below
   const uint32_t ncol = 2 * nb;
-  uint32_t gsz = 16;  // tiles per group of the column kernels; at most 512 groups for the single-workgroup step
-  while ((nblocks64 + gsz - 1) / gsz > 512) gsz *= 2;
+  uint32_t gsz = 16;  // tiles per group of the column kernels; at most COL_MAX_GROUPS groups (two levels of 16 and 32)
+  while ((nblocks64 + gsz - 1) / gsz > COL_MAX_GROUPS) gsz *= 2;
   const uint32_t ngroups = (uint32_t)((nblocks64 + gsz - 1) / gsz);
+  const uint32_t nsuper = (ngroups + COL_SUPER - 1) / COL_SUPER;
   uint32_t *partial = nullptr;
-  GG_TRY(ctx->dev_alloc((void **)&partial, (((uint64_t)ngroups + 1) * ncol + 3) * sizeof(uint32_t)));
-  uint32_t *coltot = partial + (uint64_t)ngroups * ncol;  // column totals, then column (= bucket) starts
+  GG_TRY(ctx->dev_alloc((void **)&partial, (((uint64_t)ngroups + nsuper + 1) * ncol + 3) * sizeof(uint32_t)));
+  uint32_t *super = partial + (uint64_t)ngroups * ncol;    // [nsuper][ncol] sums of the supergroups; zeroed with coltot
+  uint32_t *coltot = super + (uint64_t)nsuper * ncol;      // column totals, then column (= bucket) starts
   uint32_t *mirror_tally = coltot + ncol;                   // [3] rows sampled / mirrored (h > 0), != 0: the paired
                                                             // densification met a pair that is not mirrored; zeroed with coltot
   {
@@ -2027,8 +2047,8 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     if (span < V) span = V;
     GG_LAUNCH(ctx, "dict_init", k_dict_init, dim3((unsigned)((span + 255) / 256)), dim3(256), 0,
               (const int64_t *)ctx->c_vid.dev, V, csr->ht,
-              csr->ht_cap, tab, 2 * npairs, dir, dm, st, (uint32_t)csr->part, (uint32_t)csr->n_parts, csr->vid, coltot,
-              ncol + 3);
+              csr->ht_cap, tab, 2 * npairs, dir, dm, st, (uint32_t)csr->part, (uint32_t)csr->n_parts, csr->vid, super,
+              (nsuper + 1) * ncol + 3);  // (at most 33 * 2048 + 3 words: the grid has 2^20 threads or more)
     GG_LAUNCH(ctx, "dict_insert", k_dict_insert, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, csr->vid, V, csr->ht,
               csr->ht_cap, tab, dir, dm, idx_bits, (uint32_t)npairs, st, (const int64_t *)ctx->c_src.dev,
               (const int64_t *)ctx->c_dst.dev, h, mirror_tally);
@@ -2063,9 +2083,10 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
   GG_TRY(ctx->dev_alloc((void **)&cstart, (2 * nb + 1) * sizeof(uint32_t)));
   GG_TRY(ctx->dev_alloc((void **)&part_of, pmax * sizeof(uint4)));
   GG_TRY(ctx->dev_alloc((void **)&offs, pmax * g.ss * sizeof(uint32_t)));
-  GG_TRY(ctx->dev_alloc((void **)&substart, (uint64_t)2 * nb * (g.ss < 64 ? 64 : g.ss) * sizeof(uint32_t)));
+  if (!vsort)  // (the vertex-sorted form has no sub-buckets: its rows step finds every start from the offset rows)
+    GG_TRY(ctx->dev_alloc((void **)&substart, (uint64_t)2 * nb * g.ss * sizeof(uint32_t)));
   GG_LAUNCH(ctx, "col_partial", k_col_partial, dim3(ngroups), dim3(1024), 0, (const uint32_t *)counts, nblocks64, ncol, gsz,
-            partial, coltot, g.derive, g.nt1, (const uint32_t *)mirror_tally);
+            partial, super, coltot, g.derive, g.nt1, (const uint32_t *)mirror_tally);
   GG_LAUNCH(ctx, "col_scan", k_col_scan, dim3(1), dim3(1024), 0, coltot, nb, bstart, cstart, part_of, st, g.derive,
             (const uint32_t *)mirror_tally);
   if (!rowid) {
@@ -2077,8 +2098,10 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_HIP(hipEventRecord(ctx->status_ev, ctx->stream));
     ctx->status_early = true;
   }
-  GG_LAUNCH(ctx, "col_apply", k_col_apply, dim3(ngroups), dim3(1024), 0, counts, nblocks64, ncol, gsz,
-            (const uint32_t *)partial, (const uint32_t *)coltot, g.nt1, (const BuildStatus *)st);
+  GG_LAUNCH(ctx, "col_apply", k_col_apply, dim3(ngroups, (ncol + COL_APPLY_THREADS - 1) / COL_APPLY_THREADS),
+            dim3(COL_APPLY_THREADS), 0, counts, nblocks64, ncol, gsz,
+            (const uint32_t *)partial, (const uint32_t *)super, (const uint32_t *)coltot, g.nt1,
+            (const BuildStatus *)st);
 
   // ---- A ----------------------------------------------------------------------------------------------------
   const size_t words = g.pack ? 1 : 2;
@@ -2150,22 +2173,19 @@ int csr_build_fast(gg_ctx *ctx, gg_csr *csr, BuildStatus *st, int *taken) {
     GG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_vsort_pipe), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)lds_v));
     uint16_t *offs16 = reinterpret_cast<uint16_t *>(offs);  // (rows of nk + 1 16-bit offsets inside the same block)
-    uint32_t *gstart = substart;                            // [2 nb][64]
     GG_LAUNCH(ctx, "sub_sort", k_vsort_pipe, dim3(grid_p), dim3(FB_THREADS), lds_v, part_f, part_r,
               (const uint32_t *)cstart, (const uint4 *)part_of, g, offs16);
     const uint32_t nk = 1u << low, vg = nk < (uint32_t)FB_VG ? nk : (uint32_t)FB_VG;
-    // the group sums: one launch, which reads the form from the status block itself
-    GG_LAUNCH(ctx, "sub_totals", k_vgroups, dim3(2 * nb), dim3(64), 0, (const uint16_t *)offs16,
-              (const uint32_t *)bstart, (const uint32_t *)cstart, g, gstart, (const BuildStatus *)st);
+    // (no launch for the groups' first rows: every wave of k_vrows sums them from the offset words it loads)
     if (g.derive)  // (the derived-reverse form: nb buckets of both halves' entries; the rotation counts, not the rows)
       GG_LAUNCH(ctx, "leaf_rows", k_vrows<true>, dim3((unsigned)((uint64_t)nb * (nk / vg))), dim3(64), 0,
                 (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart, (const uint32_t *)cstart,
-                (const uint16_t *)offs16, (const uint32_t *)gstart, g, V, (const BuildStatus *)st, csr->off, csr->nbr,
-                csr->roff, csr->rot, csr->rrow_index);
+                (const uint16_t *)offs16, g, V, (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rot,
+                csr->rrow_index);
     GG_LAUNCH(ctx, g.derive ? "leaf_rows_plain" : "leaf_rows", k_vrows<false>, dim3((unsigned)(2ull * nb * (nk / vg))),
               dim3(64), 0, (const uint32_t *)part_f, (const uint32_t *)part_r, (const uint32_t *)bstart,
-              (const uint32_t *)cstart, (const uint16_t *)offs16, (const uint32_t *)gstart, g, V,
-              (const BuildStatus *)st, csr->off, csr->nbr, csr->roff, csr->rnbr_rows, csr->rrow_index);
+              (const uint32_t *)cstart, (const uint16_t *)offs16, g, V, (const BuildStatus *)st, csr->off, csr->nbr,
+              csr->roff, csr->rnbr_rows, csr->rrow_index);
   } else if (g.pack && rowid) {
     GG_FB_LAUNCH_B2(true, true);
   } else if (g.pack && g.rank_atomic && GG_FB_SUBPIPE) {
